@@ -8,6 +8,10 @@ Prints ONE JSON line on rank 0.  N > 1, either form:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment)
 Rank -> GPU -> stream -> RCCL group binding lives in ONE place: 3d_reconstruction_project_amd/distributed.init().
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step).  --full adds the rest of the
+record: per-kernel brackets and roofline, repeated timed regions, the pipelined / host-API / frame-loop legs, the CPU baselines,
+the GICP secondary and the C5 leg (the --no-* options below trim --full).  --dump-outputs DIR writes the disparity map
+of the last timed step (rank 0) as DIR/disparity.npy (float32, raw CV_16S values: disparity x 16); the inputs are seeded.
 """
 import argparse
 import importlib
@@ -416,6 +420,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel brackets and roofline, --repeats, the pipelined / host_api / "
+                         "frame_loop legs, the CPU baselines, the GICP secondary and the C5 leg (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the disparity map of the last timed step (rank 0) to DIR/disparity.npy as float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gicp", action="store_true", help="skip the secondary metric (GICP iterations/s at 1M points)")
     ap.add_argument("--no-extras", action="store_true",
@@ -426,7 +435,7 @@ def main():
     ap.add_argument("--extras", action="store_true", help="accepted for compatibility: the extras are on by default")
     ap.add_argument("--no-torch", action="store_true", help="keep torch out of the process (system HIP runtime; implies --no-c5)")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 leg (8-view batch: view chain -> RCCL all-gather-v -> registration)")
-    ap.add_argument("--repeats", type=int, default=5, help="extra repetitions of the K-step timed region for ms_per_step min / median")
+    ap.add_argument("--repeats", type=int, default=5, help="with --full: extra repetitions of the K-step timed region for ms_per_step min / median")
     ap.add_argument("--lanes", type=int, default=1,
                     help="maps in flight per GPU. 1 (default): strictly one map after the other, so that the per-kernel HIP-event "
                          "durations behind `roofline` are uncontended and agree with rocprofv3 --stats; 3: the K maps go through "
@@ -438,6 +447,11 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                              # a plain run: the headline and nothing else
+        args.no_cpu_baseline = args.no_gicp = args.no_extras = args.no_c5 = True
+        args.repeats = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one.  Nothing GPU-related has been imported or called in this process.
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -463,6 +477,7 @@ def main():
         args.no_c5 = True
         if world > 1:
             raise SystemExit("--no-torch is a single-process option")
+    import numpy as np
     r3d = importlib.import_module("3d_reconstruction_project_amd")
     dist = None
     if args.no_torch:
@@ -495,8 +510,9 @@ def main():
     else:                                        # warm every lane (workspace allocation happens at a lane's first use)
         nw = max(args.warmup, lanes)
         m.compute_batch_device([dL] * nw, [dR] * nw, W, H, W, [dDs[i % lanes] for i in range(nw)])
-    ctx.set_profiling(True)
-    ctx.sgbm_profile()                         # reset accumulators
+    if args.full:
+        ctx.set_profiling(True)
+        ctx.sgbm_profile()                     # reset accumulators
     e0, e1 = ctx.event(), ctx.event()          # created before the clock starts
     barrier()
     t0 = time.perf_counter()
@@ -512,7 +528,11 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     dev_ms = ctx.elapsed_ms(e0, e1)
-    prof = ctx.sgbm_profile()                  # average per-kernel launch duration over the timed region (HIP events)
+    dump = None
+    if args.dump_outputs and rank == 0:        # read back now: the --full legs below write into the same buffers
+        dump = np.empty((H, W), np.int16)
+        ctx.d2h(dump, dDs[(args.steps - 1) % lanes])
+    prof = ctx.sgbm_profile() if args.full else {}      # average per-kernel launch duration over the timed region (HIP events)
     # robustness: the same K-step region repeated (one map in flight, profiling events off); `value` stays the first region's
     rep_ms = []
     ctx.set_profiling(False)
@@ -640,17 +660,20 @@ def main():
                                        "floor_ms_per_map": round(floor_ms, 3), "floor_maps_per_s": round(1e3 / floor_ms, 1),
                                        "achieved_frac_of_floor": round(floor_ms / (dev_ms / args.steps), 4),
                                        "frac_of_8TBs_on_B_sgm": round(ALG_BYTES["map"] * (args.steps / (dev_ms * 1e-3)) / HBM_PEAK, 4)}}
-        return {"metric": "disparity-maps/s @8MP d=128", "value": round(value, 2), "unit": "disparity-maps/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": "int16", "data": "synthetic",
-                "config": {"workload": "C2: 3264x2448 rectified pair, numDisparities=128, blockSize=5, "
-                                       "MODE_SGBM_3WAY (depth2.py params), one pair per GPU resident in HBM",
-                           "parallelism": f"dp{world} (one view per GPU, no collective in the SGM step)",
-                           "maps_in_flight_per_gpu": lanes},
-                "ms_per_step_repeats": ({"n": len(rep_ms), "min": round(min(rep_ms), 4), "median": round(sorted(rep_ms)[len(rep_ms) // 2], 4),
-                                         "max": round(max(rep_ms), 4)} if rep_ms else None),
-                "roofline": roofline, "cpu_baseline": cpu, "pipelined": piped, "host_api": host_api, "frame_loop": frame_loop, "secondary": gicp, "c5": c5}
+        out = {"metric": "disparity-maps/s @8MP d=128", "value": round(value, 2), "unit": "disparity-maps/s",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+               "vs_baseline": None, "dtype": "int16", "data": "synthetic",
+               "config": {"workload": "C2: 3264x2448 rectified pair, numDisparities=128, blockSize=5, "
+                                      "MODE_SGBM_3WAY (depth2.py params), one pair per GPU resident in HBM",
+                          "parallelism": f"dp{world} (one view per GPU, no collective in the SGM step)",
+                          "maps_in_flight_per_gpu": lanes}}
+        if args.full:
+            out.update({"ms_per_step_repeats": ({"n": len(rep_ms), "min": round(min(rep_ms), 4), "median": round(sorted(rep_ms)[len(rep_ms) // 2], 4),
+                                                 "max": round(max(rep_ms), 4)} if rep_ms else None),
+                        "roofline": roofline, "cpu_baseline": cpu, "pipelined": piped, "host_api": host_api, "frame_loop": frame_loop,
+                        "secondary": gicp, "c5": c5})
+        return out
 
     # single-rank legs that need no collective (rank 0 only): CPU baseline, frame loop, GICP at N = 1
     cpu = frame_loop = None
@@ -685,6 +708,9 @@ def main():
             traceback.print_exc()
             c5 = {"error": f"{type(e).__name__}: {e}"}
         done.set()
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "disparity.npy"), dump.astype(np.float32))
     if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(headline(c5, gicp, cpu, frame_loop)) + "\n").encode())

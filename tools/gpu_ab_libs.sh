@@ -8,7 +8,7 @@ cp $L/libr3d_hip.so /tmp/r3d_installed.so
 for r in $(seq 1 "$rounds"); do
   for v in "$@"; do
     cp $L/libr3d_$v.so $L/libr3d_hip.so
-    python bench.py --no-cpu-baseline --no-c5 --no-extras --no-gicp --repeats 0 2>/dev/null | python3 -c "
+    python bench.py --full --no-cpu-baseline --no-c5 --no-extras --no-gicp --repeats 0 2>/dev/null | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read());k=d['roofline']['kernel_ms'];print('$v',d['value'],'cost',k['cost'],'hscan',k['hscan'],'vscan',k['vscan_wta'])"
   done
 done
