@@ -1,4 +1,4 @@
-// sgm.hip -- semi-global block matching (3-way) for gfx950, hand-written for 64-wide wavefronts.
+// sgm.hip -- semi-global block matching (3-way, and MODE_HH: k_hh_path / sgm_run_hh) for gfx950, hand-written for 64-wide wavefronts.
 //
 // Replaces cv2.StereoSGBM(mode=MODE_SGBM_3WAY).compute (reference call sites: Calib_depth/depth2.py:146-158,251
 // and the other depth*.py files); the arithmetic restated here is OpenCV's stereosgbm.cpp as pinned down in
@@ -1894,6 +1894,91 @@ __global__ void __launch_bounds__(NWAVE * 64) k_vscan3(const uint2 *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// MODE_HH (OpenCV computeDisparitySGBM with fullDP): eight full-length paths over the one-stripe cost volume, folded into
+// S = sat16(S + L_r) in the contract order of the directions r = p - q:
+//   (+1,0) (+1,+1) (0,+1) (-1,+1)  (pass 1)   (-1,0) (+1,-1) (0,-1) (-1,-1)  (pass 2)
+// k_hh_path runs ONE direction over every line of its family (rows, columns, diagonals x-y = c, anti-diagonals x+y = c) with
+// the lane mapping of the v2 kernels (a disparity vector on LPC lanes x NPL packed registers, 64/LPC adjacent lines per wave):
+// one chain per line, each step moves by the family-constant stride (dy*W1 + dx)*DPW words in the [y][x][dp] volume, and the
+// loads of the next HH_RING steps are in flight while a step runs.
+// FOLD 0: S = L (first direction); 1: S = sat16(S + L); 2: the same, then wta_regs on the finished S into raw / mins (S is not
+// stored).  The lines of one wave may differ in length (diagonals): a lane group past the end of its line keeps stepping on
+// its last pixel's loads and stores nothing.
+constexpr int HH_RING = 16;
+template <int NPL, int LPC, bool PADDED, int FOLD>
+__global__ void __launch_bounds__(64) k_hh_path(const int *__restrict__ cvol, int *__restrict__ svol, SgmGeom g, int dx, int dy,
+                                                float inv_a, int16_t *__restrict__ raw, int16_t *__restrict__ mins) {
+    constexpr int DPW = NPL * LPC, LPW = 64 / LPC;
+    static_assert(NPL == 4, "one 16-byte load per lane and volume");
+    const int lane = threadIdx.x, k = lane % LPC;
+    const int W1 = g.W1, H = g.H;
+    const int nlines = dy == 0 ? H : dx == 0 ? W1 : W1 + H - 1;
+    const int lraw = blockIdx.x * LPW + lane / LPC;
+    const bool line_ok = lraw < nlines;
+    const int li = min(lraw, nlines - 1);
+    int x0, y0, n;   // first pixel of line li in the direction of travel, and the line's length
+    if (dy == 0) {
+        y0 = li; x0 = dx > 0 ? 0 : W1 - 1; n = W1;
+    } else if (dx == 0) {
+        x0 = li; y0 = dy > 0 ? 0 : H - 1; n = H;
+    } else if (dx == dy) {                                  // x - y = li - (H - 1); (xs, ys) = the top-left end
+        const int c = li - (H - 1), xs = max(c, 0), ys = max(-c, 0);
+        n = min(W1 - xs, H - ys);
+        x0 = dy > 0 ? xs : xs + n - 1; y0 = dy > 0 ? ys : ys + n - 1;
+    } else {                                                // x + y = li; (xs, ys) = the top-right end
+        const int ys = max(li - (W1 - 1), 0), xs = li - ys;
+        n = min(xs + 1, H - ys);
+        x0 = dy > 0 ? xs : xs - (n - 1); y0 = dy > 0 ? ys : ys + n - 1;
+    }
+    const int nmax = __builtin_amdgcn_readfirstlane(wave_allmax_i32(n));
+    const long stride = ((long)dy * W1 + dx) * DPW;
+    const long base = ((long)y0 * W1 + x0) * DPW + k * NPL;
+    const bool valid = 2 * NPL * k < g.D, first = k == 0, last = k == LPC - 1;
+    const int P1pk = pk_dup(g.P1), a = 100 - g.uniq;
+    int P[NPL], minp = 0;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) P[j] = valid ? 0 : PADPK;
+    int cb[HH_RING][NPL], sb[HH_RING][NPL];
+    auto load = [&](int (&c)[NPL], int (&s)[NPL], int i) {
+        const long o = base + (long)min(i, n - 1) * stride;
+        const int4 cv = *(const int4 *)(cvol + o);
+        c[0] = cv.x; c[1] = cv.y; c[2] = cv.z; c[3] = cv.w;
+        if (FOLD > 0) {
+            const int4 sv = *(const int4 *)(svol + o);
+            s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
+        }
+    };
+    auto step = [&](const int (&c)[NPL], const int (&s)[NPL], int i) {
+        sgm_step_g<NPL, LPC, PADDED>(P, minp, c, P1pk, g.P2, first, last, valid);
+        const bool on = line_ok && i < n;
+        int S[NPL];
+#pragma unroll
+        for (int j = 0; j < NPL; j++) S[j] = FOLD == 0 ? P[j] : pk_add_sat(s[j], P[j]);
+        if (FOLD < 2) {
+            if (on) *(int4 *)(svol + base + (long)i * stride) = make_int4(S[0], S[1], S[2], S[3]);
+        } else {
+            int dsp, minS;
+            wta_regs<NPL, LPC>(S, k, valid, g, a, inv_a, dsp, minS);
+            if (on && first) {
+                const size_t q = (size_t)(y0 + i * dy) * g.W + g.minX1 + x0 + i * dx;
+                raw[q] = (int16_t)dsp;
+                mins[q] = (int16_t)minS;
+            }
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < HH_RING; u++) load(cb[u], sb[u], u);
+#pragma unroll 1
+    for (int i0 = 0; i0 < nmax; i0 += HH_RING) {
+#pragma unroll
+        for (int u = 0; u < HH_RING; u++) {
+            step(cb[u], sb[u], i0 + u);
+            load(cb[u], sb[u], i0 + u + HH_RING);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_lrcheck: per row: rebuild OpenCV's disp2 / disp2cost scatter (lowest cost wins, among equal costs the
 // LARGEST x, because the original sweeps x right-to-left with a strict '>') with one LDS atomicMin on the key
 // (cost+32768)<<16 | (w-1-x), then apply the two-sided disp12MaxDiff test.  Output covers all w columns.
@@ -2210,8 +2295,9 @@ __global__ void __launch_bounds__(64) k_streambench(const int *__restrict__ in, 
 
 int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, SgmGeom &g) {
     if (!p) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: params is NULL");
-    if (p->mode != R3D_SGBM_MODE_3WAY)
-        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: only mode=STEREO_SGBM_MODE_SGBM_3WAY (2) is implemented, got %d", p->mode);
+    if (p->mode != R3D_SGBM_MODE_3WAY && p->mode != R3D_SGBM_MODE_HH)
+        return r3d_fail(ctx, R3D_E_UNSUPPORTED,
+                        "sgbm: only mode=STEREO_SGBM_MODE_HH (1) and STEREO_SGBM_MODE_SGBM_3WAY (2) are implemented, got %d", p->mode);
     if (p->numDisparities <= 0 || p->numDisparities % 16 != 0)
         return r3d_fail(ctx, R3D_E_BADARG, "sgbm: numDisparities must be a positive multiple of 16, got %d", p->numDisparities);
     if (p->numDisparities > 256) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: numDisparities > 256 not supported (got %d)", p->numDisparities);
@@ -2428,7 +2514,79 @@ int launch_vscan3(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, float 
     }
 }
 
+// MODE_HH directions r = p - q in the order they enter S (pass 1, then pass 2), and their profiling names
+constexpr int HH_DIRS[8][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {-1, 0}, {1, -1}, {0, -1}, {-1, -1}};
+constexpr const char *HH_NAMES[8] = {"hh_right", "hh_down_right", "hh_down", "hh_down_left", "hh_left", "hh_up_right", "hh_up", "hh_up_left_wta"};
+
+// one k_hh_path launch: direction `r` of HH_DIRS; the first direction writes S, the last one selects from it.  LPC = DP / 8 lanes per
+// disparity vector (4 packed registers each), 64 / LPC lines per wave.
+template <int LPC, bool PADDED>
+void launch_hh_path_l(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins) {
+    const int dx = HH_DIRS[r][0], dy = HH_DIRS[r][1];
+    const int nlines = dy == 0 ? g.H : dx == 0 ? g.W1 : g.W1 + g.H - 1;
+    const dim3 grid((nlines + 64 / LPC - 1) / (64 / LPC));
+    if (r == 0) k_hh_path<4, LPC, PADDED, 0><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
+    else if (r == 7) k_hh_path<4, LPC, PADDED, 2><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
+    else k_hh_path<4, LPC, PADDED, 1><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
+}
+template <int LPC>
+void launch_hh_path_p(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins) {
+    if (g.D != g.DP) launch_hh_path_l<LPC, true>(st, g, r, cost, svol, inv_a, raw, mins);
+    else launch_hh_path_l<LPC, false>(st, g, r, cost, svol, inv_a, raw, mins);
+}
+void launch_hh_path(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins) {
+    switch (g.DP) {
+        case 32: launch_hh_path_p<4>(st, g, r, cost, svol, inv_a, raw, mins); break;
+        case 64: launch_hh_path_p<8>(st, g, r, cost, svol, inv_a, raw, mins); break;
+        case 128: launch_hh_path_p<16>(st, g, r, cost, svol, inv_a, raw, mins); break;
+        default: launch_hh_path_p<32>(st, g, r, cost, svol, inv_a, raw, mins); break;
+    }
+}
+
 }  // namespace
+
+// MODE_HH, the whole call after the argument checks of sgm_run_impl.  Geometry: ONE stripe over rows [0, h) (no warm-up rows,
+// no tiny-image quirk).  Workspace: the 3WAY's buffers only -- the cost volume, and ws.hsum (the 3WAY's L_left + L_right
+// volume, same shape) holds S; nothing grows beyond what a 3WAY call of the same size reserves.
+// MODE_SGBM (0) would be the same launches with five directions (pass 1 and the row-local right-to-left path).
+static int sgm_run_hh(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const r3d_sgbm_params *p, SgmGeom g, const uint8_t *d_left,
+                      const uint8_t *d_right, int w, int h, int stride, int16_t *d_disp) {
+    g.stripe_sz = h;
+    g.overlap = 0;   // the cost kernel's stripe-top blocks (stripes 1..3) then start at row h and own no row
+    const size_t npix = (size_t)w * h;
+    const size_t rowBytes = (size_t)g.W1 * g.DP * 2, volBytes = rowBytes * h;
+    int rc;
+    if ((rc = r3d_reserve(ctx, ws.rec_l, npix * 8)) || (rc = r3d_reserve(ctx, ws.rec_r, npix * 8)) ||
+        (rc = r3d_reserve(ctx, ws.cost, volBytes)) || (rc = r3d_reserve(ctx, ws.cspec, rowBytes * 3 * (g.SH2 > 0 ? g.SH2 : 1))) ||
+        (rc = r3d_reserve(ctx, ws.hsum, volBytes)) || (rc = r3d_reserve(ctx, ws.raw, npix * 2)) ||
+        (rc = r3d_reserve(ctx, ws.mins, npix * 2)) || (rc = r3d_reserve(ctx, ws.lrd, npix * 2)) || (rc = r3d_reserve(ctx, ws.flags, 256)))
+        return rc;
+    ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = g.DP; ctx->last_impl = 0;
+    r3d_prof_begin(ctx, ws);
+    r3d_prof_mark(ctx, ws, st, "prefilter");
+    k_prefilter<<<dim3((w + 255) / 256, (h + PF_ROWS - 1) / PF_ROWS, 2), 256, 0, st>>>(d_left, d_right, stride, w, h, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
+    R3D_HIP(ctx, hipGetLastError());
+    r3d_prof_mark(ctx, ws, st, "cost");
+    if ((rc = launch_cost2(ctx, ws, g, st, false))) return rc;   // also the envelope's tracked-maximum pass where it applies
+    const float inv_a = 1.0f / (float)(100 - g.uniq);
+    for (int r = 0; r < 8; r++) {
+        r3d_prof_mark(ctx, ws, st, HH_NAMES[r]);
+        launch_hh_path(st, g, r, (const int *)ws.cost.p, (int *)ws.hsum.p, inv_a, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p);
+        R3D_HIP(ctx, hipGetLastError());
+    }
+    r3d_prof_mark(ctx, ws, st, "lrcheck");
+    k_lrcheck<<<h, 256, (size_t)w * 4, st>>>((const int16_t *)ws.raw.p, (const int16_t *)ws.mins.p, g, (int16_t *)ws.lrd.p);
+    R3D_HIP(ctx, hipGetLastError());
+    r3d_prof_mark(ctx, ws, st, "median3");
+    k_median3<<<dim3((w + 255) / 256, h), 256, 0, st>>>((const int16_t *)ws.lrd.p, d_disp, w, h);
+    R3D_HIP(ctx, hipGetLastError());
+    if (p->speckleWindowSize > 0) {
+        r3d_prof_mark(ctx, ws, st, "speckles");
+        if ((rc = r3d_speckle_run(ctx, ws, st, d_disp, w, h, g.invalid, p->speckleWindowSize, 16 * p->speckleRange))) return rc;
+    }
+    r3d_prof_end(ctx, ws, st);
+    return R3D_OK;
+}
 
 int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int write, int delay, int reps, float *ms) {
     R3D_HIP(ctx, hipSetDevice(ctx->device));
@@ -2516,6 +2674,7 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = 0; ctx->last_dp = 0;
         return R3D_OK;
     }
+    if (p->mode == R3D_SGBM_MODE_HH) return sgm_run_hh(ctx, ws, st, p, g, d_left, d_right, w, h, stride, d_disp);
     // R3D_SGM_IMPL (read below as well): the v1 and v3 kernel generations only know 128 / 256 slots per column
     {
         const char *e = getenv("R3D_SGM_IMPL");

@@ -159,8 +159,9 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, device=0):
 
 def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0, preFilterCap=0,
                       uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=STEREO_SGBM_MODE_SGBM, device=0):
-    """Factory with cv2.StereoSGBM_create's keyword names and defaults.  Only MODE_SGBM_3WAY is implemented (the
-    mode every reference call site passes); other modes raise at compute()."""
+    """Factory with cv2.StereoSGBM_create's keyword names and defaults.  MODE_SGBM_3WAY (the mode every reference call
+    site passes) and MODE_HH (eight full-image paths, no stripes) are implemented; MODE_SGBM and MODE_HH4 raise at
+    compute()."""
     return StereoSGBM(minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio,
                       speckleWindowSize, speckleRange, mode, device)
 

@@ -74,7 +74,9 @@ int r3d_event_elapsed_ms(r3d_ctx *ctx, void *start, void *stop, float *out_ms); 
  *   Calib_depth/depth1.py:202-214,331  depth2.py:146-158,251  depth3.py:234-246,339
  *   Calib_depth/depth4.py:156-168,254  depth_test.py:162-174,260
  * Field names and meaning equal the StereoSGBM_create keyword arguments the reference passes.
- * Only mode == R3D_SGBM_MODE_3WAY (cv2.STEREO_SGBM_MODE_SGBM_3WAY == 2) is implemented. */
+ * mode: R3D_SGBM_MODE_3WAY (cv2.STEREO_SGBM_MODE_SGBM_3WAY == 2) or R3D_SGBM_MODE_HH (cv2.STEREO_SGBM_MODE_HH == 1: eight
+ * full-image paths, no stripes); MODE_SGBM (0) and MODE_HH4 (3) are refused with R3D_E_UNSUPPORTED. */
+#define R3D_SGBM_MODE_HH 1
 #define R3D_SGBM_MODE_3WAY 2
 typedef struct {
     int32_t minDisparity;

@@ -1,6 +1,7 @@
-"""One-off wide fuzz of the HIP SGBM against the C oracle (bit-exact): random sizes, disparity counts, block sizes,
-penalties, uniqueness / LR / speckle / prefilter settings, images with texture, shifts, noise and flat areas.
-Usage (GPU box): python tools/gpu_fuzz_sgbm.py [cases] [seed]"""
+"""One-off wide fuzz of the HIP SGBM (bit-exact): random sizes, disparity counts, block sizes, penalties, uniqueness / LR /
+speckle / prefilter settings, images with texture, shifts, noise and flat areas.  mode 2 (3WAY, default) is compared with the C
+oracle, mode 1 (MODE_HH) with the numpy restatement tests/sgbm_hh_ref.py.
+Usage (GPU box): python tools/gpu_fuzz_sgbm.py [cases] [seed] [mode]"""
 import importlib, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,6 +10,9 @@ from oracle import sgbm_oracle as so
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
+mode = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+if mode == 1:
+    from tests import sgbm_hh_ref as hh
 bad = 0
 t0 = time.time()
 for case in range(cases):
@@ -34,14 +38,14 @@ for case in range(cases):
     else:
         v = int(rng.integers(0, 256)); L = np.full((H, W), v, np.uint8); R = np.full((H, W), int(rng.integers(0, 256)), np.uint8)
     try:
-        got = r3d.StereoSGBM_create(numDisparities=D, mode=2, **kw).compute(L, R)
+        got = r3d.StereoSGBM_create(numDisparities=D, mode=mode, **kw).compute(L, R)
     except r3d.R3DError as e:
         print("case", case, "raised", e, W, H, D, kw, flush=True)
         continue
-    want = so.compute(L, R, so.make_params(numDisparities=D, **kw), nthreads=8)
+    want = hh.compute(L, R, numDisparities=D, **kw) if mode == 1 else so.compute(L, R, so.make_params(numDisparities=D, **kw), nthreads=8)
     if not np.array_equal(got, want):
         bad += 1
         print(f"MISMATCH case {case}: W={W} H={H} D={D} kind={kind} {kw}: {(got != want).sum()} pixels", flush=True)
     if case % 50 == 49:
         print(f"{case + 1} cases, {bad} mismatches, {time.time() - t0:.0f}s", flush=True)
-print("DONE", cases, "cases", bad, "mismatches")
+print("DONE", cases, "cases", bad, "mismatches", "mode", mode)
