@@ -966,37 +966,57 @@ __global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int
         sgm_step_g<NPL, LPC, PADDED>(R, minr, c, P1pk, g.P2, first, last, valid);
         store_sum(hrow + (size_t)x * DPW, l, R);
     }
-    // round(s): A = costs of segment s (backward), B = costs of segment s-1 (forward), pre <- segment s-3
-    auto bwd_round = [&](int (&A)[K][NPL], int (&B)[K][NPL], int (&pre)[K][NPL], int sidx) {
+    // The checkpoint a round starts from is requested one round EARLY (ckn / ckm): the memory queue retires in order, so a
+    // checkpoint loaded where it is used waits for every load and store issued before it -- the round's own prefetch and
+    // the previous round's 16 sum stores -- and with one wave per SIMD nothing hides that drain.
+    int ckn[NPL], ckm = 0;
+    auto fetch_ck = [&](int sidx) {
+        const int sc = max(sidx, 0);
+#pragma unroll
+        for (int j = 0; j < NPL; j++) ckn[j] = ck[(size_t)sc * CKS + j];
+        ckm = ckrow[(size_t)sc * CKS + DPW];
+    };
+    // round(s): A = costs of segment s (backward), B = costs of segment s-1 (forward), pre <- segment s-3;
+    // LA = L_left of segment s (left by the round before), LB <- L_left of segment s-1.
+    // SWAP: the rounds alternate the roles of llA and llB instead of copying llB into llA after every round (4 moves per
+    // column).  Only where the six buffers overflow the 256 VGPRs anyway (DP = 128, K = 16: one wave per SIMD either way): in
+    // the smaller layouts the copy lets the two buffers share registers, and the swap costs them their second wave per SIMD.
+    constexpr bool SWAP = 6 * K * NPL > 256;
+    auto bwd_round = [&](int (&A)[K][NPL], int (&B)[K][NPL], int (&pre)[K][NPL], int (&LA)[K][NPL], int (&LB)[K][NPL], int sidx) {
+#pragma unroll
+        for (int j = 0; j < NPL; j++) P[j] = ckn[j];           // the state entering segment s-1
+        minp = ckm;
+        fetch_ck(sidx - 2);
         load_seg(pre, sidx - 3);
         int *hp = hrow + (size_t)sidx * K * DPW;
         if (sidx > 0) {
-            load_ck(sidx - 1);
             int mAB = (minr & 0xffff) | (minp << 16);
 #pragma unroll
             for (int u = 0; u < K; u++) {
                 sgm_step_dual_g<NPL, LPC, PADDED>(R, P, mAB, A[K - 1 - u], B[u], P1pk, P2pk, first, last, valid);
-                store_sum(hp + (size_t)(K - 1 - u) * DPW, llA[K - 1 - u], R);
+                store_sum(hp + (size_t)(K - 1 - u) * DPW, LA[K - 1 - u], R);
 #pragma unroll
-                for (int j = 0; j < NPL; j++) llB[u][j] = P[j];
+                for (int j = 0; j < NPL; j++) LB[u][j] = P[j];
             }
             minr = lo16(mAB);
-            minp = hi16(mAB);
         } else {
 #pragma unroll
             for (int u = 0; u < K; u++) {
                 sgm_step_g<NPL, LPC, PADDED>(R, minr, A[K - 1 - u], P1pk, g.P2, first, last, valid);
-                store_sum(hp + (size_t)(K - 1 - u) * DPW, llA[K - 1 - u], R);
+                store_sum(hp + (size_t)(K - 1 - u) * DPW, LA[K - 1 - u], R);
             }
         }
+        if (!SWAP) {
 #pragma unroll
-        for (int u = 0; u < K; u++)
+            for (int u = 0; u < K; u++)
 #pragma unroll
-            for (int j = 0; j < NPL; j++) llA[u][j] = llB[u][j];
+                for (int j = 0; j < NPL; j++) LA[u][j] = LB[u][j];
+        }
     };
     if (nfull > 0) {
         load_seg(c0, nfull - 1); load_seg(c1, nfull - 2); load_seg(c2, nfull - 3);
         load_ck(nfull - 1);
+        fetch_ck(nfull - 2);
 #pragma unroll
         for (int u = 0; u < K; u++) {
             sgm_step_g<NPL, LPC, PADDED>(P, minp, c0[u], P1pk, g.P2, first, last, valid);
@@ -1005,10 +1025,10 @@ __global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int
         }
 #pragma unroll 1
         for (int s = nfull - 1; s >= 0; s -= 4) {
-            bwd_round(c0, c1, c3, s);
-            if (s - 1 >= 0) bwd_round(c1, c2, c0, s - 1);
-            if (s - 2 >= 0) bwd_round(c2, c3, c1, s - 2);
-            if (s - 3 >= 0) bwd_round(c3, c0, c2, s - 3);
+            bwd_round(c0, c1, c3, llA, llB, s);
+            if (s - 1 >= 0) bwd_round(c1, c2, c0, SWAP ? llB : llA, SWAP ? llA : llB, s - 1);
+            if (s - 2 >= 0) bwd_round(c2, c3, c1, llA, llB, s - 2);
+            if (s - 3 >= 0) bwd_round(c3, c0, c2, SWAP ? llB : llA, SWAP ? llA : llB, s - 3);
         }
     }
 }
