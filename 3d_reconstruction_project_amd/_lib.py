@@ -87,6 +87,7 @@ _SIGS = {
     "r3d_set_profiling": ([_vp, ctypes.c_int], ctypes.c_int),
     "r3d_sgbm_profile": ([_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32], ctypes.c_int),
     "r3d_sgbm_debug_fetch": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "r3d_sgbm_debug_hh_partial": ([_vp, ctypes.c_int32, _vp], ctypes.c_int),
 }
 
 

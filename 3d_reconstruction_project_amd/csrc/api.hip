@@ -368,4 +368,20 @@ int r3d_sgbm_debug_fetch(r3d_ctx *ctx, int16_t *cost, int16_t *hsum, int16_t *ra
     return R3D_OK;
 }
 
+int r3d_sgbm_debug_hh_partial(r3d_ctx *ctx, int32_t n_dirs, int16_t *S_out) {
+    R3D_ROCTX_RANGE("r3d_sgbm_debug_hh_partial");
+    if (!ctx) return R3D_E_BADARG;
+    if (ctx->last_w == 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_hh_partial: no sgbm call yet");
+    if (ctx->last_mode != R3D_SGBM_MODE_HH) return r3d_fail(ctx, R3D_E_BADARG, "debug_hh_partial: the last call was not MODE_HH (mode %d)", ctx->last_mode);
+    if (ctx->last_w1 <= 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_hh_partial: the last call had an empty matching range (all-invalid map), no volumes exist");
+    if (n_dirs < 1 || n_dirs > 8) return r3d_fail(ctx, R3D_E_BADARG, "debug_hh_partial: n_dirs must be in 1..8, got %d", n_dirs);
+    if (!S_out) return r3d_fail(ctx, R3D_E_BADARG, "debug_hh_partial: S_out is NULL");
+    if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "context poisoned by an earlier timed-out call: destroy it");
+    if (int rc = r3d_sgm_hh_partial(ctx, n_dirs)) return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t vol = (size_t)ctx->last_h * ctx->last_w1 * ctx->last_dp * 2;
+    R3D_HIP(ctx, hipMemcpy(S_out, ctx->ws[0].hsum.p, vol, hipMemcpyDeviceToHost));
+    return R3D_OK;
+}
+
 }  // extern "C"

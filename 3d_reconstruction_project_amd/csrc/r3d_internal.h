@@ -45,6 +45,13 @@ struct r3d_sgm_ws {
     bool ev_created = false;
 };
 
+// derived parameters of one sgbm call (sgm.hip: derive_geom), passed to every SGM kernel by value
+struct SgmGeom {
+    int W, H, minD, D, NP, minX1, maxX1, W1, SW2, SH2, P1, P2, uniq, d12, ftzero, stripe_sz, overlap, invalid;
+    int DP;  // disparity slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 that holds D (v2 kernels; v1 and v3
+             // only know 128 / 256 = NP * 128)
+};
+
 struct r3d_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -61,6 +68,8 @@ struct r3d_ctx {
     hipEvent_t fork_ev = nullptr;
     // geometry of the last sgbm call (for debug fetch)
     int last_w = 0, last_h = 0, last_w1 = 0, last_dp = 0, last_impl = 0;
+    int last_mode = -1;        // r3d_sgbm_params.mode of that call
+    SgmGeom last_geom = {};    // as its kernels saw it (MODE_HH: one stripe); r3d_sgbm_debug_hh_partial launches from it
     // profiling sums accumulate per kernel name over all lanes
     const char *acc_name[R3D_MAX_PROF] = {};
     double acc_ms[R3D_MAX_PROF] = {};
@@ -137,6 +146,7 @@ struct r3d_roctx_scope {
 // sgm.hip
 int r3d_sgm_run(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
                 int w, int h, int stride, int16_t *d_disp);
+int r3d_sgm_hh_partial(r3d_ctx *ctx, int n_dirs);
 int r3d_selftest_run(r3d_ctx *ctx);
 int r3d_speckle_run(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, int16_t *d_img, int w, int h, int newVal, int maxSize, int maxDiff);
 int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int write, int delay, int reps, float *ms);

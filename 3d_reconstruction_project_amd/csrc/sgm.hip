@@ -31,12 +31,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 #ifndef R3D_COST_STAGE
 #define R3D_COST_STAGE 1   /* where k_cost2 stages the next input row: 1 right after the barrier (default: 0.67 -> 0.64 ms), 2 between the box sum and its stores (0.65) */
 #endif
-struct SgmGeom {
-    int W, H, minD, D, NP, minX1, maxX1, W1, SW2, SH2, P1, P2, uniq, d12, ftzero, stripe_sz, overlap, invalid;
-    int DP;  // disparity slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 that holds D (v2 kernels; v1 and v3
-             // only know 128 / 256 = NP * 128)
-};
-
 constexpr int PADPK = 0x7fff7fff;  // SHRT_MAX in both halves: the d=-1 / d=D padding of every path buffer
 
 __device__ __forceinline__ s16x2 as_s(int v) { return __builtin_bit_cast(s16x2, v); }
@@ -2538,28 +2532,29 @@ int launch_vscan3(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, float 
 constexpr int HH_DIRS[8][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {-1, 0}, {1, -1}, {0, -1}, {-1, -1}};
 constexpr const char *HH_NAMES[8] = {"hh_right", "hh_down_right", "hh_down", "hh_down_left", "hh_left", "hh_up_right", "hh_up", "hh_up_left_wta"};
 
-// one k_hh_path launch: direction `r` of HH_DIRS; the first direction writes S, the last one selects from it.  LPC = DP / 8 lanes per
-// disparity vector (4 packed registers each), 64 / LPC lines per wave.
+// one k_hh_path launch: direction `r` of HH_DIRS; the first direction writes S, the last one selects from it (store_last: it
+// stores S like the six before it and touches neither raw nor mins -- r3d_sgm_hh_partial).  LPC = DP / 8 lanes per disparity
+// vector (4 packed registers each), 64 / LPC lines per wave.
 template <int LPC, bool PADDED>
-void launch_hh_path_l(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins) {
+void launch_hh_path_l(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins, bool store_last) {
     const int dx = HH_DIRS[r][0], dy = HH_DIRS[r][1];
     const int nlines = dy == 0 ? g.H : dx == 0 ? g.W1 : g.W1 + g.H - 1;
     const dim3 grid((nlines + 64 / LPC - 1) / (64 / LPC));
     if (r == 0) k_hh_path<4, LPC, PADDED, 0><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
-    else if (r == 7) k_hh_path<4, LPC, PADDED, 2><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
+    else if (r == 7 && !store_last) k_hh_path<4, LPC, PADDED, 2><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
     else k_hh_path<4, LPC, PADDED, 1><<<grid, 64, 0, st>>>(cost, svol, g, dx, dy, inv_a, raw, mins);
 }
 template <int LPC>
-void launch_hh_path_p(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins) {
-    if (g.D != g.DP) launch_hh_path_l<LPC, true>(st, g, r, cost, svol, inv_a, raw, mins);
-    else launch_hh_path_l<LPC, false>(st, g, r, cost, svol, inv_a, raw, mins);
+void launch_hh_path_p(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins, bool store_last) {
+    if (g.D != g.DP) launch_hh_path_l<LPC, true>(st, g, r, cost, svol, inv_a, raw, mins, store_last);
+    else launch_hh_path_l<LPC, false>(st, g, r, cost, svol, inv_a, raw, mins, store_last);
 }
-void launch_hh_path(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins) {
+void launch_hh_path(hipStream_t st, const SgmGeom &g, int r, const int *cost, int *svol, float inv_a, int16_t *raw, int16_t *mins, bool store_last = false) {
     switch (g.DP) {
-        case 32: launch_hh_path_p<4>(st, g, r, cost, svol, inv_a, raw, mins); break;
-        case 64: launch_hh_path_p<8>(st, g, r, cost, svol, inv_a, raw, mins); break;
-        case 128: launch_hh_path_p<16>(st, g, r, cost, svol, inv_a, raw, mins); break;
-        default: launch_hh_path_p<32>(st, g, r, cost, svol, inv_a, raw, mins); break;
+        case 32: launch_hh_path_p<4>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
+        case 64: launch_hh_path_p<8>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
+        case 128: launch_hh_path_p<16>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
+        default: launch_hh_path_p<32>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
     }
 }
 
@@ -2582,6 +2577,7 @@ static int sgm_run_hh(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const r3d_sg
         (rc = r3d_reserve(ctx, ws.mins, npix * 2)) || (rc = r3d_reserve(ctx, ws.lrd, npix * 2)) || (rc = r3d_reserve(ctx, ws.flags, 256)))
         return rc;
     ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = g.DP; ctx->last_impl = 0;
+    ctx->last_mode = p->mode; ctx->last_geom = g;
     r3d_prof_begin(ctx, ws);
     r3d_prof_mark(ctx, ws, st, "prefilter");
     k_prefilter<<<dim3((w + 255) / 256, (h + PF_ROWS - 1) / PF_ROWS, 2), 256, 0, st>>>(d_left, d_right, stride, w, h, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
@@ -2605,6 +2601,21 @@ static int sgm_run_hh(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const r3d_sg
         if ((rc = r3d_speckle_run(ctx, ws, st, d_disp, w, h, g.invalid, p->speckleWindowSize, 16 * p->speckleRange))) return rc;
     }
     r3d_prof_end(ctx, ws, st);
+    return R3D_OK;
+}
+
+// debug / stage parity (r3d_sgbm_debug_hh_partial): directions 0 .. n_dirs-1 again over the cost volume the last MODE_HH call left in
+// lane 0's workspace, with the launches of sgm_run_hh (same geometry, grid and direction table), every direction storing: ws.hsum
+// then holds S after n_dirs directions.  raw, mins and lrd are not written.  The caller has checked the arguments.
+int r3d_sgm_hh_partial(r3d_ctx *ctx, int n_dirs) {
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    r3d_sgm_ws &ws = ctx->ws[0];
+    const SgmGeom &g = ctx->last_geom;
+    const float inv_a = 1.0f / (float)(100 - g.uniq);
+    for (int r = 0; r < n_dirs; r++) {
+        launch_hh_path(ctx->stream, g, r, (const int *)ws.cost.p, (int *)ws.hsum.p, inv_a, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p, true);
+        R3D_HIP(ctx, hipGetLastError());
+    }
     return R3D_OK;
 }
 
@@ -2692,6 +2703,7 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         k_fill_s16<<<(unsigned)std::min<size_t>((np + 255) / 256, 4096), 256, 0, st>>>(d_disp, np, (int16_t)((g.minD - 1) * 16));
         R3D_HIP(ctx, hipGetLastError());
         ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = 0; ctx->last_dp = 0;
+        ctx->last_mode = p->mode; ctx->last_geom = g;
         return R3D_OK;
     }
     if (p->mode == R3D_SGBM_MODE_HH) return sgm_run_hh(ctx, ws, st, p, g, d_left, d_right, w, h, stride, d_disp);
@@ -2718,6 +2730,7 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
     if (pass == 1) g.stripe_sz = h;                    // one stripe: rows [0, h) from row 0 (the other three own no row)
     if ((tiny || pass == 1) && (rc = r3d_reserve(ctx, ws.lrd2, npix * 2))) return rc;
     ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = NPW * 2;
+    ctx->last_mode = p->mode; ctx->last_geom = g;
     if ((rc = r3d_reserve(ctx, ws.flags, 256))) return rc;
     r3d_prof_begin(ctx, ws);
 

@@ -147,6 +147,19 @@ class StereoSGBM:
             out["raw"] = raw
         return out
 
+    def debug_hh_partial(self, n):
+        """MODE_HH stage parity: S after the first n directions (1..8, contract order) of the last compute, int16 [H, W1, D].
+        The library runs those directions again over the cost volume of that compute; afterwards debug_fetch's hsum is this
+        volume, its cost and raw are unchanged."""
+        D = self._p["numDisparities"]
+        minD = self._p["minDisparity"]
+        H, W = self._last_shape
+        W1 = max((W + min(minD, 0)) - max(minD + D, 0), 0)
+        dp = next((c for c in (32, 64, 128, 256) if D <= c), 256)
+        S = np.empty((H, W1, dp), np.int16)
+        self.context.call("r3d_sgbm_debug_hh_partial", int(n), S.ctypes.data_as(ctypes.c_void_p))
+        return S[:, :, :D]
+
 
 def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, device=0):
     """cv2.filterSpeckles on an int16 image; returns the filtered copy."""

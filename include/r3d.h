@@ -122,10 +122,20 @@ int r3d_set_profiling(r3d_ctx *ctx, int enabled);
 int r3d_sgbm_profile(r3d_ctx *ctx, float *ms, int32_t max_slots, char *names, int32_t names_bytes);
 
 /* debug / stage parity: copies intermediate results of the LAST sgbm call to HOST buffers (NULL = skip).
- *   cost   int16 [h][w1][dp]  aggregated block cost C (dp = 128 if D<=128 else 256; entries d>=D undefined)
- *   hsum   int16 [h][w1][dp]  L_left + L_right
+ *   cost   int16 [h][w1][dp]  aggregated block cost C (dp = the smallest of 32 / 64 / 128 / 256 that holds D, of 128 / 256
+ *                             under R3D_SGM_IMPL=v1 / v3; entries d>=D undefined)
+ *   hsum   int16 [h][w1][dp]  MODE_SGBM_3WAY: L_left + L_right; MODE_HH: S after the first seven directions (the eighth is fused
+ *                             with the selection and never stored)
  *   raw    int16 [h][w]       disparity after the row LR check, before the 3x3 median */
 int r3d_sgbm_debug_fetch(r3d_ctx *ctx, int16_t *cost, int16_t *hsum, int16_t *raw);
+
+/* debug / stage parity, MODE_HH only: S after the first n_dirs directions (1..8, contract order) of the LAST
+ * r3d_sgbm_compute* call on this context, int16 [h][w1][dp] to a HOST buffer (layout as r3d_sgbm_debug_fetch).
+ * Runs those directions again over the cost volume that call left behind, with the same launches as the call itself except
+ * that every direction stores S (the eighth too), then synchronises and copies.  Overwrites what r3d_sgbm_debug_fetch returns
+ * as hsum; cost and raw stay valid.  R3D_E_BADARG: no call yet, the last call was not MODE_HH or had an empty matching range,
+ * n_dirs outside 1..8, S_out NULL. */
+int r3d_sgbm_debug_hh_partial(r3d_ctx *ctx, int32_t n_dirs, int16_t *S_out);
 
 /* ---- point clouds (float64 xyz triplets, like the legacy open3d.geometry.PointCloud the reference passes) ----- */
 

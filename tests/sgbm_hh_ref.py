@@ -113,6 +113,25 @@ def aggregate(C, P1, P2, sum_order=None):
     return S
 
 
+def direction_volume(C, r, P1, P2):
+    """L_r (int32 [H, W1, D]) of the one direction r: _direction with a fold that stores."""
+    Lr = np.zeros(C.shape, np.int32)
+
+    def fold(i, L):
+        Lr[i] = L
+    _direction(C, r, P1, P2, fold)
+    return Lr
+
+
+def partial_sums(C, P1, P2):
+    """[S_1 .. S_8] (int16 [H, W1, D] each): S after the first n directions, "simd" order (one saturating add per direction)."""
+    out, S = [], np.zeros(C.shape, np.int32)
+    for r in DIRECTIONS:
+        S = _sat16(S + direction_volume(C, r, P1, P2))
+        out.append(S.astype(np.int16))
+    return out
+
+
 def _trunc_div(n, d):
     q = np.abs(n) // d
     return np.where(n >= 0, q, -q)

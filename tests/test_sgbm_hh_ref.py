@@ -15,8 +15,11 @@ def _kw(D, bs, minD=0, uniq=15, **extra):
                      disp12MaxDiff=1, uniquenessRatio=uniq, preFilterCap=63), **extra)
 
 
-@pytest.mark.parametrize("W,H,D,minD,bs,uniq,seed", [(60, 14, 16, 0, 3, 10, 3), (50, 9, 32, -5, 5, 0, 4), (45, 11, 16, 3, 7, 15, 5),
-                                                     (40, 3, 16, 0, 1, 5, 6), (70, 7, 48, -47, 5, 0, 7), (36, 12, 16, 0, 11, 15, 8)])
+CASES = [(60, 14, 16, 0, 3, 10, 3), (50, 9, 32, -5, 5, 0, 4), (45, 11, 16, 3, 7, 15, 5),
+         (40, 3, 16, 0, 1, 5, 6), (70, 7, 48, -47, 5, 0, 7), (36, 12, 16, 0, 11, 15, 8)]
+
+
+@pytest.mark.parametrize("W,H,D,minD,bs,uniq,seed", CASES)
 @pytest.mark.parametrize("order", hh.SUM_ORDERS)
 def test_vectorised_and_literal_restatements_agree(W, H, D, minD, bs, uniq, seed, order):
     L, R, _ = synth.stereo_pair(W, H, D, seed=seed)
@@ -70,3 +73,33 @@ def test_empty_matching_range_is_all_invalid():
     L = np.zeros((5, 40), np.uint8)
     kw = _kw(48, 3, minD=0)
     assert (hh.compute(L, L, **kw) == -16).all() and (hh.compute_literal(L, L, **kw) == -16).all()
+
+
+@pytest.mark.parametrize("W,H,D,minD,bs,uniq,seed", CASES + [(120, 40, 32, 0, 9, 15, 0)])
+def test_last_partial_sum_is_the_aggregate(W, H, D, minD, bs, uniq, seed):
+    """partial_sums keeps every stage of the fold aggregate runs; the last case saturates at both rails."""
+    L, R, _ = synth.stereo_pair(W, H, D, seed=seed)
+    kw = _kw(D, bs, minD, uniq)
+    g = hh.derive(W, **kw)
+    C = hh.block_cost(L, R, kw)
+    Sn = hh.partial_sums(C, g["P1"], g["P2"])
+    assert len(Sn) == 8 and all(S.dtype == np.int16 and S.shape == C.shape for S in Sn)
+    np.testing.assert_array_equal(Sn[-1], hh.aggregate(C, g["P1"], g["P2"], "simd"))
+    np.testing.assert_array_equal(Sn[0], hh.direction_volume(C, hh.DIRECTIONS[0], g["P1"], g["P2"]))
+    if bs == 9:
+        assert (Sn[-1] == hh.SHRT_MIN).any() and (Sn[-1] == hh.SHRT_MAX).any()
+
+
+@pytest.mark.parametrize("r", hh.DIRECTIONS)
+def test_direction_volume_commutes_with_point_reflection(r):
+    """Turning the volume by 180 degrees turns direction r into -r: a property of the recurrence that does not depend on
+    how _direction enumerates the lines (rows for dy = 0, shifted rows otherwise)."""
+    D = 32
+    L, R, _ = synth.stereo_pair(70, 23, D, seed=2)
+    kw = _kw(D, 5)
+    g = hh.derive(70, **kw)
+    C = hh.block_cost(L, R, kw)
+    a = hh.direction_volume(C, r, g["P1"], g["P2"])
+    b = hh.direction_volume(np.ascontiguousarray(C[::-1, ::-1]), (-r[0], -r[1]), g["P1"], g["P2"])[::-1, ::-1]
+    assert a.dtype == np.int32 and a.shape == C.shape and a.any()
+    np.testing.assert_array_equal(a, b)
