@@ -4,7 +4,7 @@
 // and the other depth*.py files); the arithmetic restated here is OpenCV's stereosgbm.cpp as pinned down in
 // oracle/sgbm3way.c (every QUIRK listed there is reproduced bit for bit).
 //
-// Data layout in HBM (all int16 unless noted; "dp" = 128 for D<=128, 256 otherwise; w1 = maxX1-minX1):
+// Data layout in HBM (all int16 unless noted; "dp" = the smallest of 32 / 64 / 128 / 256 / 512 slots that holds D; w1 = maxX1-minX1):
 //   rec_l/rec_r  uint2 [h][w]       per pixel: (g, g_lo, g_hi, i | i_lo, i_hi, 0, 0): prefiltered gradient, raw
 //                                   intensity and their Birchfield-Tomasi half-pixel intervals
 //   cost         [h][w1][dp]        aggregated block cost C (blockSize x blockSize box of the BT pixel cost)
@@ -480,7 +480,12 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
     // pair words: 6 dwords per right pixel, plus 8 dwords of padding after every 16 pixels: lanes of one column group
     // read records 16 apart (16*6 dwords = 32 mod 64 banks -> 4-way conflicts); with the pad the eight chunks land on
     // eight different multiples of 8 banks and the four column groups of a half-wave fill the gaps: conflict-free.
-    constexpr int SWN = NRR * 6 + (NRR / 16 + 1) * 8;
+    // LPC = 32 (DP = 512): a half-wave (the 32 lanes one ds_read_b64 cycle serves) is ONE column group of 32 chunks, and a chunk
+    // stride of 16*6 + 8 = 104 = 40 mod 64 banks only has 8 distinct positions (4-way conflicts).  A pad of 2 dwords makes the
+    // stride 98 = 2 * 49: chunk c starts at bank pair 49*c mod 32, a permutation of the 32 pairs, so the 32 8-byte reads of a
+    // half-wave cover the 64 banks exactly once (and every record stays 8-byte aligned).  By construction, not measured.
+    constexpr int PAD = LPC == 32 ? 2 : 8;
+    constexpr int SWN = NRR * 6 + (NRR / 16 + 1) * PAD;
     __shared__ int sW[2][SWN];            // right-image pair words of one row, double buffered
     __shared__ uint2 sL[2][TC];           // left records of one row
     __shared__ int sV[2][TC * DPW];       // vertical box sums of the tile, double buffered
@@ -521,25 +526,38 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
 
     // (a) staging of an image row: the raw records are fetched one iteration EARLY into registers (fetch), and turned
     // into LDS pair words one iteration later (commit), so the global-load latency is never waited for inside a row
-    static_assert(NRR <= NT, "one pair-word record per thread");
-    uint2 pfL = make_uint2(0, 0), pfA = make_uint2(0, 0), pfB = make_uint2(0, 0);
+    // One pair-word record per thread and pass: NREC = 1 up to DP = 256; DP = 512 has NRR = 16 + 512 = 528 records for its 512
+    // threads, so the last 16 go through a second pass of the first 16 threads (two more uint2 in flight per thread).
+    constexpr int NREC = (NRR + NT - 1) / NT;
+    static_assert(NRR <= NREC * NT && NREC <= 2, "pair-word records per thread");
+    uint2 pfL = make_uint2(0, 0), pfA[NREC], pfB[NREC];
+#pragma unroll
+    for (int q = 0; q < NREC; q++) pfA[q] = pfB[q] = make_uint2(0, 0);
     auto fetch = [&](int row) {
         const uint2 *lr = recL + (size_t)row * g.W, *rr = recR + (size_t)row * g.W;
         if (tid < TC) pfL = lr[min(max(t0 - SH2 + tid, 0), g.W1 - 1) + g.minX1];
-        if (tid < NRR) {
-            const int r = r_base + tid;
-            pfA = rr[min(max(r, 0), g.W - 1)];
-            pfB = rr[min(max(r - 1, 0), g.W - 1)];
+#pragma unroll
+        for (int q = 0; q < NREC; q++) {
+            const int i = tid + q * NT;
+            if (i < NRR) {
+                const int r = r_base + i;
+                pfA[q] = rr[min(max(r, 0), g.W - 1)];
+                pfB[q] = rr[min(max(r - 1, 0), g.W - 1)];
+            }
         }
     };
     auto commit = [&](int b) {
         if (tid < TC) sL[b][tid] = pfL;
-        if (tid < NRR) {
-            const uint2 A = pfA, B = pfB;
-            int *o = &sW[b][tid * 6 + (tid >> 4) * 8];
-            o[0] = __builtin_amdgcn_perm(B.x, A.x, 0x0c040c00); o[1] = __builtin_amdgcn_perm(B.x, A.x, 0x0c050c01);
-            o[2] = __builtin_amdgcn_perm(B.x, A.x, 0x0c060c02); o[3] = __builtin_amdgcn_perm(B.x, A.x, 0x0c070c03);
-            o[4] = __builtin_amdgcn_perm(B.y, A.y, 0x0c040c00); o[5] = __builtin_amdgcn_perm(B.y, A.y, 0x0c050c01);
+#pragma unroll
+        for (int q = 0; q < NREC; q++) {
+            const int i = tid + q * NT;
+            if (i < NRR) {
+                const uint2 A = pfA[q], B = pfB[q];
+                int *o = &sW[b][i * 6 + (i >> 4) * PAD];
+                o[0] = __builtin_amdgcn_perm(B.x, A.x, 0x0c040c00); o[1] = __builtin_amdgcn_perm(B.x, A.x, 0x0c050c01);
+                o[2] = __builtin_amdgcn_perm(B.x, A.x, 0x0c060c02); o[3] = __builtin_amdgcn_perm(B.x, A.x, 0x0c070c03);
+                o[4] = __builtin_amdgcn_perm(B.y, A.y, 0x0c040c00); o[5] = __builtin_amdgcn_perm(B.y, A.y, 0x0c050c01);
+            }
         }
     };
     // (b) BT pixel cost of this lane's 16 disparities from buffer b
@@ -556,7 +574,7 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
             // (2-way) and the pair costs 16 LDS cycles instead of 4 -- the 31 % bank conflicts of the round-2/3 counters.
             typedef int v2i __attribute__((ext_vector_type(2)));
             typedef const volatile __attribute__((address_space(3))) v2i lds_v2i;   // (a plain volatile pointer would read through flat_load)
-            lds_v2i *p = (lds_v2i *)&sW[b][rj * 6 + (rj >> 4) * 8];
+            lds_v2i *p = (lds_v2i *)&sW[b][rj * 6 + (rj >> 4) * PAD];
             const v2i a = p[0], bq = p[1], c = p[2];       // (Vg, Vg0) (Vg1, Vi) (Vi0, Vi1)
             const int cg = bt_cost_pk(Ug, Ug0, Ug1, a.x, a.y, bq.x);
             const int ci = bt_cost_pk(Ui, Ui0, Ui1, bq.y, c.x, c.y);
@@ -2314,14 +2332,16 @@ int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, SgmGeom &g
                         "sgbm: only mode=STEREO_SGBM_MODE_HH (1) and STEREO_SGBM_MODE_SGBM_3WAY (2) are implemented, got %d", p->mode);
     if (p->numDisparities <= 0 || p->numDisparities % 16 != 0)
         return r3d_fail(ctx, R3D_E_BADARG, "sgbm: numDisparities must be a positive multiple of 16, got %d", p->numDisparities);
-    if (p->numDisparities > 256) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: numDisparities > 256 not supported (got %d)", p->numDisparities);
+    if (p->numDisparities > 512) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: numDisparities > 512 not supported (got %d)", p->numDisparities);
     if (p->blockSize < 1 || p->blockSize % 2 == 0 || p->blockSize > 11)
         return r3d_fail(ctx, R3D_E_BADARG, "sgbm: blockSize must be odd in [1, 11], got %d", p->blockSize);
     if (w <= 0 || h <= 0 || w > 65536) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: bad image size %dx%d", w, h);
     g.W = w; g.H = h;
     g.minD = p->minDisparity; g.D = p->numDisparities;
+    // NP: 128-slot units of the v1 / v3 layouts (1 or 2).  Those generations stop at D = 256 (sgm_run_impl refuses them above it), and
+    // the v2 launchers choose their D > 256 instantiations by DP, so NP stays 2 there and is never read as a size.
     g.NP = g.D <= 128 ? 1 : 2;
-    g.DP = g.D <= 32 ? 32 : g.D <= 64 ? 64 : g.D <= 128 ? 128 : 256;
+    g.DP = g.D <= 32 ? 32 : g.D <= 64 ? 64 : g.D <= 128 ? 128 : g.D <= 256 ? 256 : 512;
     const int maxD = g.minD + g.D;
     g.minX1 = maxD > 0 ? maxD : 0;
     g.maxX1 = w + (g.minD < 0 ? g.minD : 0);
@@ -2338,6 +2358,9 @@ int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, SgmGeom &g
     g.stripe_sz = (h + 3) / 4;
     g.overlap = (p->blockSize / 2 + 1) + (g.stripe_sz + 9) / 10;
     g.invalid = (g.minD - 1) * 16;
+    // Volume addressing (a DP = 512 volume passes 4 GiB at 8 MP): every row, column-segment and line offset into cost / cspec /
+    // hsum / ckpt is formed in size_t or long in every kernel; the only int-typed word products are offsets INSIDE one row
+    // (x * DP/2 <= 65536 * 256 = 2^24 by the width check above) and LDS indices, so no further argument check is needed.
     // exact-int16 envelope (DESIGN.md "arithmetic envelope"): no packed add may wrap
     // static half: the block cost must fit int16 at all and P2 <= 16383; when the worst-case block cost exceeds 16383
     // the cost kernel tracks the actual maximum and the call fails loudly only if THIS image pair leaves the envelope
@@ -2427,6 +2450,7 @@ int launch_cost2(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st,
         case 32: return launch_cost2_l<2, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
         case 64: return launch_cost2_l<4, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
         case 128: return launch_cost2_l<8, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
+        case 512: return launch_cost2_l<32, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);   // 2 columns per wave, 16-column tiles
         default: return launch_cost2_l<16, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
     }
 }
@@ -2491,6 +2515,9 @@ int launch_vscan2(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const SgmGeom &g
             }
         } else if (force == 4) k_vscan2<4, 16><<<dim3((g.W1 + 3) / 4, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
         else k_vscan2<8, 8><<<dim3((g.W1 + 7) / 8, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
+    } else if (g.DP == 512) {
+        // 16 disparities per lane on 32 lanes, 2 columns per wave (NPL = 16 would need whole 32-disparity lanes; D is a multiple of 16)
+        k_vscan2<8, 32><<<dim3((g.W1 + 1) / 2, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
     } else {
         k_vscan2<8, 16><<<dim3((g.W1 + 3) / 4, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
     }
@@ -2554,6 +2581,7 @@ void launch_hh_path(hipStream_t st, const SgmGeom &g, int r, const int *cost, in
         case 32: launch_hh_path_p<4>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
         case 64: launch_hh_path_p<8>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
         case 128: launch_hh_path_p<16>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
+        case 512: launch_hh_path_p<64>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;   // one line per wave
         default: launch_hh_path_p<32>(st, g, r, cost, svol, inv_a, raw, mins, store_last); break;
     }
 }
@@ -2707,9 +2735,13 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         return R3D_OK;
     }
     if (p->mode == R3D_SGBM_MODE_HH) return sgm_run_hh(ctx, ws, st, p, g, d_left, d_right, w, h, stride, d_disp);
-    // R3D_SGM_IMPL (read below as well): the v1 and v3 kernel generations only know 128 / 256 slots per column
+    // R3D_SGM_IMPL (read below as well): the v1 and v3 kernel generations only know 128 / 256 slots per column, and only the
+    // default generation has the 512-slot instantiations (v4 and v5 would run their 256-slot kernels over a 512-slot volume)
     {
         const char *e = getenv("R3D_SGM_IMPL");
+        if (g.DP > 256 && e && (!strcmp(e, "v1") || !strcmp(e, "v3") || !strcmp(e, "v4") || !strcmp(e, "v5")))
+            return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: numDisparities > 256 (got %d) needs the default kernel generation v2, R3D_SGM_IMPL=%s stops at 256",
+                            g.D, e);
         if (e && (!strcmp(e, "v1") || !strcmp(e, "v3"))) g.DP = g.NP * 128;
     }
     const int NPW = g.DP / 2;   // 32-bit words (disparity pairs) per cost-volume column
@@ -2882,9 +2914,12 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         // DP = 64 / 32: still 16 lanes per row and 4 rows per wave (612 waves at C2 height), with 2 / 1 registers per lane and
         // proportionally longer segments so that a segment stays 128 registers of loads in flight
         constexpr int K64 = 16, K32 = 32;
+        // DP = 512: 4 registers x 64 lanes = ONE row per wave (h waves), segments of K2 columns as at DP = 256: the same
+        // 6 * K2 * 4 registers of cost / L_left buffers per lane, and one more butterfly stage per step
+        const bool wide = g.DP == 512;
         const bool small = g.DP < 128;
         const bool four = (g.DP == 128 && !rows2) || small;
-        const int rpw = four ? 4 : 2, npl = g.DP == 32 ? 1 : g.DP == 64 ? 2 : four ? 4 : 2 * g.NP;
+        const int rpw = wide ? 1 : four ? 4 : 2, npl = g.DP == 32 ? 1 : g.DP == 64 ? 2 : four ? 4 : 2 * g.NP;
         // R3D_HSCAN_K=8: 8-column segments for the D <= 128 layout (half the registers of the default 16: two waves fit a SIMD); A/B
         static const bool k8_env = [] { const char *e = getenv("R3D_HSCAN_K"); return e && !strcmp(e, "8"); }();
         const bool k8 = k8_env && g.DP == 128 && four;
@@ -2907,6 +2942,10 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
                 k_hscan2<2, 32, K1b, false, 1><<<nw2, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
                 k_hscan2<4, 16, K1b, false, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
             }
+        } else
+        if (wide) {
+            if (padded) k_hscan2<4, 64, K2, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
+            else k_hscan2<4, 64, K2, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
         } else
         if (g.DP == 32) {
             if (padded) k_hscan2<1, 16, K32, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);

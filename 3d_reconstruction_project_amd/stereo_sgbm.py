@@ -128,10 +128,10 @@ class StereoSGBM:
         minD = self._p["minDisparity"]
         H, W = self._last_shape
         W1 = (W + min(minD, 0)) - max(minD + D, 0)
-        # slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 that holds D (128 / 256 for the v1 / v3 kernels)
+        # slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 / 512 that holds D (128 / 256 for the v1 / v3 kernels)
         import os
         legacy = os.environ.get("R3D_SGM_IMPL") in ("v1", "v3")
-        dp = next(c for c in ((128, 256) if legacy else (32, 64, 128, 256)) if D <= c)
+        dp = next(c for c in ((128, 256) if legacy else (32, 64, 128, 256, 512)) if D <= c)
         out = {}
         cost = np.empty((H, W1, dp), np.int16) if want_cost else None
         hsum = np.empty((H, W1, dp), np.int16) if want_hsum else None
@@ -155,7 +155,7 @@ class StereoSGBM:
         minD = self._p["minDisparity"]
         H, W = self._last_shape
         W1 = max((W + min(minD, 0)) - max(minD + D, 0), 0)
-        dp = next((c for c in (32, 64, 128, 256) if D <= c), 256)
+        dp = next((c for c in (32, 64, 128, 256, 512) if D <= c), 512)
         S = np.empty((H, W1, dp), np.int16)
         self.context.call("r3d_sgbm_debug_hh_partial", int(n), S.ctypes.data_as(ctypes.c_void_p))
         return S[:, :, :D]
@@ -174,7 +174,8 @@ def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0
                       uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=STEREO_SGBM_MODE_SGBM, device=0):
     """Factory with cv2.StereoSGBM_create's keyword names and defaults.  MODE_SGBM_3WAY (the mode every reference call
     site passes) and MODE_HH (eight full-image paths, no stripes) are implemented; MODE_SGBM and MODE_HH4 raise at
-    compute()."""
+    compute().  numDisparities: a multiple of 16 up to 512 (above 256 the cost volumes use 512 slots per column: 1 KB per
+    cost column and volume, two volumes per map in flight)."""
     return StereoSGBM(minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio,
                       speckleWindowSize, speckleRange, mode, device)
 

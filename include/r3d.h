@@ -80,7 +80,7 @@ int r3d_event_elapsed_ms(r3d_ctx *ctx, void *start, void *stop, float *out_ms); 
 #define R3D_SGBM_MODE_3WAY 2
 typedef struct {
     int32_t minDisparity;
-    int32_t numDisparities; /* multiple of 16, <= 256 */
+    int32_t numDisparities; /* multiple of 16, <= 512 (above 256: default kernel generation only; 1 KB per cost column and volume) */
     int32_t blockSize;      /* odd, 1..11 */
     int32_t P1, P2;
     int32_t disp12MaxDiff;
@@ -122,15 +122,16 @@ int r3d_set_profiling(r3d_ctx *ctx, int enabled);
 int r3d_sgbm_profile(r3d_ctx *ctx, float *ms, int32_t max_slots, char *names, int32_t names_bytes);
 
 /* debug / stage parity: copies intermediate results of the LAST sgbm call to HOST buffers (NULL = skip).
- *   cost   int16 [h][w1][dp]  aggregated block cost C (dp = the smallest of 32 / 64 / 128 / 256 that holds D, of 128 / 256
- *                             under R3D_SGM_IMPL=v1 / v3; entries d>=D undefined)
+ *   cost   int16 [h][w1][dp]  aggregated block cost C (dp = the smallest of 32 / 64 / 128 / 256 / 512 that holds D, of 128 / 256
+ *                             under R3D_SGM_IMPL=v1 / v3; entries d>=D undefined).  A volume is h*w1*dp*2 bytes, which
+ *                             passes 4 GiB at 8 MP with dp = 512: the host buffers must hold that much.
  *   hsum   int16 [h][w1][dp]  MODE_SGBM_3WAY: L_left + L_right; MODE_HH: S after the first seven directions (the eighth is fused
  *                             with the selection and never stored)
  *   raw    int16 [h][w]       disparity after the row LR check, before the 3x3 median */
 int r3d_sgbm_debug_fetch(r3d_ctx *ctx, int16_t *cost, int16_t *hsum, int16_t *raw);
 
 /* debug / stage parity, MODE_HH only: S after the first n_dirs directions (1..8, contract order) of the LAST
- * r3d_sgbm_compute* call on this context, int16 [h][w1][dp] to a HOST buffer (layout as r3d_sgbm_debug_fetch).
+ * r3d_sgbm_compute* call on this context, int16 [h][w1][dp] to a HOST buffer (layout and dp, up to 512, as r3d_sgbm_debug_fetch).
  * Runs those directions again over the cost volume that call left behind, with the same launches as the call itself except
  * that every direction stores S (the eighth too), then synchronises and copies.  Overwrites what r3d_sgbm_debug_fetch returns
  * as hsum; cost and raw stay valid.  R3D_E_BADARG: no call yet, the last call was not MODE_HH or had an empty matching range,
