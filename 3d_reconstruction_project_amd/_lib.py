@@ -82,6 +82,9 @@ _SIGS = {
     "r3d_sgbm_compute_dev": ([_vp, ctypes.POINTER(SgbmParams), _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp], ctypes.c_int),
     "r3d_sgbm_compute_batch_dev": ([_vp, ctypes.POINTER(SgbmParams), ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp], ctypes.c_int),
     "r3d_sgbm_compute_batch_events_dev": ([_vp, ctypes.POINTER(SgbmParams), ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_sgbm_compute_cn": ([_vp, ctypes.POINTER(SgbmParams), _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp], ctypes.c_int),
+    "r3d_sgbm_compute_cn_dev": ([_vp, ctypes.POINTER(SgbmParams), _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp], ctypes.c_int),
+    "r3d_sgbm_compute_batch_cn_dev": ([_vp, ctypes.POINTER(SgbmParams), ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
     "r3d_stream_wait_event": ([_vp, _vp], ctypes.c_int),
     "r3d_filter_speckles": ([_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "r3d_set_profiling": ([_vp, ctypes.c_int], ctypes.c_int),

@@ -264,23 +264,38 @@ int r3d_sgbm_profile(r3d_ctx *ctx, float *ms, int32_t max_slots, char *names, in
     return n;
 }
 
+// The entry points without _cn are the single-channel case of the ones with it.
 int r3d_sgbm_compute_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right, int32_t w,
                          int32_t h, int32_t stride, int16_t *d_disp) {
     R3D_ROCTX_RANGE("r3d_sgbm_compute_dev");
     if (!ctx) return R3D_E_BADARG;
-    return r3d_sgm_run(ctx, 0, ctx->stream, p, d_left, d_right, w, h, stride, d_disp);
+    return r3d_sgm_run(ctx, 0, ctx->stream, p, d_left, d_right, w, h, stride, 1, d_disp);
+}
+
+int r3d_sgbm_compute_cn_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right, int32_t w,
+                            int32_t h, int32_t stride, int32_t cn, int16_t *d_disp) {
+    R3D_ROCTX_RANGE("r3d_sgbm_compute_cn_dev");
+    if (!ctx) return R3D_E_BADARG;
+    return r3d_sgm_run(ctx, 0, ctx->stream, p, d_left, d_right, w, h, stride, cn, d_disp);
 }
 
 int r3d_sgbm_compute_batch_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_t n, const uint8_t *const *d_left,
                                const uint8_t *const *d_right, int32_t w, int32_t h, int32_t stride, int16_t *const *d_disp) {
-    return r3d_sgbm_compute_batch_events_dev(ctx, p, n, d_left, d_right, w, h, stride, d_disp, nullptr);
+    return r3d_sgbm_compute_batch_cn_dev(ctx, p, n, d_left, d_right, w, h, stride, 1, d_disp, nullptr);
 }
 
 int r3d_sgbm_compute_batch_events_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_t n, const uint8_t *const *d_left,
                                       const uint8_t *const *d_right, int32_t w, int32_t h, int32_t stride, int16_t *const *d_disp,
                                       void *const *done_events) {
+    return r3d_sgbm_compute_batch_cn_dev(ctx, p, n, d_left, d_right, w, h, stride, 1, d_disp, done_events);
+}
+
+int r3d_sgbm_compute_batch_cn_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_t n, const uint8_t *const *d_left,
+                                  const uint8_t *const *d_right, int32_t w, int32_t h, int32_t stride, int32_t cn, int16_t *const *d_disp,
+                                  void *const *done_events) {
     R3D_ROCTX_RANGE("r3d_sgbm_compute_batch_dev");
     if (!ctx) return R3D_E_BADARG;
+    if (cn != 1 && cn != 3) return r3d_fail(ctx, R3D_E_BADARG, "sgbm batch: images must have 1 or 3 channels, got %d", cn);
     if (n < 0 || (n > 0 && (!d_left || !d_right || !d_disp))) return r3d_fail(ctx, R3D_E_BADARG, "sgbm batch: bad argument");
     if (n == 0) return R3D_OK;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
@@ -299,7 +314,7 @@ int r3d_sgbm_compute_batch_events_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, in
     int rc = R3D_OK;
     for (int i = 0; i < n && rc == R3D_OK; i++) {
         const int l = i % lanes;
-        rc = r3d_sgm_run(ctx, l, ctx->ws[l].stream, p, d_left[i], d_right[i], w, h, stride, d_disp[i]);
+        rc = r3d_sgm_run(ctx, l, ctx->ws[l].stream, p, d_left[i], d_right[i], w, h, stride, cn, d_disp[i]);
         if (rc == R3D_OK && done_events && done_events[i]) {
             // a stale or foreign-device event handle fails here: remember it, stop launching, and STILL run the join below
             const hipError_t e = hipEventRecord((hipEvent_t)done_events[i], ctx->ws[l].stream);
@@ -321,17 +336,23 @@ int r3d_sgbm_compute_batch_events_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, in
 
 int r3d_sgbm_compute(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *left, const uint8_t *right, int32_t w, int32_t h,
                      int32_t stride, int16_t *disp) {
+    return r3d_sgbm_compute_cn(ctx, p, left, right, w, h, stride, 1, disp);
+}
+
+int r3d_sgbm_compute_cn(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *left, const uint8_t *right, int32_t w, int32_t h,
+                        int32_t stride, int32_t cn, int16_t *disp) {
     R3D_ROCTX_RANGE("r3d_sgbm_compute");
     if (!ctx) return R3D_E_BADARG;
     if (!left || !right || !disp) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: null host pointer");
-    if (w <= 0 || h <= 0 || stride < w) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: bad size %dx%d stride %d", w, h, stride);
+    if (cn != 1 && cn != 3) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: images must have 1 or 3 channels, got %d", cn);
+    if (w <= 0 || h <= 0 || stride < w * cn) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: bad size %dx%d (%d channel(s)) stride %d", w, h, cn, stride);
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ib = (size_t)stride * h, ob = (size_t)w * h * 2;
     int rc;
     if ((rc = r3d_reserve(ctx, ctx->img_l, ib)) || (rc = r3d_reserve(ctx, ctx->img_r, ib)) || (rc = r3d_reserve(ctx, ctx->out, ob))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync(ctx->img_l.p, left, ib, hipMemcpyHostToDevice, ctx->stream));
     R3D_HIP(ctx, hipMemcpyAsync(ctx->img_r.p, right, ib, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = r3d_sgm_run(ctx, 0, ctx->stream, p, (const uint8_t *)ctx->img_l.p, (const uint8_t *)ctx->img_r.p, w, h, stride, (int16_t *)ctx->out.p))) return rc;
+    if ((rc = r3d_sgm_run(ctx, 0, ctx->stream, p, (const uint8_t *)ctx->img_l.p, (const uint8_t *)ctx->img_r.p, w, h, stride, cn, (int16_t *)ctx->out.p))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync(disp, ctx->out.p, ob, hipMemcpyDeviceToHost, ctx->stream));
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;

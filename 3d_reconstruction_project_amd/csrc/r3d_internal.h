@@ -50,6 +50,7 @@ struct SgmGeom {
     int W, H, minD, D, NP, minX1, maxX1, W1, SW2, SH2, P1, P2, uniq, d12, ftzero, stripe_sz, overlap, invalid;
     int DP;  // disparity slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 that holds D (v2 kernels; v1 and v3
              // only know 128 / 256 = NP * 128)
+    int CN;  // channels of the image pair (1 grey, 3 colour: the block cost is the sum over the channels)
 };
 
 struct r3d_ctx {
@@ -145,7 +146,7 @@ struct r3d_roctx_scope {
 
 // sgm.hip
 int r3d_sgm_run(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
-                int w, int h, int stride, int16_t *d_disp);
+                int w, int h, int stride, int cn, int16_t *d_disp);
 int r3d_sgm_hh_partial(r3d_ctx *ctx, int n_dirs);
 int r3d_selftest_run(r3d_ctx *ctx);
 int r3d_speckle_run(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, int16_t *d_img, int w, int h, int newVal, int maxSize, int maxDiff);

@@ -5,9 +5,10 @@
 // oracle/sgbm3way.c (every QUIRK listed there is reproduced bit for bit).
 //
 // Data layout in HBM (all int16 unless noted; "dp" = the smallest of 32 / 64 / 128 / 256 / 512 slots that holds D; w1 = maxX1-minX1):
-//   rec_l/rec_r  uint2 [h][w]       per pixel: (g, g_lo, g_hi, i | i_lo, i_hi, 0, 0): prefiltered gradient, raw
-//                                   intensity and their Birchfield-Tomasi half-pixel intervals
-//   cost         [h][w1][dp]        aggregated block cost C (blockSize x blockSize box of the BT pixel cost)
+//   rec_l/rec_r  uint2 [cn][h][w]   per pixel and channel: (g, g_lo, g_hi, i | i_lo, i_hi, 0, 0): prefiltered gradient, raw
+//                                   intensity and their Birchfield-Tomasi half-pixel intervals (cn = 1 grey, 3 colour)
+//   cost         [h][w1][dp]        aggregated block cost C (blockSize x blockSize box of the BT pixel cost, summed over the
+//                                   channels: k_cost2 runs once per channel, channels 1 and 2 add to what is stored)
 //   cspec        [3][SH2][w1][dp]   C of the first SH2 rows of stripes 1..3 (box replicated at the stripe top)
 //   hsum         [h][w1][dp]        L_left + L_right
 //   raw / mins   [h][w]             WTA disparity (x16, before LR check) and its aggregated cost
@@ -300,16 +301,20 @@ __global__ void __launch_bounds__(256) k_fill_s16(int16_t *__restrict__ p, size_
 // halo; a thread keeps the three rows of its column in registers and rolls them), the gradient / intensity pair of 258
 // positions is computed from LDS, and each thread forms its pixel's two intervals from its neighbours' pairs.  All global
 // loads use clamped coordinates (no branch around a load).
+// CN (1 or 3): channels of the interleaved source images (img[y * ld + x * CN + c]).  blockIdx.z = 2 * c + side: channel c of
+// every pixel is prefiltered on its own, as a grey image would be, into plane c of the record images (rec[c][h][w]).
 #define PF_ROWS 8
+template <int CN>
 __global__ void __launch_bounds__(256) k_prefilter(const uint8_t *__restrict__ L, const uint8_t *__restrict__ R, int ld,
                                                    int W, int H, int ft, uint2 *__restrict__ recL, uint2 *__restrict__ recR) {
     __shared__ int raw[260];  // rows y-1 | y << 8 | y+1 << 16 at columns x0-2 .. x0+257
     __shared__ int gi[258];   // gradient | intensity << 8 at columns x0-1 .. x0+256
     const int t = threadIdx.x, x0 = blockIdx.x * 256, yb = blockIdx.y * PF_ROWS;
-    const uint8_t *img = blockIdx.z == 0 ? L : R;
-    uint2 *rec = blockIdx.z == 0 ? recL : recR;
+    const int side = CN == 1 ? blockIdx.z : blockIdx.z & 1, ch = CN == 1 ? 0 : blockIdx.z >> 1;
+    const uint8_t *img = (side == 0 ? L : R) + ch;
+    uint2 *rec = (side == 0 ? recL : recR) + (size_t)ch * W * H;
     const int xc = min(max(x0 - 2 + t, 0), W - 1), xe = min(max(x0 + 254 + (t & 3), 0), W - 1);
-    auto px = [&](int yy, int xx) { return (int)img[(size_t)min(max(yy, 0), H - 1) * ld + xx]; };
+    auto px = [&](int yy, int xx) { return (int)img[(size_t)min(max(yy, 0), H - 1) * ld + xx * CN]; };
     int a = px(yb - 1, xc), r = px(yb, xc), ae = px(yb - 1, xe), re = px(yb, xe);
     int bn = px(yb + 1, xc), ben = px(yb + 1, xe);   // the row below, requested ONE iteration early (its round trip ran on the critical path of every row)
     const int x = x0 + t;
@@ -471,12 +476,17 @@ __global__ void __launch_bounds__(COST_NW * 64) k_cost(const uint2 *__restrict__
 // VCH (v3): the vertical path L_top is aggregated right here, on the freshly summed block cost that is still in
 // registers: one workgroup column-tile per STRIPE marches from the stripe's first warm-up row to its last row, and
 // writes C and L_top for the rows the stripe owns (the warm-up rows' special block costs never leave the chip).
-template <int LPC, int SH2, bool TRACK, bool VCH, int NWAVE>
+// ACC (colour pairs, channels 1 and 2; never with VCH): the block cost of this launch's channel is ADDED to what the launches of the
+// earlier channels left in cvol / cspec (read-add-store by the lane that stores; every launch covers the same entries).  The sum
+// of the channels stays below 32768 per entry (derive_geom), so the one 32-bit add of two packed entries carries nothing across.
+// TRACK then looks at the summed value: it is set on the last channel's launch only.
+template <int LPC, int SH2, bool TRACK, bool VCH, int NWAVE, bool ACC = false>
 __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ recL, const uint2 *__restrict__ recR, SgmGeom g,
                                                             int *__restrict__ cvol, int *__restrict__ cspec, int BAND, int nMain,
                                                             int *__restrict__ maxc, int *__restrict__ ltvol, int tile0) {
     constexpr int NPL = 8, CW = 64 / LPC, TC = NWAVE * CW, TO = TC - 2 * SH2, DP = 16 * LPC, DPW = NPL * LPC;
     constexpr int R = 2 * SH2 + 1, NRR = TC + DP, NT = NWAVE * 64;
+    static_assert(!(ACC && VCH), "the fused vertical path runs on the complete block cost");
     // pair words: 6 dwords per right pixel, plus 8 dwords of padding after every 16 pixels: lanes of one column group
     // read records 16 apart (16*6 dwords = 32 mod 64 banks -> 4-way conflicts); with the pad the eight chunks land on
     // eight different multiples of 8 banks and the four column groups of a half-wave fill the gaps: conflict-free.
@@ -672,6 +682,11 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
                 }
             } else {
                 int *o = optr + (size_t)(t - 2 * SH2) * rowWords;
+                if constexpr (ACC) {
+                    const int4 a0 = *(const int4 *)o, a1 = *(const int4 *)(o + 4);
+                    c[0] = pk_add_nc(c[0], a0.x); c[1] = pk_add_nc(c[1], a0.y); c[2] = pk_add_nc(c[2], a0.z); c[3] = pk_add_nc(c[3], a0.w);
+                    c[4] = pk_add_nc(c[4], a1.x); c[5] = pk_add_nc(c[5], a1.y); c[6] = pk_add_nc(c[6], a1.z); c[7] = pk_add_nc(c[7], a1.w);
+                }
 #if R3D_EXP_COST == 1
                 if ((c[0] ^ c[1] ^ c[2] ^ c[3] ^ c[4] ^ c[5] ^ c[6] ^ c[7]) == 0x12345678) *(int4 *)o = make_int4(c[0], c[1], c[2], c[3]);   // timing experiment: no stores
 #else
@@ -2325,8 +2340,13 @@ __global__ void __launch_bounds__(64) k_streambench(const int *__restrict__ in, 
     if (acc == 0x12345678) out[0] = acc;
 }
 
-int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, SgmGeom &g) {
+// worst-case block cost of a pair (all CN channels summed) above 16383: the cost kernel then tracks the actual maximum
+inline bool sgm_track(const SgmGeom &g) { return (long)g.CN * (2 * g.SH2 + 1) * (2 * g.SH2 + 1) * (2L * g.ftzero + 63) > 16383; }
+
+int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, int cn, SgmGeom &g) {
     if (!p) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: params is NULL");
+    if (cn != 1 && cn != 3) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: images must have 1 or 3 channels, got %d", cn);
+    g.CN = cn;
     if (p->mode != R3D_SGBM_MODE_3WAY && p->mode != R3D_SGBM_MODE_HH)
         return r3d_fail(ctx, R3D_E_UNSUPPORTED,
                         "sgbm: only mode=STEREO_SGBM_MODE_HH (1) and STEREO_SGBM_MODE_SGBM_3WAY (2) are implemented, got %d", p->mode);
@@ -2364,11 +2384,12 @@ int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, SgmGeom &g
     // exact-int16 envelope (DESIGN.md "arithmetic envelope"): no packed add may wrap
     // static half: the block cost must fit int16 at all and P2 <= 16383; when the worst-case block cost exceeds 16383
     // the cost kernel tracks the actual maximum and the call fails loudly only if THIS image pair leaves the envelope
-    const long cmax = (long)p->blockSize * p->blockSize * (2L * g.ftzero + 63);
+    // (a colour pair's block cost is the sum over its channels, so the bound carries the channel count)
+    const long cmax = (long)cn * p->blockSize * p->blockSize * (2L * g.ftzero + 63);
     if (cmax > 32767 || g.P2 > 16383 || g.ftzero > 127)
         return r3d_fail(ctx, R3D_E_UNSUPPORTED,
-                        "sgbm: blockSize=%d preFilterCap=%d P2=%d leave the exact int16 envelope (max block cost %ld > 32767 or P2 > 16383)",
-                        p->blockSize, p->preFilterCap, g.P2, cmax);
+                        "sgbm: blockSize=%d preFilterCap=%d P2=%d channels=%d leave the exact int16 envelope (max block cost %ld > 32767 or P2 > 16383)",
+                        p->blockSize, p->preFilterCap, g.P2, cn, cmax);
     if ((long)g.minD * 16 - 16 < -32768 || ((long)maxD) * 16 > 32767)
         return r3d_fail(ctx, R3D_E_BADARG, "sgbm: disparity range [%d, %d) does not fit the x16 int16 output", g.minD, maxD);
     return R3D_OK;
@@ -2376,8 +2397,9 @@ int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, SgmGeom &g
 
 // col_lo / col_hi: cost columns of a column slab (whole tiles: [ceil(col_lo / TO), ceil(col_hi / TO)) of the tile grid, so
 // consecutive slabs partition the tiles); col_hi < 0 = the whole width
-template <int LPC, int SH2, bool TRACK, bool VCH, int NWAVE>
-int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only = false) {
+// chan: the channel whose record planes are read; ACC (chan > 0): its block cost is added to the stored one (see k_cost2)
+template <int LPC, int SH2, bool TRACK, bool VCH, int NWAVE, bool ACC>
+int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
     constexpr int CW = 64 / LPC, TC = NWAVE * CW, TO = TC - 2 * SH2;
     if (TO <= 0) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: tile too small for this block size");
     const int all_tiles = (g.W1 + TO - 1) / TO;
@@ -2393,7 +2415,7 @@ int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t s
     int slots = slots_of[dev].load(std::memory_order_relaxed);
     if (slots == 0) {
         int v = 1, c = 256;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void *)k_cost2<LPC, SH2, TRACK, VCH, NWAVE>, NWAVE * 64, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void *)k_cost2<LPC, SH2, TRACK, VCH, NWAVE, ACC>, NWAVE * 64, 0);
         (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, ctx->device);
         slots = (v < 1 ? 1 : v) * (c < 1 ? 256 : c);
         slots_of[dev].store(slots, std::memory_order_relaxed);
@@ -2410,8 +2432,9 @@ int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t s
     }
     int *maxc = (int *)ws.flags.p + 8;
     if (TRACK) R3D_HIP(ctx, hipMemsetAsync(maxc, 0, 4, st));
-    k_cost2<LPC, SH2, TRACK, VCH, NWAVE><<<dim3(tiles, VCH ? 4 : nMain + nSpec), NWAVE * 64, 0, st>>>(
-        (const uint2 *)ws.rec_l.p, (const uint2 *)ws.rec_r.p, g, (int *)ws.cost.p, (int *)ws.cspec.p, BAND, nMain, maxc, (int *)ws.ltop.p, tile_lo);
+    const size_t plane = (size_t)chan * g.W * g.H;
+    k_cost2<LPC, SH2, TRACK, VCH, NWAVE, ACC><<<dim3(tiles, VCH ? 4 : nMain + nSpec), NWAVE * 64, 0, st>>>(
+        (const uint2 *)ws.rec_l.p + plane, (const uint2 *)ws.rec_r.p + plane, g, (int *)ws.cost.p, (int *)ws.cspec.p, BAND, nMain, maxc, (int *)ws.ltop.p, tile_lo);
     R3D_HIP(ctx, hipGetLastError());
     if (TRACK) {
         // data-dependent half of the exact-int16 envelope: only reached when the static bound cannot prove it
@@ -2423,36 +2446,58 @@ int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t s
     }
     return R3D_OK;
 }
-template <int LPC, int SH2, bool TRACK, bool VCH>
-int launch_cost2_t(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only = false) {
+template <int LPC, int SH2, bool TRACK, bool VCH, bool ACC>
+int launch_cost2_t(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
     // 8 waves = 64-column tiles (2*SH2 halo columns); R3D_COST_NWAVE=4 selects 32-column tiles for A/B measurements
     static const bool four = [] { const char *e = getenv("R3D_COST_NWAVE"); return e && !strcmp(e, "4"); }();
     if constexpr (LPC == 8 && 4 * (64 / LPC) > 2 * SH2) {
-        if (four) return launch_cost2_n<LPC, SH2, TRACK, VCH, 4>(ctx, ws, g, st, col_lo, col_hi, spec_only);
+        if (four) return launch_cost2_n<LPC, SH2, TRACK, VCH, 4, ACC>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
     }
-    return launch_cost2_n<LPC, SH2, TRACK, VCH, 8>(ctx, ws, g, st, col_lo, col_hi, spec_only);
+    return launch_cost2_n<LPC, SH2, TRACK, VCH, 8, ACC>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
 }
-template <int LPC, bool VCH>
-int launch_cost2_l(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only = false) {
-    const bool track = (long)(2 * g.SH2 + 1) * (2 * g.SH2 + 1) * (2L * g.ftzero + 63) > 16383;
+template <int LPC, bool VCH, bool ACC>
+int launch_cost2_l(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
+    const bool track = sgm_track(g) && chan == g.CN - 1;   // on the summed value: the last channel's launch
+#define R3D_C2(S, T) launch_cost2_t<LPC, S, T, VCH, ACC>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan)
     switch (g.SH2) {
-        case 0: return launch_cost2_t<LPC, 0, false, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 1: return launch_cost2_t<LPC, 1, false, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 2: return launch_cost2_t<LPC, 2, false, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 3: return track ? launch_cost2_t<LPC, 3, true, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only) : launch_cost2_t<LPC, 3, false, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 4: return track ? launch_cost2_t<LPC, 4, true, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only) : launch_cost2_t<LPC, 4, false, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        default: return launch_cost2_t<LPC, 5, true, VCH>(ctx, ws, g, st, col_lo, col_hi, spec_only);
+        case 0: return R3D_C2(0, false);
+        case 1: return R3D_C2(1, false);
+        case 2: return R3D_C2(2, false);
+        case 3: return track ? R3D_C2(3, true) : R3D_C2(3, false);
+        case 4: return track ? R3D_C2(4, true) : R3D_C2(4, false);
+        default:   // blockSize 11: always tracked; three channels of it never pass the static bound of derive_geom
+            if constexpr (ACC) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: blockSize 11 with 3-channel images is outside the exact int16 envelope");
+            else return R3D_C2(5, true);
+    }
+#undef R3D_C2
+}
+template <int LPC>
+int launch_cost2_c(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
+    return chan > 0 ? launch_cost2_l<LPC, false, true>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan)
+                    : launch_cost2_l<LPC, false, false>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
+}
+int launch_cost2(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, bool vch, int col_lo = 0, int col_hi = -1, bool spec_only = false,
+                 int chan = 0) {
+    if (vch) return g.NP == 1 ? launch_cost2_l<8, true, false>(ctx, ws, g, st, 0, -1, false, 0) : launch_cost2_l<16, true, false>(ctx, ws, g, st, 0, -1, false, 0);
+    switch (g.DP) {  // LPC = DP / 16 lanes per column
+        case 32: return launch_cost2_c<2>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
+        case 64: return launch_cost2_c<4>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
+        case 128: return launch_cost2_c<8>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
+        case 512: return launch_cost2_c<32>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);   // 2 columns per wave, 16-column tiles
+        default: return launch_cost2_c<16>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
     }
 }
-int launch_cost2(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, bool vch, int col_lo = 0, int col_hi = -1, bool spec_only = false) {
-    if (vch) return g.NP == 1 ? launch_cost2_l<8, true>(ctx, ws, g, st, 0, -1) : launch_cost2_l<16, true>(ctx, ws, g, st, 0, -1);
-    switch (g.DP) {  // LPC = DP / 16 lanes per column
-        case 32: return launch_cost2_l<2, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 64: return launch_cost2_l<4, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 128: return launch_cost2_l<8, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-        case 512: return launch_cost2_l<32, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);   // 2 columns per wave, 16-column tiles
-        default: return launch_cost2_l<16, false>(ctx, ws, g, st, col_lo, col_hi, spec_only);
-    }
+// the whole cost stage of a pair: channel 0 stores C, the further channels of a colour pair add theirs (cost and cspec alike)
+int launch_cost2_all(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st) {
+    for (int c = 0; c < g.CN; c++)
+        if (int rc = launch_cost2(ctx, ws, g, st, false, 0, -1, false, c)) return rc;
+    return R3D_OK;
+}
+// prefilter of both images, every channel: record planes rec_l / rec_r [CN][h][w]
+void launch_prefilter(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, const uint8_t *d_left, const uint8_t *d_right, int stride) {
+    const dim3 grid((g.W + 255) / 256, (g.H + PF_ROWS - 1) / PF_ROWS, 2 * g.CN);
+    if (g.CN == 1) k_prefilter<1><<<grid, 256, 0, st>>>(d_left, d_right, stride, g.W, g.H, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
+    else k_prefilter<3><<<grid, 256, 0, st>>>(d_left, d_right, stride, g.W, g.H, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
 }
 // k_cost_fwd (v5) for the DP = 128 layout: block cost along rows + forward chain + checkpoints
 int launch_cost_fwd(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, int *cost, int *hsum, int *ckpt) {
@@ -2599,7 +2644,7 @@ static int sgm_run_hh(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const r3d_sg
     const size_t npix = (size_t)w * h;
     const size_t rowBytes = (size_t)g.W1 * g.DP * 2, volBytes = rowBytes * h;
     int rc;
-    if ((rc = r3d_reserve(ctx, ws.rec_l, npix * 8)) || (rc = r3d_reserve(ctx, ws.rec_r, npix * 8)) ||
+    if ((rc = r3d_reserve(ctx, ws.rec_l, npix * 8 * g.CN)) || (rc = r3d_reserve(ctx, ws.rec_r, npix * 8 * g.CN)) ||
         (rc = r3d_reserve(ctx, ws.cost, volBytes)) || (rc = r3d_reserve(ctx, ws.cspec, rowBytes * 3 * (g.SH2 > 0 ? g.SH2 : 1))) ||
         (rc = r3d_reserve(ctx, ws.hsum, volBytes)) || (rc = r3d_reserve(ctx, ws.raw, npix * 2)) ||
         (rc = r3d_reserve(ctx, ws.mins, npix * 2)) || (rc = r3d_reserve(ctx, ws.lrd, npix * 2)) || (rc = r3d_reserve(ctx, ws.flags, 256)))
@@ -2608,10 +2653,10 @@ static int sgm_run_hh(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const r3d_sg
     ctx->last_mode = p->mode; ctx->last_geom = g;
     r3d_prof_begin(ctx, ws);
     r3d_prof_mark(ctx, ws, st, "prefilter");
-    k_prefilter<<<dim3((w + 255) / 256, (h + PF_ROWS - 1) / PF_ROWS, 2), 256, 0, st>>>(d_left, d_right, stride, w, h, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
+    launch_prefilter(st, ws, g, d_left, d_right, stride);
     R3D_HIP(ctx, hipGetLastError());
     r3d_prof_mark(ctx, ws, st, "cost");
-    if ((rc = launch_cost2(ctx, ws, g, st, false))) return rc;   // also the envelope's tracked-maximum pass where it applies
+    if ((rc = launch_cost2_all(ctx, ws, g, st))) return rc;   // also the envelope's tracked-maximum pass where it applies
     const float inv_a = 1.0f / (float)(100 - g.uniq);
     for (int r = 0; r < 8; r++) {
         r3d_prof_mark(ctx, ws, st, HH_NAMES[r]);
@@ -2712,19 +2757,19 @@ int r3d_selftest_run(r3d_ctx *ctx) {
 // and including the LR check, its map left in ws.lrd2 -- the rows QUIRK_SMALL_IMAGE_STRIPES hands out in place of a clamped
 // stripe's own.
 static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
-                        int w, int h, int stride, int16_t *d_disp, int pass);
+                        int w, int h, int stride, int cn, int16_t *d_disp, int pass);
 int r3d_sgm_run(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
-                int w, int h, int stride, int16_t *d_disp) {
-    return sgm_run_impl(ctx, lane, st, p, d_left, d_right, w, h, stride, d_disp, 0);
+                int w, int h, int stride, int cn, int16_t *d_disp) {
+    return sgm_run_impl(ctx, lane, st, p, d_left, d_right, w, h, stride, cn, d_disp, 0);
 }
 static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
-                        int w, int h, int stride, int16_t *d_disp, int pass) {
+                        int w, int h, int stride, int cn, int16_t *d_disp, int pass) {
     r3d_sgm_ws &ws = ctx->ws[lane];
     if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "context poisoned by an earlier timed-out call: destroy it");
     SgmGeom g;
-    if (int rc = derive_geom(ctx, p, w, h, g)) return rc;
+    if (int rc = derive_geom(ctx, p, w, h, cn, g)) return rc;
     if (!d_left || !d_right || !d_disp) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: null image pointer");
-    if (stride < w) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: stride %d < width %d", stride, w);
+    if (stride < w * cn) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: stride %d < width %d x %d channel(s)", stride, w, cn);
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     if (g.W1 <= 0) {  // minX1 >= maxX1: like the original, an all-invalid map, no error
         const size_t np = (size_t)w * h;
@@ -2742,6 +2787,10 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         if (g.DP > 256 && e && (!strcmp(e, "v1") || !strcmp(e, "v3") || !strcmp(e, "v4") || !strcmp(e, "v5")))
             return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: numDisparities > 256 (got %d) needs the default kernel generation v2, R3D_SGM_IMPL=%s stops at 256",
                             g.D, e);
+        // ... and only the default generation sums the block cost of a colour pair over its channels
+        if (g.CN != 1 && e && (!strcmp(e, "v1") || !strcmp(e, "v3") || !strcmp(e, "v4") || !strcmp(e, "v5")))
+            return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: %d-channel images need the default kernel generation v2, R3D_SGM_IMPL=%s takes single-channel images only",
+                            g.CN, e);
         if (e && (!strcmp(e, "v1") || !strcmp(e, "v3"))) g.DP = g.NP * 128;
     }
     const int NPW = g.DP / 2;   // 32-bit words (disparity pairs) per cost-volume column
@@ -2749,8 +2798,8 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
     const size_t rowBytes = (size_t)g.W1 * NPW * 4;
     const size_t volBytes = rowBytes * h;
     int rc;
-    if ((rc = r3d_reserve(ctx, ws.rec_l, npix * 8))) return rc;
-    if ((rc = r3d_reserve(ctx, ws.rec_r, npix * 8))) return rc;
+    if ((rc = r3d_reserve(ctx, ws.rec_l, npix * 8 * g.CN))) return rc;   // one record plane per channel
+    if ((rc = r3d_reserve(ctx, ws.rec_r, npix * 8 * g.CN))) return rc;
     if ((rc = r3d_reserve(ctx, ws.cost, volBytes))) return rc;
     if ((rc = r3d_reserve(ctx, ws.cspec, rowBytes * 3 * (g.SH2 > 0 ? g.SH2 : 1)))) return rc;
     if ((rc = r3d_reserve(ctx, ws.raw, npix * 2))) return rc;
@@ -2767,7 +2816,7 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
     r3d_prof_begin(ctx, ws);
 
     r3d_prof_mark(ctx, ws, st, "prefilter");
-    k_prefilter<<<dim3((w + 255) / 256, (h + PF_ROWS - 1) / PF_ROWS, 2), 256, 0, st>>>(d_left, d_right, stride, w, h, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
+    launch_prefilter(st, ws, g, d_left, d_right, stride);
     R3D_HIP(ctx, hipGetLastError());
 
     // implementation generations kept side by side for A/B measurements: R3D_SGM_IMPL = v1 | v2 (default) | v3.
@@ -2837,8 +2886,9 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
     constexpr int KOV = 16;
     // R3D_SGM_FWD=wide: the forward launches use k_hscan2<PHASE 1> (whole register file: cannot share a SIMD with cost waves)
     static const bool lowreg = [] { const char *e = getenv("R3D_SGM_FWD"); return !(e && !strcmp(e, "wide")); }();
-    const bool track = (long)(2 * g.SH2 + 1) * (2 * g.SH2 + 1) * (2L * g.ftzero + 63) > 16383;
-    const bool overlapped = !use_v1 && n_slabs >= 2 && g.DP == 128 && !rows2_env && !track && g.W1 / KOV >= 8 * n_slabs;
+    const bool track = sgm_track(g);
+    // (a colour pair takes the sequential order: every slab would need its three channel launches before the scan may follow)
+    const bool overlapped = !use_v1 && n_slabs >= 2 && g.DP == 128 && !rows2_env && !track && g.CN == 1 && g.W1 / KOV >= 8 * n_slabs;
     // v5: cost + forward chain fused (k_cost_fwd), then the backward phase of k_hscan2; D <= 128 layouts with 128 slots only, and only
     // where the static envelope bound holds (no TRACK pass); otherwise the v2 kernels below
     const bool fused_fwd = impl == 5 && g.DP == 128 && !track && g.W1 / 16 >= 1;
@@ -2898,7 +2948,7 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
     } else {
     if (!use_v1) {
         r3d_prof_mark(ctx, ws, st, "cost");
-        if ((rc = launch_cost2(ctx, ws, g, st, false))) return rc;
+        if ((rc = launch_cost2_all(ctx, ws, g, st))) return rc;
     }
     r3d_prof_mark(ctx, ws, st, "hscan");
     if (use_v1) {
@@ -2998,7 +3048,7 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         // second run (workspaces are reused: this pass's LR-checked map is complete in ws.lrd, stream-ordered), then the assembly
         const bool prof = ctx->profiling;
         ctx->profiling = false;
-        rc = sgm_run_impl(ctx, lane, st, p, d_left, d_right, w, h, stride, d_disp, 1);
+        rc = sgm_run_impl(ctx, lane, st, p, d_left, d_right, w, h, stride, cn, d_disp, 1);
         ctx->profiling = prof;
         if (rc) return rc;
         k_tiny_assemble<<<dim3((w + 255) / 256, h), 256, 0, st>>>((int16_t *)ws.lrd.p, (const int16_t *)ws.lrd2.p, g);

@@ -5,6 +5,7 @@ Reference surface (Calib_depth/depth1.py:202-214,240-265,331; depth2.py:146-158,
                                     disp12MaxDiff=..., uniquenessRatio=..., speckleWindowSize=..., speckleRange=...,
                                     preFilterCap=..., mode=cv2.STEREO_SGBM_MODE_SGBM_3WAY)
     disp = matcher.compute(gray_left, gray_right)        # int16 [H,W], disparity x16, invalid = (minD-1)*16
+    disp = matcher.compute(bgr_left, bgr_right)          # cv2 takes CV_8UC3 pairs too: the pixel cost is summed over the channels
     matcher.setBlockSize(b); matcher.getNumDisparities(); ...
 Same keyword names, defaults, getters/setters and error behaviour (an exception on bad input).  All arithmetic
 runs in the HIP library (csrc/sgm.hip) through the C ABI in include/r3d.h.
@@ -58,42 +59,53 @@ class StereoSGBM:
     def params_struct(self):
         return _lib.SgbmParams(*[int(self._p[k]) for k in _FIELDS])
 
-    def compute(self, left, right):
-        """left, right: uint8 [H,W] rectified grayscale.  Returns int16 [H,W]."""
+    @staticmethod
+    def _pair(left, right):
+        """The two images of a pair as contiguous uint8 arrays and their channel count: both [H,W] (1) or both [H,W,3] (3)."""
         left = np.asarray(left)
         right = np.asarray(right)
-        if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 2 or left.shape != right.shape:
-            raise ValueError("StereoSGBM.compute expects two uint8 single-channel images of equal size "
-                             "(the reference converts with cv2.cvtColor(..., COLOR_BGR2GRAY) first)")
-        left = np.ascontiguousarray(left)
-        right = np.ascontiguousarray(right)
-        H, W = left.shape
+        if (left.dtype != np.uint8 or right.dtype != np.uint8 or left.shape != right.shape
+                or not (left.ndim == 2 or (left.ndim == 3 and left.shape[2] == 3))):
+            raise ValueError("StereoSGBM.compute expects two uint8 images of equal size and kind, both single-channel [H,W] "
+                             "or both 3-channel [H,W,3] (cv2's CV_8UC1 / CV_8UC3)")
+        return np.ascontiguousarray(left), np.ascontiguousarray(right), 1 if left.ndim == 2 else 3
+
+    def compute(self, left, right):
+        """left, right: uint8 rectified images, both grey [H,W] or both colour [H,W,3] (any channel order: the pixel cost is
+        the sum over the channels).  Returns int16 [H,W]."""
+        left, right, cn = self._pair(left, right)
+        H, W = left.shape[:2]
         self._last_shape = (H, W)
         disp = np.empty((H, W), np.int16)
         p = self.params_struct()
         vp = ctypes.c_void_p
-        self.context.call("r3d_sgbm_compute", ctypes.byref(p), left.ctypes.data_as(vp), right.ctypes.data_as(vp),
-                          W, H, W, disp.ctypes.data_as(vp))
+        self.context.call("r3d_sgbm_compute_cn", ctypes.byref(p), left.ctypes.data_as(vp), right.ctypes.data_as(vp),
+                          W, H, W * cn, cn, disp.ctypes.data_as(vp))
         return disp
 
-    def compute_device(self, d_left, d_right, width, height, stride, d_disp):
-        """Device-pointer variant (ints): enqueues on the context stream, no synchronisation."""
+    def compute_device(self, d_left, d_right, width, height, stride, d_disp, channels=1):
+        """Device-pointer variant (ints): enqueues on the context stream, no synchronisation.  channels: 1, or 3 for
+        interleaved colour images (stride in bytes per row, >= width * channels)."""
         p = self.params_struct()
         vp = ctypes.c_void_p
-        self.context.call("r3d_sgbm_compute_dev", ctypes.byref(p), vp(d_left), vp(d_right), int(width), int(height),
-                          int(stride), vp(d_disp))
+        self.context.call("r3d_sgbm_compute_cn_dev", ctypes.byref(p), vp(d_left), vp(d_right), int(width), int(height),
+                          int(stride), int(channels), vp(d_disp))
 
-    def compute_batch_device(self, d_lefts, d_rights, width, height, stride, d_disps, done_events=None):
+    def compute_batch_device(self, d_lefts, d_rights, width, height, stride, d_disps, done_events=None, channels=1):
         """Device-pointer batch (lists of ints): maps are pipelined over the library's internal lanes.  done_events (list of
         Context.event() handles or None entries): map i's completion is recorded into done_events[i], so a consumer on another
-        context can wait for it (Context.wait_event) while later maps are still running."""
+        context can wait for it (Context.wait_event) while later maps are still running.  channels: as compute_device."""
         n = len(d_lefts)
         assert len(d_rights) == n and len(d_disps) == n and (done_events is None or len(done_events) == n)
         if n > 1:   # three lanes + the context stream (+ the consumers' streams): more than HIP's default four hardware queues
             _lib.warn_if_few_hw_queues(int(os.environ.get("R3D_SGM_LANES", "3")) + 2)
         arr = ctypes.c_void_p * n
         p = self.params_struct()
-        if done_events is None:
+        if channels != 1:
+            self.context.call("r3d_sgbm_compute_batch_cn_dev", ctypes.byref(p), n, arr(*d_lefts), arr(*d_rights), int(width),
+                              int(height), int(stride), int(channels), arr(*d_disps),
+                              arr(*done_events) if done_events is not None else None)
+        elif done_events is None:
             self.context.call("r3d_sgbm_compute_batch_dev", ctypes.byref(p), n, arr(*d_lefts), arr(*d_rights), int(width),
                               int(height), int(stride), arr(*d_disps))
         else:
@@ -101,14 +113,20 @@ class StereoSGBM:
                               int(height), int(stride), arr(*d_disps), arr(*done_events))
 
     def compute_batch(self, lefts, rights):
-        """lefts / rights: sequences of uint8 [H,W] images of equal size -> list of int16 disparity maps."""
+        """lefts / rights: sequences of uint8 images of equal size and kind ([H,W] or [H,W,3]) -> list of int16 disparity maps."""
         ctx = self.context
-        H, W = np.asarray(lefts[0]).shape
+        shape = np.asarray(lefts[0]).shape
+        if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
+            raise ValueError(f"StereoSGBM.compute_batch expects [H,W] or [H,W,3] images, got shape {shape}")
+        if any(np.asarray(a).shape != shape for a in list(lefts) + list(rights)):
+            raise ValueError("StereoSGBM.compute_batch expects images of one size and kind (all [H,W] or all [H,W,3])")
+        H, W = shape[:2]
+        cn = 1 if len(shape) == 2 else 3
         dl = [ctx.to_device(np.ascontiguousarray(a, dtype=np.uint8)) for a in lefts]
         dr = [ctx.to_device(np.ascontiguousarray(a, dtype=np.uint8)) for a in rights]
         dd = [ctx.alloc(W * H * 2) for _ in lefts]
         try:
-            self.compute_batch_device(dl, dr, W, H, W, dd)
+            self.compute_batch_device(dl, dr, W, H, W * cn, dd, channels=cn)
             ctx.sync()
             out = []
             for d in dd:
@@ -122,7 +140,8 @@ class StereoSGBM:
         return out
 
     def debug_fetch(self, want_cost=False, want_hsum=False, want_raw=True):
-        """Stage outputs of the last compute (parity tests): dict of int16 arrays."""
+        """Stage outputs of the last compute (parity tests): dict of int16 arrays.  The cost volume of a colour pair is the
+        sum over its channels."""
         ctx = self.context
         D = self._p["numDisparities"]
         minD = self._p["minDisparity"]
@@ -174,7 +193,7 @@ def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0
                       uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=STEREO_SGBM_MODE_SGBM, device=0):
     """Factory with cv2.StereoSGBM_create's keyword names and defaults.  MODE_SGBM_3WAY (the mode every reference call
     site passes) and MODE_HH (eight full-image paths, no stripes) are implemented; MODE_SGBM and MODE_HH4 raise at
-    compute().  numDisparities: a multiple of 16 up to 512 (above 256 the cost volumes use 512 slots per column: 1 KB per
+    compute().  compute() takes grey [H,W] or colour [H,W,3] pairs, as cv2 does.  numDisparities: a multiple of 16 up to 512 (above 256 the cost volumes use 512 slots per column: 1 KB per
     cost column and volume, two volumes per map in flight)."""
     return StereoSGBM(minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio,
                       speckleWindowSize, speckleRange, mode, device)

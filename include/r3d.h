@@ -98,6 +98,18 @@ int r3d_sgbm_compute(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *left
 int r3d_sgbm_compute_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
                          int32_t w, int32_t h, int32_t stride, int16_t *d_disp);
 
+/* The same for pairs of `cn` channels, as cv2.StereoSGBM.compute takes CV_8UC1 or CV_8UC3: cn = 1 (the calls above) or cn = 3,
+ * interleaved (pixel x of a row at byte x*cn, any channel order), `stride` bytes per row >= w*cn; any other cn: R3D_E_BADARG.
+ * A 3-channel pair's pixel cost is the sum over the channels of the single-channel cost of that channel's plane (OpenCV's
+ * calcPixelCostBT with cn == 3; hence the 3 in the usual P1 = 8*3*bs^2, P2 = 32*3*bs^2); everything after the block cost is
+ * unchanged.  The exact-int16 envelope carries the channel count: cn * blockSize^2 * (2*ftzero + 63) > 32767 is refused
+ * (R3D_E_UNSUPPORTED), above 16383 the call fails only if this pair's summed block cost really passes 16383 (preFilterCap 63,
+ * cn = 3: blockSize <= 5 always fits, 7 depends on the images, >= 9 is refused).  Default kernel generation only. */
+int r3d_sgbm_compute_cn(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *left, const uint8_t *right, int32_t w,
+                        int32_t h, int32_t stride, int32_t cn, int16_t *disp);
+int r3d_sgbm_compute_cn_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
+                            int32_t w, int32_t h, int32_t stride, int32_t cn, int16_t *d_disp);
+
 /* n independent pairs of equal size (a multi-view batch, BASELINE config C5, or consecutive video frames): the maps
  * are spread over up to 3 internal lanes (own stream + workspace each) so that kernels of different maps overlap;
  * forks from / joins into the ctx stream, i.e. to the caller it behaves like n r3d_sgbm_compute_dev calls. */
@@ -109,6 +121,11 @@ int r3d_sgbm_compute_batch_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_t n
 int r3d_sgbm_compute_batch_events_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_t n, const uint8_t *const *d_left,
                                       const uint8_t *const *d_right, int32_t w, int32_t h, int32_t stride, int16_t *const *d_disp,
                                       void *const *done_events);
+
+/* the batch for pairs of cn channels (1 or 3, as r3d_sgbm_compute_cn); done_events may be NULL (no events) */
+int r3d_sgbm_compute_batch_cn_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_t n, const uint8_t *const *d_left,
+                                  const uint8_t *const *d_right, int32_t w, int32_t h, int32_t stride, int32_t cn,
+                                  int16_t *const *d_disp, void *const *done_events);
 
 /* cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) on an int16 image, in place (host buffer): the last stage of
  * StereoSGBM.compute when speckleWindowSize > 0 (Calib_depth/depth4.py:164-165, depth_test.py:170-171) */
@@ -122,7 +139,7 @@ int r3d_set_profiling(r3d_ctx *ctx, int enabled);
 int r3d_sgbm_profile(r3d_ctx *ctx, float *ms, int32_t max_slots, char *names, int32_t names_bytes);
 
 /* debug / stage parity: copies intermediate results of the LAST sgbm call to HOST buffers (NULL = skip).
- *   cost   int16 [h][w1][dp]  aggregated block cost C (dp = the smallest of 32 / 64 / 128 / 256 / 512 that holds D, of 128 / 256
+ *   cost   int16 [h][w1][dp]  aggregated block cost C, summed over the channels of a colour pair (dp = the smallest of 32 / 64 / 128 / 256 / 512 that holds D, of 128 / 256
  *                             under R3D_SGM_IMPL=v1 / v3; entries d>=D undefined).  A volume is h*w1*dp*2 bytes, which
  *                             passes 4 GiB at 8 MP with dp = 512: the host buffers must hold that much.
  *   hsum   int16 [h][w1][dp]  MODE_SGBM_3WAY: L_left + L_right; MODE_HH: S after the first seven directions (the eighth is fused
