@@ -220,6 +220,41 @@ def fgs_filter(src, ch, cv, lam, lambda_attenuation=0.25, num_iter=3):
     return cur
 
 
+def _fgs_pass64(cur, C, lam):
+    """_fgs_pass with every operation in float64 (cur float64, C the float32 weights, lam the float32 lambda): the
+    reference the float32 operation orders are measured against."""
+    H, W = C.shape
+    C = C.astype(np.float64)
+    lam = float(lam)
+    cc = np.empty((H, W), np.float64)
+    c0 = lam * C[:, 0]
+    denom = 1.0 - c0
+    cc[:, 0] = c0 / denom
+    cur[:, 0] = cur[:, 0] / denom
+    for j in range(1, W):
+        a = lam * C[:, j - 1]
+        c = lam * C[:, j]
+        denom = ((1.0 - a) - c) - a * cc[:, j - 1]
+        cc[:, j] = c / denom
+        cur[:, j] = (cur[:, j] - a * cur[:, j - 1]) / denom
+    for j in range(W - 2, -1, -1):
+        cur[:, j] = cur[:, j] - cc[:, j] * cur[:, j + 1]
+    return cur
+
+
+def fgs_filter64(src, ch, cv, lam, lambda_attenuation=0.25, num_iter=3):
+    """fgs_filter solved in float64: the same systems (float32 weights, the same float32-rounded lambda sequence), so the
+    difference to fgs_filter is the rounding error of the float32 recurrences alone."""
+    cur = np.array(src, np.float64, copy=True)
+    lam = f32(lam)
+    cvt = np.ascontiguousarray(cv.T)
+    for _ in range(num_iter):
+        cur = _fgs_pass64(cur, ch, lam)
+        cur = np.ascontiguousarray(_fgs_pass64(np.ascontiguousarray(cur.T), cvt, lam).T)
+        lam = f32(lam * f32(lambda_attenuation))
+    return cur
+
+
 def _box_mean_reflect101(a_int, r):
     """boxFilter(normalize=true, BORDER_REFLECT_101) of an integer-valued float plane: sums are exact in the fp64
     accumulators OpenCV uses for 32F sources, result = float32(sum * (1/k^2))."""
@@ -251,7 +286,7 @@ def wls_rois(W, H, min_disp, num_disp):
     return left, right
 
 
-def wls_confidence(disp_left, disp_right, min_disp, num_disp, radius, lrc_thresh=24):
+def wls_confidence(disp_left, disp_right, min_disp, num_disp, radius, lrc_thresh=24, roll_off=0.001):
     """computeConfidenceMap: depth-discontinuity maps of both views inside their ROIs, then the LR-consistency test;
     x255.  Pixels whose right-view partner falls outside the right ROI keep their discontinuity value [recalled]."""
     H, W = disp_left.shape
@@ -259,8 +294,8 @@ def wls_confidence(disp_left, disp_right, min_disp, num_disp, radius, lrc_thresh
     ddl = np.zeros((H, W), np.float32)
     ddr = np.zeros((H, W), np.float32)
     if lw > 0:
-        ddl[:, lx:lx + lw] = depth_discontinuity(disp_left[:, lx:lx + lw], radius)
-        ddr[:, rx:rx + rw] = depth_discontinuity(disp_right[:, rx:rx + rw], radius)
+        ddl[:, lx:lx + lw] = depth_discontinuity(disp_left[:, lx:lx + lw], radius, roll_off)
+        ddr[:, rx:rx + rw] = depth_discontinuity(disp_right[:, rx:rx + rw], radius, roll_off)
     conf = ddl.copy()
     j = np.arange(W)[None, :].repeat(H, 0)
     dl = disp_left.astype(np.int64)
@@ -277,27 +312,57 @@ def wls_confidence(disp_left, disp_right, min_disp, num_disp, radius, lrc_thresh
     return (f32(255) * conf).astype(np.float32)
 
 
-def wls_filter(disp_left, guide, disp_right, min_disp, num_disp, block_size, lam=8000.0, sigma_color=1.5,
-               lrc_thresh=24, return_confidence=False):
-    """DisparityWLSFilter::filter(disp_left, left_view, None, disp_right) of a filter made by
-    createDisparityWLSFilter(sgbm_left): int16 in, int16 out; outside the ROI the output is 16*(minD-1)."""
+def _wls_planes(disp_left, guide, disp_right, min_disp, num_disp, block_size, sigma_color, lrc_thresh, radius, roll_off):
+    """The parts of wls_filter before the smoother: -> (dl, (lx, lw), conf, ch, cv, c, dm); ch..dm are None for an empty ROI."""
     dl = np.asarray(disp_left, np.int16)
     dr = np.asarray(disp_right, np.int16)
     H, W = dl.shape
-    radius = int(np.ceil(0.5 * block_size))
+    if radius is None:
+        radius = int(np.ceil(0.5 * block_size))
     (lx, ly, lw, lh), _ = wls_rois(W, H, min_disp, num_disp)
+    conf = wls_confidence(dl, dr, min_disp, num_disp, radius, lrc_thresh, roll_off)
+    if lw <= 0:
+        return dl, (lx, lw), conf, None, None, None, None
+    g = np.asarray(guide)[:, lx:lx + lw]
+    ch, cv = fgs_weights(g, fgs_lut(sigma_color, 1 if g.ndim == 2 else g.shape[2]))
+    c = conf[:, lx:lx + lw]
+    dm = c * dl[:, lx:lx + lw].astype(np.float32)
+    return dl, (lx, lw), conf, ch, cv, c, dm
+
+
+def wls_filter(disp_left, guide, disp_right, min_disp, num_disp, block_size, lam=8000.0, sigma_color=1.5,
+               lrc_thresh=24, return_confidence=False, radius=None, num_iter=3, lambda_attenuation=0.25, roll_off=0.001,
+               return_quotient=False):
+    """DisparityWLSFilter::filter(disp_left, left_view, None, disp_right) of a filter made by
+    createDisparityWLSFilter(sgbm_left): int16 in, int16 out; outside the ROI the output is 16*(minD-1).
+    radius overrides ceil(0.5*block_size); num_iter / lambda_attenuation / roll_off are the constants the filter fixes.
+    return_quotient appends the float32 quotient before rint (ROI-sized, [H, 0] for an empty ROI)."""
+    dl, (lx, lw), conf, ch, cv, c, dm = _wls_planes(disp_left, guide, disp_right, min_disp, num_disp, block_size, sigma_color,
+                                                    lrc_thresh, radius, roll_off)
+    H, W = dl.shape
     out = np.full((H, W), 16 * (min_disp - 1), np.int16)
-    conf = wls_confidence(dl, dr, min_disp, num_disp, radius, lrc_thresh)
+    q = np.zeros((H, 0), np.float32)
     if lw > 0:
-        g = np.asarray(guide)[:, lx:lx + lw]
-        ch, cv = fgs_weights(g, fgs_lut(sigma_color, 1 if g.ndim == 2 else g.shape[2]))
-        c = conf[:, lx:lx + lw]
-        dm = c * dl[:, lx:lx + lw].astype(np.float32)
-        dmf = fgs_filter(dm, ch, cv, lam)
-        cf = fgs_filter(c, ch, cv, lam)
+        dmf = fgs_filter(dm, ch, cv, lam, lambda_attenuation, num_iter)
+        cf = fgs_filter(c, ch, cv, lam, lambda_attenuation, num_iter)
         q = dmf * (f32(1) / (cf + f32(0.00001)))
         out[:, lx:lx + lw] = np.clip(np.rint(q), -32768, 32767).astype(np.int16)
-    return (out, conf) if return_confidence else out
+    res = (out,) + ((conf,) if return_confidence else ()) + ((q,) if return_quotient else ())
+    return res if len(res) > 1 else out
+
+
+def wls_quotient64(disp_left, guide, disp_right, min_disp, num_disp, block_size, lam=8000.0, sigma_color=1.5, lrc_thresh=24,
+                   radius=None, num_iter=3, lambda_attenuation=0.25, roll_off=0.001):
+    """The quotient of wls_filter before rint with both smoother runs and the division in float64, from the same float32
+    planes (confidence, confidence * disparity, weights): what the float32 quotient would be without the rounding of the
+    recurrences.  ROI-sized float64, [H, 0] for an empty ROI."""
+    dl, (lx, lw), conf, ch, cv, c, dm = _wls_planes(disp_left, guide, disp_right, min_disp, num_disp, block_size, sigma_color,
+                                                    lrc_thresh, radius, roll_off)
+    if lw <= 0:
+        return np.zeros((dl.shape[0], 0), np.float64)
+    dmf = fgs_filter64(dm, ch, cv, lam, lambda_attenuation, num_iter)
+    cf = fgs_filter64(c, ch, cv, lam, lambda_attenuation, num_iter)
+    return dmf / (cf + float(f32(0.00001)))
 
 
 def normalize_minmax(src, alpha=0.0, beta=255.0):
