@@ -124,6 +124,24 @@ def _preload_torch():
             torch_preloaded = False
 
 
+_allow_missing = False
+
+
+def use_library(path, allow_missing=False):
+    """Binds another build of libr3d_hip.so instead of lib/libr3d_hip.so; call it BEFORE the first load() (the A/B tools time
+    the library of another commit against this one, process by process).  allow_missing: entry points that build does not
+    export stay unbound (calling one raises AttributeError) instead of failing the load.  Returns the unbound names."""
+    global LIB_PATH, _allow_missing
+    if _lib is not None:
+        raise RuntimeError("use_library: the library is already loaded")
+    LIB_PATH, _allow_missing = os.path.abspath(path), bool(allow_missing)
+    if not allow_missing:
+        return []
+    _preload_torch()
+    lib = ctypes.CDLL(LIB_PATH)
+    return [name for name in _SIGS if not hasattr(lib, name)]
+
+
 def load():
     """Loads libr3d_hip.so (no GPU needed to dlopen; any compute call needs one)."""
     global _lib
@@ -135,6 +153,8 @@ def load():
         _preload_torch()
         lib = ctypes.CDLL(LIB_PATH)
         for name, (argt, rest) in _SIGS.items():
+            if _allow_missing and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.argtypes = argt
             fn.restype = rest

@@ -20,6 +20,9 @@ _lib.register({
     "r3d_disparity_to_cloud_dev": ([_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double, _vp,
                                     ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, _vp, _vp,
                                     ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "r3d_disparity_to_cloud_color_dev": ([_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double, _vp,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
     "r3d_knn_graph": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, _vp, _vp], ctypes.c_int),
     "r3d_orient_normals": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp], ctypes.c_int),
     "r3d_orient_normals_graph": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int64, _vp], ctypes.c_int),
@@ -127,6 +130,9 @@ _lib.register({
     "r3d_model_download": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "r3d_disparity_to_cloud_resident": ([_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double, _vp,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _i64p], ctypes.c_int),
+    "r3d_disparity_to_cloud_color_resident": ([_vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double, _vp,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp, _i64p], ctypes.c_int),
     "r3d_icp_dev": ([_vp, ctypes.POINTER(_lib.IcpParams), _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp,
                      ctypes.POINTER(_lib.IcpStats)], ctypes.c_int),
     "r3d_transform_points_dev": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp], ctypes.c_int),
@@ -194,10 +200,22 @@ def reproject_disparity(disp, Q, min_disparity=0, want_pixels=False, ctx=None):
     return (out, pix[:m.value].copy()) if want_pixels else out
 
 
+def _color_args(d_color, width, color_stride, color_channels, color_order):
+    """The four colour arguments of the r3d_disparity_to_cloud_color_* entry points (the library checks channels and stride)."""
+    if color_order not in ("bgr", "rgb"):
+        raise ValueError(f"color_order must be 'bgr' or 'rgb', got {color_order!r}")
+    cn = int(color_channels)
+    return _vp(d_color), int(color_stride) if color_stride is not None else int(width) * cn, cn, int(color_order == "bgr")
+
+
 def disparity_to_cloud_device(d_disp, width, height, Q, min_disparity=0, max_depth=None, pose=None, voxel=0.01,
-                              normal_radius=None, max_nn=30, capacity=None, ctx=None):
+                              normal_radius=None, max_nn=30, capacity=None, ctx=None, d_color=None, color_stride=None,
+                              color_channels=3, color_order="bgr"):
     """Device-resident disparity -> cloud chain (r3d_disparity_to_cloud_dev): d_disp is the device pointer (int) of an
-    int16 [height,width] map as written by StereoSGBM.compute_device.  Returns (points [M,3], normals [M,3] or None)."""
+    int16 [height,width] map as written by StereoSGBM.compute_device.  Returns (points [M,3], normals [M,3] or None).
+    d_color (device pointer of a uint8 image of the map's size; color_stride: bytes per row, default width * color_channels;
+    color_channels 1 or 3; color_order "bgr" as cv2 stores it, or "rgb") colours the cloud from that image
+    (r3d_disparity_to_cloud_color_dev): returns (points, normals, colors [M,3] in r, g, b order, byte / 255)."""
     ctx = ctx or _lib.default_context()
     Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(4, 4)
     P = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(4, 4)
@@ -205,11 +223,15 @@ def disparity_to_cloud_device(d_disp, width, height, Q, min_disparity=0, max_dep
     pts = np.empty((cap, 3))
     nrm = np.empty((cap, 3)) if max_nn and max_nn > 0 else None
     m = ctypes.c_int64()
-    ctx.call("r3d_disparity_to_cloud_dev", _vp(d_disp), int(width), int(height), _ptr(Q), int(min_disparity) * 16,
-             float(max_depth) if max_depth else -1.0, _ptr(P), float(voxel) if voxel else -1.0,
-             float(normal_radius) if normal_radius else -1.0, int(max_nn) if max_nn else 0, cap, _ptr(pts), _ptr(nrm),
-             ctypes.byref(m))
-    return pts[:m.value].copy(), (nrm[:m.value].copy() if nrm is not None else None)
+    head = (_vp(d_disp), int(width), int(height), _ptr(Q), int(min_disparity) * 16, float(max_depth) if max_depth else -1.0, _ptr(P),
+            float(voxel) if voxel else -1.0, float(normal_radius) if normal_radius else -1.0, int(max_nn) if max_nn else 0)
+    if d_color is None:
+        ctx.call("r3d_disparity_to_cloud_dev", *head, cap, _ptr(pts), _ptr(nrm), ctypes.byref(m))
+        return pts[:m.value].copy(), (nrm[:m.value].copy() if nrm is not None else None)
+    col = np.empty((cap, 3))
+    ctx.call("r3d_disparity_to_cloud_color_dev", *head, *_color_args(d_color, width, color_stride, color_channels, color_order), cap,
+             _ptr(pts), _ptr(nrm), _ptr(col), ctypes.byref(m))
+    return pts[:m.value].copy(), (nrm[:m.value].copy() if nrm is not None else None), col[:m.value].copy()
 
 
 def knn_graph(points, k, radius=0.0, want_d2=True, ctx=None):
@@ -428,17 +450,26 @@ class ResidentModel:
 
 
 def disparity_to_cloud_resident(d_disp, width, height, Q, d_out_points, d_out_normals, capacity, min_disparity=0, max_depth=None,
-                                pose=None, voxel=0.01, normal_radius=None, max_nn=30, ctx=None):
+                                pose=None, voxel=0.01, normal_radius=None, max_nn=30, ctx=None, d_color=None, color_stride=None,
+                                color_channels=3, color_order="bgr", d_out_colors=None):
     """r3d_disparity_to_cloud_resident: like disparity_to_cloud_device, but the cloud is written to the caller's DEVICE buffers
-    (pointers as ints, `capacity` triplets each; e.g. torch tensors' data_ptr()).  Returns the number of points."""
+    (pointers as ints, `capacity` triplets each; e.g. torch tensors' data_ptr()).  Returns the number of points.
+    d_color / color_stride / color_channels / color_order as in disparity_to_cloud_device; the colours go to d_out_colors
+    (r3d_disparity_to_cloud_color_resident)."""
     ctx = ctx or _lib.default_context()
     Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(4, 4)
     P = None if pose is None else np.ascontiguousarray(pose, dtype=np.float64).reshape(4, 4)
     m = ctypes.c_int64()
-    ctx.call("r3d_disparity_to_cloud_resident", _vp(d_disp), int(width), int(height), _ptr(Q), int(min_disparity) * 16,
-             float(max_depth) if max_depth else -1.0, _ptr(P), float(voxel) if voxel else -1.0,
-             float(normal_radius) if normal_radius else -1.0, int(max_nn) if max_nn else 0, int(capacity), _vp(d_out_points),
-             _vp(d_out_normals) if d_out_normals else None, ctypes.byref(m))
+    head = (_vp(d_disp), int(width), int(height), _ptr(Q), int(min_disparity) * 16, float(max_depth) if max_depth else -1.0, _ptr(P),
+            float(voxel) if voxel else -1.0, float(normal_radius) if normal_radius else -1.0, int(max_nn) if max_nn else 0)
+    d_nrm = _vp(d_out_normals) if d_out_normals else None
+    if d_color is None:
+        if d_out_colors:
+            raise ValueError("d_out_colors given without d_color")
+        ctx.call("r3d_disparity_to_cloud_resident", *head, int(capacity), _vp(d_out_points), d_nrm, ctypes.byref(m))
+    else:
+        ctx.call("r3d_disparity_to_cloud_color_resident", *head, *_color_args(d_color, width, color_stride, color_channels, color_order),
+                 int(capacity), _vp(d_out_points), d_nrm, _vp(d_out_colors) if d_out_colors else None, ctypes.byref(m))
     return m.value
 
 

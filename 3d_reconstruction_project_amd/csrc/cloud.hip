@@ -543,8 +543,45 @@ __global__ void __launch_bounds__(256) k_seg_starts(const int *__restrict__ flag
 // (A form that staged 64 voxels' members through LDS windows was measured 3x SLOWER: where voxels are larger than the window only
 // one lane walks at a time; 16 members per thread and round trip instead of 8: 2x slower.)
 constexpr int VM_BIG = 192;
-template <class T>
-__global__ void __launch_bounds__(256) k_voxel_mean_t(const double *__restrict__ a, const int *__restrict__ idx, const int *__restrict__ starts,
+// What member j of the index list contributes is the kernels' LD parameter: fetch(j) issues the member's loads and returns what
+// they bring, value() turns that into the three summands -- two steps, so that a kernel can keep several members' loads in
+// flight before the first conversion waits for one.  MemberXyz: row j of a float64 [n,3] array.
+struct MemberXyz {
+    struct Raw { double x, y, z; };
+    const double *__restrict__ a;
+    __device__ __forceinline__ Raw fetch(int64_t j) const { return Raw{a[j * 3], a[j * 3 + 1], a[j * 3 + 2]}; }
+    template <class T>
+    static __device__ __forceinline__ void value(const Raw &m, T &x, T &y, T &z) { x = (T)m.x; y = (T)m.y; z = (T)m.z; }
+};
+// MemberColor<CN>: the colour of the pixel that compacted point j came from (pix[j], the row-major index k_reproject wrote), read
+// from a uint8 image with CN = 1 or 3 interleaved channels: (double)byte / 255.0 as k_backproject, in r, g, b order (bgr: the
+// pixel's bytes are b, g, r).  No [w*h,3] float64 colour array ever exists: the means are summed from the bytes.  CN is a template
+// parameter so that a pixel's bytes sit at constant offsets from one address.  (Read off the gfx950 listing, hipcc -S, of
+// k_voxel_mean_t: with run-time channel offsets a thread's eight members were fetched channel by channel, three dependent groups
+// of eight byte loads; in this form a 3-channel pixel is one 16-bit and one 8-bit load and the eight members go out as two groups
+// of eight loads.  The two forms were not timed against each other.)
+struct ColorImage { const unsigned char *img; int w, stride, bgr; };
+template <int CN>
+struct MemberColor {
+    struct Raw { unsigned char v[CN]; };
+    const int *__restrict__ pix;
+    ColorImage c;
+    __device__ __forceinline__ Raw fetch(int64_t j) const {
+        const int p = pix[j];
+        const unsigned char *__restrict__ q = c.img + (int64_t)(p / c.w) * c.stride + (p % c.w) * CN;
+        Raw m;
+#pragma unroll
+        for (int k = 0; k < CN; k++) m.v[k] = q[k];
+        return m;
+    }
+    template <class T>
+    __device__ __forceinline__ void value(const Raw &m, T &r, T &g, T &b) const {
+        const unsigned char v0 = m.v[0], v1 = m.v[CN / 2], v2 = m.v[CN - 1];
+        r = (T)((double)(c.bgr ? v2 : v0) / 255.0); g = (T)((double)v1 / 255.0); b = (T)((double)(c.bgr ? v0 : v2) / 255.0);
+    }
+};
+template <class T, class LD>
+__global__ void __launch_bounds__(256) k_voxel_mean_t(LD ld, const int *__restrict__ idx, const int *__restrict__ starts,
                                                       int64_t nseg, int64_t n, double *__restrict__ out, int *__restrict__ big_list,
                                                       int *__restrict__ big_count) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -563,11 +600,14 @@ __global__ void __launch_bounds__(256) k_voxel_mean_t(const double *__restrict__
     T x = 0, y = 0, z = 0;
     for (int i0 = b; i0 < e; i0 += 8) {
         int64_t j[8];
+        typename LD::Raw m[8];
         T X[8], Y[8], Z[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) j[u] = idx[min(i0 + u, e - 1)];
 #pragma unroll
-        for (int u = 0; u < 8; u++) { X[u] = (T)a[j[u] * 3]; Y[u] = (T)a[j[u] * 3 + 1]; Z[u] = (T)a[j[u] * 3 + 2]; }
+        for (int u = 0; u < 8; u++) m[u] = ld.fetch(j[u]);
+#pragma unroll
+        for (int u = 0; u < 8; u++) ld.value(m[u], X[u], Y[u], Z[u]);
 #pragma unroll
         for (int u = 0; u < 8; u++)
             if (i0 + u < e) { x += X[u]; y += Y[u]; z += Z[u]; }
@@ -609,8 +649,8 @@ __global__ void __launch_bounds__(256) k_voxel_mean_sorted(const double *__restr
 }
 __device__ __forceinline__ double readlane_t(double v, int l) { return __longlong_as_double((long long)readlane_u64((unsigned long long)__double_as_longlong(v), l)); }
 __device__ __forceinline__ float readlane_t(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-template <class T>
-__global__ void __launch_bounds__(64) k_voxel_mean_big(const double *__restrict__ a, const int *__restrict__ idx, const int *__restrict__ starts,
+template <class T, class LD>
+__global__ void __launch_bounds__(64) k_voxel_mean_big(LD ld, const int *__restrict__ idx, const int *__restrict__ starts,
                                                        int64_t nseg, int64_t n, double *__restrict__ out, const int *__restrict__ big_list,
                                                        const int *__restrict__ big_count) {
     const int lane = threadIdx.x, nbig = *big_count;
@@ -618,14 +658,13 @@ __global__ void __launch_bounds__(64) k_voxel_mean_big(const double *__restrict_
         const int64_t s = big_list[q];
         const int b = starts[s], e = s + 1 < nseg ? starts[s + 1] : (int)n;
         T x = 0, y = 0, z = 0;
-        int64_t j = idx[min(b + lane, e - 1)];
-        T X = (T)a[j * 3], Y = (T)a[j * 3 + 1], Z = (T)a[j * 3 + 2];
+        T X, Y, Z;
+        ld.value(ld.fetch(idx[min(b + lane, e - 1)]), X, Y, Z);
         for (int c = b; c < e; c += 64) {
-            const int64_t jn = idx[min(c + 64 + lane, e - 1)];                      // next chunk in flight while this one is added
-            const T Xn = (T)a[jn * 3], Yn = (T)a[jn * 3 + 1], Zn = (T)a[jn * 3 + 2];
+            const typename LD::Raw mn = ld.fetch(idx[min(c + 64 + lane, e - 1)]);   // next chunk in flight while this one is added
             const int lim = min(64, e - c);
             for (int t = 0; t < lim; t++) { x += readlane_t(X, t); y += readlane_t(Y, t); z += readlane_t(Z, t); }
-            X = Xn; Y = Yn; Z = Zn;
+            ld.value(mn, X, Y, Z);
         }
         if (lane == 0) {
             const T cnt = (T)(e - b);
@@ -2046,6 +2085,15 @@ __global__ void __launch_bounds__(256) k_reproject(const int16_t *__restrict__ d
     xyz[o * 3] = X / W; xyz[o * 3 + 1] = Y / W; xyz[o * 3 + 2] = Z / W;
     if (pix) pix[o] = (int)i;
 }
+// colours of the compacted points (no voxel grid): one thread per point
+template <int CN>
+__global__ void __launch_bounds__(256) k_gather_colors(MemberColor<CN> ld, int64_t m, double *__restrict__ rgb) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    double r, g, b;
+    ld.value(ld.fetch(i), r, g, b);
+    rgb[i * 3] = r; rgb[i * 3 + 1] = g; rgb[i * 3 + 2] = b;
+}
 
 // ------------------------------------------------------------------------------------------------ depth image -> cloud
 // open3d.geometry.PointCloud.create_from_rgbd_image(RGBDImage.create_from_color_and_depth(color, depth, depth_scale, depth_trunc,
@@ -2274,7 +2322,20 @@ struct PinRead {
     }
 };
 
-// big_ws: >= (nseg + 16) ints of scratch (the counter, then the list)
+// means of the members `ld` loads through the index list: voxels up to VM_BIG members by a thread each, the listed rest by a wave
+// each; scratch: (nseg + 16) ints (the counter, then the list)
+template <class T, class LD>
+static inline int launch_voxel_mean_ld(r3d_ctx *ctx, DevArena &ar, LD ld, const int *idx, const int *starts, int64_t nseg, int64_t n, double *out) {
+    int *ws = (int *)ar.get((size_t)(nseg + 16) * 4);
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemsetAsync(ws, 0, 64, ctx->stream));
+    const unsigned nb = (unsigned)((nseg + 255) / 256);
+    const unsigned nbig = (unsigned)std::min<int64_t>(nseg, 4096);
+    k_voxel_mean_t<T, LD><<<nb, 256, 0, ctx->stream>>>(ld, idx, starts, nseg, n, out, ws + 16, ws);
+    k_voxel_mean_big<T, LD><<<nbig, 64, 0, ctx->stream>>>(ld, idx, starts, nseg, n, out, ws + 16, ws);
+    R3D_HIP(ctx, hipGetLastError());
+    return R3D_OK;
+}
 static inline int launch_voxel_mean(r3d_ctx *ctx, DevArena &ar, bool f32, const double *a, const int *idx, const int *starts, int64_t nseg, int64_t n,
                                     double *out, const double *sorted = nullptr) {
     if (sorted) {   // `a` in sorted order is available (the sort wrote it): contiguous streams, no index list
@@ -2285,20 +2346,8 @@ static inline int launch_voxel_mean(r3d_ctx *ctx, DevArena &ar, bool f32, const 
         R3D_HIP(ctx, hipGetLastError());
         return R3D_OK;
     }
-    int *ws = (int *)ar.get((size_t)(nseg + 16) * 4);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemsetAsync(ws, 0, 64, ctx->stream));
-    const unsigned nb = (unsigned)((nseg + 255) / 256);
-    const unsigned nbig = (unsigned)std::min<int64_t>(nseg, 4096);
-    if (f32) {
-        k_voxel_mean_t<float><<<nb, 256, 0, ctx->stream>>>(a, idx, starts, nseg, n, out, ws + 16, ws);
-        k_voxel_mean_big<float><<<nbig, 64, 0, ctx->stream>>>(a, idx, starts, nseg, n, out, ws + 16, ws);
-    } else {
-        k_voxel_mean_t<double><<<nb, 256, 0, ctx->stream>>>(a, idx, starts, nseg, n, out, ws + 16, ws);
-        k_voxel_mean_big<double><<<nbig, 64, 0, ctx->stream>>>(a, idx, starts, nseg, n, out, ws + 16, ws);
-    }
-    R3D_HIP(ctx, hipGetLastError());
-    return R3D_OK;
+    if (f32) return launch_voxel_mean_ld<float>(ctx, ar, MemberXyz{a}, idx, starts, nseg, n, out);
+    return launch_voxel_mean_ld<double>(ctx, ar, MemberXyz{a}, idx, starts, nseg, n, out);
 }
 
 struct Grid {
@@ -3534,17 +3583,32 @@ int r3d_reproject_disparity(r3d_ctx *ctx, const int16_t *disp, int32_t w, int32_
     return R3D_OK;
 }
 
+// colour request of the _color entry points: the device image the cloud is coloured from and where the colours go
+struct CloudColor { const uint8_t *d_img; int32_t stride, channels, bgr; double *out; };
+
 static int disparity_to_cloud_impl(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, int32_t h, const double *Q4x4, int32_t min_valid_x16,
                                    double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
-                                   int64_t capacity, double *out_xyz, double *out_normals, int64_t *out_n, bool device_out) {
+                                   int64_t capacity, double *out_xyz, double *out_normals, int64_t *out_n, bool device_out,
+                                   const CloudColor *color = nullptr) {
     if (!ctx) return R3D_E_BADARG;
     if (!d_disp || !Q4x4 || !out_xyz || !out_n || w <= 0 || h <= 0 || capacity < 0)
         return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud: bad argument");
     if (max_nn > 128) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "disparity_to_cloud: max_nn > 128 not supported");
     if (max_nn > 0 && !out_normals) return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud: normals requested without an output array");
+    ColorImage img{};
+    if (color) {
+        if (!color->d_img) return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud_color: no colour image (the colourless entry points take none)");
+        if (color->channels != 1 && color->channels != 3)
+            return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud_color: %d colour channels, must be 1 or 3", (int)color->channels);
+        if ((int64_t)color->stride < (int64_t)w * color->channels)
+            return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud_color: row stride %d below %d pixels of %d bytes", (int)color->stride, (int)w, (int)color->channels);
+        if (!color->out) return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud_color: no output array for the colours");
+        img = ColorImage{color->d_img, w, color->stride, color->bgr};
+    }
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    double *d_p;
+    double *d_p, *d_c = nullptr;
+    int *d_pix = nullptr;
     int64_t m;
     int rc;
     // depth filter off: still drop points at infinity (W = 0, e.g. disparity 0), which no voxel grid can hold
@@ -3553,7 +3617,7 @@ static int disparity_to_cloud_impl(r3d_ctx *ctx, const int16_t *d_disp, int32_t 
     // enqueued over the upper bound w * h before the count is known; the voxel sort's test travels with the segment count; the
     // normal grid reuses the box (voxel means lie inside it)
     double box[6];
-    if ((rc = reproject_core(ctx, ar, d_disp, w, h, Q4x4, min_valid_x16, max_depth > 0 ? max_depth : 1.0e300, false, &d_p, nullptr, &m, pose4x4, box))) return rc;
+    if ((rc = reproject_core(ctx, ar, d_disp, w, h, Q4x4, min_valid_x16, max_depth > 0 ? max_depth : 1.0e300, color != nullptr, &d_p, &d_pix, &m, pose4x4, box))) return rc;
     *out_n = 0;
     if (m == 0) return R3D_OK;
     if (voxel > 0) {
@@ -3563,8 +3627,22 @@ static int disparity_to_cloud_impl(r3d_ctx *ctx, const int16_t *d_disp, int32_t 
         if (ar.rc) return ar.rc;
         if ((rc = launch_voxel_mean(ctx, ar, false, d_p, V.idx, V.starts, V.nseg, m, d_v, V.sorted))) return rc;
         R3D_HIP(ctx, hipGetLastError());
+        if (color) {   // voxel colours straight from the image bytes, in the members' order (the pose does not touch colours)
+            d_c = (double *)ar.get((size_t)V.nseg * 24);
+            if (ar.rc) return ar.rc;
+            if (color->channels == 3) rc = launch_voxel_mean_ld<double>(ctx, ar, MemberColor<3>{d_pix, img}, V.idx, V.starts, V.nseg, m, d_c);
+            else rc = launch_voxel_mean_ld<double>(ctx, ar, MemberColor<1>{d_pix, img}, V.idx, V.starts, V.nseg, m, d_c);
+            if (rc) return rc;
+        }
         d_p = d_v;
         m = V.nseg;
+    } else if (color) {
+        d_c = (double *)ar.get((size_t)m * 24);
+        if (ar.rc) return ar.rc;
+        const unsigned nb = (unsigned)((m + 255) / 256);
+        if (color->channels == 3) k_gather_colors<3><<<nb, 256, 0, ctx->stream>>>(MemberColor<3>{d_pix, img}, m, d_c);
+        else k_gather_colors<1><<<nb, 256, 0, ctx->stream>>>(MemberColor<1>{d_pix, img}, m, d_c);
+        R3D_HIP(ctx, hipGetLastError());
     }
     *out_n = m;
     if (m > capacity) return r3d_fail(ctx, R3D_E_BADARG, "disparity_to_cloud: %lld points, output arrays hold %lld", (long long)m, (long long)capacity);
@@ -3573,6 +3651,7 @@ static int disparity_to_cloud_impl(r3d_ctx *ctx, const int16_t *d_disp, int32_t 
     const hipMemcpyKind kind = device_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     R3D_HIP(ctx, hipMemcpyAsync(out_xyz, d_p, (size_t)m * 24, kind, ctx->stream));
     if (d_n) R3D_HIP(ctx, hipMemcpyAsync(out_normals, d_n, (size_t)m * 24, kind, ctx->stream));
+    if (d_c) R3D_HIP(ctx, hipMemcpyAsync(color->out, d_c, (size_t)m * 24, kind, ctx->stream));
     // device outputs stay ordered on the context stream (the caller's next kernel or collective on that stream sees them);
     // the arena is only reused by later calls on the same stream, so no wait is needed here either
     if (!device_out) R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3593,6 +3672,26 @@ int r3d_disparity_to_cloud_resident(r3d_ctx *ctx, const int16_t *d_disp, int32_t
     R3D_ROCTX_RANGE("r3d_disparity_to_cloud_resident");
     return disparity_to_cloud_impl(ctx, d_disp, w, h, Q4x4, min_valid_x16, max_depth, pose4x4, voxel, normal_radius, max_nn, capacity,
                                    d_out_xyz, d_out_normals, out_n, true);
+}
+
+int r3d_disparity_to_cloud_color_dev(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, int32_t h, const double *Q4x4, int32_t min_valid_x16,
+                                     double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
+                                     const uint8_t *d_color, int32_t color_stride, int32_t color_channels, int32_t color_bgr,
+                                     int64_t capacity, double *out_xyz, double *out_normals, double *out_colors, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_disparity_to_cloud_color_dev");
+    const CloudColor color{d_color, color_stride, color_channels, color_bgr, out_colors};
+    return disparity_to_cloud_impl(ctx, d_disp, w, h, Q4x4, min_valid_x16, max_depth, pose4x4, voxel, normal_radius, max_nn, capacity,
+                                   out_xyz, out_normals, out_n, false, &color);
+}
+
+int r3d_disparity_to_cloud_color_resident(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, int32_t h, const double *Q4x4, int32_t min_valid_x16,
+                                          double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
+                                          const uint8_t *d_color, int32_t color_stride, int32_t color_channels, int32_t color_bgr,
+                                          int64_t capacity, double *d_out_xyz, double *d_out_normals, double *d_out_colors, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_disparity_to_cloud_color_resident");
+    const CloudColor color{d_color, color_stride, color_channels, color_bgr, d_out_colors};
+    return disparity_to_cloud_impl(ctx, d_disp, w, h, Q4x4, min_valid_x16, max_depth, pose4x4, voxel, normal_radius, max_nn, capacity,
+                                   d_out_xyz, d_out_normals, out_n, true, &color);
 }
 
 int r3d_align_point_clouds(r3d_ctx *ctx, const r3d_align_params *p, const double *src, const double *src_colors, int64_t ns,

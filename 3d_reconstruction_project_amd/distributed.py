@@ -149,6 +149,27 @@ def _all_gather_fixed(t):
     return out
 
 
+def common_planes(local):
+    """Plane count of the view tensors of ALL ranks: 2 (points, normals) or 3 (+ colours).  local: this rank's {view_id: tensor}.
+    Raises ValueError on EVERY rank when the views disagree, here or across ranks (one tiny collective carries each rank's
+    count, so no rank is left waiting in the payload exchange, whose shape depends on it); a rank without views follows the rest."""
+    import torch
+    counts = sorted({int(t.shape[0]) if t.dim() == 3 else -1 for t in local.values()})
+    mine = 0 if not counts else (counts[0] if len(counts) == 1 and counts[0] in (2, 3) else -1)
+    d = _dist()
+    if d is not None and (d.get_world_size() > 1 or os.environ.get("R3D_FORCE_DIST")):
+        seen = _all_gather_fixed(torch.tensor([mine], dtype=torch.int64, device=exchange_device())).cpu().numpy().reshape(-1)
+    else:
+        seen = np.array([mine])
+    seen = sorted({int(c) for c in seen} - {0})
+    if mine == -1:
+        raise ValueError(f"every view must be a [2, n, 3] tensor or every view a [3, n, 3] tensor; this rank holds {[tuple(t.shape) for t in local.values()]}")
+    if len(seen) > 1:
+        raise ValueError("every view must be a [2, n, 3] tensor or every view a [3, n, 3] tensor (colours on all views or on none); "
+                         f"the ranks hold plane counts {seen}")
+    return seen[0] if seen else 2
+
+
 def gather_views(local, n_views, planes=2):
     """The exchange step.  local: {view_id: tensor [planes, n_v, 3] float64} owned by this rank (plane 0 = points, plane 1 =
     normals), all on exchange_device().  Returns {view_id: tensor [planes, n_v, 3]} for ALL views on every rank; the tensors

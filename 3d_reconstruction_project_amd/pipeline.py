@@ -139,59 +139,101 @@ def scaled_Q(Q, scale, unit=1.0):
     return Q
 
 
+def _color_image(color, left, H, W):
+    """The image a view's cloud is coloured from: `left` itself (color=True) or a uint8 [H,W] / [H,W,3] array of the pair's size."""
+    img = left if color is True else np.asarray(color)
+    if img.dtype != np.uint8 or img.shape[:2] != (H, W) or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+        raise ValueError(f"color: expected a uint8 image [{H},{W}] or [{H},{W},3], got {img.dtype} {tuple(img.shape)}")
+    return np.ascontiguousarray(img)
+
+
 def view_to_cloud(left, right, Q, matcher, voxel=0.01, normal_radius=None, max_nn=30, pose=None, max_depth=None,
-                  device_resident=True):
-    """One stereo view -> down-sampled cloud with normals.  pose (4x4, optional) is applied to the cloud.
+                  device_resident=True, color=None, color_order="bgr"):
+    """One stereo view -> down-sampled cloud with normals.  pose (4x4, optional) is applied to the cloud.  left / right: uint8
+    [H,W] or [H,W,3] (BGR pairs, as the matcher takes them).
     device_resident (default): the disparity map never leaves HBM; the matcher writes it with compute_device and
     r3d_disparity_to_cloud_dev chains reprojection, depth filter, pose, voxel grid and normals on the device, so only the
     two input images go up and the final cloud comes down.  False: the same stages through the host-buffer entry points
-    (identical results; kept for callers that want the intermediate arrays)."""
+    (identical results; kept for callers that want the intermediate arrays).
+    color: None (no colours, as before), True (colour the cloud from `left`) or a uint8 [H,W] / [H,W,3] image of the pair's
+    size (e.g. the rectified BGR frame of a grey pair); color_order "bgr" (cv2) or "rgb" says how a 3-channel image is stored.
+    The cloud's .colors are r, g, b in [0, 1]; a voxel's colour is the mean over its members."""
+    if color_order not in ("bgr", "rgb"):
+        raise ValueError(f"color_order must be 'bgr' or 'rgb', got {color_order!r}")
+    L = np.ascontiguousarray(left, dtype=np.uint8)
+    R = np.ascontiguousarray(right, dtype=np.uint8)
+    H, W = L.shape[:2]
+    cn = 1 if L.ndim == 2 else L.shape[2]
+    img = None if color is None else _color_image(color, L, H, W)
     if device_resident:
         ctx = matcher.context
-        L = np.ascontiguousarray(left, dtype=np.uint8)
-        R = np.ascontiguousarray(right, dtype=np.uint8)
-        H, W = L.shape
         d_l, d_r, d_d = ctx.to_device(L), ctx.to_device(R), ctx.alloc(W * H * 2)
+        d_c = None
         try:
-            matcher.compute_device(d_l, d_r, W, H, W, d_d)
-            pts, nrm = cloud_ops.disparity_to_cloud_device(d_d, W, H, Q, matcher.getMinDisparity(), max_depth, pose, voxel,
-                                                           normal_radius or 2 * voxel, max_nn, ctx=ctx)
+            matcher.compute_device(d_l, d_r, W, H, W * cn, d_d, channels=cn)
+            ckw = {}
+            if img is not None:
+                d_c = d_l if img is L else ctx.to_device(img)
+                ckw = dict(d_color=d_c, color_channels=1 if img.ndim == 2 else 3, color_order=color_order)
+            res = cloud_ops.disparity_to_cloud_device(d_d, W, H, Q, matcher.getMinDisparity(), max_depth, pose, voxel,
+                                                      normal_radius or 2 * voxel, max_nn, ctx=ctx, **ckw)
         finally:
-            for p in (d_l, d_r, d_d):
+            for p in (d_l, d_r, d_d) + ((d_c,) if d_c is not None and d_c != d_l else ()):
                 ctx.free(p)
-        return PointCloud(pts, normals=nrm) if len(pts) else PointCloud()
-    disp = matcher.compute(left, right)
-    pts = cloud_ops.reproject_disparity(disp, Q, matcher.getMinDisparity())
+        if not len(res[0]):
+            return PointCloud()
+        return PointCloud(res[0], res[2] if img is not None else None, res[1])
+    disp = matcher.compute(L, R)
+    pts, pix = cloud_ops.reproject_disparity(disp, Q, matcher.getMinDisparity(), want_pixels=True)
     if len(pts):                                       # zero disparities reproject to infinity (W = 0): never part of a cloud
-        pts = pts[np.abs(pts[:, 2]) <= (max_depth if max_depth is not None else 1.0e300)]
+        keep = np.abs(pts[:, 2]) <= (max_depth if max_depth is not None else 1.0e300)
+        pts, pix = pts[keep], pix[keep]
     if len(pts) == 0:
         return PointCloud()
+    cols = None
+    if img is not None:
+        cols = img.reshape(H * W, -1)[pix] / 255.0
+        cols = np.repeat(cols, 3, 1) if cols.shape[1] == 1 else (cols[:, ::-1] if color_order == "bgr" else cols)
     if pose is not None:
         pts = cloud_ops.transform_points(pts, pose)
-    pts, _, _ = cloud_ops.voxel_down_sample(pts, voxel)
+    pts, cols, _ = cloud_ops.voxel_down_sample(pts, voxel, colors=cols)
     nrm = cloud_ops.estimate_normals(pts, normal_radius or 2 * voxel, max_nn)
-    return PointCloud(pts, normals=nrm)
+    return PointCloud(pts, cols, nrm)
+
+
+def _color_out(out, d_color):
+    """Where the colours of a device-tensor view chain go: plane 2 of a [3, capacity, 3] `out` (None without a colour image)."""
+    if d_color is None:
+        return None
+    if out.dim() != 3 or out.shape[0] != 3 or out.shape[2] != 3:
+        raise ValueError(f"out: with d_color a [3, capacity, 3] tensor is needed (plane 2 receives the colours), got {tuple(out.shape)}")
+    return out[2].data_ptr()
 
 
 def view_to_cloud_tensors(d_left, d_right, d_disp, width, height, Q, matcher, out, voxel=0.01, normal_radius=None, max_nn=30,
-                          pose=None, max_depth=None):
+                          pose=None, max_depth=None, d_color=None, color_stride=None, color_channels=3, color_order="bgr"):
     """One stereo view whose images are already in HBM -> cloud left in HBM.  d_left / d_right / d_disp: device pointers
     (uint8 images, int16 disparity scratch); out: float64 torch tensor [2, capacity, 3] on the matcher's device that receives
     points (plane 0) and normals (plane 1).  Returns the tensor view out[:, :n] ([2, n, 3]).  Nothing crosses PCIe but the
     point count.  The library kernels are ordered with torch's current stream (distributed.shared_stream): whatever torch
-    queued on the inputs before the call is seen, and torch ops / collectives queued on `out` afterwards see the cloud."""
+    queued on the inputs before the call is seen, and torch ops / collectives queued on `out` afterwards see the cloud.
+    d_color (device pointer of a uint8 image of the map's size; color_stride / color_channels / color_order as in
+    cloud_ops.disparity_to_cloud_device): `out` must then be [3, capacity, 3] and plane 2 receives the colours.  The matched
+    images d_left / d_right are one-channel with rows `width` bytes apart; only d_color may have three channels."""
     ctx = matcher.context
+    d_out_colors = _color_out(out, d_color)
     with distributed.shared_stream(ctx):
         matcher.compute_device(d_left, d_right, width, height, width, d_disp)
         cap = out.shape[1]
         n = cloud_ops.disparity_to_cloud_resident(d_disp, width, height, Q, out[0].data_ptr(), out[1].data_ptr(), cap,
                                                   matcher.getMinDisparity(), max_depth, pose, voxel, normal_radius or 2 * voxel,
-                                                  max_nn, ctx=ctx)
+                                                  max_nn, ctx=ctx, d_color=d_color, color_stride=color_stride,
+                                                  color_channels=color_channels, color_order=color_order, d_out_colors=d_out_colors)
     return out[:, :n]
 
 
 def views_to_cloud_tensors(pairs, d_disps, width, height, Q, matcher, outs, cloud_ctx, voxel=0.01, normal_radius=None, max_nn=30,
-                           poses=None, max_depth=None):
+                           poses=None, max_depth=None, d_colors=None, color_stride=None, color_channels=3, color_order="bgr"):
     """Several views owned by ONE GPU (a rank that holds more than one view of the C5 batch): the same results as one
     view_to_cloud_tensors call per view, but the SGM maps go through the matcher's batch entry point (three maps in flight on
     the library's lanes, r3d_sgbm_compute_batch_events_dev) and the cloud stages of view i (reprojection -> voxel grid ->
@@ -199,11 +241,18 @@ def views_to_cloud_tensors(pairs, d_disps, width, height, Q, matcher, outs, clou
     with its own stream and arena, or a LIST of them -- the cloud stages are a chain of small kernels with host round trips in
     between, so each extra context gets its own host thread (ctypes releases the GIL) and the chains of different views overlap.
     pairs: [(d_left, d_right)] device pointers; d_disps: one int16 device buffer PER view; outs: one [2, capacity, 3] float64
-    tensor per view.  Returns [out_i[:, :n_i]]."""
+    tensor per view.  Returns [out_i[:, :n_i]].
+    d_colors: one device uint8 image per view (color_stride / color_channels / color_order as in view_to_cloud_tensors); every
+    outs[i] must then be [3, capacity, 3] and its plane 2 receives the colours.  The matched pairs are one-channel images with
+    rows `width` bytes apart; only the colour images may have three channels."""
     import torch
     ctx = matcher.context
     n = len(pairs)
     cctxs = list(cloud_ctx) if isinstance(cloud_ctx, (list, tuple)) else [cloud_ctx]
+    if d_colors is not None and len(d_colors) != n:
+        raise ValueError(f"d_colors: {len(d_colors)} images for {n} views")
+    d_cols = list(d_colors) if d_colors is not None else [None] * n
+    d_out_cols = [_color_out(o, c) for o, c in zip(outs, d_cols)]
     assert len(d_disps) == n and len(outs) == n and all(c is not ctx for c in cctxs) and len({id(c) for c in cctxs}) == len(cctxs)
     dev = outs[0].device
     evs = [ctx.event() for _ in range(n)]
@@ -230,7 +279,9 @@ def views_to_cloud_tensors(pairs, d_disps, width, height, Q, matcher, outs, clou
                         k = cloud_ops.disparity_to_cloud_resident(d_disps[i], width, height, Q, outs[i][0].data_ptr(), outs[i][1].data_ptr(),
                                                                   outs[i].shape[1], matcher.getMinDisparity(), max_depth,
                                                                   None if poses is None else poses[i], voxel, normal_radius or 2 * voxel,
-                                                                  max_nn, ctx=c)
+                                                                  max_nn, ctx=c, d_color=d_cols[i], color_stride=color_stride,
+                                                                  color_channels=color_channels, color_order=color_order,
+                                                                  d_out_colors=d_out_cols[i])
                         res[i] = outs[i][:, :k]
                 if len(cctxs) == 1:
                     chain(0)
@@ -262,6 +313,9 @@ def multi_view_fuse_tensors(local, n_views, threshold=0.02, mode=cloud_ops.GICP,
     [2, N, 3] tensor, which every rank ends up holding (rank 0 hands it to the mesher, mesh_reconstruction.py:22-37).
     Returns (fused tensor, {view_id: T}).  `register(src [2,n,3], tgt [2,m,3]) -> 4x4` and `transform(block, T) -> block`
     replace the HIP calls in the CPU (gloo) tests; with device tensors and no stubs the HIP library does the work.
+    Views may carry a third plane, colours ([3, n, 3], pipeline.view_to_cloud_tensors with d_color): it travels through the same
+    all-gather and is copied unchanged into a fused [3, N, 3] tensor (the stubs still see and return planes 0 and 1 only).  All
+    views must have the same number of planes: ValueError otherwise, on every rank, before the first collective.
     timings (dict, optional) receives exchange_ms / register_ms / fuse_ms measured with events on the shared stream.
     (A rank that owns several views registers them one after the other: running them on several contexts / host threads at
     once was measured -- 7 registrations of 109 k-point clouds: 2.8 ms sequential, 3.3-3.8 ms on two contexts, 2.5-3.0 ms on
@@ -304,8 +358,9 @@ def _multi_view_fuse_on_stream(local, n_views, threshold, mode, max_iteration, r
         b.synchronize()
         return a.elapsed_time(b)
 
+    planes = distributed.common_planes(local)            # 2, or 3 with colours; raises on every rank if the views disagree
     t0 = mark()
-    everyone = distributed.gather_views(local, n_views)
+    everyone = distributed.gather_views(local, n_views, planes=planes)
     t1 = mark()
     ref = everyone[0]
     mine = {}
@@ -317,7 +372,7 @@ def _multi_view_fuse_on_stream(local, n_views, threshold, mode, max_iteration, r
             if v == 0:
                 return np.eye(4)
             if register is not None:
-                return np.asarray(register(everyone[v], ref), dtype=np.float64)
+                return np.asarray(register(everyone[v][:2], ref[:2]), dtype=np.float64)
             src = everyone[v]
             return cloud_ops.registration_device(src[0].data_ptr(), src.shape[1], ref[0].data_ptr(), ref.shape[1], threshold,
                                                  mode=mode, max_iteration=max_iteration, d_source_normals=src[1].data_ptr(),
@@ -329,13 +384,15 @@ def _multi_view_fuse_on_stream(local, n_views, threshold, mode, max_iteration, r
     t2 = mark()
     Ts = distributed.gather_transforms(mine, n_views)
     total = sum(everyone[v].shape[1] for v in range(n_views))
-    fused = torch.empty((2, total, 3), dtype=torch.float64, device=dev)
+    fused = torch.empty((planes, total, 3), dtype=torch.float64, device=dev)
     o = 0
     blocks = []
     for v in range(n_views):
         blk, n = everyone[v], everyone[v].shape[1]
+        if planes == 3:
+            fused[2, o:o + n] = blk[2]                 # colours: no rigid transform touches them
         if transform is not None:
-            fused[:, o:o + n] = transform(blk, Ts[v])
+            fused[:2, o:o + n] = transform(blk[:2], Ts[v])
         elif n:
             blocks.append((blk[0].data_ptr(), n, Ts[v], fused[0, o:o + n].data_ptr(), False))
             blocks.append((blk[1].data_ptr(), n, Ts[v], fused[1, o:o + n].data_ptr(), True))
@@ -352,13 +409,15 @@ def multi_view_fuse(local_clouds, n_views, threshold=0.02, mode=cloud_ops.GICP, 
     """Host-cloud front end of multi_view_fuse_tensors.  local_clouds: {view_id: PointCloud with normals} owned by this rank.
     The clouds go up once (to the device the exchange runs on), everything else stays there; returns
     (fused PointCloud, {view_id: T}).  `register(src [n,6], tgt [m,6]) -> 4x4` may replace the HIP registration (the CPU tests
-    inject a stub; rows are xyz | normal)."""
+    inject a stub; rows are xyz | normal).  Clouds with colours keep them: the colours ride along as a third plane and the fused
+    cloud has .colors; colours on some views only (on any rank) raise ValueError."""
     import torch
     dev = distributed.exchange_device()
     local = {}
     for v, pc in local_clouds.items():
-        p, _, n = as_arrays(pc)
-        local[v] = torch.from_numpy(np.stack([p, n if n is not None else np.zeros_like(p)], 0)).to(dev)
+        p, c, n = as_arrays(pc)
+        planes = [p, n if n is not None else np.zeros_like(p)] + ([c] if c is not None else [])
+        local[v] = torch.from_numpy(np.stack(planes, 0)).to(dev)
     reg = tr = None
     if register is not None:
         def reg(src, tgt):
@@ -370,4 +429,4 @@ def multi_view_fuse(local_clouds, n_views, threshold=0.02, mode=cloud_ops.GICP, 
             return torch.stack([blk[0] @ R.T + t, blk[1] @ R.T], 0)
     fused, Ts = multi_view_fuse_tensors(local, n_views, threshold, mode, max_iteration, reg, tr, ctx)
     arr = fused.cpu().numpy()
-    return PointCloud(arr[0], normals=arr[1]), Ts
+    return PointCloud(arr[0], arr[2] if len(arr) == 3 else None, arr[1]), Ts

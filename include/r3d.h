@@ -206,6 +206,21 @@ int r3d_disparity_to_cloud_dev(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, i
                                double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
                                int64_t capacity, double *out_xyz, double *out_normals, int64_t *out_n);
 
+/* r3d_disparity_to_cloud_dev with colours (the scanner half's clouds all carry them: create_from_rgbd_image, main.py:42-45).
+ * d_color: DEVICE uint8 image of the map's size, color_channels (1 or 3) interleaved bytes per pixel, rows color_stride BYTES
+ * apart (>= w * color_channels); typically the rectified left image that is in HBM next to the map.  A point's colour is
+ * (double)byte / 255.0 of the pixel it was reprojected from, in r, g, b order: color_bgr != 0 reverses a 3-channel pixel (cv2
+ * images are BGR, Open3D colours RGB), one channel gives r = g = b.  With the voxel grid on, a voxel's colour is the mean of its
+ * members' colours summed in index order (legacy voxel_down_sample), read straight from the image bytes: the extra device
+ * memory is the pixel-index array (4 w h bytes) and the output, never a [w*h,3] float64 colour array.  The pose does not touch
+ * colours; max_depth and the W = 0 drop apply as to the points.  out_colors: room for `capacity` triplets.  Points and normals
+ * are bit for bit those of r3d_disparity_to_cloud_dev.  R3D_E_BADARG: d_color or out_colors NULL (the colourless function is the
+ * way to get no colours), color_channels not 1 or 3, color_stride < w * color_channels. */
+int r3d_disparity_to_cloud_color_dev(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, int32_t h, const double *Q4x4, int32_t min_valid_x16,
+                                     double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
+                                     const uint8_t *d_color, int32_t color_stride, int32_t color_channels, int32_t color_bgr,
+                                     int64_t capacity, double *out_xyz, double *out_normals, double *out_colors, int64_t *out_n);
+
 /* k-nearest-neighbour graph (indices in the caller's numbering, nearest first, the point itself first; missing
  * entries -1 / 1e300).  radius <= 0: unbounded.  Feeds orient_normals_consistent_tangent_plane(k)
  * (normal_estimation.py:21), whose spanning-tree propagation is sequential host work.  d2 may be NULL. */
@@ -343,6 +358,12 @@ int r3d_model_download(r3d_model *m, double *xyz, double *colors, double *normal
 int r3d_disparity_to_cloud_resident(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, int32_t h, const double *Q4x4, int32_t min_valid_x16,
                                     double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
                                     int64_t capacity, double *d_out_xyz, double *d_out_normals, int64_t *out_n);
+/* r3d_disparity_to_cloud_color_dev with DEVICE output arrays (d_out_colors: capacity triplets, required): the third plane of the
+ * multi-view exchange */
+int r3d_disparity_to_cloud_color_resident(r3d_ctx *ctx, const int16_t *d_disp, int32_t w, int32_t h, const double *Q4x4, int32_t min_valid_x16,
+                                          double max_depth, const double *pose4x4, double voxel, double normal_radius, int32_t max_nn,
+                                          const uint8_t *d_color, int32_t color_stride, int32_t color_channels, int32_t color_bgr,
+                                          int64_t capacity, double *d_out_xyz, double *d_out_normals, double *d_out_colors, int64_t *out_n);
 int r3d_icp_dev(r3d_ctx *ctx, const r3d_icp_params *p, const double *d_src, int64_t ns, const double *d_src_normals, const double *d_tgt,
                 int64_t nt, const double *d_tgt_normals, const double *init4x4, double *T4x4, r3d_icp_stats *stats);
 int r3d_transform_points_dev(r3d_ctx *ctx, const double *d_xyz, int64_t n, const double *T4x4, int32_t rotate_only, double *d_out);
