@@ -36,6 +36,7 @@ P2P, P2PLANE, GICP = 0, 1, 2
 _lib.register({
     "r3d_debug_sort_by_cell": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
     "r3d_debug_exclusive_scan": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp], ctypes.c_int),
+    "r3d_debug_icp_correspondences": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp], ctypes.c_int),
 })
 
 
@@ -59,6 +60,20 @@ def debug_sort_by_cell(points, origin, cell, dims, key_order, impl=0, ctx=None):
     ctx.call("r3d_debug_sort_by_cell", p.ctypes.data_as(_vp), len(p), org.ctypes.data_as(_vp), float(cell), d.ctypes.data_as(_vp), int(key_order),
              int(impl), idx.ctypes.data_as(_vp), keys.ctypes.data_as(_vp))
     return idx, keys
+
+
+def debug_icp_correspondences(source, target, max_correspondence_distance, T=None, want_d2=True, ctx=None):
+    """r3d_debug_icp_correspondences: (corr [ns] int32, d2 [ns]) of one evaluation of the registration's search at pose T:
+    corr[i] is the index of the target nearest to T * source[i], -1 where none lies within the distance (d2 = 1e300)."""
+    ctx = ctx or _lib.default_context()
+    s = np.ascontiguousarray(source, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(target, dtype=np.float64).reshape(-1, 3)
+    T0 = None if T is None else np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+    corr = np.empty(len(s), np.int32)
+    d2 = np.empty(len(s)) if want_d2 else None
+    ctx.call("r3d_debug_icp_correspondences", s.ctypes.data_as(_vp), len(s), t.ctypes.data_as(_vp), len(t), float(max_correspondence_distance),
+             None if T0 is None else T0.ctypes.data_as(_vp), corr.ctypes.data_as(_vp), None if d2 is None else d2.ctypes.data_as(_vp))
+    return corr, d2
 
 
 class AlignParams(ctypes.Structure):

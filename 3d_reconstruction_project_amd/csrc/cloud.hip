@@ -2007,6 +2007,32 @@ __global__ void __launch_bounds__(64) k_icp_eval_t(GridView g, const double *__r
     }
 }
 
+// r3d_debug_icp_correspondences: brings one evaluation's correspondences back to the caller's numbering.  `corr` is indexed by the
+// Morton-sorted source and holds target slots (k_icp_search's output, from_slots) or target original indices (k_icp_eval's corr);
+// `perm` is the source sort.  The squared distance is recomputed with the search's own expression, as k_icp_accum does.
+__global__ void __launch_bounds__(256) k_icp_corr_readout(GridView g, const double *__restrict__ src, const int *__restrict__ perm, int64_t ns,
+                                                          const IcpState *__restrict__ st, const double *__restrict__ tgt /* caller's order */,
+                                                          const int *__restrict__ corr, int from_slots, int *__restrict__ corr_out,
+                                                          double *__restrict__ d2_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ns) return;
+    const Rigid T = load_rigid(st);
+    int c = corr[i];
+    if (from_slots && c >= 0) c = g.idx[c];
+    double d2 = 1e300;
+    if (c >= 0) {
+        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
+        const double px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
+        const double py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
+        const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
+        const double dx = tgt[(int64_t)c * 3] - px, dy = tgt[(int64_t)c * 3 + 1] - py, dz = tgt[(int64_t)c * 3 + 2] - pz;
+        d2 = dx * dx + dy * dy + dz * dz;
+    }
+    const int o = perm[i];
+    corr_out[o] = c;
+    d2_out[o] = d2;
+}
+
 __global__ void __launch_bounds__(256) k_transform(const double *__restrict__ in, int64_t n, Rigid T, int rotate_only, double *__restrict__ out) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -3203,12 +3229,16 @@ int normals_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t n, doubl
     return R3D_OK;
 }
 
+// r3d_debug_icp_correspondences' output (host arrays, the caller's numbering)
+struct IcpReadout { int32_t *corr; double *d2; };
+
 // ICP / point-to-plane / GICP loop on clouds that are already in device memory (d_sn / d_tn may be null where the mode
 // allows it); everything below r3d_icp's argument checks and uploads
 static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double *d_s, int64_t ns, double *d_sn, double *d_t, int64_t nt,
                     double *d_tn, const double *init4x4, double *T4x4, r3d_icp_stats *stats,
                     std::chrono::steady_clock::time_point t_begin, const double *tgt_enclosing = nullptr /* grid_build's `enclosing` */,
-                    double tgt_spacing = 0 /* grid_build's `spacing_hint`: voxel size the target was down-sampled with */) {
+                    double tgt_spacing = 0 /* grid_build's `spacing_hint`: voxel size the target was down-sampled with */,
+                    const IcpReadout *readout = nullptr /* r3d_debug_icp_correspondences: one evaluation at the initial pose, no loop */) {
     int rc;
     Grid G;
     double occ = 3.0;   // points per occupied cell the search grid aims at (R3D_ICP_OCC: A/B)
@@ -3277,6 +3307,7 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     double T[16];
     if (init4x4) memcpy(T, init4x4, sizeof T);
     else for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0);
+    int *sidx;
     {
         double *d_s0 = (double *)ar.get((size_t)ns * 24);
         if (ar.rc) return ar.rc;
@@ -3284,7 +3315,6 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
         int dims[3] = {G.v.nx, G.v.ny, G.v.nz};
         void *sk;
         bool sk32;
-        int *sidx;
         if ((rc = sort_by_cell(ctx, ar, d_s0, ns, G.mn, G.v.cell, dims, 2, &sk, &sk32, &sidx))) return rc;
         double *d_ss = (double *)ar.get((size_t)ns * 24);
         if (ar.rc) return ar.rc;
@@ -3333,17 +3363,18 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     R3D_HIP(ctx, hipMemcpyAsync(d_st, hst, sizeof *hst, hipMemcpyHostToDevice, ctx->stream));
     const int max_it = p->max_iteration;
     // one evaluation + one step of the loop, enqueued without waiting (both return at once when the loop has ended)
-    auto enqueue_eval = [&](bool publish) {
+    // (`corr`: the read-out's one evaluation -- the kernels' optional output, and no step behind it; the loop passes nullptr)
+    auto enqueue_eval = [&](bool publish, int *corr = nullptr) {
         const double eps = p->gicp_epsilon > 0 ? p->gicp_epsilon : 1e-3;
         const double md = p->max_correspondence_distance;
         if (tiled_impl) {
             switch (p->mode) {
-                case MODE_P2P: k_icp_eval_t<MODE_P2P><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, nullptr); break;
-                case MODE_P2PLANE: k_icp_eval_t<MODE_P2PLANE><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, nullptr); break;
-                default: k_icp_eval_t<MODE_GICP><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, nullptr); break;
+                case MODE_P2P: k_icp_eval_t<MODE_P2P><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
+                case MODE_P2PLANE: k_icp_eval_t<MODE_P2PLANE><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
+                default: k_icp_eval_t<MODE_GICP><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
             }
         } else {
-#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, nullptr)
+#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr)
 #define R3D_ICP_MODES(S)                                            \
     switch (p->mode) {                                              \
         case MODE_P2P: R3D_ICP_LAUNCH(MODE_P2P, S); break;          \
@@ -3369,9 +3400,24 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
 #undef R3D_ICP_MODES
 #undef R3D_ICP_LAUNCH
         }
+        if (corr) return;
         k_icp_step<<<1, 1024, 0, ctx->stream>>>(d_part, nblocks, d_st, ns, p->mode, max_it, p->relative_fitness, p->relative_rmse, d_mirror,
                                                 publish ? 1 : 0);
     };
+    if (readout) {
+        int *d_corr = (int *)ar.get((size_t)ns * 4), *d_corr_out = (int *)ar.get((size_t)ns * 4);
+        double *d_d2_out = (double *)ar.get((size_t)ns * 8);
+        if (ar.rc) return ar.rc;
+        enqueue_eval(false, d_corr);
+        // the split form's search writes target slots to d_nn (and leaves `corr` alone): converted through g.idx here
+        k_icp_corr_readout<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(G.v, d_s, sidx, ns, d_st, d_t, split_impl ? d_nn : d_corr,
+                                                                                  split_impl ? 1 : 0, d_corr_out, d_d2_out);
+        R3D_HIP(ctx, hipGetLastError());
+        R3D_HIP(ctx, hipMemcpyAsync(readout->corr, d_corr_out, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (readout->d2) R3D_HIP(ctx, hipMemcpyAsync(readout->d2, d_d2_out, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return R3D_OK;
+    }
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const auto t_loop = std::chrono::steady_clock::now();
     // The loop of RegistrationICP (evaluate, test, update) runs on the device; the host enqueues ICP_BATCH evaluations at a
@@ -4549,6 +4595,27 @@ extern "C" int r3d_debug_sort_by_cell(r3d_ctx *ctx, const double *xyz, int64_t n
     if (keys_out && k32)
         for (int64_t i = 0; i < n; i++) keys_out[i] = k4[(size_t)i];
     return R3D_OK;
+}
+
+// diagnostic: the registration's correspondence search on its own -- icp_core's set-up (point-to-point), one evaluation at pose T
+extern "C" int r3d_debug_icp_correspondences(r3d_ctx *ctx, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                                             double max_correspondence_distance, const double *T4x4, int32_t *corr_out, double *d2_out) {
+    R3D_ROCTX_RANGE("r3d_debug_icp_correspondences");
+    if (!ctx) return R3D_E_BADARG;
+    if (!src || !tgt || !corr_out || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_correspondences: bad argument");
+    if (!(max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_correspondences: max_correspondence_distance must be > 0");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    int rc;
+    double *d_t, *d_s;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    r3d_icp_params p = {};
+    p.mode = MODE_P2P;
+    p.max_correspondence_distance = max_correspondence_distance;
+    double T[16];
+    const IcpReadout ro = {corr_out, d2_out};
+    return icp_core(ctx, ar, &p, d_s, ns, nullptr, d_t, nt, nullptr, T4x4, T, nullptr, std::chrono::steady_clock::now(), nullptr, 0, &ro);
 }
 
 extern "C" int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t n, int32_t op, int32_t *out) {

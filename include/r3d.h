@@ -55,6 +55,13 @@ int r3d_debug_sort_by_cell(r3d_ctx *ctx, const double *xyz, int64_t n, const dou
 /* diagnostic: the hand-written exclusive scan (k_scan_sums + k_scan_apply) on n int32 host values; op 0 = sum, 1 = running maximum
  * (values >= 0).  out[i] = op over in[0 .. i-1], out[0] = 0. */
 int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t n, int32_t op, int32_t *out);
+/* diagnostic: the registration's correspondence search on its own.  Runs r3d_icp's set-up in the point-to-point mode (target grid,
+ * packed / float32 / exact candidate selection, Morton sort of the source; the same R3D_ICP_* and R3D_CELL_TABLE switches) and ONE
+ * evaluation at pose T4x4 (NULL: identity).  corr_out[i]: index into tgt of the target nearest to T * src[i] under (squared
+ * distance, index), or -1 when that distance is not below max_correspondence_distance; d2_out (may be NULL): the squared
+ * distance, 1e300 where there is none. */
+int r3d_debug_icp_correspondences(r3d_ctx *ctx, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                                  double max_correspondence_distance, const double *T4x4, int32_t *corr_out, double *d2_out);
 /* checks the cross-lane primitives (DPP shifts, permlane swaps, wave reductions) the kernels rely on */
 int r3d_selftest(r3d_ctx *ctx);
 
