@@ -125,7 +125,7 @@ void r3d_destroy(r3d_ctx *ctx) {
     for (r3d_buf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (r3d_sgm_ws &ws : ctx->ws) {
-        r3d_buf *wb[] = {&ws.rec_l, &ws.rec_r, &ws.cost, &ws.cspec, &ws.hsum, &ws.ltop, &ws.ckpt, &ws.raw, &ws.mins, &ws.lrd, &ws.lrd2, &ws.flags, &ws.spk_l, &ws.spk_c};
+        r3d_buf *wb[] = {&ws.rec_l, &ws.rec_r, &ws.cost, &ws.cspec, &ws.hsum, &ws.ckpt, &ws.raw, &ws.mins, &ws.lrd, &ws.lrd2, &ws.flags, &ws.spk_l, &ws.spk_c};
         for (r3d_buf *b : wb)
             if (b->p) (void)hipFree(b->p);
         if (ws.ev_created)
@@ -133,11 +133,6 @@ void r3d_destroy(r3d_ctx *ctx) {
                 for (int i = 0; i <= R3D_MAX_PROF; i++) (void)hipEventDestroy(ps.ev[i]);
         if (ws.stream) (void)hipStreamDestroy(ws.stream);
         if (ws.done) (void)hipEventDestroy(ws.done);
-        if (ws.aux) (void)hipStreamDestroy(ws.aux);
-        if (ws.vs_fork) (void)hipEventDestroy(ws.vs_fork);
-        if (ws.vs_join) (void)hipEventDestroy(ws.vs_join);
-        for (hipEvent_t e : ws.slab_ev)
-            if (e) (void)hipEventDestroy(e);
     }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     if (ctx->icp_ev) (void)hipEventDestroy(ctx->icp_ev);
@@ -381,10 +376,7 @@ int r3d_sgbm_debug_fetch(r3d_ctx *ctx, int16_t *cost, int16_t *hsum, int16_t *ra
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t vol = (size_t)ctx->last_h * ctx->last_w1 * ctx->last_dp * 2;
     if (cost) R3D_HIP(ctx, hipMemcpy(cost, ctx->ws[0].cost.p, vol, hipMemcpyDeviceToHost));
-    if (hsum) {
-        if (ctx->last_impl == 3) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "debug_fetch: the v3 pipeline never materialises L_left + L_right (set R3D_SGM_IMPL=v2)");
-        R3D_HIP(ctx, hipMemcpy(hsum, ctx->ws[0].hsum.p, vol, hipMemcpyDeviceToHost));
-    }
+    if (hsum) R3D_HIP(ctx, hipMemcpy(hsum, ctx->ws[0].hsum.p, vol, hipMemcpyDeviceToHost));
     if (raw) R3D_HIP(ctx, hipMemcpy(raw, ctx->ws[0].lrd.p, (size_t)ctx->last_w * ctx->last_h * 2, hipMemcpyDeviceToHost));
     return R3D_OK;
 }

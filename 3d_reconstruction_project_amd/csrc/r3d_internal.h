@@ -28,18 +28,14 @@ struct r3d_prof_set {
 
 #define R3D_SGM_MAX_LANES 6   /* workspaces that can exist; r3d_sgbm_compute_batch* uses R3D_SGM_LANES of them (env, default 3) */
 #define R3D_SGM_LANES 3
-#define R3D_SGM_SLABS 8   // most column slabs of the cost / forward-scan overlap (sgm.hip)
 
 // one SGM pipeline lane: its own grow-only workspace, stream and profiling event ring.  Single-map calls use lane 0 on
 // the context stream; r3d_sgbm_compute_batch_dev spreads maps over the lanes so that kernels with complementary
 // bottlenecks (cost: VALU + writes, hscan: HBM, vscan: mixed) of consecutive maps overlap.
 struct r3d_sgm_ws {
-    r3d_buf rec_l, rec_r, cost, cspec, hsum, ltop, ckpt, raw, mins, lrd, lrd2, flags, spk_l, spk_c;
+    r3d_buf rec_l, rec_r, cost, cspec, hsum, ckpt, raw, mins, lrd, lrd2, flags, spk_l, spk_c;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    hipStream_t aux = nullptr;                       // second stream of the lane: cost slabs ahead of the forward scan
-    hipEvent_t vs_fork = nullptr, vs_join = nullptr;   // the balanced split of the vertical scan (tail launch on `aux`)
-    hipEvent_t slab_ev[R3D_SGM_SLABS + 1] = {};      // [j]: cost of slab j written; [R3D_SGM_SLABS]: fork point
     r3d_prof_set prof[R3D_PROF_SETS];
     int prof_cur = 0;
     bool ev_created = false;
@@ -48,8 +44,7 @@ struct r3d_sgm_ws {
 // derived parameters of one sgbm call (sgm.hip: derive_geom), passed to every SGM kernel by value
 struct SgmGeom {
     int W, H, minD, D, NP, minX1, maxX1, W1, SW2, SH2, P1, P2, uniq, d12, ftzero, stripe_sz, overlap, invalid;
-    int DP;  // disparity slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 that holds D (v2 kernels; v1 and v3
-             // only know 128 / 256 = NP * 128)
+    int DP;  // disparity slots per cost-volume column: the smallest of 32 / 64 / 128 / 256 / 512 that holds D
     int CN;  // channels of the image pair (1 grey, 3 colour: the block cost is the sum over the channels)
 };
 
@@ -68,7 +63,7 @@ struct r3d_ctx {
     r3d_sgm_ws ws[R3D_SGM_MAX_LANES];
     hipEvent_t fork_ev = nullptr;
     // geometry of the last sgbm call (for debug fetch)
-    int last_w = 0, last_h = 0, last_w1 = 0, last_dp = 0, last_impl = 0;
+    int last_w = 0, last_h = 0, last_w1 = 0, last_dp = 0;
     int last_mode = -1;        // r3d_sgbm_params.mode of that call
     SgmGeom last_geom = {};    // as its kernels saw it (MODE_HH: one stripe); r3d_sgbm_debug_hh_partial launches from it
     // profiling sums accumulate per kernel name over all lanes

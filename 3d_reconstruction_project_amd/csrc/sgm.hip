@@ -12,9 +12,11 @@
 //   cspec        [3][SH2][w1][dp]   C of the first SH2 rows of stripes 1..3 (box replicated at the stripe top)
 //   hsum         [h][w1][dp]        L_left + L_right
 //   raw / mins   [h][w]             WTA disparity (x16, before LR check) and its aggregated cost
-// Lane mapping of every volume kernel: one wavefront owns ONE (row, column) disparity vector; lane l holds the
-// 2*NP consecutive disparities d = 2*NP*l .. 2*NP*l+2*NP-1 as NP packed int16x2 registers, so a wave reads or
-// writes 256*NP contiguous bytes per pixel and the d-1 / d+1 neighbours come from one DPP wave shift each way.
+// Lane mapping of every volume kernel: a disparity vector of dp entries lies on LPC adjacent lanes, NPL packed int16x2 registers
+// (2*NPL consecutive disparities) per lane, dp = 2*NPL*LPC, so a wave holds 64/LPC vectors (rows, columns or lines) and the
+// d-1 / d+1 neighbours come from one DPP shift each way ("Generic lane mapping" below).
+// Pipeline of a MODE_SGBM_3WAY call (sgm_run_impl): k_prefilter -> k_cost2 (once per channel) -> k_hscan2 -> k_vscan2 (vertical
+// path + winner-take-all) -> k_lrcheck -> (k_tiny_assemble) -> k_median3 -> (speckle filter).
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,12 +28,6 @@ namespace {
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-#ifndef R3D_EXP_COST
-#define R3D_EXP_COST 0   /* timing experiments on k_cost2 (wrong results): 1 = no stores, 2 = no loads inside the loop */
-#endif
-#ifndef R3D_COST_STAGE
-#define R3D_COST_STAGE 1   /* where k_cost2 stages the next input row: 1 right after the barrier (default: 0.67 -> 0.64 ms), 2 between the box sum and its stores (0.65) */
-#endif
 constexpr int PADPK = 0x7fff7fff;  // SHRT_MAX in both halves: the d=-1 / d=D padding of every path buffer
 
 __device__ __forceinline__ s16x2 as_s(int v) { return __builtin_bit_cast(s16x2, v); }
@@ -74,6 +70,8 @@ __device__ __forceinline__ int wave_allmax_i32(int v) { typedef int T; R3D_BUTTE
 // One SGM path step for one disparity vector (OpenCV accumulateCostsLeftTop / accumulateCostsRight):
 //   L[d] = C[d] + min(Lp[d], Lp[d-1]+P1, Lp[d+1]+P1, minp+P2) - (minp+P2),   Lp[-1] = Lp[D] = SHRT_MAX
 // P holds Lp on entry and L on exit; minp (wave-uniform) holds min_d Lp on entry and min_d L on exit.
+// This wave-wide form (one vector of 128*NP disparities per wave) and sgm_step_dual are the definitions k_selftest holds the
+// generic forms against; the kernels use sgm_step_g / sgm_step_dual_g.
 // The packed adds cannot overflow inside the envelope checked on the host (C <= 16383, P2 <= 16383); the
 // +P1 on the SHRT_MAX padding saturates (v_pk_add_i16 clamp), which never wins the min.
 template <int NP>
@@ -102,7 +100,7 @@ __device__ __forceinline__ void sgm_step(int (&P)[NP], int &minp, const int (&C)
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Generic lane mapping (v2 kernels): a disparity vector of DP = 2*NPL*LPC entries is spread over LPC adjacent lanes,
+// Generic lane mapping of the volume kernels: a disparity vector of DP = 2*NPL*LPC entries is spread over LPC adjacent lanes,
 // NPL packed registers (2*NPL consecutive disparities) per lane, so one wave holds 64/LPC independent vectors.
 // Cross-lane work (2 DPP shifts + log2(LPC) butterfly stages) is amortised over NPL registers.
 template <int LPC>
@@ -348,120 +346,14 @@ __global__ void __launch_bounds__(256) k_prefilter(const uint8_t *__restrict__ L
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// k_cost: Birchfield-Tomasi pixel cost -> blockSize x blockSize box sum -> cost volume.
-// Workgroup = 8 waves, one tile of TX cost columns, marching down a band of rows 8 at a time:
-//   phase 1: wave w computes the horizontal box sums hsum(x, r) of image row r for the tile (sliding along x;
-//            the last 2*SW2+1 pixel-cost vectors live in a per-wave LDS ring) into an LDS ring of rows;
-//   phase 2: wave w sums the 2*SH2+1 ring rows around output row y and streams C(y, tile) to HBM
-//            (TX*256*NP contiguous bytes per wave).
-// Replicated borders: columns clamp to [0, w1) in COST coordinates, rows clamp to [clampTop, h-1].
 __device__ __forceinline__ int bt_cost_pk(int U, int U0, int U1, int V, int V0, int V1) {
     int c0 = pk_umax(pk_usub_sat(U, V1), pk_usub_sat(V0, U));
     int c1 = pk_umax(pk_usub_sat(V, U1), pk_usub_sat(U0, V));
     return pk_umin(c0, c1);
 }
 
-constexpr int COST_NW = 8;
-
-template <int NP>
-__global__ void __launch_bounds__(COST_NW * 64) k_cost(const uint2 *__restrict__ recL, const uint2 *__restrict__ recR, SgmGeom g,
-                                                       int *__restrict__ cvol, int *__restrict__ cspec, int TX, int BAND,
-                                                       int nMain, int RING) {
-    extern __shared__ int lds[];
-    constexpr int NPW = NP * 64;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int NR = COST_NW + 2 * g.SH2;
-    int *hs = lds;                                          // [NR][TX][NPW]
-    int *ring = lds + (size_t)NR * TX * NPW + w * RING * NPW;  // per wave [RING][NPW]
-    const int xt0 = blockIdx.x * TX;
-    const size_t rowWords = (size_t)g.W1 * NPW;
-    int y0, y1, clampTop;
-    int *obase;  // output row y lives at obase + (y - y0) * rowWords
-    if ((int)blockIdx.y < nMain) {
-        y0 = blockIdx.y * BAND;
-        y1 = min(y0 + BAND, g.H);
-        clampTop = 0;
-        obase = cvol + (size_t)y0 * rowWords;
-    } else {
-        const int n = blockIdx.y - nMain + 1;
-        const int ss = max(min(n * g.stripe_sz - g.overlap, g.H), 0);
-        y0 = ss;
-        y1 = min(ss + g.SH2, g.H);
-        clampTop = ss;
-        obase = cspec + (size_t)(n - 1) * g.SH2 * rowWords;
-    }
-    const int ntx = min(TX, g.W1 - xt0);
-    int have = max(y0 - g.SH2, clampTop) - 1;
-    for (int yb = y0; yb < y1; yb += COST_NW) {
-        const int need = min(yb + COST_NW - 1 + g.SH2, g.H - 1);
-        // ---- phase 1
-        for (int r = have + 1 + w; r <= need; r += COST_NW) {
-            const uint2 *lrow = recL + (size_t)r * g.W;
-            const uint2 *rrow = recR + (size_t)r * g.W;
-            int *hrow = hs + (size_t)(r % NR) * TX * NPW;
-            int acc[NP];
-#pragma unroll
-            for (int j = 0; j < NP; j++) acc[j] = 0;
-            const int kstart = xt0 - g.SW2, kend = xt0 + ntx - 1 + g.SW2;
-            for (int k = kstart; k <= kend; ++k) {
-                const int xc = min(max(k, 0), g.W1 - 1);
-                const int x = xc + g.minX1;
-                const uint2 lr = lrow[x];  // wave-uniform
-                const int Ug = (lr.x & 255) * 0x10001, Ug0 = ((lr.x >> 8) & 255) * 0x10001, Ug1 = ((lr.x >> 16) & 255) * 0x10001;
-                const int Ui = (lr.x >> 24) * 0x10001, Ui0 = (lr.y & 255) * 0x10001, Ui1 = ((lr.y >> 8) & 255) * 0x10001;
-                const int rbase = x - g.minD - 2 * NP * lane;  // right column of this lane's lowest disparity
-                const int slot = (k - kstart) & (RING - 1);
-                const int oslot = (k - 2 * g.SW2 - kstart) & (RING - 1);
-                const bool emit = k >= xt0 + g.SW2;
-#pragma unroll
-                for (int j = 0; j < NP; j++) {
-                    const int ra = min(max(rbase - 2 * j, 0), g.W - 1);      // d even  (low half)
-                    const int rb = min(max(rbase - 2 * j - 1, 0), g.W - 1);  // d odd   (high half)
-                    const uint2 A = rrow[ra], B = rrow[rb];
-                    const int Vg = __builtin_amdgcn_perm(B.x, A.x, 0x0c040c00), Vg0 = __builtin_amdgcn_perm(B.x, A.x, 0x0c050c01);
-                    const int Vg1 = __builtin_amdgcn_perm(B.x, A.x, 0x0c060c02), Vi = __builtin_amdgcn_perm(B.x, A.x, 0x0c070c03);
-                    const int Vi0 = __builtin_amdgcn_perm(B.y, A.y, 0x0c040c00), Vi1 = __builtin_amdgcn_perm(B.y, A.y, 0x0c050c01);
-                    const int cg = bt_cost_pk(Ug, Ug0, Ug1, Vg, Vg0, Vg1);
-                    const int ci = bt_cost_pk(Ui, Ui0, Ui1, Vi, Vi0, Vi1);
-                    const int pix = pk_add(cg, (ci >> 2) & 0x3fff3fff);  // gradient + (intensity >> 2), both halves
-                    acc[j] = pk_add(acc[j], pix);
-                    ring[slot * NPW + lane * NP + j] = pix;
-                    if (emit) {
-                        hrow[(k - g.SW2 - xt0) * NPW + lane * NP + j] = acc[j];
-                        acc[j] = pk_sub(acc[j], ring[oslot * NPW + lane * NP + j]);
-                    }
-                }
-            }
-        }
-        have = need;
-        __syncthreads();
-        // ---- phase 2
-        const int yo = yb + w;
-        if (yo < y1) {
-            int *orow = obase + (size_t)(yo - y0) * rowWords + (size_t)xt0 * NPW;
-            for (int xt = 0; xt < ntx; ++xt) {
-                int s[NP];
-#pragma unroll
-                for (int j = 0; j < NP; j++) s[j] = 0;
-                for (int dy = -g.SH2; dy <= g.SH2; ++dy) {
-                    const int rr = min(max(yo + dy, clampTop), g.H - 1);
-                    const int *h = hs + ((size_t)(rr % NR) * TX + xt) * NPW + lane * NP;
-#pragma unroll
-                    for (int j = 0; j < NP; j++) s[j] = pk_add(s[j], h[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < NP; j++) orow[xt * NPW + lane * NP + j] = s[j];
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// k_cost2: same result as k_cost, restructured for the vector pipes (v1 was bound by the scalar ALU: ~35 SALU per
-// column step, and every load was waited on immediately).
+// k_cost2: Birchfield-Tomasi pixel cost -> blockSize x blockSize box sum -> cost volume, on the vector pipes.
 // Mapping: lane = (column g = lane / LPC, disparity chunk k = lane % LPC), 16 disparities (8 packed registers) per lane,
 // CW = 64/LPC adjacent columns per wave, NWAVE waves per workgroup = one tile of TC = NWAVE*CW columns (2*SH2 of them
 // halo) that marches DOWN a band of rows:
@@ -472,21 +364,18 @@ __global__ void __launch_bounds__(COST_NW * 64) k_cost(const uint2 *__restrict__
 //            (c) vertical sums go to an LDS tile; one barrier; (d) each lane adds the 2*SH2+1 neighbouring columns
 //                (ds_read_b128) and streams C to HBM, 2 KB contiguous per wave.
 // Borders: columns clamp in cost coordinates, rows clamp to [clampTop, h-1] (replication, as the original).
-
-// VCH (v3): the vertical path L_top is aggregated right here, on the freshly summed block cost that is still in
-// registers: one workgroup column-tile per STRIPE marches from the stripe's first warm-up row to its last row, and
-// writes C and L_top for the rows the stripe owns (the warm-up rows' special block costs never leave the chip).
-// ACC (colour pairs, channels 1 and 2; never with VCH): the block cost of this launch's channel is ADDED to what the launches of the
+// blockIdx.y: the first nMain blocks each own a band of BAND rows of the main volume; the last three own the first SH2 rows of
+// stripes 1..3 (cspec), whose box is replicated at the stripe top.
+// ACC (colour pairs, channels 1 and 2): the block cost of this launch's channel is ADDED to what the launches of the
 // earlier channels left in cvol / cspec (read-add-store by the lane that stores; every launch covers the same entries).  The sum
 // of the channels stays below 32768 per entry (derive_geom), so the one 32-bit add of two packed entries carries nothing across.
 // TRACK then looks at the summed value: it is set on the last channel's launch only.
-template <int LPC, int SH2, bool TRACK, bool VCH, int NWAVE, bool ACC = false>
+template <int LPC, int SH2, bool TRACK, int NWAVE, bool ACC = false>
 __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ recL, const uint2 *__restrict__ recR, SgmGeom g,
                                                             int *__restrict__ cvol, int *__restrict__ cspec, int BAND, int nMain,
-                                                            int *__restrict__ maxc, int *__restrict__ ltvol, int tile0) {
+                                                            int *__restrict__ maxc, int tile0) {
     constexpr int NPL = 8, CW = 64 / LPC, TC = NWAVE * CW, TO = TC - 2 * SH2, DP = 16 * LPC, DPW = NPL * LPC;
     constexpr int R = 2 * SH2 + 1, NRR = TC + DP, NT = NWAVE * 64;
-    static_assert(!(ACC && VCH), "the fused vertical path runs on the complete block cost");
     // pair words: 6 dwords per right pixel, plus 8 dwords of padding after every 16 pixels: lanes of one column group
     // read records 16 apart (16*6 dwords = 32 mod 64 banks -> 4-way conflicts); with the pad the eight chunks land on
     // eight different multiples of 8 banks and the four column groups of a half-wave fill the gaps: conflict-free.
@@ -501,22 +390,17 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
     __shared__ int sV[2][TC * DPW];       // vertical box sums of the tile, double buffered
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, k = lane % LPC, grp = lane / LPC;
     const int cl = w * CW + grp;                       // local column 0..TC-1
-    const int t0 = (blockIdx.x + tile0) * TO;          // first OUTPUT cost column of the tile (tile0: column-slab launches)
+    // first OUTPUT cost column of the tile.  tile0 is always 0 (every launch covers the whole width): kept as an argument so that the
+    // instruction stream equals the previous build's
+    const int t0 = (blockIdx.x + tile0) * TO;
     const int xc = min(max(t0 - SH2 + cl, 0), g.W1 - 1);   // cost column this lane evaluates (replicated at the borders)
     const int x = xc + g.minX1;                        // image column
     const int r_base = max(t0 - SH2, 0) + g.minX1 - g.minD - (DP - 1);
     const int ri0 = min(max(x - g.minD - 16 * k - r_base, 15), NRR - 1);   // pair-word index of this lane's lowest disparity
     const size_t rowWords = (size_t)g.W1 * DPW;
-    int y0, y1, clampTop, out_start = 0;
+    int y0, y1, clampTop;
     int *obase;
-    if (VCH) {
-        const int n = blockIdx.y;                       // stripe
-        y0 = max(min(n * g.stripe_sz - g.overlap, g.H), 0);
-        y1 = min((n + 1) * g.stripe_sz, g.H);
-        clampTop = y0;
-        out_start = min(n * g.stripe_sz, g.H);
-        obase = cvol + (size_t)y0 * rowWords;
-    } else if ((int)blockIdx.y < nMain) {
+    if ((int)blockIdx.y < nMain) {
         y0 = blockIdx.y * BAND; y1 = min(y0 + BAND, g.H); clampTop = 0;
         obase = cvol + (size_t)y0 * rowWords;
     } else {
@@ -527,12 +411,6 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
     }
     if (y0 >= y1) return;
     auto crow = [&](int yy) { return min(max(yy, clampTop), g.H - 1); };
-    // vertical path state (VCH)
-    int LT[NPL], ltmin = 0;
-    const bool lane_valid = 16 * k < g.D;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) LT[j] = lane_valid ? 0 : PADPK;
-    const int P1pk = pk_dup(g.P1);
 
     // (a) staging of an image row: the raw records are fetched one iteration EARLY into registers (fetch), and turned
     // into LDS pair words one iteration later (commit), so the global-load latency is never waited for inside a row
@@ -616,8 +494,8 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
     // The staging of row t+2 sits right AFTER the barrier (buffer t&1 is free from there on), not before it: its wait for the
     // prefetched records is an s_waitcnt vmcnt(0) (the count cannot be known across the conditional stores), which also waits for
     // this wave's own stores of C -- issued a whole iteration earlier here, most of an iteration earlier in the old order, where
-    // waves 0-2 stalled on them (~1.8 us of write latency against a 2.1 us iteration) and the other five at the barrier behind them:
-    // 0.68 -> 0.59 ms with the loads removed (R3D_EXP_COST=2, wrong results), the same as with the stores removed (=1).
+    // waves 0-2 stalled on them (~1.8 us of write latency against a 2.1 us iteration) and the other five at the barrier behind them
+    // (DESIGN.md section 4).
     const int niter = (y1 - y0) + 2 * SH2;
 #pragma unroll 1
     for (int t = 0; t < niter; t++) {
@@ -644,10 +522,8 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
             *(int4 *)&sV[b][cl * DPW + (DPW / 2) * ((cl & 1) ^ 1) + 4 * k] = make_int4(vs[4], vs[5], vs[6], vs[7]);
         }
         __syncthreads();
-#if R3D_COST_STAGE == 1
-        commit(b);
-        fetch(crow(y0 - SH2 + t + 3));
-#endif
+        commit(b);                                      // row t+2 (fetched during iteration t-1) into the buffer this iteration just read
+        fetch(crow(y0 - SH2 + t + 3));                  // row t+3, consumed by the next iteration's commit
         const bool do_out = outp && is_out;
         int c[NPL];
 #pragma unroll
@@ -662,38 +538,15 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
                 c[4] = pk_add_nc(c[4], v1.x); c[5] = pk_add_nc(c[5], v1.y); c[6] = pk_add_nc(c[6], v1.z); c[7] = pk_add_nc(c[7], v1.w);
             }
         }
-        // between the box sum and its stores: the staging's vmcnt(0) then waits for stores that are exactly one iteration old
-#if R3D_COST_STAGE == 2
-        commit(b);                                      // row t+2 (fetched during iteration t-1) into the buffer this iteration just read
-#if R3D_EXP_COST != 2
-        fetch(crow(y0 - SH2 + t + 3));                  // row t+3, consumed by the next iteration's commit
-#endif
-#endif
         if (do_out) {
-            if (VCH) {
-                sgm_step_g<NPL, LPC, true>(LT, ltmin, c, P1pk, g.P2, k == 0, k == LPC - 1, lane_valid);
-                if (y0 + t - 2 * SH2 >= out_start) {
-                    const size_t ro = (size_t)(t - 2 * SH2) * rowWords;
-                    int *o = optr + ro, *l = ltvol + (optr - cvol) + ro;
-                    *(int4 *)o = make_int4(c[0], c[1], c[2], c[3]);
-                    *(int4 *)(o + 4) = make_int4(c[4], c[5], c[6], c[7]);
-                    *(int4 *)l = make_int4(LT[0], LT[1], LT[2], LT[3]);
-                    *(int4 *)(l + 4) = make_int4(LT[4], LT[5], LT[6], LT[7]);
-                }
-            } else {
-                int *o = optr + (size_t)(t - 2 * SH2) * rowWords;
-                if constexpr (ACC) {
-                    const int4 a0 = *(const int4 *)o, a1 = *(const int4 *)(o + 4);
-                    c[0] = pk_add_nc(c[0], a0.x); c[1] = pk_add_nc(c[1], a0.y); c[2] = pk_add_nc(c[2], a0.z); c[3] = pk_add_nc(c[3], a0.w);
-                    c[4] = pk_add_nc(c[4], a1.x); c[5] = pk_add_nc(c[5], a1.y); c[6] = pk_add_nc(c[6], a1.z); c[7] = pk_add_nc(c[7], a1.w);
-                }
-#if R3D_EXP_COST == 1
-                if ((c[0] ^ c[1] ^ c[2] ^ c[3] ^ c[4] ^ c[5] ^ c[6] ^ c[7]) == 0x12345678) *(int4 *)o = make_int4(c[0], c[1], c[2], c[3]);   // timing experiment: no stores
-#else
-                *(int4 *)o = make_int4(c[0], c[1], c[2], c[3]);
-                *(int4 *)(o + 4) = make_int4(c[4], c[5], c[6], c[7]);
-#endif
+            int *o = optr + (size_t)(t - 2 * SH2) * rowWords;
+            if constexpr (ACC) {
+                const int4 a0 = *(const int4 *)o, a1 = *(const int4 *)(o + 4);
+                c[0] = pk_add_nc(c[0], a0.x); c[1] = pk_add_nc(c[1], a0.y); c[2] = pk_add_nc(c[2], a0.z); c[3] = pk_add_nc(c[3], a0.w);
+                c[4] = pk_add_nc(c[4], a1.x); c[5] = pk_add_nc(c[5], a1.y); c[6] = pk_add_nc(c[6], a1.z); c[7] = pk_add_nc(c[7], a1.w);
             }
+            *(int4 *)o = make_int4(c[0], c[1], c[2], c[3]);
+            *(int4 *)(o + 4) = make_int4(c[4], c[5], c[6], c[7]);
             if (TRACK && 16 * k < g.D) {
 #pragma unroll
                 for (int j = 0; j < NPL; j++) cmax = pk_umax(cmax, c[j]);
@@ -707,203 +560,18 @@ __global__ void __launch_bounds__(NWAVE * 64) k_cost2(const uint2 *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_hscan: one wave per image row: forward scan writes L_left, backward scan adds L_right in place.
-template <int NP, int U>
-__device__ __forceinline__ void load_run(int (&buf)[U][NP], const int *__restrict__ row, int x0, int dir, int W1, int NPW) {
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int x = min(max(x0 + dir * u, 0), W1 - 1);
-#pragma unroll
-        for (int j = 0; j < NP; j++) buf[u][j] = row[(size_t)x * NPW + j];
-    }
-}
-
-template <int NP>
-__global__ void __launch_bounds__(64) k_hscan(const int *__restrict__ cvol, int *__restrict__ hvol, SgmGeom g) {
-    constexpr int NPW = NP * 64, U = 16;
-    const int lane = threadIdx.x, y = blockIdx.x;
-    const int *crow = cvol + (size_t)y * g.W1 * NPW + lane * NP;
-    int *hrow = hvol + (size_t)y * g.W1 * NPW + lane * NP;
-    const bool valid = 2 * NP * lane < g.D;
-    const int P1pk = pk_dup(g.P1), W1 = g.W1;
-    int P[NP], minp = 0;
-    int cA[U][NP], cB[U][NP], lA[U][NP], lB[U][NP];
-#pragma unroll
-    for (int j = 0; j < NP; j++) P[j] = valid ? 0 : PADPK;
-
-#define HS_FWD(buf, xb)                                                    \
-    _Pragma("unroll") for (int u = 0; u < U; u++) {                        \
-        const int x = (xb) + u;                                            \
-        if (x < W1) {                                                      \
-            sgm_step<NP>(P, minp, buf[u], P1pk, g.P2, valid);              \
-            _Pragma("unroll") for (int j = 0; j < NP; j++) hrow[(size_t)x * NPW + j] = P[j]; \
-        }                                                                  \
-    }
-    load_run<NP, U>(cA, crow, 0, 1, W1, NPW);
-    for (int x0 = 0; x0 < W1; x0 += 2 * U) {
-        load_run<NP, U>(cB, crow, x0 + U, 1, W1, NPW);
-        HS_FWD(cA, x0)
-        load_run<NP, U>(cA, crow, x0 + 2 * U, 1, W1, NPW);
-        HS_FWD(cB, x0 + U)
-    }
-#undef HS_FWD
-    // backward: the L_left values written above are read back by the same lanes (same wave => program order)
-    minp = 0;
-#pragma unroll
-    for (int j = 0; j < NP; j++) P[j] = valid ? 0 : PADPK;
-#define HS_BWD(cb, lb, xb)                                                 \
-    _Pragma("unroll") for (int u = 0; u < U; u++) {                        \
-        const int x = (xb)-u;                                              \
-        if (x >= 0) {                                                      \
-            sgm_step<NP>(P, minp, cb[u], P1pk, g.P2, valid);               \
-            _Pragma("unroll") for (int j = 0; j < NP; j++) hrow[(size_t)x * NPW + j] = pk_add(lb[u][j], P[j]); \
-        }                                                                  \
-    }
-    load_run<NP, U>(cA, crow, W1 - 1, -1, W1, NPW);
-    load_run<NP, U>(lA, hrow, W1 - 1, -1, W1, NPW);
-    for (int x0 = W1 - 1; x0 >= 0; x0 -= 2 * U) {
-        load_run<NP, U>(cB, crow, x0 - U, -1, W1, NPW);
-        load_run<NP, U>(lB, hrow, x0 - U, -1, W1, NPW);
-        HS_BWD(cA, lA, x0)
-        load_run<NP, U>(cA, crow, x0 - 2 * U, -1, W1, NPW);
-        load_run<NP, U>(lA, hrow, x0 - 2 * U, -1, W1, NPW);
-        HS_BWD(cB, lB, x0 - U)
-    }
-#undef HS_BWD
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_vscan: one wave per (stripe, CPW adjacent cost columns): marches down the stripe's rows keeping the CPW
-// L_top vectors in registers (CPW independent dependency chains => ILP), adds L_left+L_right, and does the
-// winner-take-all, uniqueness test and sub-pixel interpolation of every output row.
-template <int NP>
-__device__ __forceinline__ int read_s(const int (&S)[NP], int d) {  // d wave-uniform
-    const int l = __builtin_amdgcn_readfirstlane(d / (2 * NP));
-    int v;
-    if (NP == 1) v = __builtin_amdgcn_readlane(S[0], l);
-    else {
-        const int v0 = __builtin_amdgcn_readlane(S[0], l), v1 = __builtin_amdgcn_readlane(S[NP - 1], l);
-        v = ((d >> 1) & 1) ? v1 : v0;
-    }
-    return (d & 1) ? hi16(v) : lo16(v);
-}
-
-template <int NP, int CPW>
-__global__ void __launch_bounds__(64) k_vscan(const int *__restrict__ cvol, const int *__restrict__ cspec,
-                                              const int *__restrict__ hvol, SgmGeom g, int16_t *__restrict__ raw,
-                                              int16_t *__restrict__ mins) {
-    constexpr int NPW = NP * 64;
-    const int lane = threadIdx.x, n = blockIdx.y, xc0 = blockIdx.x * CPW;
-    const size_t rowWords = (size_t)g.W1 * NPW;
-    const int src_start = max(min(n * g.stripe_sz - g.overlap, g.H), 0);
-    const int src_end = min((n + 1) * g.stripe_sz, g.H);
-    const int out_start = min(n * g.stripe_sz, g.H);
-    if (src_start >= src_end) return;  // stripe lies below the image (tiny h)
-    const bool valid = 2 * NP * lane < g.D;
-    const int P1pk = pk_dup(g.P1);
-    int P[CPW][NP], minp[CPW], col[CPW];
-#pragma unroll
-    for (int c = 0; c < CPW; c++) {
-        minp[c] = 0;
-        col[c] = min(xc0 + c, g.W1 - 1) * NPW + lane * NP;
-#pragma unroll
-        for (int j = 0; j < NP; j++) P[c][j] = valid ? 0 : PADPK;
-    }
-    int cc[CPW][NP], hh[CPW][NP], cn[CPW][NP], hn[CPW][NP];
-    auto crow_of = [&](int y) -> const int * {
-        return (n > 0 && y < src_start + g.SH2) ? cspec + ((size_t)(n - 1) * g.SH2 + (y - src_start)) * rowWords
-                                                 : cvol + (size_t)y * rowWords;
-    };
-    auto load_row = [&](int y, int (&cb)[CPW][NP], int (&hb)[CPW][NP]) {
-        const int yy = min(y, src_end - 1);
-        const int *cr = crow_of(yy);
-        const int *hr = hvol + (size_t)yy * rowWords;
-        const bool wantH = yy >= out_start;
-#pragma unroll
-        for (int c = 0; c < CPW; c++)
-#pragma unroll
-            for (int j = 0; j < NP; j++) {
-                cb[c][j] = cr[col[c] + j];
-                hb[c][j] = wantH ? hr[col[c] + j] : 0;
-            }
-    };
-    auto process = [&](int y, int (&cb)[CPW][NP], int (&hb)[CPW][NP]) {
-#pragma unroll
-        for (int c = 0; c < CPW; c++) sgm_step<NP>(P[c], minp[c], cb[c], P1pk, g.P2, valid);
-        if (y < out_start) return;
-        int odisp = g.invalid, omin = 0x7fff;
-#pragma unroll
-        for (int c = 0; c < CPW; c++) {
-            int S[NP];
-            unsigned key = 0xffffffffu;
-#pragma unroll
-            for (int j = 0; j < NP; j++) {
-                S[j] = pk_add_sat(hb[c][j], P[c][j]);
-                const int d0 = 2 * NP * lane + 2 * j;
-                const unsigned k0 = ((unsigned)(lo16(S[j]) + 32768) << 8) | (unsigned)d0;
-                const unsigned k1 = ((unsigned)(hi16(S[j]) + 32768) << 8) | (unsigned)(d0 + 1);
-                key = min(key, min(k0, k1));
-            }
-            key = valid ? key : 0xffffffffu;
-            key = wave_allmin_u32(key);
-            const int best = __builtin_amdgcn_readfirstlane((int)(key & 255u));
-            const int minS = __builtin_amdgcn_readfirstlane((int)(key >> 8) - 32768);
-            bool bad = false;
-            if (g.uniq > 0) {
-                bool lb = false;
-#pragma unroll
-                for (int j = 0; j < NP; j++) {
-                    const int d0 = 2 * NP * lane + 2 * j;
-                    lb |= (lo16(S[j]) * (100 - g.uniq) < minS * 100) && (abs(d0 - best) > 1);
-                    lb |= (hi16(S[j]) * (100 - g.uniq) < minS * 100) && (abs(d0 + 1 - best) > 1);
-                }
-                bad = __any(lb && valid);
-            }
-            int dsp = g.invalid;
-            if (!bad) {
-                if (0 < best && best < g.D - 1) {
-                    const int sm = read_s<NP>(S, best - 1), sp = read_s<NP>(S, best + 1);
-                    const int den = max(sm + sp - 2 * minS, 1);
-                    dsp = best * 16 + ((sm - sp) * 16 + den) / (den * 2);
-                } else
-                    dsp = best * 16;
-                dsp += g.minD * 16;
-            }
-            if (lane == c && xc0 + c < g.W1) { odisp = dsp; omin = minS; }
-        }
-        if (lane < CPW && xc0 + lane < g.W1) {
-            const size_t o = (size_t)y * g.W + g.minX1 + xc0 + lane;
-            raw[o] = (int16_t)odisp;
-            mins[o] = (int16_t)omin;
-        }
-    };
-    load_row(src_start, cc, hh);
-    for (int y = src_start; y < src_end; y += 2) {
-        load_row(y + 1, cn, hn);
-        process(y, cc, hh);
-        load_row(y + 2, cc, hh);
-        if (y + 1 < src_end) process(y + 1, cn, hn);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_hscan2: one wave per image row, NO spill of L_left to HBM.
-//   phase 1: forward chain over the row; the state entering every K-column segment is check-pointed (8 B/lane);
+// k_hscan2: the two horizontal paths of 64 / LPC image rows per wave (LPC lanes x NPL packed registers per row), NO spill of L_left to HBM.
+//   phase 1: forward chain over the row; the state entering every K-column segment is check-pointed (DP + 16 bytes per row);
 //   phase 2: segments right-to-left: the segment's C values are loaded ONCE into registers, the forward chain is
 //            recomputed from the checkpoint (L_left of the segment stays in registers), then the backward chain
 //            runs over the same registers and streams L_left + L_right to HBM.
-// HBM traffic per row: C read twice, sum written once, + 2 * 8 B * 64 * W1/K of checkpoints (6 % at K = 32).
-// A tail of W1 % K columns uses the v1 scheme (L_left parked in the output row).
-// PHASE 3: both phases in one launch (as described above).  PHASE 1 / 2: the two phases as separate launches, phase 1 over the
-// segments [seg0, seg1) only, so that it can follow the cost kernel slab by slab (cost of slab j+1 overlaps the forward chain
-// over slab j): the state entering segment seg0 is read from the checkpoint the previous launch left, the state entering seg1
-// is left for the next one; the launch with seg1 == nfull also runs the tail columns.  Phase 2 only needs the checkpoints.
-template <int NPL, int LPC, int K, bool PADDED, int PHASE = 3>
-__global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int *__restrict__ hvol, int *__restrict__ ckpt, SgmGeom g,
-                                               int seg0, int seg1) {
+// HBM traffic per row: C read twice, sum written once, + 2 * (DP + 16) B * W1/K of checkpoints.
+// A tail of W1 % K columns parks its L_left in the output row between the two phases (written forward, read back and replaced by
+// the sum by the same lanes).
+template <int NPL, int LPC, int K, bool PADDED>
+__global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int *__restrict__ hvol, int *__restrict__ ckpt, SgmGeom g) {
     // words per column, rows per wave; CKS: words of one checkpoint = the DP/2 packed words of L + its minimum, padded to 16 B.
-    // Checkpoints are addressed by IMAGE ROW, not by wave and lane, so that the two phases may use different lane mappings
-    // (R3D_HSCAN_SPLIT: forward sweep with 2 rows per wave, backward sweep with 4)
+    // Checkpoints are addressed by image row.
     constexpr int DPW = NPL * LPC, RPW = 64 / LPC, CKS = DPW + 4;
     const int lane = threadIdx.x, k = lane % LPC;
     const int yraw = blockIdx.x * RPW + lane / LPC;
@@ -920,8 +588,7 @@ __global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int
     int c0[K][NPL], c1[K][NPL], c2[K][NPL], c3[K][NPL], llA[K][NPL], llB[K][NPL];
 #pragma unroll
     for (int j = 0; j < NPL; j++) P[j] = valid ? 0 : PADPK;
-    // phase-1 range launches never read past their own slab (the cost kernel may still be writing the next one)
-    const int seg_hi = PHASE == 1 ? min(seg1, nfull) : nfull;
+    const int seg_hi = nfull;   // segments of the forward sweep (a local of its own: DESIGN.md section 7)
     auto load_seg = [&](int (&buf)[K][NPL], int sidx) {
         const int sc = min(max(sidx, 0), max(seg_hi - 1, 0));
         const int *p = crow + (size_t)sc * K * DPW;
@@ -953,23 +620,18 @@ __global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int
 #pragma unroll
         for (int u = 0; u < K; u++) sgm_step_g<NPL, LPC, PADDED>(P, minp, cur[u], P1pk, g.P2, first, last, valid);
     };
-    const int sb = PHASE == 1 ? max(seg0, 0) : 0;
-    if (PHASE & 1) {
-    if (PHASE == 1 && sb > 0) load_ck(sb);
-    if (seg_hi > sb) {
-        load_seg(c0, sb); load_seg(c1, sb + 1); load_seg(c2, sb + 2);
+    if (seg_hi > 0) {
+        load_seg(c0, 0); load_seg(c1, 1); load_seg(c2, 2);
 #pragma unroll 1
-        for (int s0 = sb; s0 < seg_hi; s0 += 4) {
+        for (int s0 = 0; s0 < seg_hi; s0 += 4) {
             fwd_round(c0, c3, s0);
             if (s0 + 1 < seg_hi) fwd_round(c1, c0, s0 + 1);
             if (s0 + 2 < seg_hi) fwd_round(c2, c1, s0 + 2);
             if (s0 + 3 < seg_hi) fwd_round(c3, c2, s0 + 3);
         }
     }
-    if (PHASE == 1 && seg_hi < nfull) save_ck(seg_hi);     // state entering the next launch's first segment
     // tail columns [nfull*K, W1): forward values parked in the output row (rows beyond the image park nothing: they
     // recompute nothing useful either, their results are never stored)
-    if (PHASE == 3 || seg_hi == nfull)
     for (int x = nfull * K; x < W1; x++) {
         int c[NPL];
 #pragma unroll
@@ -980,8 +642,6 @@ __global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int
             for (int j = 0; j < NPL; j++) hrow[(size_t)x * DPW + j] = P[j];
         }
     }
-    }
-    if (!(PHASE & 2)) return;
     // ---- phase 2: backward chain of segment s in lockstep with the recomputed forward chain of segment s-1
     int R[NPL], minr = 0;
 #pragma unroll
@@ -1061,504 +721,6 @@ __global__ void __launch_bounds__(64) k_hscan2(const int *__restrict__ cvol, int
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_cost_fwd (R3D_SGM_IMPL=v5): block cost AND forward chain in one kernel -- the forward sweep no longer reads C from HBM
-// (2 GB per 8 MP map), and the cost arithmetic runs underneath the chain instead of in front of it.
-// The chain runs along image rows, so this kernel marches ALONG rows (k_cost2 marches down them): a workgroup owns RB = 4 output
-// rows for all W1 cost columns.  Wave 0 is the chain wave (the lane mapping of k_hscan2<4, 16, ...>: 16 lanes x 4 packed registers
-// per row, 4 rows); waves 1..3 are producers: producer p evaluates, for every third column, the Birchfield-Tomasi pixel cost of
-// the RB + 2*SH2 input rows (lane = disparity pair, so a column is one wave-wide vector per row; right-image records straight from
-// global memory: a wave reads one contiguous 1 KB window per row) and the VERTICAL box sums V of the RB output rows, which go to a
-// ring of columns in LDS.  The chain wave turns V into C by a sliding horizontal sum (C(x) = C(x-1) + V'(x+SW2) - V'(x-SW2-1),
-// exact in int16 arithmetic), writes C to HBM for the backward phase (k_hscan2<PHASE 2>), runs the L_left step, and saves the
-// checkpoints that phase needs.  One workgroup barrier per KR = 12 columns; producers run one round ahead.
-// V'(xv) = V(clamp(xv, 0, W1-1)): the replicated borders of the original's box filter in cost coordinates; rows clamp to the image.
-template <int SH2, bool PADDED>
-__global__ void __launch_bounds__(256) k_cost_fwd(const uint2 *__restrict__ recL, const uint2 *__restrict__ recR, SgmGeom g,
-                                                  int *__restrict__ cvol, int *__restrict__ hvol, int *__restrict__ ckpt) {
-    constexpr int NPL = 4, LPC = 16, DPW = NPL * LPC, RB = 4, RIN = RB + 2 * SH2, R = 2 * SH2 + 1, KR = 12, NPROD = 3, K = 16, CKS = DPW + 4;
-    constexpr int CPP = KR / NPROD;                       // columns a producer evaluates per round
-    constexpr int SLOTS = 2 * KR + 2 * SH2 + 1;          // V columns alive at once: [x0 - SH2 - 1, x0 + 2 KR + SH2)
-    constexpr int RING = 256;                             // right-image records per input row kept in LDS (a window of 128 + 2 KR + SH2 is live)
-    constexpr int LSLOTS = 2 * KR + 2 * SH2 + 2;          // left-image columns kept in LDS (the prologue's KR + 2 SH2 + 1 plus one round being filed)
-    // LDS per workgroup at SH2 = 2: 29 KB + 16.1 KB + 5.6 KB = 50.7 KB: three workgroups per CU (612 workgroups at C2 = 2.4 per CU)
-    constexpr int NITEM = 2 * RIN * KR, NST = (NITEM + NPROD * 64 - 1) / (NPROD * 64);   // staged records per round; per producer thread
-    static_assert(KR % NPROD == 0 && KR + 2 * SH2 + 1 + KR <= LSLOTS, "round geometry");
-    __shared__ int sV[SLOTS][RB][DPW];
-    // records of the right image, per input row: record i sits at index (i & 255) + 1; index 0 mirrors index 256, so that the pair
-    // (i - 1, i) a lane needs is always 16 contiguous bytes
-    __shared__ uint2 sR[RIN][RING + 2];
-    // left image: per input row and column the six Birchfield-Tomasi quantities, each already splatted into both halves of a word
-    // (read by every lane of a producer at the same address: a broadcast)
-    __shared__ int sL[RIN][LSLOTS][6];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int y0 = blockIdx.x * RB, W1 = g.W1;
-    const int nr = (W1 + KR - 1) / KR;                    // rounds of KR chain columns
-    auto slot_of = [&](int xv) { int v = (xv + SH2 + 1) % SLOTS; return v < 0 ? v + SLOTS : v; };
-    auto lslot_of = [&](int xv) { int v = (xv + SH2 + 1) % LSLOTS; return v < 0 ? v + LSLOTS : v; };
-    auto row_of = [&](int q) { return min(max(y0 - SH2 + q, 0), g.H - 1); };
-    // highest right-image column the production of round t reads (t = -1: the prologue)
-    const int rofs = g.minX1 - g.minD;
-    auto rec_hi = [&](int t) { return min(KR * (t + 2) + SH2 - 1, W1 - 1) + rofs; };
-    auto put_rec = [&](int q, int i, uint2 v) {
-        sR[q][(i & (RING - 1)) + 1] = v;
-        if ((i & (RING - 1)) == RING - 1) sR[q][0] = v;
-    };
-    auto get_left = [&](int q, int xv) { return recL[(size_t)row_of(q) * g.W + min(max(xv, 0), W1 - 1) + g.minX1]; };
-    auto put_left = [&](int q, int xv, uint2 lr) {
-        int2 *o = (int2 *)&sL[q][lslot_of(xv)][0];
-        o[0] = make_int2((int)(lr.x & 255u) * 0x10001, (int)((lr.x >> 8) & 255u) * 0x10001);
-        o[1] = make_int2((int)((lr.x >> 16) & 255u) * 0x10001, (int)(lr.x >> 24) * 0x10001);
-        o[2] = make_int2((int)(lr.y & 255u) * 0x10001, (int)((lr.y >> 8) & 255u) * 0x10001);
-    };
-    // all 256 threads: what the prologue production reads (right-image window, left columns [-SH2 - 1, KR + SH2))
-    {
-        const int lo = rofs - (g.DP - 1) - 1, hi = rec_hi(-1), cnt = hi - lo + 1;
-        for (int u = threadIdx.x; u < RIN * cnt; u += 256) {
-            const int q = u / cnt, i = lo + u % cnt;
-            put_rec(q, i, recR[(size_t)row_of(q) * g.W + min(max(i, 0), g.W - 1)]);
-        }
-        constexpr int LC = KR + 2 * SH2 + 1;
-        for (int u = threadIdx.x; u < RIN * LC; u += 256) {
-            const int q = u / LC, xv = -SH2 - 1 + u % LC;
-            put_left(q, xv, get_left(q, xv));
-        }
-    }
-    __syncthreads();
-    if (wave > 0) {
-        // ---------------------------------------------------------------- producers
-        const int p = wave - 1, u0 = threadIdx.x - 64;
-        // evaluation of one column, in two halves so that the LDS reads of the next column are in flight during the arithmetic of this one
-        struct Col { uint2 A[RIN], B[RIN]; int xv; };   // (the left-image words are the same in every lane: read where they are used)
-        auto load_col = [&](int xv, Col &c) {
-            const int xc = min(max(xv, 0), W1 - 1), xi = xc + g.minX1;
-            const int r = xi - g.minD - 2 * lane;        // right column of the even disparity of this lane's pair
-            const int ri = r & (RING - 1);               // the pair (r - 1, r) = sR[.][ri], sR[.][ri + 1]
-            c.xv = xv;
-#pragma unroll
-            for (int q = 0; q < RIN; q++) { c.B[q] = sR[q][ri]; c.A[q] = sR[q][ri + 1]; }
-        };
-        auto compute_col = [&](const Col &c) {
-            int pix[RIN];
-            const int ls = lslot_of(c.xv);
-#pragma unroll
-            for (int q = 0; q < RIN; q++) {
-                const uint2 A = c.A[q], B = c.B[q];
-                const int2 *lp = (const int2 *)&sL[q][ls][0];
-                const int2 l0 = lp[0], l1 = lp[1], l2 = lp[2];           // (Ug, Ug0) (Ug1, Ui) (Ui0, Ui1): one address for the whole wave
-                const int Vg = __builtin_amdgcn_perm(B.x, A.x, 0x0c040c00), Vg0 = __builtin_amdgcn_perm(B.x, A.x, 0x0c050c01);
-                const int Vg1 = __builtin_amdgcn_perm(B.x, A.x, 0x0c060c02), Vi = __builtin_amdgcn_perm(B.x, A.x, 0x0c070c03);
-                const int Vi0 = __builtin_amdgcn_perm(B.y, A.y, 0x0c040c00), Vi1 = __builtin_amdgcn_perm(B.y, A.y, 0x0c050c01);
-                const int cg = bt_cost_pk(l0.x, l0.y, l1.x, Vg, Vg0, Vg1);
-                const int ci = bt_cost_pk(l1.y, l2.x, l2.y, Vi, Vi0, Vi1);
-                pix[q] = pk_add(cg, (ci >> 2) & 0x3fff3fff);
-            }
-            int v = 0;
-#pragma unroll
-            for (int q = 0; q < R; q++) v = pk_add(v, pix[q]);
-            int *dst = &sV[slot_of(c.xv)][0][lane];
-            dst[0] = v;
-#pragma unroll
-            for (int rr = 1; rr < RB; rr++) {
-                v = pk_add(pk_sub(v, pix[rr - 1]), pix[rr - 1 + R]);
-                dst[rr * DPW] = v;
-            }
-        };
-        // a round's new records (right image: the KR columns the window advances by; left image: the KR columns the NEXT round
-        // evaluates) are fetched at its start and filed at its end: a whole round hides the loads
-        uint2 sv[NST];
-        auto stage_fetch = [&](int t) {                  // t = -1: during the prologue
-#pragma unroll
-            for (int e = 0; e < NST; e++) {
-                const int u = u0 + e * NPROD * 64;
-                sv[e] = make_uint2(0, 0);
-                if (u < RIN * KR) {
-                    const int q = u / KR, i = rec_hi(t) + 1 + u % KR;
-                    if (i <= rec_hi(t + 1)) sv[e] = recR[(size_t)row_of(q) * g.W + min(max(i, 0), g.W - 1)];
-                } else if (u < NITEM) {
-                    const int v2 = u - RIN * KR;
-                    sv[e] = get_left(v2 / KR, KR * (t + 2) + SH2 + v2 % KR);
-                }
-            }
-        };
-        auto stage_file = [&](int t) {
-#pragma unroll
-            for (int e = 0; e < NST; e++) {
-                const int u = u0 + e * NPROD * 64;
-                if (u < RIN * KR) {
-                    const int q = u / KR, i = rec_hi(t) + 1 + u % KR;
-                    if (i <= rec_hi(t + 1)) put_rec(q, i, sv[e]);
-                } else if (u < NITEM) {
-                    const int v2 = u - RIN * KR;
-                    put_left(v2 / KR, KR * (t + 2) + SH2 + v2 % KR, sv[e]);
-                }
-            }
-        };
-        stage_fetch(-1);
-        // prologue: everything round 0 reads: xv in [-SH2 - 1, KR + SH2) (the slot at -SH2 - 1 is only ever subtracted at x = 0,
-        // where the chain does not slide; it is produced anyway so that no slot is read before it was written)
-        {
-            Col c;
-            for (int xv = -SH2 - 1 + p; xv < KR + SH2; xv += NPROD) { load_col(xv, c); compute_col(c); }
-        }
-        stage_file(-1);
-        __syncthreads();
-        for (int t = 0; t < nr; t++) {
-            const int x0 = KR * (t + 1) + SH2;           // what round t + 1 needs beyond what round t had
-            stage_fetch(t);
-            if (t + 1 < nr) {
-                Col ca, cb;
-                load_col(x0 + p, ca);
-#pragma unroll
-                for (int c = 0; c < CPP; c += 2) {
-                    if (c + 1 < CPP) load_col(x0 + p + (c + 1) * NPROD, cb);
-                    compute_col(ca);
-                    if (c + 2 < CPP) load_col(x0 + p + (c + 2) * NPROD, ca);
-                    if (c + 1 < CPP) compute_col(cb);
-                }
-            }
-            stage_file(t);
-            __syncthreads();
-        }
-        return;
-    }
-    // -------------------------------------------------------------------- chain wave
-    const int k = lane % LPC, rl = lane / LPC;
-    const int yraw = y0 + rl;
-    const bool row_ok = yraw < g.H;
-    const int y = min(yraw, g.H - 1);
-    int *crow = cvol + (size_t)y * W1 * DPW + k * NPL;
-    int *hrow = hvol + (size_t)y * W1 * DPW + k * NPL;
-    const int nfull = W1 / K, P1pk = pk_dup(g.P1);
-    int *ckrow = ckpt + (size_t)yraw * (nfull + 1) * CKS, *ck = ckrow + k * NPL;
-    const bool valid = 2 * NPL * k < g.D, first = k == 0, last = k == LPC - 1;
-    int P[NPL], C[NPL], minp = 0;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) { P[j] = valid ? 0 : PADPK; C[j] = 0; }
-    auto ldv = [&](int xv) { return *(const int4 *)&sV[slot_of(xv)][rl][k * NPL]; };
-    __syncthreads();                                      // the producers' prologue (the staging above was barrier one)
-    for (int t = 0; t < nr; t++) {
-        const int xb = KR * t;
-        // the round's V columns [xb - SH2 - 1, xb + KR + SH2) into registers first: the chain below then never waits for LDS
-        int4 v[KR + 2 * SH2 + 1];
-#pragma unroll
-        for (int i = 0; i < KR + 2 * SH2 + 1; i++) v[i] = ldv(xb - SH2 - 1 + i);
-#pragma unroll
-        for (int c = 0; c < KR; c++) {
-            const int x = xb + c;
-            if (x < W1) {
-                if (x == 0) {
-#pragma unroll
-                    for (int i = 1; i <= 2 * SH2 + 1; i++) {   // V'(-SH2) .. V'(SH2)
-                        C[0] = pk_add(C[0], v[i].x); C[1] = pk_add(C[1], v[i].y); C[2] = pk_add(C[2], v[i].z); C[3] = pk_add(C[3], v[i].w);
-                    }
-                } else {
-                    const int4 a = v[c + 2 * SH2 + 1], b = v[c];   // V'(x + SH2), V'(x - SH2 - 1)
-                    C[0] = pk_sub(pk_add(C[0], a.x), b.x); C[1] = pk_sub(pk_add(C[1], a.y), b.y);
-                    C[2] = pk_sub(pk_add(C[2], a.z), b.z); C[3] = pk_sub(pk_add(C[3], a.w), b.w);
-                }
-                if (row_ok) *(int4 *)(crow + (size_t)x * DPW) = make_int4(C[0], C[1], C[2], C[3]);
-                if ((x & (K - 1)) == 0 && x / K < nfull) {   // the state entering segment x / K (k_hscan2's checkpoint layout)
-                    const int sidx = x / K;
-                    *(int4 *)(ck + (size_t)sidx * CKS) = make_int4(P[0], P[1], P[2], P[3]);
-                    if (first) ckrow[(size_t)sidx * CKS + DPW] = minp;
-                }
-                sgm_step_g<NPL, LPC, PADDED>(P, minp, C, P1pk, g.P2, first, last, valid);
-                if (x >= nfull * K && row_ok) *(int4 *)(hrow + (size_t)x * DPW) = make_int4(P[0], P[1], P[2], P[3]);   // tail: L_left parked
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_hscan_fwd: phase 1 of k_hscan2 (forward chain + checkpoints) as a LOW-REGISTER kernel of its own, for the overlap with the
-// cost kernel.  k_hscan2 keeps 256 + 128 registers of cost segments in flight and owns the whole register file of its SIMD, so
-// none of its waves can start while cost waves occupy that SIMD (measured: cost and a k_hscan2<PHASE 1> launch on two streams
-// simply ran one after the other).  Here the rotating buffers hold K = 4 columns (64 registers), the kernel is compiled for
-// four waves per SIMD (<= 128 registers) and fits beside the two cost workgroups a CU holds (4 x 96 registers per SIMD).
-// Segments [seg0, seg1) are counted in checkpoint intervals of KCK columns (the K of the backward-phase kernel that reads the
-// checkpoints); the state entering seg0 comes from the previous launch, the state entering seg1 is left for the next one; the
-// launch that reaches the last interval also runs the tail columns (parked in the output row, as k_hscan2 does).
-template <int NPL, int LPC, int K, int KCK, bool PADDED>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_hscan_fwd(const int *__restrict__ cvol, int *__restrict__ hvol, int *__restrict__ ckpt, SgmGeom g, int seg0, int seg1) {
-    static_assert(KCK % K == 0, "checkpoint interval is a whole number of buffer segments");
-    // (Raising this wave's issue priority with s_setprio 3 was tried: the cost slabs then took 313 us instead of 200-295 and
-    // the forward slabs stayed at 200-430 us: the slowdown is in the memory system, not in the issue arbiter.)
-    constexpr int DPW = NPL * LPC, RPW = 64 / LPC, CKS = DPW + 4, RATIO = KCK / K;   // checkpoint layout: see k_hscan2
-    const int lane = threadIdx.x, k = lane % LPC;
-    const int yraw = blockIdx.x * RPW + lane / LPC;
-    const bool row_ok = yraw < g.H;
-    const int y = min(yraw, g.H - 1);
-    const int *crow = cvol + (size_t)y * g.W1 * DPW + k * NPL;
-    int *hrow = hvol + (size_t)y * g.W1 * DPW + k * NPL;
-    const int W1 = g.W1, nck = W1 / KCK, P1pk = pk_dup(g.P1);
-    int *ckrow = ckpt + (size_t)yraw * (nck + 1) * CKS, *ck = ckrow + k * NPL;
-    const bool valid = 2 * NPL * k < g.D, first = k == 0, last = k == LPC - 1;
-    const int ck_lo = max(seg0, 0), ck_hi = min(seg1, nck);
-    const int sb = ck_lo * RATIO, se = ck_hi * RATIO;          // sub-segments of K columns
-    int P[NPL], minp = 0;
-    if (ck_lo > 0) {
-#pragma unroll
-        for (int j = 0; j < NPL; j++) P[j] = ck[(size_t)ck_lo * CKS + j];
-        minp = ckrow[(size_t)ck_lo * CKS + DPW];
-    } else {
-#pragma unroll
-        for (int j = 0; j < NPL; j++) P[j] = valid ? 0 : PADPK;
-    }
-    int c0[K][NPL], c1[K][NPL], c2[K][NPL], c3[K][NPL];
-    auto load_seg = [&](int (&buf)[K][NPL], int sidx) {        // never reads past this launch's slab
-        const int sc = min(max(sidx, 0), max(se - 1, 0));
-        const int *p = crow + (size_t)sc * K * DPW;
-#pragma unroll
-        for (int u = 0; u < K; u++)
-#pragma unroll
-            for (int j = 0; j < NPL; j++) buf[u][j] = p[(size_t)u * DPW + j];
-    };
-    auto round = [&](int (&cur)[K][NPL], int (&pre)[K][NPL], int sidx) {
-        load_seg(pre, sidx + 3);
-        if (sidx % RATIO == 0) {
-#pragma unroll
-            for (int j = 0; j < NPL; j++) ck[(size_t)(sidx / RATIO) * CKS + j] = P[j];
-            if (first) ckrow[(size_t)(sidx / RATIO) * CKS + DPW] = minp;
-        }
-#pragma unroll
-        for (int u = 0; u < K; u++) sgm_step_g<NPL, LPC, PADDED>(P, minp, cur[u], P1pk, g.P2, first, last, valid);
-    };
-    if (se > sb) {
-        load_seg(c0, sb); load_seg(c1, sb + 1); load_seg(c2, sb + 2);
-#pragma unroll 1
-        for (int s0 = sb; s0 < se; s0 += 4) {
-            round(c0, c3, s0);
-            if (s0 + 1 < se) round(c1, c0, s0 + 1);
-            if (s0 + 2 < se) round(c2, c1, s0 + 2);
-            if (s0 + 3 < se) round(c3, c2, s0 + 3);
-        }
-    }
-    if (ck_hi < nck) {                                          // state entering the next launch's first interval
-#pragma unroll
-        for (int j = 0; j < NPL; j++) ck[(size_t)ck_hi * CKS + j] = P[j];
-        if (first) ckrow[(size_t)ck_hi * CKS + DPW] = minp;
-        return;
-    }
-    for (int x = nck * KCK; x < W1; x++) {                      // tail columns: forward values parked in the output row
-        int c[NPL];
-#pragma unroll
-        for (int j = 0; j < NPL; j++) c[j] = crow[(size_t)x * DPW + j];
-        sgm_step_g<NPL, LPC, PADDED>(P, minp, c, P1pk, g.P2, first, last, valid);
-        if (row_ok) {
-#pragma unroll
-            for (int j = 0; j < NPL; j++) hrow[(size_t)x * DPW + j] = P[j];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Winner-take-all + uniqueness + sub-pixel for one disparity vector in the generic mapping (group-uniform results).
-// sS: per-wave LDS image (64 * NPL ints) used to fetch the winner's two neighbours with a per-group address.
-template <int NPL, int LPC>
-__device__ __forceinline__ void wta_eval(const int (&S)[NPL], int lane, int k, bool valid, const SgmGeom &g, float inv_a, int *sS,
-                                         int &dsp_out, int &minS_out) {
-    int key = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) {
-        const int d0 = 2 * NPL * k + 2 * j;
-        const int k0 = (int)((unsigned)S[j] << 16) | d0;
-        const int k1 = (S[j] & (int)0xffff0000) | (d0 + 1);
-        key = min(key, min(k0, k1));
-    }
-    if (!valid) key = 0x7fffffff;
-    key = grp_allmin<LPC>(key);
-    const int best = key & 0xffff, minS = key >> 16;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NPL; j++) sS[lane * NPL + j] = S[j];
-    __syncthreads();
-    const int gbase = (lane - k) * NPL;
-    const int dm = max(best - 1, 0), dp = min(best + 1, g.D - 1);
-    const int wm = sS[gbase + (dm >> 1)], wp = sS[gbase + (dp >> 1)];
-    const int sm = (dm & 1) ? hi16(wm) : lo16(wm), sp = (dp & 1) ? hi16(wp) : lo16(wp);
-    bool bad = false;
-    if (g.uniq > 0) {
-        const int T = ceil_div_small(minS * 100, 100 - g.uniq, inv_a);
-        int cnt;
-        if (T > 32767) cnt = valid ? 2 * NPL : 0;
-        else {
-            const int Tpk = pk_dup(max(T, -32768));
-            int acc = 0;
-#pragma unroll
-            for (int j = 0; j < NPL; j++) {
-                const int diff = as_i(__builtin_elementwise_sub_sat(as_s(S[j]), as_s(Tpk)));
-                acc = pk_sub(acc, as_i(as_s(diff) >> (s16x2){15, 15}));
-            }
-            cnt = valid ? lo16(acc) + hi16(acc) : 0;
-        }
-        cnt = grp_allsum<LPC>(cnt);
-        int win = (minS < T) ? 1 : 0;
-        if (best > 0 && sm < T) win++;
-        if (best < g.D - 1 && sp < T) win++;
-        bad = cnt > win;
-    }
-    int dsp = g.invalid;
-    if (!bad) {
-        dsp = best * 16;
-        if (0 < best && best < g.D - 1) {
-            const int den = max(sm + sp - 2 * minS, 1);
-            dsp += trunc_div_small((sm - sp) * 16 + den, den * 2);
-        }
-        dsp += g.minD * 16;
-    }
-    dsp_out = dsp;
-    minS_out = minS;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// k_hscan3 (v3): k_hscan2 whose backward phase finishes the pixel: S = (L_left + L_right) + L_top, winner-take-all,
-// uniqueness and sub-pixel happen in the same step, so only the disparity and its cost leave the kernel -- the
-// L_left + L_right volume is never written.  L_top comes from k_cost2<VCH>; its loads are off the dependency chain.
-template <int NPL, int LPC, int K, bool PADDED>
-__global__ void __launch_bounds__(64) k_hscan3(const int *__restrict__ cvol, const int *__restrict__ ltvol, int *__restrict__ tail,
-                                               int *__restrict__ ckpt, SgmGeom g, float inv_a, int16_t *__restrict__ raw,
-                                               int16_t *__restrict__ mins) {
-    constexpr int DPW = NPL * LPC, RPW = 64 / LPC, CKW = (NPL + 1) * 64;
-    __shared__ int sS[64 * NPL];
-    const int lane = threadIdx.x, k = lane % LPC;
-    const int yraw = blockIdx.x * RPW + lane / LPC;
-    const bool row_ok = yraw < g.H;
-    const int y = min(yraw, g.H - 1);
-    const int *crow = cvol + (size_t)y * g.W1 * DPW + k * NPL;
-    const int *lrow = ltvol + (size_t)y * g.W1 * DPW + k * NPL;
-    int *trow = tail + (size_t)y * K * DPW + k * NPL;                 // parking space of the tail columns' L_left
-    const int W1 = g.W1, nfull = W1 / K, P1pk = pk_dup(g.P1), P2pk = pk_dup(g.P2);
-    int *ck = ckpt + (size_t)blockIdx.x * (nfull + 1) * CKW + lane * (NPL + 1);
-    const bool valid = 2 * NPL * k < g.D, first = k == 0, last = k == LPC - 1;
-    int P[NPL], minp = 0;
-    int c0[K][NPL], c1[K][NPL], c2[K][NPL], c3[K][NPL], llA[K][NPL], llB[K][NPL], ltA[K][NPL], ltB[K][NPL];
-#pragma unroll
-    for (int j = 0; j < NPL; j++) P[j] = valid ? 0 : PADPK;
-    auto load_seg = [&](int (&buf)[K][NPL], const int *row, int sidx) {
-        const int sc = min(max(sidx, 0), max(nfull - 1, 0));
-        const int *p = row + (size_t)sc * K * DPW;
-#pragma unroll
-        for (int u = 0; u < K; u++)
-#pragma unroll
-            for (int j = 0; j < NPL; j++) buf[u][j] = p[(size_t)u * DPW + j];
-    };
-    auto save_ck = [&](int sidx) {
-#pragma unroll
-        for (int j = 0; j < NPL; j++) ck[(size_t)sidx * CKW + j] = P[j];
-        ck[(size_t)sidx * CKW + NPL] = minp;
-    };
-    auto load_ck = [&](int sidx) {
-#pragma unroll
-        for (int j = 0; j < NPL; j++) P[j] = ck[(size_t)sidx * CKW + j];
-        minp = ck[(size_t)sidx * CKW + NPL];
-    };
-    // finishes cost column xcol: S, WTA, stores
-    auto finish = [&](int xcol, const int (&ll)[NPL], const int (&lr)[NPL], const int (&lt)[NPL]) {
-        int S[NPL];
-#pragma unroll
-        for (int j = 0; j < NPL; j++) S[j] = pk_add_sat(pk_add(ll[j], lr[j]), lt[j]);
-        int dsp, mS;
-        wta_eval<NPL, LPC>(S, lane, k, valid, g, inv_a, sS, dsp, mS);
-        if (first && row_ok) {
-            const size_t o = (size_t)y * g.W + g.minX1 + xcol;
-            raw[o] = (int16_t)dsp;
-            mins[o] = (int16_t)mS;
-        }
-    };
-    // ---- phase 1: forward chain, checkpoint the state entering every segment
-    auto fwd_round = [&](int (&cur)[K][NPL], int (&pre)[K][NPL], int sidx) {
-        load_seg(pre, crow, sidx + 3);
-        save_ck(sidx);
-#pragma unroll
-        for (int u = 0; u < K; u++) sgm_step_g<NPL, LPC, PADDED>(P, minp, cur[u], P1pk, g.P2, first, last, valid);
-    };
-    if (nfull > 0) {
-        load_seg(c0, crow, 0); load_seg(c1, crow, 1); load_seg(c2, crow, 2);
-#pragma unroll 1
-        for (int s0 = 0; s0 < nfull; s0 += 4) {
-            fwd_round(c0, c3, s0);
-            if (s0 + 1 < nfull) fwd_round(c1, c0, s0 + 1);
-            if (s0 + 2 < nfull) fwd_round(c2, c1, s0 + 2);
-            if (s0 + 3 < nfull) fwd_round(c3, c2, s0 + 3);
-        }
-    }
-    for (int x = nfull * K; x < W1; x++) {
-        int c[NPL];
-#pragma unroll
-        for (int j = 0; j < NPL; j++) c[j] = crow[(size_t)x * DPW + j];
-        sgm_step_g<NPL, LPC, PADDED>(P, minp, c, P1pk, g.P2, first, last, valid);
-        if (row_ok) {
-#pragma unroll
-            for (int j = 0; j < NPL; j++) trow[(size_t)(x - nfull * K) * DPW + j] = P[j];
-        }
-    }
-    // ---- phase 2
-    int R[NPL], minr = 0;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) R[j] = valid ? 0 : PADPK;
-    for (int x = W1 - 1; x >= nfull * K; x--) {
-        int c[NPL], l[NPL], t[NPL];
-#pragma unroll
-        for (int j = 0; j < NPL; j++) {
-            c[j] = crow[(size_t)x * DPW + j];
-            l[j] = row_ok ? trow[(size_t)(x - nfull * K) * DPW + j] : 0;
-            t[j] = lrow[(size_t)x * DPW + j];
-        }
-        sgm_step_g<NPL, LPC, PADDED>(R, minr, c, P1pk, g.P2, first, last, valid);
-        finish(x, l, R, t);
-    }
-    // round(s): A = costs of segment s (backward), B = costs of segment s-1 (forward), pre <- segment s-3;
-    //           TA = L_top of segment s, TB <- L_top of segment s-1 (one round of lead, off the chain)
-    auto bwd_round = [&](int (&A)[K][NPL], int (&B)[K][NPL], int (&pre)[K][NPL], int (&TA)[K][NPL], int (&TB)[K][NPL], int sidx) {
-        load_seg(pre, crow, sidx - 3);
-        load_seg(TB, lrow, sidx - 1);
-        if (sidx > 0) {
-            load_ck(sidx - 1);
-            int mAB = (minr & 0xffff) | (minp << 16);
-#pragma unroll
-            for (int u = 0; u < K; u++) {
-                sgm_step_dual_g<NPL, LPC, PADDED>(R, P, mAB, A[K - 1 - u], B[u], P1pk, P2pk, first, last, valid);
-                finish(sidx * K + K - 1 - u, llA[K - 1 - u], R, TA[K - 1 - u]);
-#pragma unroll
-                for (int j = 0; j < NPL; j++) llB[u][j] = P[j];
-            }
-            minr = lo16(mAB);
-            minp = hi16(mAB);
-        } else {
-#pragma unroll
-            for (int u = 0; u < K; u++) {
-                sgm_step_g<NPL, LPC, PADDED>(R, minr, A[K - 1 - u], P1pk, g.P2, first, last, valid);
-                finish(sidx * K + K - 1 - u, llA[K - 1 - u], R, TA[K - 1 - u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < K; u++)
-#pragma unroll
-            for (int j = 0; j < NPL; j++) llA[u][j] = llB[u][j];
-    };
-    if (nfull > 0) {
-        load_seg(c0, crow, nfull - 1); load_seg(c1, crow, nfull - 2); load_seg(c2, crow, nfull - 3);
-        load_seg(ltA, lrow, nfull - 1);
-        load_ck(nfull - 1);
-#pragma unroll
-        for (int u = 0; u < K; u++) {
-            sgm_step_g<NPL, LPC, PADDED>(P, minp, c0[u], P1pk, g.P2, first, last, valid);
-#pragma unroll
-            for (int j = 0; j < NPL; j++) llA[u][j] = P[j];
-        }
-#pragma unroll 1
-        for (int s = nfull - 1; s >= 0; s -= 4) {
-            bwd_round(c0, c1, c3, ltA, ltB, s);
-            if (s - 1 >= 0) bwd_round(c1, c2, c0, ltB, ltA, s - 1);
-            if (s - 2 >= 0) bwd_round(c2, c3, c1, ltA, ltB, s - 2);
-            if (s - 3 >= 0) bwd_round(c3, c0, c2, ltB, ltA, s - 3);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // k_vscan2: vertical path + winner-take-all with 16 disparities per lane (NPL = 8): LPC = DP/16 lanes per column,
 // CPW = 64/LPC adjacent columns per wave, each column an independent chain inside its lane group.  Everything after
 // the path step -- argmin (32-bit keys cost<<16|d, v_min3 tree + group butterfly), uniqueness (packed compare against
@@ -1571,7 +733,7 @@ __global__ void __launch_bounds__(64) k_vscan2(const int *__restrict__ cvol, con
     constexpr int CPW = 64 / LPC, DPW = NPL * LPC;  // columns per wave, words per column
     static_assert(NPL == 4 || NPL == 8 || NPL == 16, "one, two or four 16-byte loads per lane");
     const int lane = threadIdx.x, k = lane % LPC, grp = lane / LPC, n = blockIdx.y;
-    const int xc = col0 + blockIdx.x * CPW + grp;   // col0: first cost column of this launch (the balanced split below)
+    const int xc = col0 + blockIdx.x * CPW + grp;   // cost column of this lane group; col0 is always 0, kept as tile0 is in k_cost2
     const bool col_ok = xc < g.W1;
     const size_t rowWords = (size_t)g.W1 * DPW;
     const int src_start = max(min(n * g.stripe_sz - g.overlap, g.H), 0);
@@ -1776,176 +938,11 @@ __device__ __forceinline__ void wta_regs(const int (&S)[NPL], int k, bool valid,
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_vscan3 (R3D_SGM_IMPL=v4): the vertical pass RECOMPUTES the block cost instead of reading it.  Same result as
-// k_vscan2; HBM traffic: the two record images + the L_left + L_right volume (read once) -- the 2 GB read of C is gone,
-// and so are the special stripe-top rows (cspec): the stripe's own march produces them.
-// Structure = k_cost2's producer loop (one workgroup per STRIPE x column tile marching down the stripe from its first
-// warm-up row; pixel cost -> vertical window in registers -> LDS tile -> horizontal box sum), whose freshly summed C
-// vector -- still in registers, in the 16-disparities-per-lane mapping -- feeds the L_top recurrence, S = (L_l + L_r) + L_t,
-// winner-take-all, uniqueness and sub-pixel of the same lane group.  The L_l + L_r rows are requested two rows ahead
-// into two register buffers (the loop is unrolled by two, so buffer and LDS slot are static).
-template <int LPC, int SH2, int NWAVE>
-__global__ void __launch_bounds__(NWAVE * 64) k_vscan3(const uint2 *__restrict__ recL, const uint2 *__restrict__ recR, SgmGeom g,
-                                                       const int *__restrict__ hvol, float inv_a, int16_t *__restrict__ raw,
-                                                       int16_t *__restrict__ mins) {
-    constexpr int NPL = 8, CW = 64 / LPC, TC = NWAVE * CW, TO = TC - 2 * SH2, DP = 16 * LPC, DPW = NPL * LPC;
-    constexpr int R = 2 * SH2 + 1, NRR = TC + DP, NT = NWAVE * 64;
-    constexpr int SWN = NRR * 6 + (NRR / 16 + 1) * 8;   // pair-word layout: see k_cost2
-    __shared__ int sW[2][SWN];
-    __shared__ uint2 sL[2][TC];
-    __shared__ int sV[2][TC * DPW];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, k = lane % LPC, grp = lane / LPC;
-    const int cl = w * CW + grp;
-    const int t0 = blockIdx.x * TO;
-    const int xc = min(max(t0 - SH2 + cl, 0), g.W1 - 1);
-    const int x = xc + g.minX1;
-    const int r_base = max(t0 - SH2, 0) + g.minX1 - g.minD - (DP - 1);
-    const int ri0 = min(max(x - g.minD - 16 * k - r_base, 15), NRR - 1);
-    const size_t rowWords = (size_t)g.W1 * DPW;
-    const int n = blockIdx.y;
-    const int y0 = max(min(n * g.stripe_sz - g.overlap, g.H), 0), y1 = min((n + 1) * g.stripe_sz, g.H);
-    const int out_start = min(n * g.stripe_sz, g.H);
-    if (y0 >= y1) return;
-    auto crow = [&](int yy) { return min(max(yy, y0), g.H - 1); };
-    const bool lane_valid = 16 * k < g.D, first = k == 0, last = k == LPC - 1;
-    const int P1pk = pk_dup(g.P1), a = 100 - g.uniq;
-    int LT[NPL], ltmin = 0;
-#pragma unroll
-    for (int j = 0; j < NPL; j++) LT[j] = lane_valid ? 0 : PADPK;
-
-    static_assert(NRR <= NT, "one pair-word record per thread");
-    uint2 pfL = make_uint2(0, 0), pfA = make_uint2(0, 0), pfB = make_uint2(0, 0);
-    auto fetch = [&](int row) {
-        const uint2 *lr = recL + (size_t)row * g.W, *rr = recR + (size_t)row * g.W;
-        if (tid < TC) pfL = lr[min(max(t0 - SH2 + tid, 0), g.W1 - 1) + g.minX1];
-        if (tid < NRR) {
-            const int r = r_base + tid;
-            pfA = rr[min(max(r, 0), g.W - 1)];
-            pfB = rr[min(max(r - 1, 0), g.W - 1)];
-        }
-    };
-    auto commit = [&](int b) {
-        if (tid < TC) sL[b][tid] = pfL;
-        if (tid < NRR) {
-            const uint2 A = pfA, B = pfB;
-            int *o = &sW[b][tid * 6 + (tid >> 4) * 8];
-            o[0] = __builtin_amdgcn_perm(B.x, A.x, 0x0c040c00); o[1] = __builtin_amdgcn_perm(B.x, A.x, 0x0c050c01);
-            o[2] = __builtin_amdgcn_perm(B.x, A.x, 0x0c060c02); o[3] = __builtin_amdgcn_perm(B.x, A.x, 0x0c070c03);
-            o[4] = __builtin_amdgcn_perm(B.y, A.y, 0x0c040c00); o[5] = __builtin_amdgcn_perm(B.y, A.y, 0x0c050c01);
-        }
-    };
-    auto pixel_cost = [&](int b, int (&pix)[NPL]) {
-        const uint2 lr = sL[b][cl];
-        const int Ug = __builtin_amdgcn_perm(lr.x, lr.x, 0x0c000c00), Ug0 = __builtin_amdgcn_perm(lr.x, lr.x, 0x0c010c01);
-        const int Ug1 = __builtin_amdgcn_perm(lr.x, lr.x, 0x0c020c02), Ui = __builtin_amdgcn_perm(lr.x, lr.x, 0x0c030c03);
-        const int Ui0 = __builtin_amdgcn_perm(lr.y, lr.y, 0x0c000c00), Ui1 = __builtin_amdgcn_perm(lr.y, lr.y, 0x0c010c01);
-#pragma unroll
-        for (int j = 0; j < NPL; j++) {
-            const int rj = ri0 - 2 * j;
-            typedef int v2i __attribute__((ext_vector_type(2)));           // three ds_read_b64, never ds_read2_b64: see k_cost2
-            typedef const volatile __attribute__((address_space(3))) v2i lds_v2i;
-            lds_v2i *p = (lds_v2i *)&sW[b][rj * 6 + (rj >> 4) * 8];
-            const v2i aa = p[0], bq = p[1], c = p[2];
-            const int cg = bt_cost_pk(Ug, Ug0, Ug1, aa.x, aa.y, bq.x);
-            const int ci = bt_cost_pk(Ui, Ui0, Ui1, bq.y, c.x, c.y);
-            pix[j] = pk_add(cg, (ci >> 2) & 0x3fff3fff);
-        }
-    };
-    int ring[R][NPL / 2], vs[NPL];
-#pragma unroll
-    for (int j = 0; j < NPL; j++) vs[j] = 0;
-#pragma unroll
-    for (int q = 0; q < R; q++)
-#pragma unroll
-        for (int j = 0; j < NPL / 2; j++) ring[q][j] = 0;
-    const int ocol = t0 - SH2 + cl;                        // cost column of this lane group
-    const bool is_out = cl >= SH2 && cl < TC - SH2 && ocol < g.W1;
-    const int tile_x0 = t0 - SH2;
-    const int *hptr = hvol + (size_t)min(max(ocol, 0), g.W1 - 1) * DPW + k * NPL;
-    // L_left + L_right of output row y (only rows the stripe owns are ever read)
-    auto hload = [&](int y, int (&hb)[NPL]) {
-        if (y >= out_start && y < y1) {
-            const int4 h0 = *(const int4 *)(hptr + (size_t)y * rowWords), h1 = *(const int4 *)(hptr + (size_t)y * rowWords + 4);
-            hb[0] = h0.x; hb[1] = h0.y; hb[2] = h0.z; hb[3] = h0.w; hb[4] = h1.x; hb[5] = h1.y; hb[6] = h1.z; hb[7] = h1.w;
-        }
-    };
-    int hA[NPL], hB[NPL];
-#pragma unroll
-    for (int j = 0; j < NPL; j++) hA[j] = hB[j] = 0;
-    // iteration t: image row e = y0 - SH2 + t enters the vertical window (inputs in LDS buffer b = t & 1, staged one
-    // iteration earlier); from t = 2*SH2 on the window is full and output row y = y0 + t - 2*SH2 is produced
-    auto iter = [&](int t, int b, int (&hb)[NPL]) {
-        int pn[NPL];
-        pixel_cost(b, pn);
-#pragma unroll
-        for (int j = 0; j < NPL / 2; j++) {
-            const int old = ring[0][j];
-            vs[2 * j] = pk_add(pk_sub(vs[2 * j], __builtin_amdgcn_perm(old, old, 0x0c010c00)), pn[2 * j]);
-            vs[2 * j + 1] = pk_add(pk_sub(vs[2 * j + 1], __builtin_amdgcn_perm(old, old, 0x0c030c02)), pn[2 * j + 1]);
-        }
-#pragma unroll
-        for (int q = 0; q + 1 < R; q++)
-#pragma unroll
-            for (int j = 0; j < NPL / 2; j++) ring[q][j] = ring[q + 1][j];
-#pragma unroll
-        for (int j = 0; j < NPL / 2; j++) ring[R - 1][j] = __builtin_amdgcn_perm(pn[2 * j + 1], pn[2 * j], 0x06040200);
-        const bool outp = t >= 2 * SH2;
-        if (outp) {
-            *(int4 *)&sV[b][cl * DPW + (DPW / 2) * (cl & 1) + 4 * k] = make_int4(vs[0], vs[1], vs[2], vs[3]);
-            *(int4 *)&sV[b][cl * DPW + (DPW / 2) * ((cl & 1) ^ 1) + 4 * k] = make_int4(vs[4], vs[5], vs[6], vs[7]);
-        }
-        commit(b ^ 1);
-        fetch(crow(y0 - SH2 + t + 2));
-        __syncthreads();
-        if (outp && is_out) {
-            int c[NPL];
-#pragma unroll
-            for (int j = 0; j < NPL; j++) c[j] = 0;
-#pragma unroll
-            for (int i = -SH2; i <= SH2; i++) {
-                const int col = min(max(tile_x0 + cl + i, 0), g.W1 - 1) - tile_x0;
-                const int4 v0 = *(const int4 *)&sV[b][col * DPW + (DPW / 2) * (col & 1) + 4 * k];
-                const int4 v1 = *(const int4 *)&sV[b][col * DPW + (DPW / 2) * ((col & 1) ^ 1) + 4 * k];
-                c[0] = pk_add(c[0], v0.x); c[1] = pk_add(c[1], v0.y); c[2] = pk_add(c[2], v0.z); c[3] = pk_add(c[3], v0.w);
-                c[4] = pk_add(c[4], v1.x); c[5] = pk_add(c[5], v1.y); c[6] = pk_add(c[6], v1.z); c[7] = pk_add(c[7], v1.w);
-            }
-            sgm_step_g<NPL, LPC, true>(LT, ltmin, c, P1pk, g.P2, first, last, lane_valid);
-            const int y = y0 + t - 2 * SH2;
-            if (y >= out_start) {
-                int S[NPL];
-#pragma unroll
-                for (int j = 0; j < NPL; j++) S[j] = pk_add_sat(hb[j], LT[j]);
-                hload(y + 2, hb);
-                int dsp, mS;
-                wta_regs<NPL, LPC>(S, k, lane_valid, g, a, inv_a, dsp, mS);
-                if (first) {
-                    const size_t o = (size_t)y * g.W + g.minX1 + ocol;
-                    raw[o] = (int16_t)dsp;
-                    mins[o] = (int16_t)mS;
-                }
-            } else
-                hload(y + 2, hb);
-        }
-    };
-    fetch(crow(y0 - SH2));
-    commit(0);
-    fetch(crow(y0 - SH2 + 1));
-    if (is_out) { hload(y0, hA); hload(y0 + 1, hB); }
-    __syncthreads();
-    const int niter = (y1 - y0) + 2 * SH2;
-#pragma unroll 1
-    for (int t = 0; t < niter; t += 2) {
-        iter(t, 0, hA);
-        if (t + 1 < niter) iter(t + 1, 1, hB);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // MODE_HH (OpenCV computeDisparitySGBM with fullDP): eight full-length paths over the one-stripe cost volume, folded into
 // S = sat16(S + L_r) in the contract order of the directions r = p - q:
 //   (+1,0) (+1,+1) (0,+1) (-1,+1)  (pass 1)   (-1,0) (+1,-1) (0,-1) (-1,-1)  (pass 2)
 // k_hh_path runs ONE direction over every line of its family (rows, columns, diagonals x-y = c, anti-diagonals x+y = c) with
-// the lane mapping of the v2 kernels (a disparity vector on LPC lanes x NPL packed registers, 64/LPC adjacent lines per wave):
+// the generic lane mapping (a disparity vector on LPC lanes x NPL packed registers, 64/LPC adjacent lines per wave):
 // one chain per line, each step moves by the family-constant stride (dy*W1 + dx)*DPW words in the [y][x][dp] volume, and the
 // loads of the next HH_RING steps are in flight while a step runs.
 // FOLD 0: S = L (first direction); 1: S = sat16(S + L); 2: the same, then wta_regs on the finished S into raw / mins (S is not
@@ -2264,7 +1261,7 @@ __global__ void __launch_bounds__(64) k_selftest(int *out) {
                 if (got != c + mm - (mq0 + 9)) bad |= 1 << 25;
             }
     }
-    // generic group helpers (v2 kernels), LPC = 8 and 16
+    // generic group helpers, LPC = 8 and 16
     {
         auto val = [](int l) { return (l * 37 + 11) % 101 - 50; };
         const int k8 = lane % 8, k16 = lane % 16;
@@ -2358,9 +1355,8 @@ int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, int cn, Sg
     if (w <= 0 || h <= 0 || w > 65536) return r3d_fail(ctx, R3D_E_BADARG, "sgbm: bad image size %dx%d", w, h);
     g.W = w; g.H = h;
     g.minD = p->minDisparity; g.D = p->numDisparities;
-    // NP: 128-slot units of the v1 / v3 layouts (1 or 2).  Those generations stop at D = 256 (sgm_run_impl refuses them above it), and
-    // the v2 launchers choose their D > 256 instantiations by DP, so NP stays 2 there and is never read as a size.
-    g.NP = g.D <= 128 ? 1 : 2;
+    g.NP = g.D <= 128 ? 1 : 2;   // read by nothing (every kernel and launcher goes by DP); the field stays so that SgmGeom, which every
+                                 // kernel takes by value, keeps its argument layout
     g.DP = g.D <= 32 ? 32 : g.D <= 64 ? 64 : g.D <= 128 ? 128 : g.D <= 256 ? 256 : 512;
     const int maxD = g.minD + g.D;
     g.minX1 = maxD > 0 ? maxD : 0;
@@ -2395,27 +1391,22 @@ int derive_geom(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, int cn, Sg
     return R3D_OK;
 }
 
-// col_lo / col_hi: cost columns of a column slab (whole tiles: [ceil(col_lo / TO), ceil(col_hi / TO)) of the tile grid, so
-// consecutive slabs partition the tiles); col_hi < 0 = the whole width
-// chan: the channel whose record planes are read; ACC (chan > 0): its block cost is added to the stored one (see k_cost2)
-template <int LPC, int SH2, bool TRACK, bool VCH, int NWAVE, bool ACC>
-int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
-    constexpr int CW = 64 / LPC, TC = NWAVE * CW, TO = TC - 2 * SH2;
-    if (TO <= 0) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: tile too small for this block size");
-    const int all_tiles = (g.W1 + TO - 1) / TO;
-    const int tile_lo = col_hi < 0 ? 0 : std::min((col_lo + TO - 1) / TO, all_tiles);
-    const int tile_hi = col_hi < 0 ? all_tiles : std::min((col_hi + TO - 1) / TO, all_tiles);
-    const int tiles = tile_hi - tile_lo;
-    if (tiles <= 0) return R3D_OK;
+// One launch of k_cost2: the block cost of channel `chan` (its record planes), stored (ACC false: channel 0) or added to what the
+// earlier channels stored (ACC: chan > 0; see k_cost2), for the main volume and the stripe-top rows alike.
+template <int LPC, int SH2, bool TRACK, bool ACC>
+int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int chan) {
+    constexpr int NWAVE = 8, CW = 64 / LPC, TC = NWAVE * CW, TO = TC - 2 * SH2;   // 8 waves: 64-column tiles at 128 slots, 2*SH2 of them halo
+    static_assert(TO > 0, "tile too small for this block size");
+    const int tiles = (g.W1 + TO - 1) / TO;
     // size the row bands so that one round of workgroups fills the chip (each band pays 2*SH2 extra rows of pixel cost)
-    // occupancy x CU count, queried once per instantiation AND device (slab launches call this several times per map; contexts of
-    // different devices / threads may race here: the slot is written once with a complete value, readers see 0 or that value)
+    // occupancy x CU count, queried once per instantiation AND device (contexts of different devices / threads may race here: the
+    // slot is written once with a complete value, readers see 0 or that value)
     static std::atomic<int> slots_of[R3D_MAX_DEVICES];
     const int dev = ctx->device >= 0 && ctx->device < R3D_MAX_DEVICES ? ctx->device : 0;
     int slots = slots_of[dev].load(std::memory_order_relaxed);
     if (slots == 0) {
         int v = 1, c = 256;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void *)k_cost2<LPC, SH2, TRACK, VCH, NWAVE, ACC>, NWAVE * 64, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, (const void *)k_cost2<LPC, SH2, TRACK, NWAVE, ACC>, NWAVE * 64, 0);
         (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, ctx->device);
         slots = (v < 1 ? 1 : v) * (c < 1 ? 256 : c);
         slots_of[dev].store(slots, std::memory_order_relaxed);
@@ -2424,17 +1415,13 @@ int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t s
     if (nb < 1) nb = 1;
     int BAND = (g.H + nb - 1) / nb;
     if (BAND < 16) BAND = 16;
-    int nMain = (g.H + BAND - 1) / BAND;
+    const int nMain = (g.H + BAND - 1) / BAND;
     const int nSpec = SH2 > 0 ? 3 : 0;
-    if (spec_only) {      // only the stripe-top rows (cspec): the main volume comes from k_cost_fwd
-        if (nSpec == 0) return R3D_OK;
-        nMain = 0;
-    }
     int *maxc = (int *)ws.flags.p + 8;
     if (TRACK) R3D_HIP(ctx, hipMemsetAsync(maxc, 0, 4, st));
     const size_t plane = (size_t)chan * g.W * g.H;
-    k_cost2<LPC, SH2, TRACK, VCH, NWAVE, ACC><<<dim3(tiles, VCH ? 4 : nMain + nSpec), NWAVE * 64, 0, st>>>(
-        (const uint2 *)ws.rec_l.p + plane, (const uint2 *)ws.rec_r.p + plane, g, (int *)ws.cost.p, (int *)ws.cspec.p, BAND, nMain, maxc, (int *)ws.ltop.p, tile_lo);
+    k_cost2<LPC, SH2, TRACK, NWAVE, ACC><<<dim3(tiles, nMain + nSpec), NWAVE * 64, 0, st>>>(
+        (const uint2 *)ws.rec_l.p + plane, (const uint2 *)ws.rec_r.p + plane, g, (int *)ws.cost.p, (int *)ws.cspec.p, BAND, nMain, maxc, 0);
     R3D_HIP(ctx, hipGetLastError());
     if (TRACK) {
         // data-dependent half of the exact-int16 envelope: only reached when the static bound cannot prove it
@@ -2446,19 +1433,10 @@ int launch_cost2_n(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t s
     }
     return R3D_OK;
 }
-template <int LPC, int SH2, bool TRACK, bool VCH, bool ACC>
-int launch_cost2_t(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
-    // 8 waves = 64-column tiles (2*SH2 halo columns); R3D_COST_NWAVE=4 selects 32-column tiles for A/B measurements
-    static const bool four = [] { const char *e = getenv("R3D_COST_NWAVE"); return e && !strcmp(e, "4"); }();
-    if constexpr (LPC == 8 && 4 * (64 / LPC) > 2 * SH2) {
-        if (four) return launch_cost2_n<LPC, SH2, TRACK, VCH, 4, ACC>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-    }
-    return launch_cost2_n<LPC, SH2, TRACK, VCH, 8, ACC>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-}
-template <int LPC, bool VCH, bool ACC>
-int launch_cost2_l(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
+template <int LPC, bool ACC>
+int launch_cost2_l(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int chan) {
     const bool track = sgm_track(g) && chan == g.CN - 1;   // on the summed value: the last channel's launch
-#define R3D_C2(S, T) launch_cost2_t<LPC, S, T, VCH, ACC>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan)
+#define R3D_C2(S, T) launch_cost2_n<LPC, S, T, ACC>(ctx, ws, g, st, chan)
     switch (g.SH2) {
         case 0: return R3D_C2(0, false);
         case 1: return R3D_C2(1, false);
@@ -2471,26 +1449,21 @@ int launch_cost2_l(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t s
     }
 #undef R3D_C2
 }
-template <int LPC>
-int launch_cost2_c(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, int col_lo, int col_hi, bool spec_only, int chan) {
-    return chan > 0 ? launch_cost2_l<LPC, false, true>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan)
-                    : launch_cost2_l<LPC, false, false>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-}
-int launch_cost2(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st, bool vch, int col_lo = 0, int col_hi = -1, bool spec_only = false,
-                 int chan = 0) {
-    if (vch) return g.NP == 1 ? launch_cost2_l<8, true, false>(ctx, ws, g, st, 0, -1, false, 0) : launch_cost2_l<16, true, false>(ctx, ws, g, st, 0, -1, false, 0);
-    switch (g.DP) {  // LPC = DP / 16 lanes per column
-        case 32: return launch_cost2_c<2>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-        case 64: return launch_cost2_c<4>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-        case 128: return launch_cost2_c<8>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-        case 512: return launch_cost2_c<32>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);   // 2 columns per wave, 16-column tiles
-        default: return launch_cost2_c<16>(ctx, ws, g, st, col_lo, col_hi, spec_only, chan);
-    }
-}
 // the whole cost stage of a pair: channel 0 stores C, the further channels of a colour pair add theirs (cost and cspec alike)
-int launch_cost2_all(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st) {
-    for (int c = 0; c < g.CN; c++)
-        if (int rc = launch_cost2(ctx, ws, g, st, false, 0, -1, false, c)) return rc;
+int launch_cost2(r3d_ctx *ctx, r3d_sgm_ws &ws, const SgmGeom &g, hipStream_t st) {
+    for (int chan = 0; chan < g.CN; chan++) {
+        int rc;
+#define R3D_CL(LPC) rc = chan > 0 ? launch_cost2_l<LPC, true>(ctx, ws, g, st, chan) : launch_cost2_l<LPC, false>(ctx, ws, g, st, chan)
+        switch (g.DP) {  // LPC = DP / 16 lanes per column
+            case 32: R3D_CL(2); break;
+            case 64: R3D_CL(4); break;
+            case 128: R3D_CL(8); break;
+            case 256: R3D_CL(16); break;
+            default: R3D_CL(32); break;   // 512 slots: 2 columns per wave, 16-column tiles
+        }
+#undef R3D_CL
+        if (rc) return rc;
+    }
     return R3D_OK;
 }
 // prefilter of both images, every channel: record planes rec_l / rec_r [CN][h][w]
@@ -2499,105 +1472,47 @@ void launch_prefilter(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, co
     if (g.CN == 1) k_prefilter<1><<<grid, 256, 0, st>>>(d_left, d_right, stride, g.W, g.H, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
     else k_prefilter<3><<<grid, 256, 0, st>>>(d_left, d_right, stride, g.W, g.H, g.ftzero, (uint2 *)ws.rec_l.p, (uint2 *)ws.rec_r.p);
 }
-// k_cost_fwd (v5) for the DP = 128 layout: block cost along rows + forward chain + checkpoints
-int launch_cost_fwd(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, int *cost, int *hsum, int *ckpt) {
-    const uint2 *rl = (const uint2 *)ws.rec_l.p, *rr = (const uint2 *)ws.rec_r.p;
-    const int nwg = (g.H + 3) / 4;
-    const bool padded = g.D != g.DP;
-#define R3D_CF(S)                                                                                           \
-    case S:                                                                                                 \
-        if (padded) k_cost_fwd<S, true><<<nwg, 256, 0, st>>>(rl, rr, g, cost, hsum, ckpt);                    \
-        else k_cost_fwd<S, false><<<nwg, 256, 0, st>>>(rl, rr, g, cost, hsum, ckpt);                          \
-        break;
-    switch (g.SH2) {
-        R3D_CF(0) R3D_CF(1) R3D_CF(2) R3D_CF(3) R3D_CF(4) R3D_CF(5)
-        default: return -1;
-    }
-#undef R3D_CF
-    return (int)hipGetLastError();
-}
 
-
-// launcher of k_vscan2.  Variants: 16 columns per wave (NPL = 16, LPC = 4: 784 waves at C2, no
-// SIMD carries two; needs whole 32-disparity lanes) is the default where it applies, 8 columns (NPL = 8, LPC = 8) otherwise;
-// R3D_VSCAN_COLS = 4 | 8 | 16 forces one for A/B runs (4 columns: 3136 finer-grained waves, measured 1.15 ms against 0.89 ms for 8:
-// the extra cross-lane stages cost more than the better SIMD balance returns; 16 vs 8: 0.921 vs 0.956 ms interleaved).
-// Balanced split (R3D_VSCAN_SPLIT=1; DEFAULT OFF: measured slower).  The kernel is one chain per wave, limited by what a CU's
-// memory pipeline keeps in flight, so it lasts as long as its most loaded CU: 784 single-wave workgroups at C2 are three per CU
-// on 240 CUs and FOUR on 16, and those 16 set the time (tools/gpu_balance_probe.py: 117 us per million cells with 784 waves, 108
-// with exactly 768 at W = 3200).  The split cuts the launch into a main part whose wave count is a multiple of 256 and a tail of
-// the remaining columns in the 8-column mapping (half the load per wave) running concurrently on the lane's second stream.
-// MEASURED (interleaved on one box): 0.960 ms with the split against 0.822-0.828 ms without -- a wave of the 8-column mapping
-// needs longer per row (its extra cross-lane stage), and the join waits for it; the imbalance costs less than that.
-int launch_vscan2(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const SgmGeom &g, float inv_a, const int *cost, const int *cspec, const int *hsum,
-                  int16_t *raw, int16_t *mins) {
-    static const int force = [] { const char *e = getenv("R3D_VSCAN_COLS"); return e ? atoi(e) : 0; }();
-    static const bool split_on = [] { const char *e = getenv("R3D_VSCAN_SPLIT"); return e && !strcmp(e, "1"); }();
-    if (g.DP == 32) {
-        k_vscan2<4, 4><<<dim3((g.W1 + 15) / 16, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-    } else if (g.DP == 64) {
-        k_vscan2<8, 4><<<dim3((g.W1 + 15) / 16, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-    } else if (g.DP == 128) {
-        const bool ok16 = g.D % 32 == 0;
-        if ((force == 16 || force == 0) && ok16) {
-            const int groups = (g.W1 + 15) / 16, main_groups = (groups / 64) * 64;
-            if (split_on && main_groups >= 64 && main_groups < groups) {
-                if (!ws.aux) R3D_HIP(ctx, hipStreamCreateWithFlags(&ws.aux, hipStreamNonBlocking));
-                if (!ws.vs_fork) {
-                    R3D_HIP(ctx, hipEventCreateWithFlags(&ws.vs_fork, hipEventDisableTiming));
-                    R3D_HIP(ctx, hipEventCreateWithFlags(&ws.vs_join, hipEventDisableTiming));
-                }
-                const int col0 = main_groups * 16, tail_cols = g.W1 - col0;
-                R3D_HIP(ctx, hipEventRecord(ws.vs_fork, st));
-                R3D_HIP(ctx, hipStreamWaitEvent(ws.aux, ws.vs_fork, 0));
-                k_vscan2<8, 8><<<dim3((tail_cols + 7) / 8, 4), 64, 0, ws.aux>>>(cost, cspec, hsum, g, inv_a, raw, mins, col0);
-                R3D_HIP(ctx, hipEventRecord(ws.vs_join, ws.aux));
-                SgmGeom gm = g;
-                k_vscan2<16, 4><<<dim3(main_groups, 4), 64, 0, st>>>(cost, cspec, hsum, gm, inv_a, raw, mins, 0);
-                R3D_HIP(ctx, hipStreamWaitEvent(st, ws.vs_join, 0));
-            } else {
-                k_vscan2<16, 4><<<dim3(groups, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-            }
-        } else if (force == 4) k_vscan2<4, 16><<<dim3((g.W1 + 3) / 4, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-        else k_vscan2<8, 8><<<dim3((g.W1 + 7) / 8, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-    } else if (g.DP == 512) {
-        // 16 disparities per lane on 32 lanes, 2 columns per wave (NPL = 16 would need whole 32-disparity lanes; D is a multiple of 16)
-        k_vscan2<8, 32><<<dim3((g.W1 + 1) / 2, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-    } else {
-        k_vscan2<8, 16><<<dim3((g.W1 + 3) / 4, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
-    }
-    return (int)hipGetLastError();
+// launcher of k_hscan2: per slot layout the lane mapping (NPL packed registers x LPC lanes per row, 64 / LPC rows per wave) and the
+// segment length K:
+//   32 / 64 / 128 slots: 16 lanes per row = 4 rows per wave (612 waves at 2448 rows <= 1024 SIMDs, so no SIMD carries two; with 2 rows
+//                        per wave 1224 waves left 200 SIMDs with double work) and 1 / 2 / 4 registers per lane, K = 32 / 16 / 16;
+//   256 slots: 4 registers x 32 lanes, 2 rows per wave, K = 6;   512 slots: 4 x 64, ONE row per wave (one more butterfly stage per
+//              step), K = 6 as at 256: the same 6 * K * 4 registers of cost / L_left buffers per lane.
+// Reserves the checkpoints: one per image row and segment (k_hscan2 addresses them by row), rounded up to whole waves.
+template <int NPL, int LPC, int K>
+int launch_hscan2_l(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const SgmGeom &g) {
+    constexpr int RPW = 64 / LPC, DPW = NPL * LPC;
+    const int nwaves = (g.H + RPW - 1) / RPW;
+    if (int rc = r3d_reserve(ctx, ws.ckpt, (size_t)(g.H + 8) * (g.W1 / K + 1) * (DPW + 4) * 4)) return rc;
+    const int *cp = (const int *)ws.cost.p;
+    int *hp = (int *)ws.hsum.p, *kp = (int *)ws.ckpt.p;
+    if (g.D != g.DP) k_hscan2<NPL, LPC, K, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g);
+    else k_hscan2<NPL, LPC, K, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g);
+    R3D_HIP(ctx, hipGetLastError());
+    return R3D_OK;
 }
-
-// launcher of k_vscan3 (the vertical pass that recomputes C): LPC = DP / 16 lanes per column as in k_cost2, one workgroup per
-// stripe and 64 / 32-column tile (2 * SH2 halo columns)
-template <int LPC>
-int launch_vscan3_l(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, float inv_a, const int *hsum, int16_t *raw, int16_t *mins) {
-    // (4-wave workgroups of 32 columns capped at 128 registers, so that two fit a SIMD beside another kernel's waves, spill 29
-    // registers and measured 3.04 ms against 1.66 ms: profiles/r04_ab_vscan3.log)
-    constexpr int NWAVE = 8, CW = 64 / LPC, TC = NWAVE * CW;
-    const uint2 *rl = (const uint2 *)ws.rec_l.p, *rr = (const uint2 *)ws.rec_r.p;
-#define R3D_VS3(S)                                                                                                          \
-    case S: {                                                                                                               \
-        constexpr int TO = TC - 2 * S;                                                                                      \
-        if constexpr (TO > 0)                                                                                               \
-            k_vscan3<LPC, S, NWAVE><<<dim3((g.W1 + TO - 1) / TO, 4), NWAVE * 64, 0, st>>>(rl, rr, g, hsum, inv_a, raw, mins); \
-        else return -1;                                                                                                     \
-    } break;
-    switch (g.SH2) {
-        R3D_VS3(0) R3D_VS3(1) R3D_VS3(2) R3D_VS3(3) R3D_VS3(4) R3D_VS3(5)
-        default: return -1;
-    }
-#undef R3D_VS3
-    return (int)hipGetLastError();
-}
-int launch_vscan3(hipStream_t st, const r3d_sgm_ws &ws, const SgmGeom &g, float inv_a, const int *hsum, int16_t *raw, int16_t *mins) {
+int launch_hscan2(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const SgmGeom &g) {
     switch (g.DP) {
-        case 32: return launch_vscan3_l<2>(st, ws, g, inv_a, hsum, raw, mins);
-        case 64: return launch_vscan3_l<4>(st, ws, g, inv_a, hsum, raw, mins);
-        case 128: return launch_vscan3_l<8>(st, ws, g, inv_a, hsum, raw, mins);
-        default: return launch_vscan3_l<16>(st, ws, g, inv_a, hsum, raw, mins);
+        case 32: return launch_hscan2_l<1, 16, 32>(ctx, ws, st, g);
+        case 64: return launch_hscan2_l<2, 16, 16>(ctx, ws, st, g);
+        case 128: return launch_hscan2_l<4, 16, 16>(ctx, ws, st, g);
+        case 256: return launch_hscan2_l<4, 32, 6>(ctx, ws, st, g);
+        default: return launch_hscan2_l<4, 64, 6>(ctx, ws, st, g);
     }
+}
+
+// launcher of k_vscan2, one mapping per slot layout.  128 slots: 16 columns per wave (NPL = 16, LPC = 4: 784 waves at 3136 cost
+// columns, no SIMD carries two) where D fills whole 32-disparity lanes, 8 columns (NPL = 8, LPC = 8) otherwise, as at D = 80 or 112.
+// 512 slots: 16 disparities per lane on 32 lanes, 2 columns per wave (NPL = 16 would need whole 32-disparity lanes; D is a
+// multiple of 16).
+void launch_vscan2(hipStream_t st, const SgmGeom &g, float inv_a, const int *cost, const int *cspec, const int *hsum, int16_t *raw, int16_t *mins) {
+    if (g.DP == 32) k_vscan2<4, 4><<<dim3((g.W1 + 15) / 16, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
+    else if (g.DP == 64) k_vscan2<8, 4><<<dim3((g.W1 + 15) / 16, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
+    else if (g.DP == 128 && g.D % 32 == 0) k_vscan2<16, 4><<<dim3((g.W1 + 15) / 16, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
+    else if (g.DP == 128) k_vscan2<8, 8><<<dim3((g.W1 + 7) / 8, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
+    else if (g.DP == 256) k_vscan2<8, 16><<<dim3((g.W1 + 3) / 4, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
+    else k_vscan2<8, 32><<<dim3((g.W1 + 1) / 2, 4), 64, 0, st>>>(cost, cspec, hsum, g, inv_a, raw, mins, 0);
 }
 
 // MODE_HH directions r = p - q in the order they enter S (pass 1, then pass 2), and their profiling names
@@ -2649,14 +1564,14 @@ static int sgm_run_hh(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, const r3d_sg
         (rc = r3d_reserve(ctx, ws.hsum, volBytes)) || (rc = r3d_reserve(ctx, ws.raw, npix * 2)) ||
         (rc = r3d_reserve(ctx, ws.mins, npix * 2)) || (rc = r3d_reserve(ctx, ws.lrd, npix * 2)) || (rc = r3d_reserve(ctx, ws.flags, 256)))
         return rc;
-    ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = g.DP; ctx->last_impl = 0;
+    ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = g.DP;
     ctx->last_mode = p->mode; ctx->last_geom = g;
     r3d_prof_begin(ctx, ws);
     r3d_prof_mark(ctx, ws, st, "prefilter");
     launch_prefilter(st, ws, g, d_left, d_right, stride);
     R3D_HIP(ctx, hipGetLastError());
     r3d_prof_mark(ctx, ws, st, "cost");
-    if ((rc = launch_cost2_all(ctx, ws, g, st))) return rc;   // also the envelope's tracked-maximum pass where it applies
+    if ((rc = launch_cost2(ctx, ws, g, st))) return rc;   // also the envelope's tracked-maximum pass where it applies
     const float inv_a = 1.0f / (float)(100 - g.uniq);
     for (int r = 0; r < 8; r++) {
         r3d_prof_mark(ctx, ws, st, HH_NAMES[r]);
@@ -2780,22 +1695,8 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
         return R3D_OK;
     }
     if (p->mode == R3D_SGBM_MODE_HH) return sgm_run_hh(ctx, ws, st, p, g, d_left, d_right, w, h, stride, d_disp);
-    // R3D_SGM_IMPL (read below as well): the v1 and v3 kernel generations only know 128 / 256 slots per column, and only the
-    // default generation has the 512-slot instantiations (v4 and v5 would run their 256-slot kernels over a 512-slot volume)
-    {
-        const char *e = getenv("R3D_SGM_IMPL");
-        if (g.DP > 256 && e && (!strcmp(e, "v1") || !strcmp(e, "v3") || !strcmp(e, "v4") || !strcmp(e, "v5")))
-            return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: numDisparities > 256 (got %d) needs the default kernel generation v2, R3D_SGM_IMPL=%s stops at 256",
-                            g.D, e);
-        // ... and only the default generation sums the block cost of a colour pair over its channels
-        if (g.CN != 1 && e && (!strcmp(e, "v1") || !strcmp(e, "v3") || !strcmp(e, "v4") || !strcmp(e, "v5")))
-            return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sgbm: %d-channel images need the default kernel generation v2, R3D_SGM_IMPL=%s takes single-channel images only",
-                            g.CN, e);
-        if (e && (!strcmp(e, "v1") || !strcmp(e, "v3"))) g.DP = g.NP * 128;
-    }
-    const int NPW = g.DP / 2;   // 32-bit words (disparity pairs) per cost-volume column
     const size_t npix = (size_t)w * h;
-    const size_t rowBytes = (size_t)g.W1 * NPW * 4;
+    const size_t rowBytes = (size_t)g.W1 * g.DP * 2;
     const size_t volBytes = rowBytes * h;
     int rc;
     if ((rc = r3d_reserve(ctx, ws.rec_l, npix * 8 * g.CN))) return rc;   // one record plane per channel
@@ -2810,236 +1711,23 @@ static int sgm_run_impl(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_p
     const bool tiny = pass == 0 && tiny_quirk && g.stripe_sz < h && g.stripe_sz - g.overlap < 0;   // stripe 1 exists and its start is clamped
     if (pass == 1) g.stripe_sz = h;                    // one stripe: rows [0, h) from row 0 (the other three own no row)
     if ((tiny || pass == 1) && (rc = r3d_reserve(ctx, ws.lrd2, npix * 2))) return rc;
-    ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = NPW * 2;
+    ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = g.DP;
     ctx->last_mode = p->mode; ctx->last_geom = g;
     if ((rc = r3d_reserve(ctx, ws.flags, 256))) return rc;
+    if ((rc = r3d_reserve(ctx, ws.hsum, volBytes))) return rc;   // after the small buffers: the order of first reservation places the two volumes
     r3d_prof_begin(ctx, ws);
 
     r3d_prof_mark(ctx, ws, st, "prefilter");
     launch_prefilter(st, ws, g, d_left, d_right, stride);
     R3D_HIP(ctx, hipGetLastError());
-
-    // implementation generations kept side by side for A/B measurements: R3D_SGM_IMPL = v1 | v2 (default) | v3.
-    // v3 (L_top fused into the cost kernel, WTA fused into hscan) moves 2.7 GB less but measured 5.0 ms against 3.45 ms
-    // for v2 on C2, so it is not the default.
-    static const int impl = [] { const char *e = getenv("R3D_SGM_IMPL"); return !e ? 2 : !strcmp(e, "v1") ? 1 : !strcmp(e, "v3") ? 3 : !strcmp(e, "v4") ? 4 : !strcmp(e, "v5") ? 5 : 2; }();
-    const bool use_v1 = impl == 1;
-    ctx->last_impl = impl;
-    const float inv_a = 1.0f / (float)(100 - g.uniq);
-    if (impl == 3) {
-        if ((rc = r3d_reserve(ctx, ws.ltop, volBytes))) return rc;
-        r3d_prof_mark(ctx, ws, st, "cost_vpath");
-        if ((rc = launch_cost2(ctx, ws, g, st, true))) return rc;
-        r3d_prof_mark(ctx, ws, st, "hscan_wta");
-        constexpr int K1 = 12, K2 = 6;
-        const int K = g.NP == 1 ? K1 : K2;
-        const bool padded = g.D != 128 * g.NP;
-        const int nwaves = (h + 1) / 2;
-        if ((rc = r3d_reserve(ctx, ws.ckpt, (size_t)nwaves * (g.W1 / K + 1) * (2 * g.NP + 1) * 64 * 4))) return rc;
-        if ((rc = r3d_reserve(ctx, ws.hsum, (size_t)h * K * NPW * 4 + 4096))) return rc;   // tail parking only
-        const int *cp = (const int *)ws.cost.p, *lp = (const int *)ws.ltop.p;
-        int *tp = (int *)ws.hsum.p, *kp = (int *)ws.ckpt.p;
-        int16_t *rp = (int16_t *)ws.raw.p, *mp = (int16_t *)ws.mins.p;
-        if (g.NP == 1) {
-            if (padded) k_hscan3<2, 32, K1, true><<<nwaves, 64, 0, st>>>(cp, lp, tp, kp, g, inv_a, rp, mp);
-            else k_hscan3<2, 32, K1, false><<<nwaves, 64, 0, st>>>(cp, lp, tp, kp, g, inv_a, rp, mp);
-        } else {
-            if (padded) k_hscan3<4, 32, K2, true><<<nwaves, 64, 0, st>>>(cp, lp, tp, kp, g, inv_a, rp, mp);
-            else k_hscan3<4, 32, K2, false><<<nwaves, 64, 0, st>>>(cp, lp, tp, kp, g, inv_a, rp, mp);
-        }
-        R3D_HIP(ctx, hipGetLastError());
-    } else {
-    if ((rc = r3d_reserve(ctx, ws.hsum, volBytes))) return rc;
-    if (use_v1) {
-        r3d_prof_mark(ctx, ws, st, "cost");
-        const int TX = 16, BAND = 64;
-        int RING = 8;
-        while (RING < 2 * g.SW2 + 2) RING *= 2;
-        const int NR = COST_NW + 2 * g.SH2;
-        const size_t lds = ((size_t)NR * TX + (size_t)COST_NW * RING) * NPW * 4;
-        const int nMain = (h + BAND - 1) / BAND;
-        const int nSpec = g.SH2 > 0 ? 3 : 0;
-        dim3 grid((g.W1 + TX - 1) / TX, nMain + nSpec);
-        if (g.NP == 1) {
-            R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_cost<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            k_cost<1><<<grid, COST_NW * 64, lds, st>>>((const uint2 *)ws.rec_l.p, (const uint2 *)ws.rec_r.p, g, (int *)ws.cost.p, (int *)ws.cspec.p, TX, BAND, nMain, RING);
-        } else {
-            R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_cost<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            k_cost<2><<<grid, COST_NW * 64, lds, st>>>((const uint2 *)ws.rec_l.p, (const uint2 *)ws.rec_r.p, g, (int *)ws.cost.p, (int *)ws.cspec.p, TX, BAND, nMain, RING);
-        }
-        R3D_HIP(ctx, hipGetLastError());
-    }
-    // Column-slab overlap of the cost kernel with the forward phase of the horizontal scan (R3D_SGM_OVERLAP = number of slabs;
-    // DEFAULT OFF: measured slower, see below).  The forward chain at column x only needs C of columns <= x, so the
-    // cost kernel runs slab by slab (left to right) on a second stream while k_hscan2<PHASE 1> follows one slab behind on the
-    // map's own stream; the backward phase (PHASE 2), which needs every checkpoint, and everything after it stay as they were.
-    // A kernel of this kind lasts as long as ONE of its waves' chains, whatever the number of waves, so splitting by ROWS
-    // (or running the vertical scan behind the backward sweep) shortens nothing; only the cost kernel, whose work is not a
-    // chain, can hide behind a chain kernel.
-    // MEASURED (round 2, profiles/r02_overlap_trace.txt, interleaved A/B on one box): the two kernels do run concurrently, but
-    // each then takes 1.5-3x its time alone (cost slab 176 -> 200-310 us, forward slab 120-140 -> 175-455 us), whether the
-    // forward launches own their SIMD (k_hscan2<PHASE 1>, 280 registers) or share it (k_hscan_fwd, 97 registers) and whatever
-    // the chain wave's issue priority: a write stream and a latency-bound read chain interleaved in HBM cost each other more
-    // than running back to back.  320-334 maps/s sequential vs 305-331 overlapped, so the sequential order stays the default.
-    static const int n_slabs = [] { const char *e = getenv("R3D_SGM_OVERLAP"); const int v = e ? atoi(e) : 0; return v < 2 ? 0 : (v > R3D_SGM_SLABS ? R3D_SGM_SLABS : v); }();
-    static const bool rows2_env = [] { const char *e = getenv("R3D_HSCAN_ROWS"); return e && !strcmp(e, "2"); }();
-    constexpr int KOV = 16;
-    // R3D_SGM_FWD=wide: the forward launches use k_hscan2<PHASE 1> (whole register file: cannot share a SIMD with cost waves)
-    static const bool lowreg = [] { const char *e = getenv("R3D_SGM_FWD"); return !(e && !strcmp(e, "wide")); }();
-    const bool track = sgm_track(g);
-    // (a colour pair takes the sequential order: every slab would need its three channel launches before the scan may follow)
-    const bool overlapped = !use_v1 && n_slabs >= 2 && g.DP == 128 && !rows2_env && !track && g.CN == 1 && g.W1 / KOV >= 8 * n_slabs;
-    // v5: cost + forward chain fused (k_cost_fwd), then the backward phase of k_hscan2; D <= 128 layouts with 128 slots only, and only
-    // where the static envelope bound holds (no TRACK pass); otherwise the v2 kernels below
-    const bool fused_fwd = impl == 5 && g.DP == 128 && !track && g.W1 / 16 >= 1;
-    if (fused_fwd) {
-        constexpr int KF = 16;
-        const int nfull = g.W1 / KF, nwaves = (h + 3) / 4;
-        const bool padded = g.D != g.DP;
-        if ((rc = r3d_reserve(ctx, ws.ckpt, (size_t)(h + 8) * (nfull + 1) * (NPW + 4) * 4))) return rc;
-        const int *cp = (const int *)ws.cost.p;
-        int *hp = (int *)ws.hsum.p, *kp = (int *)ws.ckpt.p;
-        r3d_prof_mark(ctx, ws, st, "cost_fwd");
-        if ((rc = launch_cost2(ctx, ws, g, st, false, 0, -1, true))) return rc;        // stripe-top rows (cspec) for the vertical pass
-        if (int e = launch_cost_fwd(st, ws, g, (int *)ws.cost.p, hp, kp))
-            return e < 0 ? r3d_fail(ctx, R3D_E_UNSUPPORTED, "k_cost_fwd: no instantiation for this block size")
-                         : r3d_fail(ctx, R3D_E_HIP, "k_cost_fwd launch failed: %s", hipGetErrorString((hipError_t)e));
-        r3d_prof_mark(ctx, ws, st, "hscan_bwd");
-        if (padded) k_hscan2<4, 16, KF, true, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-        else k_hscan2<4, 16, KF, false, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-    } else
-    if (overlapped) {
-        if (!ws.aux) R3D_HIP(ctx, hipStreamCreateWithFlags(&ws.aux, hipStreamNonBlocking));
-        if (!ws.slab_ev[0])
-            for (int j = 0; j <= R3D_SGM_SLABS; j++) R3D_HIP(ctx, hipEventCreateWithFlags(&ws.slab_ev[j], hipEventDisableTiming));
-        const int nfull = g.W1 / KOV, nwaves = (h + 3) / 4;
-        const bool padded = g.D != g.DP;
-        if ((rc = r3d_reserve(ctx, ws.ckpt, (size_t)(h + 8) * (nfull + 1) * (NPW + 4) * 4))) return rc;
-        const int *cp = (const int *)ws.cost.p;
-        int *hp = (int *)ws.hsum.p, *kp = (int *)ws.ckpt.p;
-        r3d_prof_mark(ctx, ws, st, "cost+hscan_fwd");
-        R3D_HIP(ctx, hipEventRecord(ws.slab_ev[R3D_SGM_SLABS], st));            // fork: prefilter done (and the previous map's readers of C)
-        R3D_HIP(ctx, hipStreamWaitEvent(ws.aux, ws.slab_ev[R3D_SGM_SLABS], 0));
-        int seg_lo = 0;
-        for (int j = 0; j < n_slabs; j++) {
-            const int seg_hi = j == n_slabs - 1 ? nfull : (int)((long)nfull * (j + 1) / n_slabs);
-            const int col_lo = seg_lo * KOV, col_hi = j == n_slabs - 1 ? g.W1 : seg_hi * KOV;
-            if ((rc = launch_cost2(ctx, ws, g, ws.aux, false, col_lo, col_hi))) return rc;
-            R3D_HIP(ctx, hipEventRecord(ws.slab_ev[j], ws.aux));
-            seg_lo = seg_hi;
-        }
-        seg_lo = 0;
-        for (int j = 0; j < n_slabs; j++) {
-            const int seg_hi = j == n_slabs - 1 ? nfull : (int)((long)nfull * (j + 1) / n_slabs);
-            R3D_HIP(ctx, hipStreamWaitEvent(st, ws.slab_ev[j], 0));
-            if (lowreg) {
-                if (padded) k_hscan_fwd<4, 16, 4, KOV, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, seg_lo, seg_hi);
-                else k_hscan_fwd<4, 16, 4, KOV, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, seg_lo, seg_hi);
-            } else {
-                if (padded) k_hscan2<4, 16, KOV, true, 1><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, seg_lo, seg_hi);
-                else k_hscan2<4, 16, KOV, false, 1><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, seg_lo, seg_hi);
-            }
-            seg_lo = seg_hi;
-        }
-        R3D_HIP(ctx, hipGetLastError());
-        r3d_prof_mark(ctx, ws, st, "hscan_bwd");
-        if (padded) k_hscan2<4, 16, KOV, true, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-        else k_hscan2<4, 16, KOV, false, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-    } else {
-    if (!use_v1) {
-        r3d_prof_mark(ctx, ws, st, "cost");
-        if ((rc = launch_cost2_all(ctx, ws, g, st))) return rc;
-    }
+    r3d_prof_mark(ctx, ws, st, "cost");
+    if ((rc = launch_cost2(ctx, ws, g, st))) return rc;
     r3d_prof_mark(ctx, ws, st, "hscan");
-    if (use_v1) {
-        if (g.NP == 1) k_hscan<1><<<h, 64, 0, st>>>((const int *)ws.cost.p, (int *)ws.hsum.p, g);
-        else k_hscan<2><<<h, 64, 0, st>>>((const int *)ws.cost.p, (int *)ws.hsum.p, g);
-    } else {
-        // D <= 128: 4 registers x 16 lanes per row = 4 rows per wave: 612 waves <= 1024 SIMDs, so no SIMD carries two
-        // waves (with 2 rows per wave 1224 waves left 200 SIMDs with double work: makespan 2x the mean);
-        // R3D_HSCAN_ROWS=2 selects the 2-rows-per-wave instantiation for A/B.  D <= 256: 4 x 32 (2 rows per wave).
-        static const bool rows2 = [] { const char *e = getenv("R3D_HSCAN_ROWS"); return e && !strcmp(e, "2"); }();
-        constexpr int K1 = 12, K1b = 16, K2 = 6;
-        const bool padded = g.D != g.DP;
-        // DP = 64 / 32: still 16 lanes per row and 4 rows per wave (612 waves at C2 height), with 2 / 1 registers per lane and
-        // proportionally longer segments so that a segment stays 128 registers of loads in flight
-        constexpr int K64 = 16, K32 = 32;
-        // DP = 512: 4 registers x 64 lanes = ONE row per wave (h waves), segments of K2 columns as at DP = 256: the same
-        // 6 * K2 * 4 registers of cost / L_left buffers per lane, and one more butterfly stage per step
-        const bool wide = g.DP == 512;
-        const bool small = g.DP < 128;
-        const bool four = (g.DP == 128 && !rows2) || small;
-        const int rpw = wide ? 1 : four ? 4 : 2, npl = g.DP == 32 ? 1 : g.DP == 64 ? 2 : four ? 4 : 2 * g.NP;
-        // R3D_HSCAN_K=8: 8-column segments for the D <= 128 layout (half the registers of the default 16: two waves fit a SIMD); A/B
-        static const bool k8_env = [] { const char *e = getenv("R3D_HSCAN_K"); return e && !strcmp(e, "8"); }();
-        const bool k8 = k8_env && g.DP == 128 && four;
-        const int K = g.DP == 32 ? K32 : g.DP == 64 ? K64 : four ? (k8 ? 8 : K1b) : (g.NP == 1 ? K1 : K2);
-        const int nwaves = (h + rpw - 1) / rpw;
-        if ((rc = r3d_reserve(ctx, ws.ckpt, (size_t)(h + 8) * (g.W1 / K + 1) * (NPW + 4) * 4))) return rc;   // by image row (k_hscan2)
-        const int *cp = (const int *)ws.cost.p;
-        int *hp = (int *)ws.hsum.p, *kp = (int *)ws.ckpt.p;
-        // R3D_HSCAN_SPLIT=1: the two phases as two launches with different lane mappings: the forward sweep (read-only, bound by
-        // the issue rate of ONE wave per SIMD at 4 rows per wave) with 2 rows per wave = 1224 waves, two per SIMD where they
-        // meet, so that one wave's dependency stalls are the other's issue slots; the backward sweep (bandwidth-bound) as it was
-        static const bool split = [] { const char *e = getenv("R3D_HSCAN_SPLIT"); return e && !strcmp(e, "1"); }();
-        (void)npl;
-        if (split && g.DP == 128 && four && g.W1 / K1b >= 1) {
-            const int nfull = g.W1 / K1b, nw2 = (h + 1) / 2;
-            if (padded) {
-                k_hscan2<2, 32, K1b, true, 1><<<nw2, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-                k_hscan2<4, 16, K1b, true, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-            } else {
-                k_hscan2<2, 32, K1b, false, 1><<<nw2, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-                k_hscan2<4, 16, K1b, false, 2><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, nfull);
-            }
-        } else
-        if (wide) {
-            if (padded) k_hscan2<4, 64, K2, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<4, 64, K2, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        } else
-        if (g.DP == 32) {
-            if (padded) k_hscan2<1, 16, K32, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<1, 16, K32, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        } else if (g.DP == 64) {
-            if (padded) k_hscan2<2, 16, K64, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<2, 16, K64, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        } else if (four && k8) {
-            if (padded) k_hscan2<4, 16, 8, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<4, 16, 8, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        } else if (four) {
-            if (padded) k_hscan2<4, 16, K1b, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<4, 16, K1b, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        } else if (g.NP == 1) {
-            if (padded) k_hscan2<2, 32, K1, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<2, 32, K1, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        } else {
-            if (padded) k_hscan2<4, 32, K2, true><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-            else k_hscan2<4, 32, K2, false><<<nwaves, 64, 0, st>>>(cp, hp, kp, g, 0, 0);
-        }
-    }
-    }  // !overlapped
-    R3D_HIP(ctx, hipGetLastError());
-
+    if ((rc = launch_hscan2(ctx, ws, st, g))) return rc;
     r3d_prof_mark(ctx, ws, st, "vscan_wta");
-    // raw must read INVALID wherever the scan does not write (columns outside [minX1, maxX1))
-    {
-        constexpr int CPW = 8;
-        dim3 grid((g.W1 + CPW - 1) / CPW, 4);
-        if (impl == 4) {
-            // v4: the vertical pass recomputes C from the record images (k_vscan3); cost / cspec are not read again
-            if (int e = launch_vscan3(st, ws, g, inv_a, (const int *)ws.hsum.p, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p))
-                return e < 0 ? r3d_fail(ctx, R3D_E_UNSUPPORTED, "k_vscan3: no instantiation for this block size")
-                             : r3d_fail(ctx, R3D_E_HIP, "k_vscan3 launch failed: %s", hipGetErrorString((hipError_t)e));
-        } else if (!use_v1) {
-            // mapping per disparity-slot layout: see launch_vscan2
-            if (int e = launch_vscan2(ctx, ws, st, g, inv_a, (const int *)ws.cost.p, (const int *)ws.cspec.p, (const int *)ws.hsum.p,
-                                      (int16_t *)ws.raw.p, (int16_t *)ws.mins.p))
-                return e < 0 ? e : r3d_fail(ctx, R3D_E_HIP, "k_vscan2 launch failed: %s", hipGetErrorString((hipError_t)e));
-        } else if (g.NP == 1) k_vscan<1, CPW><<<grid, 64, 0, st>>>((const int *)ws.cost.p, (const int *)ws.cspec.p, (const int *)ws.hsum.p, g, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p);
-        else k_vscan<2, CPW><<<grid, 64, 0, st>>>((const int *)ws.cost.p, (const int *)ws.cspec.p, (const int *)ws.hsum.p, g, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p);
-        R3D_HIP(ctx, hipGetLastError());
-    }
-    }  // impl 1 / 2
+    launch_vscan2(st, g, 1.0f / (float)(100 - g.uniq), (const int *)ws.cost.p, (const int *)ws.cspec.p, (const int *)ws.hsum.p,
+                  (int16_t *)ws.raw.p, (int16_t *)ws.mins.p);
+    R3D_HIP(ctx, hipGetLastError());
     r3d_prof_mark(ctx, ws, st, "lrcheck");
     k_lrcheck<<<h, 256, (size_t)w * 4, st>>>((const int16_t *)ws.raw.p, (const int16_t *)ws.mins.p, g, (int16_t *)(pass == 1 ? ws.lrd2.p : ws.lrd.p));
     R3D_HIP(ctx, hipGetLastError());

@@ -146,8 +146,8 @@ int r3d_set_profiling(r3d_ctx *ctx, int enabled);
 int r3d_sgbm_profile(r3d_ctx *ctx, float *ms, int32_t max_slots, char *names, int32_t names_bytes);
 
 /* debug / stage parity: copies intermediate results of the LAST sgbm call to HOST buffers (NULL = skip).
- *   cost   int16 [h][w1][dp]  aggregated block cost C, summed over the channels of a colour pair (dp = the smallest of 32 / 64 / 128 / 256 / 512 that holds D, of 128 / 256
- *                             under R3D_SGM_IMPL=v1 / v3; entries d>=D undefined).  A volume is h*w1*dp*2 bytes, which
+ *   cost   int16 [h][w1][dp]  aggregated block cost C, summed over the channels of a colour pair (dp = the smallest of 32 / 64 / 128 / 256 / 512
+ *                             that holds D; entries d>=D undefined).  A volume is h*w1*dp*2 bytes, which
  *                             passes 4 GiB at 8 MP with dp = 512: the host buffers must hold that much.
  *   hsum   int16 [h][w1][dp]  MODE_SGBM_3WAY: L_left + L_right; MODE_HH: S after the first seven directions (the eighth is fused
  *                             with the selection and never stored)

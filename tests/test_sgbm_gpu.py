@@ -188,10 +188,21 @@ def test_randomised_parameter_sweep(r3d):
         assert np.array_equal(got, want), f"case {case}: W={W} H={H} D={D} {kw}: {(got != want).sum()} pixels differ"
 
 
-@pytest.mark.parametrize("impl", ["v1", "v2", "v3", "v4", "v5"])
-def test_alternative_kernel_generations_stay_bit_exact(impl):
-    """R3D_SGM_IMPL selects the kernel generation at library load: v2 reads the cost volume in its vertical pass, v4
-    recomputes it there (k_vscan3); v1 and v3 are kept for A/B measurements."""
+def test_six_more_shapes_bit_exact_vs_oracle(r3d, synth):
+    """The shapes on which the retired kernel generations used to be compared with the oracle, one per slot layout and a few
+    ragged ones, on the one generation there is."""
+    for W, H, D, seed in ((333, 121, 64, 2), (500, 203, 128, 5), (400, 90, 256, 6), (301, 77, 48, 7), (190, 64, 16, 8), (97, 33, 32, 9)):
+        L, R, _ = synth.stereo_pair(W, H, D, seed=seed)
+        got = _gpu(r3d, D, C2_KW).compute(L, R)
+        assert np.array_equal(got, _oracle(L, R, D, C2_KW, nthreads=4)), (W, H, D)
+
+
+def test_stale_generation_switch_is_inert():
+    """R3D_SGM_IMPL used to select a kernel generation at the first call, and the generations it selected knew neither 512
+    slots nor colour pairs: a value left over in the environment must change nothing.  In a process of its own, since the
+    variable was read once per process: a 512-slot pair, a 3-channel pair and a small grey pair, each bit-equal to the oracle
+    (the colour pair has equal channels and three times the penalties, which the grey oracle answers; a coloured one goes
+    against the restatement of tests/sgbm_color_ref.py as well)."""
     import subprocess
     import sys
     from tests.conftest import ROOT
@@ -200,15 +211,24 @@ def test_alternative_kernel_generations_stay_bit_exact(impl):
         f"sys.path.insert(0, {ROOT!r})\n"
         "r3d = importlib.import_module('3d_reconstruction_project_amd')\n"
         "from oracle import sgbm_oracle as so\n"
-        "kw = dict(minDisparity=0, blockSize=5, P1=600, P2=2400, disp12MaxDiff=1, uniquenessRatio=15, speckleWindowSize=0, speckleRange=2, preFilterCap=63)\n"
-        "for W, H, D, seed in ((333, 121, 64, 2), (500, 203, 128, 5), (400, 90, 256, 6), (301, 77, 48, 7), (190, 64, 16, 8), (97, 33, 32, 9)):\n"
+        "from tests import sgbm_color_ref as cr\n"
+        "def kw(ps):\n"
+        "    return dict(minDisparity=0, blockSize=5, P1=600 * ps, P2=2400 * ps, disp12MaxDiff=1, uniquenessRatio=15,\n"
+        "                speckleWindowSize=0, speckleRange=2, preFilterCap=63)\n"
+        "for W, H, D, seed, colour in ((300, 20, 272, 1, False), (190, 64, 16, 8, True), (97, 33, 32, 9, False)):\n"
         "    L, R, _ = r3d.synth.stereo_pair(W, H, D, seed=seed)\n"
-        "    got = r3d.StereoSGBM_create(numDisparities=D, mode=2, **kw).compute(L, R)\n"
-        "    want = so.compute(L, R, so.make_params(numDisparities=D, **kw), nthreads=4)\n"
-        "    assert np.array_equal(got, want), (W, H, D)\n"
+        "    want = so.compute(L, R, so.make_params(numDisparities=D, **kw(1)), nthreads=4)\n"
+        "    assert (want[:, D:] != -16).mean() > 0.5, (W, H, D)\n"
+        "    if colour:\n"
+        "        L, R = (np.ascontiguousarray(np.stack([a, a, a], -1)) for a in (L, R))\n"
+        "    m = r3d.StereoSGBM_create(numDisparities=D, mode=2, **kw(3 if colour else 1))\n"
+        "    assert np.array_equal(m.compute(L, R), want), (W, H, D)\n"
+        "    if colour:\n"
+        "        L, R = cr.color_pair(r3d.synth, W, H, D, seed=seed)\n"
+        "        assert np.array_equal(m.compute(L, R), cr.compute_3way(L, R, numDisparities=D, **kw(3))), (W, H, D, 'coloured')\n"
         "print('OK')\n")
-    env = dict(os.environ, R3D_SGM_IMPL=impl)
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
+    env = dict(os.environ, R3D_SGM_IMPL="v4")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
     assert "OK" in out.stdout, out.stdout + out.stderr
 
 

@@ -49,13 +49,12 @@ def stage_case(W, H, D, seed):
     L, R, _ = r3d.synth.stereo_pair(W, H, D, seed=seed)
     m = r3d.StereoSGBM_create(numDisparities=D, mode=2, **KW)
     got = m.compute(L, R)
-    want_h = os.environ.get("R3D_SGM_IMPL", "v2") != "v3"
-    st = m.debug_fetch(want_cost=True, want_hsum=want_h, want_raw=True)
+    st = m.debug_fetch(want_cost=True, want_hsum=True, want_raw=True)
     p = so.make_params(numDisparities=D, **KW)
     want, want_raw = so.compute(L, R, p, nthreads=8, return_raw=True)
     C = so.cost_rows(L, R, p, 0, 0, H)
     n = mism("cost", st["cost"], C)
-    if n == 0 and want_h and W * H * D <= 96 * 64 * 32:
+    if n == 0 and W * H * D <= 96 * 64 * 32:
         hs = np.zeros_like(C, dtype=np.int64)
         W1 = C.shape[1]
         for y in range(H):

@@ -1,10 +1,10 @@
 #!/bin/bash
-# Issue / wait / LDS / traffic counters of the SGM kernels of one R3D_SGM_IMPL setting (separate --pmc passes, nothing else
-# traced; raw output stays in /tmp, the per-kernel means land in gpurun_out/<tag>_pmc_sgm.json).
-# Usage (GPU box, repository root): tools/gpu_pmc_sgm.sh <tag> [impl]
+# Issue / wait / LDS / traffic counters of the SGM kernels (separate --pmc passes, nothing else
+# traced; raw output stays in /tmp, the per-kernel means land in the output folder as <tag>_pmc_sgm.json).
+# Usage (GPU box, repository root): tools/gpu_pmc_sgm.sh <tag>
 set -o pipefail
-tag="${1:-r}"; impl="${2:-v2}"
-export TMPDIR=/tmp R3D_SGM_IMPL="$impl"
+tag="${1:-r}"
+export TMPDIR=/tmp
 root="$PWD"; out="$root/gpurun_out"; mkdir -p "$out"
 cd /tmp
 run() {  # run <dir> <counters...>
