@@ -52,6 +52,12 @@ class IcpParams(ctypes.Structure):
                 ("relative_rmse", ctypes.c_double), ("gicp_epsilon", ctypes.c_double)]
 
 
+class ColoredIcpParams(ctypes.Structure):
+    """r3d_colored_icp_params: the registration parameters (icp.mode = 3) + the coloured mode's own."""
+    _fields_ = [("icp", IcpParams), ("lambda_geometric", ctypes.c_double), ("gradient_radius", ctypes.c_double),
+                ("gradient_max_nn", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class IcpStats(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int32), ("converged", ctypes.c_int32), ("correspondences", ctypes.c_int64),
                 ("fitness", ctypes.c_double), ("inlier_rmse", ctypes.c_double), ("setup_ms", ctypes.c_double),

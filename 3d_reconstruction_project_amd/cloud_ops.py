@@ -32,6 +32,15 @@ _lib.register({
 })
 
 P2P, P2PLANE, GICP = 0, 1, 2
+COLORED = 3     # registration_colored / registration_colored_device only: r3d_icp itself refuses it
+
+_lib.register({
+    "r3d_color_gradients": ([_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_icp_colored": ([_vp, ctypes.POINTER(_lib.ColoredIcpParams), _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                         ctypes.POINTER(_lib.IcpStats)], ctypes.c_int),
+    "r3d_icp_colored_dev": ([_vp, ctypes.POINTER(_lib.ColoredIcpParams), _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                             ctypes.POINTER(_lib.IcpStats)], ctypes.c_int),
+})
 
 _lib.register({
     "r3d_debug_sort_by_cell": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
@@ -322,6 +331,44 @@ def registration(source, target, max_correspondence_distance, init=None, mode=P2
     return _stats_dict(T, st)
 
 
+def color_gradients(points, normals, colors, radius, max_nn=30, ctx=None):
+    """r3d_color_gradients: the coloured registration's set-up on its own (InitializePointCloudForColoredICP).  Returns
+    (intensity [n] = (r + g + b) / 3, gradient [n,3]): the least-squares gradient of the intensity in every point's tangent plane
+    over its hybrid neighbourhood (radius, max_nn); zero with fewer than 4 neighbours or a singular system."""
+    ctx = ctx or _lib.default_context()
+    p, n, c = _c(points), _c(normals), _c(colors)
+    inten, grad = np.empty(len(p)), np.empty((len(p), 3))
+    if len(p) == 0:
+        return inten, grad
+    ctx.call("r3d_color_gradients", _ptr(p), _ptr(n), _ptr(c), len(p), float(radius), int(max_nn), _ptr(inten), _ptr(grad))
+    return inten, grad
+
+
+def _colored_params(max_correspondence_distance, lambda_geometric, max_iteration, relative_fitness, relative_rmse, gradient_radius,
+                    gradient_max_nn):
+    return _lib.ColoredIcpParams(_lib.IcpParams(COLORED, int(max_iteration), float(max_correspondence_distance), float(relative_fitness),
+                                                float(relative_rmse), 0.0),
+                                 float(lambda_geometric), float(gradient_radius) if gradient_radius else -1.0, int(gradient_max_nn), 0)
+
+
+def registration_colored(source, source_colors, target, target_normals, target_colors, max_correspondence_distance, init=None,
+                         lambda_geometric=0.968, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, gradient_radius=None,
+                         gradient_max_nn=30, ctx=None):
+    """registration_colored_icp (r3d_icp_colored): point-to-plane with a photometric residual per correspondence, weighted
+    lambda_geometric : 1 - lambda_geometric.  Colours are [n,3] in [0,1]; gradient_radius None: 2 * max_correspondence_distance.
+    Returns the same dict as registration()."""
+    ctx = ctx or _lib.default_context()
+    s, sc, t, tn, tc = _c(source), _c(source_colors), _c(target), _c(target_normals), _c(target_colors)
+    T0 = None if init is None else np.ascontiguousarray(init, dtype=np.float64).reshape(4, 4)
+    T = np.empty((4, 4))
+    prm = _colored_params(max_correspondence_distance, lambda_geometric, max_iteration, relative_fitness, relative_rmse, gradient_radius,
+                          gradient_max_nn)
+    st = _lib.IcpStats()
+    ctx.call("r3d_icp_colored", ctypes.byref(prm), _ptr(s), _ptr(sc), len(s), _ptr(t), _ptr(tn), _ptr(tc), len(t), _ptr(T0), _ptr(T),
+             ctypes.byref(st))
+    return _stats_dict(T, st)
+
+
 def align_point_clouds(source, target, threshold=0.02, voxel_size=0.01, max_iteration=100, mode=P2P, normal_radius=None,
                        normal_max_nn=30, source_colors=None, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
                        gicp_epsilon=1e-3, ctx=None):
@@ -500,6 +547,22 @@ def registration_device(d_source, ns, d_target, nt, max_correspondence_distance,
     st = _lib.IcpStats()
     ctx.call("r3d_icp_dev", ctypes.byref(prm), _vp(d_source), int(ns), _vp(d_source_normals) if d_source_normals else None,
              _vp(d_target), int(nt), _vp(d_target_normals) if d_target_normals else None, _ptr(T0), _ptr(T), ctypes.byref(st))
+    return _stats_dict(T, st)
+
+
+def registration_colored_device(d_source, d_source_colors, ns, d_target, d_target_normals, d_target_colors, nt,
+                                max_correspondence_distance, init=None, lambda_geometric=0.968, max_iteration=30, relative_fitness=1e-6,
+                                relative_rmse=1e-6, gradient_radius=None, gradient_max_nn=30, ctx=None):
+    """r3d_icp_colored_dev: registration_colored on clouds that are already in HBM (device pointers as ints)."""
+    ctx = ctx or _lib.default_context()
+    T0 = None if init is None else np.ascontiguousarray(init, dtype=np.float64).reshape(4, 4)
+    T = np.empty((4, 4))
+    prm = _colored_params(max_correspondence_distance, lambda_geometric, max_iteration, relative_fitness, relative_rmse, gradient_radius,
+                          gradient_max_nn)
+    st = _lib.IcpStats()
+    ctx.call("r3d_icp_colored_dev", ctypes.byref(prm), _vp(d_source), _vp(d_source_colors) if d_source_colors else None, int(ns),
+             _vp(d_target), _vp(d_target_normals) if d_target_normals else None, _vp(d_target_colors) if d_target_colors else None,
+             int(nt), _ptr(T0), _ptr(T), ctypes.byref(st))
     return _stats_dict(T, st)
 
 

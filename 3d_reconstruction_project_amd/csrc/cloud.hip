@@ -1082,9 +1082,20 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn_graph(GridView g, int64_t n, 
 //   P2PLANE: [2..22] upper triangle of J^T J (J = [p x n_t ; n_t]), [23..28] J^T r, r = (p - t).n_t
 //   GICP   : same slots with J^T J = Jb^T M^-1 Jb, J^T r = Jb^T M^-1 d, Jb = [-[p]x | I], d = p - t,
 //            M = C_t + R C_s R^T with C = I - (1-eps) n n^T   (== W^T W with W = M^-1/2 of the original)
+//   COLORED: the P2PLANE slots over TWO rows per correspondence (Open3D ColoredICP.cpp ComputeTransformation [recalled]):
+//            e = (p - t).n_t;  J_G = sg [p x n_t ; n_t], r_G = sg e;  with d_t / I_t the target's intensity gradient / intensity,
+//            I_s the source intensity, p' = p - e n_t:  m = -(d_t - (d_t.n_t) n_t),  J_I = sp [p x m ; m],
+//            r_I = sp (I_s - (d_t.(p' - t) + I_t));  sg = sqrt(lambda), sp = sqrt(1 - lambda)
 constexpr int ICP_SLOTS = 29;
 constexpr int ICP_BLOCK = 256;
-enum { MODE_P2P = 0, MODE_P2PLANE = 1, MODE_GICP = 2 };
+enum { MODE_P2P = 0, MODE_P2PLANE = 1, MODE_GICP = 2, MODE_COLORED = 3 };
+// what the coloured mode reads besides the point-to-plane inputs; passed by value behind the other kernel arguments (unused, and
+// zero, in every other mode)
+struct IcpColor {
+    const double *src_i;    // [ns] source intensity, in the order of the (Morton-sorted) source
+    const double *tgt_ig;   // [nt][4] target intensity + gradient (k_color_gradient's record), cell-sorted
+    double sg, sp;          // sqrt(lambda), sqrt(1 - lambda)
+};
 
 struct Rigid { double r[9], t[3]; };
 
@@ -1126,6 +1137,74 @@ __device__ __forceinline__ bool inv3_sym(const double m[6] /*xx xy xz yy yz zz*/
     a[0] = c00 * id; a[1] = c01 * id; a[2] = c02 * id;
     a[3] = (m[0] * m[5] - m[2] * m[2]) * id; a[4] = (m[1] * m[2] - m[0] * m[4]) * id; a[5] = (m[0] * m[3] - m[1] * m[1]) * id;
     return true;
+}
+
+// ---- coloured ICP set-up (Open3D ColoredICP.cpp InitializePointCloudForColoredICP [recalled]; contract in DESIGN.md section 4, "Coloured ICP")
+// intensity I = (r + g + b) / 3 of point idx[i] (idx null: point i), summed in that order
+__global__ void __launch_bounds__(256) k_intensity(const double *__restrict__ colors, const int *__restrict__ idx, int64_t n, double *__restrict__ out) {
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = idx ? idx[i] : i;
+    out[i] = ((colors[j * 3] + colors[j * 3 + 1]) + colors[j * 3 + 2]) / 3.0;
+}
+
+__global__ void __launch_bounds__(256) k_gather4(const double *__restrict__ src, const int *__restrict__ idx, int64_t n, double *__restrict__ dst) {
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = idx[i];
+    dst[i * 4] = src[j * 4]; dst[i * 4 + 1] = src[j * 4 + 1]; dst[i * 4 + 2] = src[j * 4 + 2]; dst[i * 4 + 3] = src[j * 4 + 3];
+}
+
+// k_color_gradient: one thread per (cell-sorted) point: the hybrid search of k_normals, then the least-squares intensity gradient
+// in the point's tangent plane.  Neighbour i >= 1 (the list's first entry is the point itself) contributes the row
+// a_i = (p_i - ((p_i - v).n) n) - v with right-hand side I_i - I_v, a last row (nn - 1) n with right-hand side 0 keeps the
+// gradient out of the normal direction; the 3x3 normal equations are summed in list order and solved with inv3_sym.  Fewer than
+// 4 neighbours, a singular system or a non-finite solution give a zero gradient (QUIRK_SINGULAR: the original's LDLT result is
+// unspecified there).  rec (the caller's numbering): [4 o] = intensity, [4 o + 1 .. 3] = gradient.
+__global__ void __launch_bounds__(KNN_BLOCK) k_color_gradient(GridView g, int64_t n, int k, double radius, const double *__restrict__ normals /* caller's numbering */,
+                                                              const double *__restrict__ inten /* cell-sorted */, double *__restrict__ rec) {
+    extern __shared__ double lds_d[];
+    double *sd = lds_d;
+    int *si = (int *)(lds_d + (size_t)k * KNN_BLOCK);
+    int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int t = threadIdx.x;
+    const double qx = g.pts[i * 3], qy = g.pts[i * 3 + 1], qz = g.pts[i * 3 + 2];
+    const int cnt = knn_query(g, qx, qy, qz, k, radius, sd, si);
+    const int64_t o = g.idx[i];
+    const double it = inten[i];
+    double grad[3] = {0.0, 0.0, 0.0};
+    if (cnt >= 4) {
+        const double nx = normals[o * 3], ny = normals[o * 3 + 1], nz = normals[o * 3 + 2];
+        double m[6] = {0, 0, 0, 0, 0, 0}, bx = 0, by = 0, bz = 0;
+        for (int j0 = 1; j0 < cnt; j0 += 4) {       // four neighbours per round trip, summed in list order
+            double X[4], Y[4], Z[4], I[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int64_t s = si[min(j0 + u, cnt - 1) * KNN_BLOCK + t];
+                X[u] = g.pts[s * 3]; Y[u] = g.pts[s * 3 + 1]; Z[u] = g.pts[s * 3 + 2];
+                I[u] = inten[s];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                if (j0 + u >= cnt) break;
+                const double dot = ((X[u] - qx) * nx + (Y[u] - qy) * ny) + (Z[u] - qz) * nz;
+                const double ax = (X[u] - dot * nx) - qx, ay = (Y[u] - dot * ny) - qy, az = (Z[u] - dot * nz) - qz;
+                const double b = I[u] - it;
+                m[0] += ax * ax; m[1] += ax * ay; m[2] += ax * az; m[3] += ay * ay; m[4] += ay * az; m[5] += az * az;
+                bx += ax * b; by += ay * b; bz += az * b;
+            }
+        }
+        const double w = (double)(cnt - 1);
+        const double lx = w * nx, ly = w * ny, lz = w * nz;
+        m[0] += lx * lx; m[1] += lx * ly; m[2] += lx * lz; m[3] += ly * ly; m[4] += ly * lz; m[5] += lz * lz;
+        double a[6];
+        if (inv3_sym(m, a)) {
+            const double gx = (a[0] * bx + a[1] * by) + a[2] * bz, gy = (a[1] * bx + a[3] * by) + a[4] * bz, gz = (a[2] * bx + a[4] * by) + a[5] * bz;
+            if (isfinite(gx) && isfinite(gy) && isfinite(gz)) { grad[0] = gx; grad[1] = gy; grad[2] = gz; }
+        }
+    }
+    rec[o * 4] = it; rec[o * 4 + 1] = grad[0]; rec[o * 4 + 2] = grad[1]; rec[o * 4 + 3] = grad[2];
 }
 
 // nearest target point inside the 3x3x3 cell block around the query (shells 0 and 1), straight from global memory, as nine
@@ -1650,7 +1729,7 @@ __device__ __forceinline__ bool icp_out_of_reach(const GridView &g, int cx, int 
 template <int MODE>
 __device__ __forceinline__ void icp_accumulate(const GridView &g, const double *__restrict__ src_n, const double *__restrict__ tgt_n,
                                                int64_t i, const Rigid &T, double eps, double px, double py, double pz, double best, int bi,
-                                               double (&acc)[29]) {
+                                               double (&acc)[29], const IcpColor &col) {
         const double tx = g.pts[(int64_t)bi * 3], ty = g.pts[(int64_t)bi * 3 + 1], tz = g.pts[(int64_t)bi * 3 + 2];
         acc[0] += 1.0;
         acc[1] += best;
@@ -1676,6 +1755,30 @@ __device__ __forceinline__ void icp_accumulate(const GridView &g, const double *
                     for (int b = a; b < 6; b++, q++) acc[q] += J[0][a] * J[0][b];
 #pragma unroll
                 for (int a = 0; a < 6; a++) acc[23 + a] += J[0][a] * rr[0];
+            } else if (MODE == MODE_COLORED) {
+                rows = 2;
+                (void)rows;
+                const double e = dx * nx + dy * ny + dz * nz;
+                // geometric row: point-to-plane's, scaled (sg = 1 leaves every product as point-to-plane forms it)
+                J[0][0] = col.sg * (py * nz - pz * ny); J[0][1] = col.sg * (pz * nx - px * nz); J[0][2] = col.sg * (px * ny - py * nx);
+                J[0][3] = col.sg * nx; J[0][4] = col.sg * ny; J[0][5] = col.sg * nz;
+                rr[0] = col.sg * e;
+                // photometric row
+                const double *ig = col.tgt_ig + (int64_t)bi * 4;
+                const double it = ig[0], gx = ig[1], gy = ig[2], gz = ig[3];
+                const double is = col.src_i[i];
+                const double gn = gx * nx + gy * ny + gz * nz;
+                const double mx = -(gx - gn * nx), my = -(gy - gn * ny), mz = -(gz - gn * nz);
+                const double i0 = (gx * ((px - e * nx) - tx) + gy * ((py - e * ny) - ty) + gz * ((pz - e * nz) - tz)) + it;
+                J[1][0] = col.sp * (py * mz - pz * my); J[1][1] = col.sp * (pz * mx - px * mz); J[1][2] = col.sp * (px * my - py * mx);
+                J[1][3] = col.sp * mx; J[1][4] = col.sp * my; J[1][5] = col.sp * mz;
+                rr[1] = col.sp * (is - i0);
+#pragma unroll
+                for (int a = 0, q = 2; a < 6; a++)
+#pragma unroll
+                    for (int b = a; b < 6; b++, q++) { acc[q] += J[0][a] * J[0][b]; acc[q] += J[1][a] * J[1][b]; }
+#pragma unroll
+                for (int a = 0; a < 6; a++) { acc[23 + a] += J[0][a] * rr[0]; acc[23 + a] += J[1][a] * rr[1]; }
             } else {
                 rows = 3;
                 (void)rows;
@@ -1744,7 +1847,8 @@ template <int MODE, int SEARCH>
 __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) k_icp_eval(GridView g, const double *__restrict__ src, const double *__restrict__ src_n,
                                                         const double *__restrict__ tgt_n /* cell-sorted order */, int64_t ns,
                                                         const IcpState *__restrict__ st, double max_dist, double eps, double *__restrict__ partial,
-                                                        int *__restrict__ corr /* optional [ns] target original index or -1 */) {
+                                                        int *__restrict__ corr /* optional [ns] target original index or -1 */,
+                                                        IcpColor col /* MODE_COLORED only */) {
     static_assert(ICP_BLOCK == 256, "nn_block_q10 assumes 256 threads");
     __shared__ int sRun[SEARCH >= SEARCH_Q10 ? 18 * ICP_BLOCK : 1];
     __shared__ __attribute__((aligned(16))) int sPoolBuf[SEARCH == SEARCH_Q10 ? (ICP_BLOCK / 64) * pool_words(POOL_Q) : 4];
@@ -1785,7 +1889,7 @@ __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) 
             nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
         }
         if (corr) corr[i] = bi >= 0 ? g.idx[bi] : -1;
-        if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc);
+        if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, col);
     }
     __shared__ double sm[ICP_BLOCK / 64][ICP_SLOTS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1874,7 +1978,7 @@ __global__ void __launch_bounds__(ICP_BLOCK, 3) k_icp_accum(GridView g, const do
         const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
         const double dx = g.pts[(int64_t)bi * 3] - px, dy = g.pts[(int64_t)bi * 3 + 1] - py, dz = g.pts[(int64_t)bi * 3 + 2] - pz;
         const double best = dx * dx + dy * dy + dz * dz;   // the search's own expression for the winner
-        icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc);
+        icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, IcpColor{});
     }
     __shared__ double sm[ICP_BLOCK / 64][ICP_SLOTS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1996,7 +2100,7 @@ __global__ void __launch_bounds__(64) k_icp_eval_t(GridView g, const double *__r
             }
             nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
             if (corr) corr[i] = bi >= 0 ? g.idx[bi] : -1;
-            if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc);
+            if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, IcpColor{});
         }
         __syncthreads();  // the next chunk overwrites the tile
     }
@@ -3229,8 +3333,31 @@ int normals_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t n, doubl
     return R3D_OK;
 }
 
+// intensity + colour gradient of a device cloud (k_color_gradient's 4-double records, the caller's numbering) into a fresh device
+// buffer; the search grid follows normals_core's rule
+int color_gradients_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t n, const double *d_n, const double *d_c, double radius, int max_nn,
+                         double **d_rec_out) {
+    Grid G;
+    const int k = (int)std::min<int64_t>(max_nn, n);
+    int rc;
+    double occ = std::max(2.0, k / 5.0);
+    if (const char *oe = getenv("R3D_KNN_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 256) occ = v; }
+    if ((rc = grid_build(ctx, ar, d_p, n, radius, occ, G, false))) return rc;
+    double *d_i = (double *)ar.get((size_t)n * 8), *d_rec = (double *)ar.get((size_t)n * 32);
+    if (ar.rc) return ar.rc;
+    k_intensity<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_c, G.v.idx, n, d_i);
+    const size_t lds = (size_t)k * KNN_BLOCK * 12;
+    R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_color_gradient, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_color_gradient<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, d_n, d_i, d_rec);
+    R3D_HIP(ctx, hipGetLastError());
+    *d_rec_out = d_rec;
+    return R3D_OK;
+}
+
 // r3d_debug_icp_correspondences' output (host arrays, the caller's numbering)
 struct IcpReadout { int32_t *corr; double *d2; };
+// the coloured mode's extra inputs (device colours of both clouds) and parameters, resolved by the entry point
+struct IcpColorInput { const double *d_sc, *d_tc; double lambda, radius; int max_nn; };
 
 // ICP / point-to-plane / GICP loop on clouds that are already in device memory (d_sn / d_tn may be null where the mode
 // allows it); everything below r3d_icp's argument checks and uploads
@@ -3238,8 +3365,12 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
                     double *d_tn, const double *init4x4, double *T4x4, r3d_icp_stats *stats,
                     std::chrono::steady_clock::time_point t_begin, const double *tgt_enclosing = nullptr /* grid_build's `enclosing` */,
                     double tgt_spacing = 0 /* grid_build's `spacing_hint`: voxel size the target was down-sampled with */,
-                    const IcpReadout *readout = nullptr /* r3d_debug_icp_correspondences: one evaluation at the initial pose, no loop */) {
+                    const IcpReadout *readout = nullptr /* r3d_debug_icp_correspondences: one evaluation at the initial pose, no loop */,
+                    const IcpColorInput *color = nullptr /* MODE_COLORED (and only then) */) {
     int rc;
+    // coloured mode: the target's intensities and gradients, once per call (a search grid of its own: the radius differs)
+    double *d_trec = nullptr;
+    if (color && (rc = color_gradients_core(ctx, ar, d_t, nt, d_tn, color->d_tc, color->radius, color->max_nn, &d_trec))) return rc;
     Grid G;
     double occ = 3.0;   // points per occupied cell the search grid aims at (R3D_ICP_OCC: A/B)
     if (const char *oe = getenv("R3D_ICP_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 64) occ = v; }
@@ -3302,6 +3433,15 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
         if (ar.rc) return ar.rc;
         k_gather3<<<(unsigned)((nt + 255) / 256), 256, 0, ctx->stream>>>(d_tn, G.v.idx, nt, d_tns);
     }
+    IcpColor colk = {};
+    if (color) {
+        double *d_trecs = (double *)ar.get((size_t)nt * 32);
+        if (ar.rc) return ar.rc;
+        k_gather4<<<(unsigned)((nt + 255) / 256), 256, 0, ctx->stream>>>(d_trec, G.v.idx, nt, d_trecs);
+        colk.tgt_ig = d_trecs;
+        colk.sg = std::sqrt(color->lambda);
+        colk.sp = std::sqrt(1.0 - color->lambda);
+    }
     // spatially sort the source once (Morton order of the target-grid cell of its initial pose) so that neighbouring threads
     // walk the same cells; sums are order-dependent only at the 1e-16 level and stay deterministic
     double T[16];
@@ -3326,6 +3466,12 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
             k_gather3<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(d_sn, sidx, ns, d_sns);
             d_sn = d_sns;
         }
+        if (color) {
+            double *d_si = (double *)ar.get((size_t)ns * 8);
+            if (ar.rc) return ar.rc;
+            k_intensity<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(color->d_sc, sidx, ns, d_si);
+            colk.src_i = d_si;
+        }
     }
     // default: per-lane search straight from global memory (L1/L2-cached gathers), two-stage (float32 top-4, exact top-3:
     // nn_block_top4; R3D_ICP_IMPL=exact keeps every distance in float64); R3D_ICP_IMPL=tiled selects the LDS-tiled
@@ -3348,6 +3494,8 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     // R3D_ICP_SPLIT=1: search and accumulation as two kernels (A/B; same partial sums bit for bit)
     static const bool split_env = [] { const char *e = getenv("R3D_ICP_SPLIT"); return e && !strcmp(e, "1"); }();
     const bool split_impl = split_env && !tiled_impl;
+    if (color && tiled_impl) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "icp_colored: the LDS-tiled kernel (R3D_ICP_IMPL=tiled) has no coloured mode");
+    if (color && split_impl) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "icp_colored: the two-kernel evaluation (R3D_ICP_SPLIT=1) has no coloured mode");
     int *d_nn = split_impl ? (int *)ar.get((size_t)ns * 4) : nullptr;
     if (ar.rc) return ar.rc;
     static_assert(sizeof(IcpState) <= ICP_SLOTS * sizeof(double), "the pinned landing buffer holds one IcpState");
@@ -3374,11 +3522,12 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
                 default: k_icp_eval_t<MODE_GICP><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
             }
         } else {
-#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr)
+#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr, colk)
 #define R3D_ICP_MODES(S)                                            \
     switch (p->mode) {                                              \
         case MODE_P2P: R3D_ICP_LAUNCH(MODE_P2P, S); break;          \
         case MODE_P2PLANE: R3D_ICP_LAUNCH(MODE_P2PLANE, S); break;  \
+        case MODE_COLORED: R3D_ICP_LAUNCH(MODE_COLORED, S); break;  \
         default: R3D_ICP_LAUNCH(MODE_GICP, S); break;               \
     }
             if (split_impl) {
@@ -4510,6 +4659,88 @@ int r3d_icp_dev(r3d_ctx *ctx, const r3d_icp_params *p, const double *d_src, int6
     DevArena ar(ctx);
     return icp_core(ctx, ar, p, const_cast<double *>(d_src), ns, const_cast<double *>(d_src_normals), const_cast<double *>(d_tgt), nt,
                     const_cast<double *>(d_tgt_normals), init4x4, T4x4, stats, t_begin);
+}
+
+// ---- coloured ICP (Open3D registration_colored_icp): the intensity gradients on their own, and the registration on host / device clouds
+int r3d_color_gradients(r3d_ctx *ctx, const double *xyz, const double *normals, const double *colors, int64_t n, double radius, int32_t max_nn,
+                        double *out_intensity, double *out_gradient) {
+    R3D_ROCTX_RANGE("r3d_color_gradients");
+    if (!ctx) return R3D_E_BADARG;
+    if (!xyz || !normals || !colors || !out_intensity || !out_gradient || n <= 0) return r3d_fail(ctx, R3D_E_BADARG, "color_gradients: bad argument");
+    if (!(radius > 0)) return r3d_fail(ctx, R3D_E_BADARG, "color_gradients: radius must be > 0 (the search is a hybrid one)");
+    if (max_nn < 1 || max_nn > 128) return r3d_fail(ctx, R3D_E_BADARG, "color_gradients: max_nn must be in 1..128");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_p, *d_n, *d_c, *d_rec;
+    int rc;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
+    if ((rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
+    if ((rc = upload(ctx, ar, colors, n * 3, &d_c))) return rc;
+    if ((rc = color_gradients_core(ctx, ar, d_p, n, d_n, d_c, radius, max_nn, &d_rec))) return rc;
+    std::vector<double> rec((size_t)n * 4);
+    R3D_HIP(ctx, hipMemcpyAsync(rec.data(), d_rec, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < n; i++) {
+        out_intensity[i] = rec[i * 4];
+        out_gradient[i * 3] = rec[i * 4 + 1]; out_gradient[i * 3 + 1] = rec[i * 4 + 2]; out_gradient[i * 3 + 2] = rec[i * 4 + 3];
+    }
+    return R3D_OK;
+}
+
+// argument checks shared by the two coloured entry points; fills the resolved parameters
+static int colored_icp_check(r3d_ctx *ctx, const char *who, const r3d_colored_icp_params *p, const void *src, const void *src_colors, int64_t ns,
+                             const void *tgt, const void *tgt_normals, const void *tgt_colors, int64_t nt, const double *T4x4, r3d_icp_params *ip,
+                             IcpColorInput *ci) {
+    if (!p || !src || !tgt || !T4x4 || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument", who);
+    if (p->icp.mode != MODE_COLORED) return r3d_fail(ctx, R3D_E_BADARG, "%s: icp.mode must be R3D_ICP_COLORED (3)", who);
+    if (!(p->icp.max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "%s: max_correspondence_distance must be > 0", who);
+    if (!src_colors || !tgt_colors) return r3d_fail(ctx, R3D_E_BADARG, "%s: source and target colours required", who);
+    if (!tgt_normals) return r3d_fail(ctx, R3D_E_BADARG, "%s: target normals required", who);
+    if (!(p->lambda_geometric >= 0.0 && p->lambda_geometric <= 1.0)) return r3d_fail(ctx, R3D_E_BADARG, "%s: lambda_geometric must lie in [0, 1]", who);
+    if (p->gradient_max_nn > 128) return r3d_fail(ctx, R3D_E_BADARG, "%s: gradient_max_nn > 128 not supported", who);
+    *ip = p->icp;
+    ci->d_sc = ci->d_tc = nullptr;
+    ci->lambda = p->lambda_geometric;
+    ci->radius = p->gradient_radius > 0 ? p->gradient_radius : 2.0 * p->icp.max_correspondence_distance;
+    ci->max_nn = p->gradient_max_nn > 0 ? p->gradient_max_nn : 30;
+    return R3D_OK;
+}
+
+int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *src, const double *src_colors, int64_t ns, const double *tgt,
+                    const double *tgt_normals, const double *tgt_colors, int64_t nt, const double *init4x4, double *T4x4, r3d_icp_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_icp_colored");
+    if (!ctx) return R3D_E_BADARG;
+    r3d_icp_params ip;
+    IcpColorInput ci;
+    int rc;
+    if ((rc = colored_icp_check(ctx, "icp_colored", p, src, src_colors, ns, tgt, tgt_normals, tgt_colors, nt, T4x4, &ip, &ci))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    DevArena ar(ctx);
+    double *d_t, *d_tn, *d_tc, *d_s, *d_sc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
+    if ((rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc))) return rc;
+    if ((rc = upload(ctx, ar, src_colors, ns * 3, &d_sc))) return rc;
+    ci.d_sc = d_sc; ci.d_tc = d_tc;
+    return icp_core(ctx, ar, &ip, d_s, ns, nullptr, d_t, nt, d_tn, init4x4, T4x4, stats, t_begin, nullptr, 0, nullptr, &ci);
+}
+
+int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *d_src, const double *d_src_colors, int64_t ns, const double *d_tgt,
+                        const double *d_tgt_normals, const double *d_tgt_colors, int64_t nt, const double *init4x4, double *T4x4, r3d_icp_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_icp_colored_dev");
+    if (!ctx) return R3D_E_BADARG;
+    r3d_icp_params ip;
+    IcpColorInput ci;
+    int rc;
+    if ((rc = colored_icp_check(ctx, "icp_colored_dev", p, d_src, d_src_colors, ns, d_tgt, d_tgt_normals, d_tgt_colors, nt, T4x4, &ip, &ci))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    DevArena ar(ctx);
+    ci.d_sc = d_src_colors; ci.d_tc = d_tgt_colors;
+    return icp_core(ctx, ar, &ip, const_cast<double *>(d_src), ns, nullptr, const_cast<double *>(d_tgt), nt, const_cast<double *>(d_tgt_normals),
+                    init4x4, T4x4, stats, t_begin, nullptr, 0, nullptr, &ci);
 }
 
 int r3d_transform_points_dev(r3d_ctx *ctx, const double *d_xyz, int64_t n, const double *T4x4, int32_t rotate_only, double *d_out) {

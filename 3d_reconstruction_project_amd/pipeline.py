@@ -316,6 +316,9 @@ def multi_view_fuse_tensors(local, n_views, threshold=0.02, mode=cloud_ops.GICP,
     Views may carry a third plane, colours ([3, n, 3], pipeline.view_to_cloud_tensors with d_color): it travels through the same
     all-gather and is copied unchanged into a fused [3, N, 3] tensor (the stubs still see and return planes 0 and 1 only).  All
     views must have the same number of planes: ValueError otherwise, on every rank, before the first collective.
+    mode=cloud_ops.COLORED registers every view to view 0 with the coloured registration (r3d_icp_colored_dev on planes 0 / 1 / 2:
+    source points and colours, target points, normals and colours); it needs three-plane views (ValueError on every rank, before
+    the payload exchange, otherwise) and the `register` stub then receives all three planes of both views.
     timings (dict, optional) receives exchange_ms / register_ms / fuse_ms measured with events on the shared stream.
     (A rank that owns several views registers them one after the other: running them on several contexts / host threads at
     once was measured -- 7 registrations of 109 k-point clouds: 2.8 ms sequential, 3.3-3.8 ms on two contexts, 2.5-3.0 ms on
@@ -359,6 +362,10 @@ def _multi_view_fuse_on_stream(local, n_views, threshold, mode, max_iteration, r
         return a.elapsed_time(b)
 
     planes = distributed.common_planes(local)            # 2, or 3 with colours; raises on every rank if the views disagree
+    colored = mode == cloud_ops.COLORED
+    if colored and planes != 3:
+        # the count is the one all ranks agreed on, so every rank raises here, before the payload exchange
+        raise ValueError("mode=COLORED registers on the views' colours: every view must be a [3, n, 3] tensor (points, normals, colours)")
     t0 = mark()
     everyone = distributed.gather_views(local, n_views, planes=planes)
     t1 = mark()
@@ -372,8 +379,14 @@ def _multi_view_fuse_on_stream(local, n_views, threshold, mode, max_iteration, r
             if v == 0:
                 return np.eye(4)
             if register is not None:
+                if colored:
+                    return np.asarray(register(everyone[v], ref), dtype=np.float64)
                 return np.asarray(register(everyone[v][:2], ref[:2]), dtype=np.float64)
             src = everyone[v]
+            if colored:
+                return cloud_ops.registration_colored_device(src[0].data_ptr(), src[2].data_ptr(), src.shape[1], ref[0].data_ptr(),
+                                                             ref[1].data_ptr(), ref[2].data_ptr(), ref.shape[1], threshold,
+                                                             max_iteration=max_iteration, ctx=c)["T"]
             return cloud_ops.registration_device(src[0].data_ptr(), src.shape[1], ref[0].data_ptr(), ref.shape[1], threshold,
                                                  mode=mode, max_iteration=max_iteration, d_source_normals=src[1].data_ptr(),
                                                  d_target_normals=ref[1].data_ptr(), ctx=c)["T"]
@@ -409,7 +422,8 @@ def multi_view_fuse(local_clouds, n_views, threshold=0.02, mode=cloud_ops.GICP, 
     """Host-cloud front end of multi_view_fuse_tensors.  local_clouds: {view_id: PointCloud with normals} owned by this rank.
     The clouds go up once (to the device the exchange runs on), everything else stays there; returns
     (fused PointCloud, {view_id: T}).  `register(src [n,6], tgt [m,6]) -> 4x4` may replace the HIP registration (the CPU tests
-    inject a stub; rows are xyz | normal).  Clouds with colours keep them: the colours ride along as a third plane and the fused
+    inject a stub; rows are xyz | normal, and xyz | normal | rgb with mode=cloud_ops.COLORED, which needs colours on every
+    view).  Clouds with colours keep them: the colours ride along as a third plane and the fused
     cloud has .colors; colours on some views only (on any rank) raise ValueError."""
     import torch
     dev = distributed.exchange_device()
@@ -420,8 +434,8 @@ def multi_view_fuse(local_clouds, n_views, threshold=0.02, mode=cloud_ops.GICP, 
         local[v] = torch.from_numpy(np.stack(planes, 0)).to(dev)
     reg = tr = None
     if register is not None:
-        def reg(src, tgt):
-            return register(torch.cat([src[0], src[1]], 1).cpu().numpy(), torch.cat([tgt[0], tgt[1]], 1).cpu().numpy())
+        def reg(src, tgt):      # rows xyz | normal, and | rgb behind them in the coloured mode (the only one that hands colours over)
+            return register(torch.cat(list(src), 1).cpu().numpy(), torch.cat(list(tgt), 1).cpu().numpy())
     if dev.type != "cuda" or register is not None:
         def tr(blk, T):
             R = torch.from_numpy(np.ascontiguousarray(T[:3, :3])).to(blk.device)

@@ -280,6 +280,36 @@ typedef struct {
 int r3d_icp(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns, const double *src_normals, const double *tgt,
             int64_t nt, const double *tgt_normals, const double *init4x4, double *T4x4, r3d_icp_stats *stats);
 
+/* replaces: o3d.pipelines.registration.registration_colored_icp(source, target, max_dist, init,
+ *           TransformationEstimationForColoredICP(lambda_geometric), ICPConvergenceCriteria(...))   [recalled, Open3D 0.18
+ *           ColoredICP.cpp; the reference never calls it: the consumer of the colours its clouds carry, main.py:42-45].
+ * The point-to-plane loop with a second, photometric residual per correspondence: intensity I = (r + g + b) / 3; once per call
+ * every target point gets the least-squares gradient of I in its tangent plane over its hybrid neighbourhood
+ * (gradient_radius, gradient_max_nn; fewer than 4 neighbours or a singular system: zero gradient); each iteration minimises
+ * lambda (geometric)^2 + (1 - lambda) (photometric)^2.  Correspondences, fitness, inlier_rmse (Euclidean) and the convergence
+ * test are those of r3d_icp.  lambda_geometric = 1 is point-to-plane bit for bit.  DESIGN.md section 4 ("Coloured ICP") has the contract.
+ * r3d_icp and r3d_icp_params are unchanged: r3d_icp keeps refusing mode 3, the coloured mode has entry points of its own. */
+#define R3D_ICP_COLORED 3
+typedef struct {
+    r3d_icp_params icp;       /* icp.mode must be R3D_ICP_COLORED; gicp_epsilon unused; Open3D's criteria default 1e-6 / 1e-6 / 30 */
+    double lambda_geometric;  /* in [0, 1]; Open3D default 0.968 */
+    double gradient_radius;   /* <= 0: 2 * icp.max_correspondence_distance (Open3D's choice) */
+    int32_t gradient_max_nn;  /* <= 0: 30 (Open3D's choice); at most 128 */
+    int32_t reserved;
+} r3d_colored_icp_params;
+/* stage parity: the set-up alone.  colors: [n,3] in [0,1]; out_intensity [n]; out_gradient [n,3].  radius > 0, max_nn in 1..128 */
+int r3d_color_gradients(r3d_ctx *ctx, const double *xyz, const double *normals, const double *colors, int64_t n, double radius,
+                        int32_t max_nn, double *out_intensity, double *out_gradient);
+/* Required: source colours, target colours, target normals (no source normals).  R3D_E_BADARG: one of them missing,
+ * lambda_geometric outside [0, 1], gradient_max_nn > 128.  The _dev form takes DEVICE clouds and, like r3d_icp_dev, returns when
+ * the loop has finished.  The A/B kernel forms (R3D_ICP_IMPL=tiled, R3D_ICP_SPLIT=1) have no coloured mode: R3D_E_UNSUPPORTED. */
+int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *src, const double *src_colors, int64_t ns,
+                    const double *tgt, const double *tgt_normals, const double *tgt_colors, int64_t nt, const double *init4x4,
+                    double *T4x4, r3d_icp_stats *stats);
+int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *d_src, const double *d_src_colors, int64_t ns,
+                        const double *d_tgt, const double *d_tgt_normals, const double *d_tgt_colors, int64_t nt, const double *init4x4,
+                        double *T4x4, r3d_icp_stats *stats);
+
 /* replaces: the whole body of PointCloudAlignment.align_point_clouds (pointcloud_alignment.py:6-43; caller main.py:48) in ONE
  * call, device-resident between the stages: voxel_down_sample(voxel_size) of both clouds (:22-23) ->
  * estimate_normals(KDTreeSearchParamHybrid(normal_radius, normal_max_nn)) on both (:27-28) -> registration (:35-39) ->
