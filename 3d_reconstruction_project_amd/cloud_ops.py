@@ -42,6 +42,16 @@ _lib.register({
                              ctypes.POINTER(_lib.IcpStats)], ctypes.c_int),
 })
 
+FPFH_DIM = 33
+_lib.register({
+    "r3d_compute_fpfh": ([_vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_compute_fpfh_dev": ([_vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_fpfh_from_spfh": ([_vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_match_features": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_match_features_dev": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp], ctypes.c_int),
+    "r3d_debug_fpfh_stages": ([_vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _vp, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+})
+
 _lib.register({
     "r3d_debug_sort_by_cell": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
     "r3d_debug_exclusive_scan": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp], ctypes.c_int),
@@ -344,6 +354,68 @@ def color_gradients(points, normals, colors, radius, max_nn=30, ctx=None):
     return inten, grad
 
 
+def _feat_rows(f):
+    """a (33, N) feature array (o3d's Feature.data) as the C ABI's [N][33] rows"""
+    f = np.asarray(f, dtype=np.float64)
+    if f.ndim != 2 or f.shape[0] != FPFH_DIM:
+        raise _lib.R3DError(-4, f"features must be a ({FPFH_DIM}, N) array, got {f.shape}")
+    return np.ascontiguousarray(f.T)
+
+
+def compute_fpfh_feature(points, normals, radius, max_nn=100, want_spfh=False, ctx=None):
+    """o3d.pipelines.registration.compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)).data: a (33, N) float64
+    array (radius None or <= 0: KDTreeSearchParamKNN(max_nn)).  want_spfh=True returns (fpfh, spfh), the first stage's simplified
+    histograms in the same shape.  Normals are required, as in Open3D."""
+    ctx = ctx or _lib.default_context()
+    p, n = _c(points), _c(normals)
+    if n is None or len(n) != len(p):
+        raise _lib.R3DError(-1, "compute_fpfh_feature: the cloud needs one normal per point")
+    f = np.empty((len(p), FPFH_DIM))
+    s = np.empty((len(p), FPFH_DIM)) if want_spfh else None
+    if len(p):
+        ctx.call("r3d_compute_fpfh", _ptr(p), _ptr(n), len(p), float(radius) if radius else -1.0, int(max_nn), _ptr(f), _ptr(s))
+    return (f.T, s.T) if want_spfh else f.T
+
+
+def fpfh_from_spfh(points, spfh, radius, max_nn=100, ctx=None):
+    """r3d_fpfh_from_spfh: the second FPFH stage alone on a given (33, N) SPFH; returns the (33, N) FPFH"""
+    ctx = ctx or _lib.default_context()
+    p, s = _c(points), _feat_rows(spfh)
+    if len(s) != len(p):
+        raise _lib.R3DError(-1, "fpfh_from_spfh: one SPFH column per point")
+    f = np.empty((len(p), FPFH_DIM))
+    if len(p):
+        ctx.call("r3d_fpfh_from_spfh", _ptr(p), len(p), float(radius) if radius else -1.0, int(max_nn), _ptr(s), _ptr(f))
+    return f.T
+
+
+def match_features(source_features, target_features, want_d2=True, ctx=None):
+    """r3d_match_features: (nn [ns] int32, d2 [ns]) -- for every source column the target column at the smallest squared
+    distance (float64, summed in row order), the smaller index on ties.  Features are (33, N) arrays."""
+    ctx = ctx or _lib.default_context()
+    s, t = _feat_rows(source_features), _feat_rows(target_features)
+    nn = np.empty(len(s), np.int32)
+    d2 = np.empty(len(s)) if want_d2 else None
+    if len(s):
+        ctx.call("r3d_match_features", _ptr(s), len(s), _ptr(t), len(t), FPFH_DIM, nn.ctypes.data_as(_vp), _ptr(d2))
+    return nn, d2
+
+
+def correspondences_from_features(source_features, target_features, mutual_filter=False, mutual_consistent_ratio=0.1, ctx=None):
+    """o3d.pipelines.registration.correspondences_from_features: int32 [M, 2] rows (source index, target index), one per source
+    feature.  mutual_filter keeps (i, j) only if i is also j's nearest source feature; if fewer than
+    mutual_consistent_ratio * ns pairs survive, the unfiltered list is returned (Open3D's fall-back).  The two searches run on
+    the device, the filter here."""
+    nn_st, _ = match_features(source_features, target_features, False, ctx)
+    ns = len(nn_st)
+    corres = np.stack([np.arange(ns, dtype=np.int32), nn_st], 1)
+    if not mutual_filter or ns == 0:
+        return corres
+    nn_ts, _ = match_features(target_features, source_features, False, ctx)
+    mutual = corres[nn_ts[nn_st] == np.arange(ns)]
+    return corres if len(mutual) < mutual_consistent_ratio * ns else mutual
+
+
 def _colored_params(max_correspondence_distance, lambda_geometric, max_iteration, relative_fitness, relative_rmse, gradient_radius,
                     gradient_max_nn):
     return _lib.ColoredIcpParams(_lib.IcpParams(COLORED, int(max_iteration), float(max_correspondence_distance), float(relative_fitness),
@@ -564,6 +636,29 @@ def registration_colored_device(d_source, d_source_colors, ns, d_target, d_targe
              _vp(d_target), _vp(d_target_normals) if d_target_normals else None, _vp(d_target_colors) if d_target_colors else None,
              int(nt), _ptr(T0), _ptr(T), ctypes.byref(st))
     return _stats_dict(T, st)
+
+
+def compute_fpfh_feature_device(d_points, d_normals, n, radius, d_fpfh, max_nn=100, d_spfh=None, ctx=None):
+    """r3d_compute_fpfh_dev: FPFH of a cloud that is already in HBM into d_fpfh ([n][33] float64 rows, a device pointer as int;
+    d_spfh optionally receives the first stage).  Enqueued on the context stream: ctx.sync() before reading the result."""
+    ctx = ctx or _lib.default_context()
+    ctx.call("r3d_compute_fpfh_dev", _vp(d_points), _vp(d_normals) if d_normals else None, int(n), float(radius) if radius else -1.0,
+             int(max_nn), _vp(d_fpfh), _vp(d_spfh) if d_spfh else None)
+
+
+def match_features_device(d_source_features, ns, d_target_features, nt, d_nn, d_d2=None, ctx=None):
+    """r3d_match_features_dev: match_features on [n][33] rows in HBM into d_nn (int32 [ns]) / d_d2 (float64 [ns]); enqueued only"""
+    ctx = ctx or _lib.default_context()
+    ctx.call("r3d_match_features_dev", _vp(d_source_features), int(ns), _vp(d_target_features), int(nt), FPFH_DIM, _vp(d_nn),
+             _vp(d_d2) if d_d2 else None)
+
+
+def debug_fpfh_stages(d_points, d_normals, n, radius, d_fpfh, max_nn=100, ctx=None):
+    """r3d_debug_fpfh_stages: dict of device ms: k_knn_graph at the same (n, k, radius), and the two FPFH stages"""
+    ctx = ctx or _lib.default_context()
+    ms = (ctypes.c_float * 3)()
+    ctx.call("r3d_debug_fpfh_stages", _vp(d_points), _vp(d_normals), int(n), float(radius) if radius else -1.0, int(max_nn), _vp(d_fpfh), ms)
+    return dict(search_ms=ms[0], spfh_ms=ms[1], fpfh_ms=ms[2])
 
 
 def transform_points_device(d_points, n, T, d_out, rotate_only=False, ctx=None):

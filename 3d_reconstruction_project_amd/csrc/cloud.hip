@@ -1207,6 +1207,200 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_color_gradient(GridView g, int64_
     rec[o * 4] = it; rec[o * 4 + 1] = grad[0]; rec[o * 4 + 2] = grad[1]; rec[o * 4 + 3] = grad[2];
 }
 
+// ------------------------------------------------------------------------------------------------ FPFH
+// Open3D pipelines/registration/Feature.cpp [recalled]; the contract is restated in DESIGN.md section 4 ("FPFH") and, executable,
+// in tests/fpfh_ref.py.  All arithmetic is float64 in the order written there (the build has -ffp-contract=off); only acos and
+// atan2 come from the device's libm, and where their last bit could decide a bin or the role swap the restatement says so.
+constexpr int FPFH_DIM = 33;
+constexpr double FPFH_PI = 3.14159265358979323846;
+
+// the search's lists of one thread, LDS columns -> global [slot][n] columns (coalesced over the wave) for k_fpfh
+__device__ __forceinline__ void fpfh_store_lists(const double *sd, const int *si, int t, int64_t i, int64_t n, int cnt, int *__restrict__ l_cnt,
+                                                 int *__restrict__ l_idx, double *__restrict__ l_d2) {
+    l_cnt[i] = cnt;
+    for (int j = 1; j < cnt; j++) {
+        l_idx[(int64_t)(j - 1) * n + i] = si[j * KNN_BLOCK + t];      // slot 0 (the point itself) is not stored
+        l_d2[(int64_t)(j - 1) * n + i] = sd[j * KNN_BLOCK + t];
+    }
+}
+
+// pair feature of (p1, n1) and (p2, n2): f[0] = atan2 angle, f[1] = v . n2', f[2] = +-cos of the better-aligned normal
+__device__ __forceinline__ void fpfh_pair(double p1x, double p1y, double p1z, double n1x, double n1y, double n1z, double p2x, double p2y, double p2z,
+                                          double n2x, double n2y, double n2z, double f[3]) {
+    f[0] = f[1] = f[2] = 0.0;
+    double dx = p2x - p1x, dy = p2y - p1y, dz = p2z - p1z;
+    const double f3 = sqrt((dx * dx + dy * dy) + dz * dz);
+    if (f3 == 0.0) return;
+    const double a1 = ((n1x * dx + n1y * dy) + n1z * dz) / f3, a2 = ((n2x * dx + n2y * dy) + n2z * dz) / f3;
+    const bool swap = acos(fabs(a1)) > acos(fabs(a2));
+    const double ax = swap ? n2x : n1x, ay = swap ? n2y : n1y, az = swap ? n2z : n1z;    // n1'
+    const double bx = swap ? n1x : n2x, by = swap ? n1y : n2y, bz = swap ? n1z : n2z;    // n2'
+    if (swap) { dx = -dx; dy = -dy; dz = -dz; }
+    double vx = dy * az - dz * ay, vy = dz * ax - dx * az, vz = dx * ay - dy * ax;       // dp x n1'
+    const double vn = sqrt((vx * vx + vy * vy) + vz * vz);
+    if (vn == 0.0) return;
+    vx /= vn; vy /= vn; vz /= vn;
+    const double wx = ay * vz - az * vy, wy = az * vx - ax * vz, wz = ax * vy - ay * vx; // n1' x v
+    f[2] = swap ? -a2 : a1;
+    f[1] = (vx * bx + vy * by) + vz * bz;
+    f[0] = atan2((wx * bx + wy * by) + wz * bz, (ax * bx + ay * by) + az * bz);
+}
+__device__ __forceinline__ int fpfh_bin(double c) {   // floor, clamped to the group's 11 bins (NaN -> 0, as a failed int conversion clamps)
+    const double fl = floor(c);
+    return fl >= 10.0 ? 10 : (fl >= 1.0 ? (int)fl : 0);
+}
+
+// k_spfh: one thread per (cell-sorted) point: the hybrid search of k_normals, the lists stored for k_fpfh, then the simplified
+// histogram.  Every increment of one point is the same h = 100 / (nn - 1), so the 33 bins are COUNTED (<= 127 each) in 8-bit
+// fields of nine registers -- three per group of 11 bins, selected with static indices -- and multiplied by h at the end; a
+// dynamically indexed double[33] would live in scratch.  Rows go out in cell-sorted order (spfh_s, what k_fpfh gathers from:
+// neighbours are near each other there) and, if asked for, in the caller's numbering.
+__global__ void __launch_bounds__(KNN_BLOCK) k_spfh(GridView g, int64_t n, int k, double radius, const double *__restrict__ nrm_s /* cell-sorted */,
+                                                    int *__restrict__ l_cnt, int *__restrict__ l_idx, double *__restrict__ l_d2,
+                                                    double *__restrict__ spfh_s, double *__restrict__ spfh_o /* caller's numbering, or null */) {
+    extern __shared__ double lds_d[];
+    double *sd = lds_d;
+    int *si = (int *)(lds_d + (size_t)k * KNN_BLOCK);
+    int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int t = threadIdx.x;
+    const double qx = g.pts[i * 3], qy = g.pts[i * 3 + 1], qz = g.pts[i * 3 + 2];
+    const int cnt = knn_query(g, qx, qy, qz, k, radius, sd, si);
+    fpfh_store_lists(sd, si, t, i, n, cnt, l_cnt, l_idx, l_d2);
+    const double nx = nrm_s[i * 3], ny = nrm_s[i * 3 + 1], nz = nrm_s[i * 3 + 2];
+    unsigned c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j0 = 1; j0 < cnt; j0 += 2) {       // two neighbours per round trip
+        double P[2][3], N[2][3];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int64_t s = si[min(j0 + u, cnt - 1) * KNN_BLOCK + t];
+#pragma unroll
+            for (int a = 0; a < 3; a++) { P[u][a] = g.pts[s * 3 + a]; N[u][a] = nrm_s[s * 3 + a]; }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            if (j0 + u >= cnt) break;
+            double f[3];
+            fpfh_pair(qx, qy, qz, nx, ny, nz, P[u][0], P[u][1], P[u][2], N[u][0], N[u][1], N[u][2], f);
+            const int b[3] = {fpfh_bin(11.0 * (f[0] + FPFH_PI) / (2.0 * FPFH_PI)), fpfh_bin(11.0 * (f[1] + 1.0) * 0.5),
+                              fpfh_bin(11.0 * (f[2] + 1.0) * 0.5)};
+#pragma unroll
+            for (int gq = 0; gq < 3; gq++) {
+                const unsigned one = 1u << ((b[gq] & 3) * 8);
+                const int w = b[gq] >> 2;
+#pragma unroll
+                for (int q = 0; q < 3; q++) c[gq * 3 + q] += w == q ? one : 0u;
+            }
+        }
+    }
+    const double h = cnt > 1 ? 100.0 / (double)(cnt - 1) : 0.0;
+    const int64_t o = g.idx[i];
+#pragma unroll
+    for (int j = 0; j < FPFH_DIM; j++) {
+        const int gq = j / 11, b = j % 11;
+        const double v = (double)((c[gq * 3 + (b >> 2)] >> ((b & 3) * 8)) & 255u) * h;
+        spfh_s[i * FPFH_DIM + j] = v;
+        if (spfh_o) spfh_o[o * FPFH_DIM + j] = v;
+    }
+}
+
+// the search and the stored lists alone (r3d_fpfh_from_spfh: the second stage on a caller-supplied SPFH)
+__global__ void __launch_bounds__(KNN_BLOCK) k_fpfh_lists(GridView g, int64_t n, int k, double radius, int *__restrict__ l_cnt, int *__restrict__ l_idx,
+                                                          double *__restrict__ l_d2) {
+    extern __shared__ double lds_d[];
+    double *sd = lds_d;
+    int *si = (int *)(lds_d + (size_t)k * KNN_BLOCK);
+    int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int cnt = knn_query(g, g.pts[i * 3], g.pts[i * 3 + 1], g.pts[i * 3 + 2], k, radius, sd, si);
+    fpfh_store_lists(sd, si, threadIdx.x, i, n, cnt, l_cnt, l_idx, l_d2);
+}
+
+// rows of 33 doubles from the caller's numbering into cell-sorted order
+__global__ void __launch_bounds__(256) k_gather_rows33(const double *__restrict__ src, const int *__restrict__ idx, int64_t n, double *__restrict__ dst) {
+    int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * FPFH_DIM) return;
+    const int64_t i = e / FPFH_DIM;
+    dst[e] = src[(int64_t)idx[i] * FPFH_DIM + (e - i * FPFH_DIM)];
+}
+
+// k_fpfh: one thread per (cell-sorted) point: the SPFH rows of its neighbours (list order, the point itself and coincident
+// points skipped) weighted by 1 / d2, each group of 11 scaled to 100, plus the point's own row.  33 + 3 accumulators with
+// static indices; the lists are k_spfh's ([slot][n]: a wave reads a slot of 64 consecutive points as one run).
+__global__ void __launch_bounds__(64) k_fpfh(int64_t n, const int *__restrict__ l_cnt, const int *__restrict__ l_idx, const double *__restrict__ l_d2,
+                                             const double *__restrict__ spfh_s, const int *__restrict__ idx, double *__restrict__ fpfh) {
+    int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int cnt = l_cnt[i];
+    double f[FPFH_DIM], sum[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < FPFH_DIM; j++) f[j] = 0.0;
+    for (int q = 1; q < cnt; q++) {
+        const double d2 = l_d2[(int64_t)(q - 1) * n + i];
+        const double *__restrict__ row = spfh_s + (int64_t)l_idx[(int64_t)(q - 1) * n + i] * FPFH_DIM;
+        if (d2 == 0.0) continue;
+#pragma unroll
+        for (int j = 0; j < FPFH_DIM; j++) {
+            const double val = row[j] / d2;
+            sum[j / 11] += val;
+            f[j] += val;
+        }
+    }
+#pragma unroll
+    for (int gq = 0; gq < 3; gq++) if (sum[gq] != 0.0) sum[gq] = 100.0 / sum[gq];
+    const double *__restrict__ own = spfh_s + i * FPFH_DIM;
+    double *__restrict__ out = fpfh + (int64_t)idx[i] * FPFH_DIM;
+#pragma unroll
+    for (int j = 0; j < FPFH_DIM; j++) out[j] = f[j] * sum[j / 11] + own[j];
+}
+
+// k_match_features: nearest target row of every source row under (sum_j (a_j - b_j)^2 in j order, target index), brute force in
+// float64.  One source row per thread in registers; the targets of this block's share (blockIdx.y of gridDim.y equal runs of
+// tiles) are staged MATCH_TILE rows at a time in LDS and read by every lane at the same address (a broadcast).  Strict < keeps
+// the smaller index inside a share; k_match_reduce folds the shares in ascending target order with the same rule.
+constexpr int MATCH_TILE = 128, MATCH_BLOCK = 256;
+__global__ void __launch_bounds__(MATCH_BLOCK) k_match_features(const double *__restrict__ src, int64_t ns, const double *__restrict__ tgt, int64_t nt,
+                                                               int64_t tiles_per_share, double *__restrict__ part_d2, int *__restrict__ part_idx) {
+    __shared__ double tile[MATCH_TILE * FPFH_DIM];
+    const int64_t i = (int64_t)blockIdx.x * MATCH_BLOCK + threadIdx.x;
+    const int64_t ic = i < ns ? i : ns - 1;     // a lane past the end works on the last row (it takes part in the staging) and writes nothing
+    double a[FPFH_DIM];
+#pragma unroll
+    for (int j = 0; j < FPFH_DIM; j++) a[j] = src[ic * FPFH_DIM + j];
+    double best = __builtin_huge_val();         // +inf: any finite distance beats it
+    int bi = -1;
+    const int64_t t0 = (int64_t)blockIdx.y * tiles_per_share * MATCH_TILE;
+    const int64_t t1 = t0 + tiles_per_share * MATCH_TILE < nt ? t0 + tiles_per_share * MATCH_TILE : nt;
+    for (int64_t tb = t0; tb < t1; tb += MATCH_TILE) {
+        const int rows = (int)(t1 - tb < MATCH_TILE ? t1 - tb : MATCH_TILE);
+        __syncthreads();
+        for (int e = threadIdx.x; e < rows * FPFH_DIM; e += MATCH_BLOCK) tile[e] = tgt[tb * FPFH_DIM + e];
+        __syncthreads();
+        for (int r = 0; r < rows; r++) {
+            const double *__restrict__ b = tile + r * FPFH_DIM;
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < FPFH_DIM; j++) { const double d = a[j] - b[j]; acc += d * d; }
+            if (acc < best) { best = acc; bi = (int)(tb + r); }
+        }
+    }
+    if (i < ns) { part_d2[(int64_t)blockIdx.y * ns + i] = best; part_idx[(int64_t)blockIdx.y * ns + i] = bi; }
+}
+__global__ void __launch_bounds__(256) k_match_reduce(const double *__restrict__ part_d2, const int *__restrict__ part_idx, int64_t ns, int shares,
+                                                      int *__restrict__ nn, double *__restrict__ d2) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ns) return;
+    double best = part_d2[i];
+    int bi = part_idx[i];
+    for (int s = 1; s < shares; s++) {
+        const double d = part_d2[(int64_t)s * ns + i];
+        const int q = part_idx[(int64_t)s * ns + i];
+        if (q >= 0 && (bi < 0 || d < best)) { best = d; bi = q; }
+    }
+    nn[i] = bi;
+    if (d2) d2[i] = best;
+}
+
 // nearest target point inside the 3x3x3 cell block around the query (shells 0 and 1), straight from global memory, as nine
 // contiguous runs.  All 18 run bounds are requested before any is used, and the candidates of a run are fetched four at a
 // time (clamped index, no branch around a load): the search is a chain of dependent gathers otherwise.
@@ -3354,6 +3548,62 @@ int color_gradients_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t 
     return R3D_OK;
 }
 
+// FPFH of a device cloud into the caller's device arrays d_fpfh / d_spfh_out ([n][33], the caller's numbering; d_spfh_out may be
+// null).  d_n == null: the second stage alone on d_spfh_in (the caller's numbering).  Nothing waits for the stream beyond the
+// grid's own bounding-box read.  The neighbour lists are STORED by the first stage (12 B x (k - 1) per point, written and read
+// once: 2.4 GB of traffic at 1 M points and k = 100) rather than searched a second time.
+// ev (optional, 3 events): recorded before the first stage, between the stages and after the second (tools/gpu_bench_fpfh.py).
+int fpfh_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, const double *d_n, const double *d_spfh_in, int64_t n, double radius, int max_nn,
+              double *d_fpfh, double *d_spfh_out, hipEvent_t *ev = nullptr) {
+    Grid G;
+    const int k = (int)std::min<int64_t>(max_nn, n);
+    int rc;
+    if ((rc = grid_build(ctx, ar, d_p, n, radius, std::max(2.0, k / 5.0), G))) return rc;
+    const size_t slots = (size_t)std::max(k - 1, 1);
+    int *l_cnt = (int *)ar.get((size_t)n * 4), *l_idx = (int *)ar.get(slots * n * 4);
+    double *l_d2 = (double *)ar.get(slots * n * 8), *spfh_s = (double *)ar.get((size_t)n * FPFH_DIM * 8);
+    double *nrm_s = d_n ? (double *)ar.get((size_t)n * 24) : nullptr;
+    if (ar.rc) return ar.rc;
+    const size_t lds = (size_t)k * KNN_BLOCK * 12;
+    const unsigned nbq = (unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK);
+    int *li = l_idx;
+    double *ld = l_d2;
+    if (ev) R3D_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+    if (d_n) {
+        k_gather3<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_n, G.v.idx, n, nrm_s);
+        R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_spfh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_spfh<<<nbq, KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, nrm_s, l_cnt, li, ld, spfh_s, d_spfh_out);
+    } else {
+        k_gather_rows33<<<(unsigned)((n * FPFH_DIM + 255) / 256), 256, 0, ctx->stream>>>(d_spfh_in, G.v.idx, n, spfh_s);
+        R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_fpfh_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_fpfh_lists<<<nbq, KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, l_cnt, li, ld);
+    }
+    R3D_HIP(ctx, hipGetLastError());
+    if (ev) R3D_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+    k_fpfh<<<nbq, 64, 0, ctx->stream>>>(n, l_cnt, li, ld, spfh_s, G.v.idx, d_fpfh);
+    R3D_HIP(ctx, hipGetLastError());
+    if (ev) R3D_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    return R3D_OK;
+}
+
+// brute-force matching costs ns * nt * 99 float64 operations: 39 ms per 10^10 pairs measured on the MI355X (profiles/fpfh.json), so
+// one call at this product runs for about a minute; beyond it the call is refused
+constexpr double MATCH_MAX_PAIRS = 1.5e13;
+int match_core(r3d_ctx *ctx, DevArena &ar, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt, int *d_nn, double *d_d2) {
+    // the targets are cut into shares so that a small source set still fills the chip (about 2048 workgroups)
+    const int64_t tiles = (nt + MATCH_TILE - 1) / MATCH_TILE, nbs = (ns + MATCH_BLOCK - 1) / MATCH_BLOCK;
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(tiles, 2048 / nbs), 65535));
+    const int64_t per = (tiles + want - 1) / want;
+    const int shares = (int)((tiles + per - 1) / per);
+    double *p_d2 = (double *)ar.get((size_t)shares * ns * 8);
+    int *p_idx = (int *)ar.get((size_t)shares * ns * 4);
+    if (ar.rc) return ar.rc;
+    k_match_features<<<dim3((unsigned)nbs, (unsigned)shares), MATCH_BLOCK, 0, ctx->stream>>>(d_src, ns, d_tgt, nt, per, p_d2, p_idx);
+    k_match_reduce<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(p_d2, p_idx, ns, shares, d_nn, d_d2);
+    R3D_HIP(ctx, hipGetLastError());
+    return R3D_OK;
+}
+
 // r3d_debug_icp_correspondences' output (host arrays, the caller's numbering)
 struct IcpReadout { int32_t *corr; double *d2; };
 // the coloured mode's extra inputs (device colours of both clouds) and parameters, resolved by the entry point
@@ -4741,6 +4991,144 @@ int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const dou
     ci.d_sc = d_src_colors; ci.d_tc = d_tgt_colors;
     return icp_core(ctx, ar, &ip, const_cast<double *>(d_src), ns, nullptr, const_cast<double *>(d_tgt), nt, const_cast<double *>(d_tgt_normals),
                     init4x4, T4x4, stats, t_begin, nullptr, 0, nullptr, &ci);
+}
+
+// ---- FPFH features and feature-space nearest neighbours (Open3D compute_fpfh_feature / CorrespondencesFromFeatures' search)
+static int fpfh_check(r3d_ctx *ctx, const char *who, const void *xyz, const void *in2, const void *out, int64_t n, int32_t max_nn) {
+    if (!xyz || !in2 || !out || n <= 0 || max_nn < 1) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument (null array, n <= 0 or max_nn < 1)", who);
+    if (max_nn > 128) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: max_nn > 128 not supported", who);
+    return R3D_OK;
+}
+
+int r3d_compute_fpfh_dev(r3d_ctx *ctx, const double *d_xyz, const double *d_normals, int64_t n, double radius, int32_t max_nn, double *d_fpfh,
+                         double *d_spfh) {
+    R3D_ROCTX_RANGE("r3d_compute_fpfh_dev");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = fpfh_check(ctx, "compute_fpfh_dev", d_xyz, d_normals, d_fpfh, n, max_nn)) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return fpfh_core(ctx, ar, d_xyz, d_normals, nullptr, n, radius, max_nn, d_fpfh, d_spfh);
+}
+
+int r3d_compute_fpfh(r3d_ctx *ctx, const double *xyz, const double *normals, int64_t n, double radius, int32_t max_nn, double *fpfh, double *spfh) {
+    R3D_ROCTX_RANGE("r3d_compute_fpfh");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = fpfh_check(ctx, "compute_fpfh", xyz, normals, fpfh, n, max_nn))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_p, *d_n;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
+    if ((rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
+    double *d_f = (double *)ar.get((size_t)n * FPFH_DIM * 8), *d_s = spfh ? (double *)ar.get((size_t)n * FPFH_DIM * 8) : nullptr;
+    if (ar.rc) return ar.rc;
+    if ((rc = fpfh_core(ctx, ar, d_p, d_n, nullptr, n, radius, max_nn, d_f, d_s))) return rc;
+    R3D_HIP(ctx, hipMemcpyAsync(fpfh, d_f, (size_t)n * FPFH_DIM * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (spfh) R3D_HIP(ctx, hipMemcpyAsync(spfh, d_s, (size_t)n * FPFH_DIM * 8, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+int r3d_fpfh_from_spfh(r3d_ctx *ctx, const double *xyz, int64_t n, double radius, int32_t max_nn, const double *spfh_in, double *fpfh) {
+    R3D_ROCTX_RANGE("r3d_fpfh_from_spfh");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = fpfh_check(ctx, "fpfh_from_spfh", xyz, spfh_in, fpfh, n, max_nn))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_p, *d_s;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
+    if ((rc = upload(ctx, ar, spfh_in, n * FPFH_DIM, &d_s))) return rc;
+    double *d_f = (double *)ar.get((size_t)n * FPFH_DIM * 8);
+    if (ar.rc) return ar.rc;
+    if ((rc = fpfh_core(ctx, ar, d_p, nullptr, d_s, n, radius, max_nn, d_f, nullptr))) return rc;
+    R3D_HIP(ctx, hipMemcpyAsync(fpfh, d_f, (size_t)n * FPFH_DIM * 8, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+static int match_check(r3d_ctx *ctx, const char *who, const void *src, int64_t ns, const void *tgt, int64_t nt, int32_t dim, const void *nn_out) {
+    if (!src || !tgt || !nn_out || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument", who);
+    if (dim != FPFH_DIM) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: dim = %d not supported (FPFH rows have 33 entries)", who, dim);
+    if (ns > 0x7fffffff || nt > 0x7fffffff || (double)ns * (double)nt > MATCH_MAX_PAIRS)
+        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: %lld x %lld rows is more than the brute-force search takes on (ns * nt <= %.0e)", who,
+                        (long long)ns, (long long)nt, MATCH_MAX_PAIRS);
+    return R3D_OK;
+}
+
+int r3d_match_features_dev(r3d_ctx *ctx, const double *d_src_feat, int64_t ns, const double *d_tgt_feat, int64_t nt, int32_t dim, int32_t *d_nn_out,
+                           double *d_d2_out) {
+    R3D_ROCTX_RANGE("r3d_match_features_dev");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = match_check(ctx, "match_features_dev", d_src_feat, ns, d_tgt_feat, nt, dim, d_nn_out)) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return match_core(ctx, ar, d_src_feat, ns, d_tgt_feat, nt, d_nn_out, d_d2_out);
+}
+
+int r3d_match_features(r3d_ctx *ctx, const double *src_feat, int64_t ns, const double *tgt_feat, int64_t nt, int32_t dim, int32_t *nn_out,
+                       double *d2_out) {
+    R3D_ROCTX_RANGE("r3d_match_features");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = match_check(ctx, "match_features", src_feat, ns, tgt_feat, nt, dim, nn_out))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t;
+    if ((rc = upload(ctx, ar, src_feat, ns * FPFH_DIM, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt_feat, nt * FPFH_DIM, &d_t))) return rc;
+    int *d_nn = (int *)ar.get((size_t)ns * 4);
+    double *d_d2 = d2_out ? (double *)ar.get((size_t)ns * 8) : nullptr;
+    if (ar.rc) return ar.rc;
+    if ((rc = match_core(ctx, ar, d_s, ns, d_t, nt, d_nn, d_d2))) return rc;
+    R3D_HIP(ctx, hipMemcpyAsync(nn_out, d_nn, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (d2_out) R3D_HIP(ctx, hipMemcpyAsync(d2_out, d_d2, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+// diagnostic (tools/gpu_bench_fpfh.py): the stages of r3d_compute_fpfh_dev timed with events in one call, next to k_knn_graph at
+// the same (n, k, radius) on the same grid -- the search both feature stages share.  ms[0] k_knn_graph, ms[1] k_spfh (with the
+// gather of the normals), ms[2] k_fpfh.  Synchronises.
+int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_normals, int64_t n, double radius, int32_t max_nn, double *d_fpfh,
+                          float *ms3) {
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if (!ms3) return r3d_fail(ctx, R3D_E_BADARG, "debug_fpfh_stages: bad argument");
+    if ((rc = fpfh_check(ctx, "debug_fpfh_stages", d_xyz, d_normals, d_fpfh, n, max_nn))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    hipEvent_t ev[5] = {};
+    for (auto &e : ev) R3D_HIP(ctx, hipEventCreate(&e));
+    {
+        DevArena ar(ctx);
+        rc = fpfh_core(ctx, ar, d_xyz, d_normals, nullptr, n, radius, max_nn, d_fpfh, nullptr, ev);
+    }
+    if (!rc) {
+        DevArena ar(ctx);
+        Grid G;
+        const int k = (int)std::min<int64_t>(max_nn, n);
+        if (!(rc = grid_build(ctx, ar, d_xyz, n, radius, std::max(2.0, k / 5.0), G))) {
+            int *d_nb = (int *)ar.get((size_t)n * k * 4);
+            double *d_d2 = (double *)ar.get((size_t)n * k * 8);
+            if (!(rc = ar.rc)) {
+                const size_t lds = (size_t)k * KNN_BLOCK * 12;
+                (void)hipFuncSetAttribute((const void *)k_knn_graph, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipEventRecord(ev[3], ctx->stream);
+                k_knn_graph<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, d_nb, d_d2);
+                (void)hipEventRecord(ev[4], ctx->stream);
+            }
+        }
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (!rc && e == hipSuccess) {
+        (void)hipEventElapsedTime(&ms3[0], ev[3], ev[4]);
+        (void)hipEventElapsedTime(&ms3[1], ev[0], ev[1]);
+        (void)hipEventElapsedTime(&ms3[2], ev[1], ev[2]);
+    }
+    for (auto &x : ev) (void)hipEventDestroy(x);
+    if (rc) return rc;
+    if (e != hipSuccess) return r3d_fail(ctx, R3D_E_HIP, "debug_fpfh_stages: %s", hipGetErrorString(e));
+    return R3D_OK;
 }
 
 int r3d_transform_points_dev(r3d_ctx *ctx, const double *d_xyz, int64_t n, const double *T4x4, int32_t rotate_only, double *d_out) {

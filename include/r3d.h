@@ -310,6 +310,32 @@ int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const dou
                         const double *d_tgt, const double *d_tgt_normals, const double *d_tgt_colors, int64_t nt, const double *init4x4,
                         double *T4x4, r3d_icp_stats *stats);
 
+/* replaces: o3d.pipelines.registration.compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) (test/check_lama1.py:246-281,
+ *           mini1.py, check8.py) and the nearest-neighbour search of CorrespondencesFromFeatures   [recalled, Open3D 0.18 Feature.cpp;
+ *           DESIGN.md section 4 ("FPFH") restates the contract, tests/fpfh_ref.py executes it].
+ * Feature rows are [n][33] float64: the memory of Open3D's 33 x N column-major Feature.data.  The neighbourhood of a point is
+ * r3d_knn_graph(k = max_nn, radius)'s (the point itself first; radius <= 0: plain kNN).  spfh (optional) receives the first
+ * stage's simplified histograms.  R3D_E_BADARG: a missing array (the normals included), n <= 0, max_nn < 1.
+ * R3D_E_UNSUPPORTED: max_nn > 128.  The _dev form takes DEVICE arrays and enqueues on the ctx stream: it returns without waiting
+ * for the result (the search grid's bounding box is the one value read back on the way). */
+int r3d_compute_fpfh(r3d_ctx *ctx, const double *xyz, const double *normals, int64_t n, double radius, int32_t max_nn, double *fpfh,
+                     double *spfh);
+int r3d_compute_fpfh_dev(r3d_ctx *ctx, const double *d_xyz, const double *d_normals, int64_t n, double radius, int32_t max_nn,
+                         double *d_fpfh, double *d_spfh);
+/* stage parity: the second stage alone on a caller-supplied SPFH ([n][33]) */
+int r3d_fpfh_from_spfh(r3d_ctx *ctx, const double *xyz, int64_t n, double radius, int32_t max_nn, const double *spfh_in, double *fpfh);
+/* nn_out[i] = the target row with the smallest sum_j (src[i][j] - tgt[.][j])^2 (float64, summed in j order; the smaller index wins
+ * ties), d2_out[i] (optional) that sum.  Brute force.  R3D_E_UNSUPPORTED: dim != 33, or ns * nt > 1.5e13 (more than a minute of work).
+ * The mutual filter of CorrespondencesFromFeatures is host code (cloud_ops.correspondences_from_features).  _dev: device arrays,
+ * enqueued on the ctx stream, no synchronisation. */
+int r3d_match_features(r3d_ctx *ctx, const double *src_feat, int64_t ns, const double *tgt_feat, int64_t nt, int32_t dim,
+                       int32_t *nn_out, double *d2_out);
+int r3d_match_features_dev(r3d_ctx *ctx, const double *d_src_feat, int64_t ns, const double *d_tgt_feat, int64_t nt, int32_t dim,
+                           int32_t *d_nn_out, double *d_d2_out);
+/* diagnostic: ms3[0] k_knn_graph at the same (n, k, radius), ms3[1] / ms3[2] the two stages of r3d_compute_fpfh_dev (events) */
+int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_normals, int64_t n, double radius, int32_t max_nn,
+                          double *d_fpfh, float *ms3);
+
 /* replaces: the whole body of PointCloudAlignment.align_point_clouds (pointcloud_alignment.py:6-43; caller main.py:48) in ONE
  * call, device-resident between the stages: voxel_down_sample(voxel_size) of both clouds (:22-23) ->
  * estimate_normals(KDTreeSearchParamHybrid(normal_radius, normal_max_nn)) on both (:27-28) -> registration (:35-39) ->
