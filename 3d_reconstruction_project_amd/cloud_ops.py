@@ -52,6 +52,30 @@ _lib.register({
     "r3d_debug_fpfh_stages": ([_vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, _vp, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
 })
 
+
+class RansacParams(ctypes.Structure):
+    """r3d_ransac_params"""
+    _fields_ = [("max_correspondence_distance", ctypes.c_double), ("edge_length_similarity", ctypes.c_double),
+                ("checker_distance", ctypes.c_double), ("confidence", ctypes.c_double), ("max_iteration", ctypes.c_int64),
+                ("seed", ctypes.c_uint64), ("ransac_n", ctypes.c_int32), ("batch", ctypes.c_int32)]
+
+
+class RansacStats(ctypes.Structure):
+    """r3d_ransac_stats"""
+    _fields_ = [("fitness", ctypes.c_double), ("inlier_rmse", ctypes.c_double), ("iterations", ctypes.c_int64),
+                ("validated", ctypes.c_int64), ("best_hypothesis", ctypes.c_int64), ("inliers", ctypes.c_int64),
+                ("setup_ms", ctypes.c_double), ("loop_ms", ctypes.c_double)]
+
+
+_ransac_sig = ([_vp, ctypes.POINTER(RansacParams), _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp,
+                ctypes.POINTER(RansacStats)], ctypes.c_int)
+_lib.register({
+    "r3d_ransac_correspondence": _ransac_sig,
+    "r3d_ransac_correspondence_dev": _ransac_sig,
+    "r3d_debug_ransac_hypotheses": ([_vp, ctypes.POINTER(RansacParams), _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64,
+                                     ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+})
+
 _lib.register({
     "r3d_debug_sort_by_cell": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
     "r3d_debug_exclusive_scan": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp], ctypes.c_int),
@@ -416,6 +440,70 @@ def correspondences_from_features(source_features, target_features, mutual_filte
     return corres if len(mutual) < mutual_consistent_ratio * ns else mutual
 
 
+def _ransac_params(max_correspondence_distance, ransac_n, edge_length, checker_distance, max_iteration, confidence, seed, batch):
+    """edge_length None: no edge-length checker; checker_distance None: max_correspondence_distance (the scripts' usage), 0: none"""
+    cd = max_correspondence_distance if checker_distance is None else checker_distance
+    return RansacParams(float(max_correspondence_distance), float(edge_length or 0.0), float(cd or 0.0), float(confidence),
+                        int(max_iteration), int(seed) & 0xFFFFFFFFFFFFFFFF, int(ransac_n), int(batch))
+
+
+def _corres_rows(corres):
+    c = np.ascontiguousarray(corres, dtype=np.int32)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise _lib.R3DError(-1, f"correspondences must be an [M, 2] array, got {c.shape}")
+    return c
+
+
+def _ransac_dict(T, st, **extra):
+    return dict(T=T, fitness=st.fitness, inlier_rmse=st.inlier_rmse, iterations=st.iterations, validated=st.validated,
+                best_hypothesis=st.best_hypothesis, inliers=st.inliers, setup_ms=st.setup_ms, loop_ms=st.loop_ms, **extra)
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, ransac_n=3, edge_length=0.9,
+                                                checker_distance=None, max_iteration=100000, confidence=0.999, seed=0, batch=0, ctx=None):
+    """o3d.pipelines.registration.registration_ransac_based_on_correspondence with TransformationEstimationPointToPoint(False),
+    CorrespondenceCheckerBasedOnEdgeLength(edge_length), CorrespondenceCheckerBasedOnDistance(checker_distance) and
+    RANSACConvergenceCriteria(max_iteration, confidence), as a pure function of (inputs, seed): DESIGN.md section 4 ("RANSAC").
+    edge_length None: no edge checker.  checker_distance None: max_correspondence_distance; 0: no distance checker.
+    Returns dict(T, fitness, inlier_rmse, correspondence_set [K, 2] int32, iterations, validated, best_hypothesis, inliers,
+    setup_ms, loop_ms); nothing survived: T = identity, fitness 0, best_hypothesis -1."""
+    ctx = ctx or _lib.default_context()
+    s, t, c = _c(source), _c(target), _corres_rows(corres)
+    prm = _ransac_params(max_correspondence_distance, ransac_n, edge_length, checker_distance, max_iteration, confidence, seed, batch)
+    T, st = np.empty((4, 4)), RansacStats()
+    mask = np.zeros(len(c), np.uint8)
+    ctx.call("r3d_ransac_correspondence", ctypes.byref(prm), _ptr(s), len(s), _ptr(t), len(t), c.ctypes.data_as(_vp), len(c), _ptr(T),
+             mask.ctypes.data_as(_vp), ctypes.byref(st))
+    return _ransac_dict(T, st, correspondence_set=c[mask != 0])
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_features, target_features, mutual_filter,
+                                                  max_correspondence_distance, ransac_n=3, edge_length=0.9, checker_distance=None,
+                                                  max_iteration=100000, confidence=0.999, seed=0, batch=0, mutual_consistent_ratio=0.1,
+                                                  ctx=None):
+    """o3d's function of that name: correspondences_from_features(source_features, target_features, mutual_filter,
+    mutual_consistent_ratio) followed by registration_ransac_based_on_correspondence.  Features are (33, N) arrays."""
+    corres = correspondences_from_features(source_features, target_features, mutual_filter, mutual_consistent_ratio, ctx)
+    return registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, ransac_n, edge_length,
+                                                       checker_distance, max_iteration, confidence, seed, batch, ctx)
+
+
+def debug_ransac_hypotheses(source, target, corres, h0, count, max_correspondence_distance, ransac_n=3, edge_length=0.9,
+                            checker_distance=None, seed=0, ctx=None):
+    """r3d_debug_ransac_hypotheses: hypotheses h0 .. h0 + count - 1 without the best / stop rule: dict(samples [count, 4] int32
+    (-1 where unused), flags (bit 0 edge checker passed, bit 1 distance checker passed), T [count, 3, 4] (zeros where bit 0 is 0),
+    inliers, err2 (0 unless both bits are set))."""
+    ctx = ctx or _lib.default_context()
+    s, t, c = _c(source), _c(target), _corres_rows(corres)
+    prm = _ransac_params(max_correspondence_distance, ransac_n, edge_length, checker_distance, 1, 0.999, seed, 0)
+    n = max(int(count), 0)
+    samples, flags, inl = np.empty((n, 4), np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+    T, err2 = np.empty((n, 3, 4)), np.empty(n)
+    ctx.call("r3d_debug_ransac_hypotheses", ctypes.byref(prm), _ptr(s), len(s), _ptr(t), len(t), c.ctypes.data_as(_vp), len(c), int(h0),
+             int(count), samples.ctypes.data_as(_vp), flags.ctypes.data_as(_vp), _ptr(T), inl.ctypes.data_as(_vp), _ptr(err2))
+    return dict(samples=samples, flags=flags, T=T, inliers=inl, err2=err2)
+
+
 def _colored_params(max_correspondence_distance, lambda_geometric, max_iteration, relative_fitness, relative_rmse, gradient_radius,
                     gradient_max_nn):
     return _lib.ColoredIcpParams(_lib.IcpParams(COLORED, int(max_iteration), float(max_correspondence_distance), float(relative_fitness),
@@ -659,6 +747,53 @@ def debug_fpfh_stages(d_points, d_normals, n, radius, d_fpfh, max_nn=100, ctx=No
     ms = (ctypes.c_float * 3)()
     ctx.call("r3d_debug_fpfh_stages", _vp(d_points), _vp(d_normals), int(n), float(radius) if radius else -1.0, int(max_nn), _vp(d_fpfh), ms)
     return dict(search_ms=ms[0], spfh_ms=ms[1], fpfh_ms=ms[2])
+
+
+def registration_ransac_based_on_correspondence_device(d_source, ns, d_target, nt, d_corres, m, max_correspondence_distance, ransac_n=3,
+                                                       edge_length=0.9, checker_distance=None, max_iteration=100000, confidence=0.999,
+                                                       seed=0, batch=0, d_inlier_mask=None, ctx=None):
+    """r3d_ransac_correspondence_dev: clouds ([n][3] float64) and pairs ([m][2] int32) already in HBM (device pointers as int).
+    Returns when the loop has finished.  d_inlier_mask (optional, uint8 [m] on the device) receives the winner's mask; the dict
+    has no correspondence_set."""
+    ctx = ctx or _lib.default_context()
+    prm = _ransac_params(max_correspondence_distance, ransac_n, edge_length, checker_distance, max_iteration, confidence, seed, batch)
+    T, st = np.empty((4, 4)), RansacStats()
+    ctx.call("r3d_ransac_correspondence_dev", ctypes.byref(prm), _vp(d_source), int(ns), _vp(d_target), int(nt), _vp(d_corres), int(m), _ptr(T),
+             _vp(d_inlier_mask) if d_inlier_mask else None, ctypes.byref(st))
+    return _ransac_dict(T, st)
+
+
+def registration_ransac_based_on_feature_matching_device(d_source, ns, d_target, nt, d_source_features, d_target_features, mutual_filter,
+                                                         max_correspondence_distance, mutual_consistent_ratio=0.1, ctx=None, **kw):
+    """The feature-matching form on device arrays ([n][33] float64 feature rows): both searches through r3d_match_features_dev, the
+    mutual filter on the host (two int32 [n] read-backs), the estimator through r3d_ransac_correspondence_dev.  Returns the dict of
+    the device form plus correspondence_set."""
+    ctx = ctx or _lib.default_context()
+    d_nn = ctx.alloc(4 * max(ns, nt))
+    try:
+        nn_st, nn_ts = np.empty(ns, np.int32), np.empty(nt, np.int32)
+        match_features_device(d_source_features, ns, d_target_features, nt, d_nn, None, ctx)
+        ctx.d2h(nn_st, d_nn)
+        corres = np.stack([np.arange(ns, dtype=np.int32), nn_st], 1)
+        if mutual_filter and ns:
+            match_features_device(d_target_features, nt, d_source_features, ns, d_nn, None, ctx)
+            ctx.d2h(nn_ts, d_nn)
+            mutual = corres[nn_ts[nn_st] == np.arange(ns)]
+            corres = corres if len(mutual) < mutual_consistent_ratio * ns else mutual
+    finally:
+        ctx.free(d_nn)
+    corres = np.ascontiguousarray(corres)
+    d_c, d_m = ctx.to_device(corres), ctx.alloc(max(len(corres), 1))
+    try:
+        res = registration_ransac_based_on_correspondence_device(d_source, ns, d_target, nt, d_c, len(corres), max_correspondence_distance,
+                                                                 d_inlier_mask=d_m, ctx=ctx, **kw)
+        mask = np.empty(len(corres), np.uint8)
+        ctx.d2h(mask, d_m)
+    finally:
+        ctx.free(d_c)
+        ctx.free(d_m)
+    res["correspondence_set"] = corres[mask != 0]
+    return res
 
 
 def transform_points_device(d_points, n, T, d_out, rotate_only=False, ctx=None):

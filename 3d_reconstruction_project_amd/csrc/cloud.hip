@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <thread>
@@ -2727,10 +2728,11 @@ int cloud_bbox(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, doubl
 
 // exclusive scan of n ints / packed 64-bit counters on the ctx stream (k_scan_sums + k_scan_apply)
 template <class T, bool MAXOP = false>
-int dev_exclusive_scan(r3d_ctx *ctx, DevArena &ar, const T *in, T *out, int64_t n, int *lo_out = nullptr, int *hi_max = nullptr) {
+int dev_exclusive_scan(r3d_ctx *ctx, DevArena &ar, const T *in, T *out, int64_t n, int *lo_out = nullptr, int *hi_max = nullptr,
+                       T *part = nullptr /* room for one T per SCAN_TILE elements, if the caller keeps one; default: from the arena */) {
     if (n <= 0) return R3D_OK;
     const int tiles = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
-    T *part = (T *)ar.get((size_t)tiles * sizeof(T));
+    if (!part) part = (T *)ar.get((size_t)tiles * sizeof(T));
     if (ar.rc) return ar.rc;
     k_scan_sums<T, MAXOP><<<tiles, SCAN_T, 0, ctx->stream>>>(in, n, part);
     k_scan_apply<T, MAXOP><<<tiles, SCAN_T, 0, ctx->stream>>>(in, n, part, out, lo_out, hi_max);
@@ -3092,8 +3094,14 @@ __host__ __device__ double det3(const double M[3][3]) {
     return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
            M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
 }
-// Eigen::umeyama(src, dst, false) from the accumulated sums: returns U (4x4) mapping src -> dst
-__host__ __device__ void umeyama_from_sums(const double *s /*ICP slots*/, double U[16]) {
+// Eigen::umeyama(src, dst, false) from the accumulated sums: returns U (4x4) mapping src -> dst.
+// rank_tol: a singular value counts when it is above rank_tol x the largest.  They are roots of the eigenvalues of sigma^T sigma,
+// whose rounding noise is ~1e-16 of the largest eigenvalue, i.e. up to ~5e-8 of the largest SINGULAR value: under the
+// registration loop's 1e-14 an exactly deficient covariance (three pairs always are: rank 2) is taken for full rank whenever that
+// noise comes out positive, and the left vector made from it is not orthogonal to the others.  The registration loop keeps its
+// value (its clouds are nowhere near deficient, and its results stay bit for bit); RANSAC, whose samples are deficient by
+// construction, passes RANSAC_RANK_TOL.
+__host__ __device__ void umeyama_from_sums(const double *s /*ICP slots*/, double U[16], double rank_tol = 1e-14) {
     const double n = s[0];
     const double ps[3] = {s[2] / n, s[3] / n, s[4] / n}, pt[3] = {s[5] / n, s[6] / n, s[7] / n};
     double sigma[3][3];  // (1/n) sum (t - mt)(p - mp)^T  = E[t p^T] - mt mp^T ; slots hold p_i t_j
@@ -3123,7 +3131,7 @@ __host__ __device__ void umeyama_from_sums(const double *s /*ICP slots*/, double
         double u[3] = {0, 0, 0};
         for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) u[r] += sigma[r][k] * Vs[k][c];
         double l = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        if (!(l > 1e-300 && sv[c] > 1e-14 * fmax(sv[0], 1e-300))) break;
+        if (!(l > 1e-300 && sv[c] > rank_tol * fmax(sv[0], 1e-300))) break;
         for (int r = 0; r < 3; r++) Us[r][c] = u[r] / l;
         rank = c + 1;
     }
@@ -3158,6 +3166,59 @@ __host__ __device__ void umeyama_from_sums(const double *s /*ICP slots*/, double
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) { R[i][j] = 0; for (int k = 0; k < 3; k++) R[i][j] += Us[i][k] * S[k] * Vs[j][k]; }
     for (int i = 0; i < 16; i++) U[i] = (i % 5 == 0);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) U[i * 4 + j] = R[i][j];
+        U[i * 4 + 3] = pt[i] - (R[i][0] * ps[0] + R[i][1] * ps[1] + R[i][2] * ps[2]);
+    }
+}
+
+// Newton steps on the rotation umeyama_from_sums returned, for RANSAC's 3-4 pair samples.  That routine goes through the eigenvectors
+// of sigma^T sigma, so its rotation is off by ~2e-17 (sigma_1 / sigma_2)^2: 2e-9 for a sample whose second singular value is 1e-4
+// of the first (measured against an SVD).  The least-squares rotation R makes R^T sigma symmetric; with A = R^T sigma, S its
+// symmetric part and R <- R exp([w]x), the first-order condition is (tr(S) I - S) w = vee(A - A^T), a 3x3 system whose smallest
+// eigenvalue is sigma_2 + sigma_3: conditioning linear in sigma_1 / sigma_2, and the step converges quadratically from a start that
+// close.  Skipped when that system is singular to 1e-8 (rank <= 1: the routine's defined answer stays) or the step is not small.
+__host__ __device__ void umeyama_polish(const double *s /*ICP slots*/, double U[16]) {
+    const double n = s[0];
+    const double ps[3] = {s[2] / n, s[3] / n, s[4] / n}, pt[3] = {s[5] / n, s[6] / n, s[7] / n};
+    double sg[3][3], R[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) { sg[i][j] = s[8 + j * 3 + i] / n - pt[i] * ps[j]; R[i][j] = U[i * 4 + j]; }
+    {   // the routine's third left vector comes from sigma v3 / |sigma v3|, which a tiny sigma_3 leaves ~1e-16 sigma_1^2 / (sigma_2 sigma_3) off
+        // the others' orthogonal complement (3e-11 seen): one Newton-Schulz step R <- R (3 I - R^T R) / 2 squares that away
+        double G[3][3], Rn[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) G[i][j] = 3.0 * (i == j) - ((R[0][i] * R[0][j] + R[1][i] * R[1][j]) + R[2][i] * R[2][j]);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) Rn[i][j] = 0.5 * ((R[i][0] * G[0][j] + R[i][1] * G[1][j]) + R[i][2] * G[2][j]);
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R[i][j] = Rn[i][j];
+    }
+    for (int it = 0; it < 2; it++) {
+        double A[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) A[i][j] = (R[0][i] * sg[0][j] + R[1][i] * sg[1][j]) + R[2][i] * sg[2][j];
+        const double a[3] = {A[2][1] - A[1][2], A[0][2] - A[2][0], A[1][0] - A[0][1]};
+        const double tr = A[0][0] + A[1][1] + A[2][2];
+        const double m00 = tr - A[0][0], m11 = tr - A[1][1], m22 = tr - A[2][2];
+        const double m01 = -0.5 * (A[0][1] + A[1][0]), m02 = -0.5 * (A[0][2] + A[2][0]), m12 = -0.5 * (A[1][2] + A[2][1]);
+        const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+        const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+        const double det = (m00 * c00 + m01 * c01) + m02 * c02;
+        if (!(tr > 0.0 && det > 1e-8 * tr * tr * tr)) break;
+        const double w[3] = {((c00 * a[0] + c01 * a[1]) + c02 * a[2]) / det, ((c01 * a[0] + c11 * a[1]) + c12 * a[2]) / det,
+                             ((c02 * a[0] + c12 * a[1]) + c22 * a[2]) / det};
+        const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+        if (!(th2 < 1e-6)) break;
+        const double f1 = 1.0 - th2 / 6.0, f2 = 0.5 - th2 / 24.0;       // sin(t) / t and (1 - cos(t)) / t^2 to below 1e-14 here
+        const double K[3][3] = {{0, -w[2], w[1]}, {w[2], 0, -w[0]}, {-w[1], w[0], 0}};
+        double E[3][3], Rn[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                E[i][j] = ((i == j) + f1 * K[i][j]) + f2 * ((K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j]);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) Rn[i][j] = (R[i][0] * E[0][j] + R[i][1] * E[1][j]) + R[i][2] * E[2][j];
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) R[i][j] = Rn[i][j];
+    }
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) U[i * 4 + j] = R[i][j];
         U[i * 4 + 3] = pt[i] - (R[i][0] * ps[0] + R[i][1] * ps[1] + R[i][2] * ps[2]);
@@ -3296,6 +3357,404 @@ int upload(r3d_ctx *ctx, DevArena &ar, const double *h, int64_t n3, double **d) 
     *d = (double *)ar.get((size_t)n3 * 8);
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemcpyAsync(*d, h, (size_t)n3 * 8, hipMemcpyHostToDevice, ctx->stream));
+    return R3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ RANSAC over correspondences
+// The contract is stated in DESIGN.md section 4 ("RANSAC") [recalled, Open3D 0.18 Registration.cpp / CorrespondenceChecker.cpp]
+// and executed in tests/ransac_ref.py: a counter-based sampler, the edge-length checker before the transform, Eigen::umeyama
+// through umeyama_from_sums, the distance checker, a score over all M pairs whose summation order depends on M alone, and the
+// best / stop rule applied in hypothesis order on the host.
+constexpr int RANSAC_TILE = 256;            // pairs per LDS tile of k_ransac_score (12 KB)
+constexpr int RANSAC_RUN = 1024;            // pairs per summation run: err2 is summed inside a run, the runs are folded in ascending order
+constexpr int RANSAC_BLOCK = 256;
+constexpr double RANSAC_RANK_TOL = 1e-6;     // umeyama_from_sums' rank test for 3-4 pair samples (see there); the tests' ill-conditioned line
+constexpr int RANSAC_MAX_BATCH = 262144, RANSAC_DEFAULT_BATCH = 65536;
+constexpr int RANSAC_PIN_SURV = 2048;       // survivors whose results fit the pinned read-back; beyond: a plain copy
+constexpr size_t RANSAC_PART_ELEMS = (size_t)16 << 20;   // per-run partials kept at most (runs x survivors); beyond: one share
+
+struct RansacDev {
+    unsigned long long seed;
+    long long h0;
+    int count, n;
+    double sim, cd2, max2;                  // edge-length similarity (<= 0: off), checker distance squared (<= 0: off), inlier distance squared
+};
+struct RansacT { double m[12]; };
+
+__host__ __device__ inline int ransac_sample(unsigned long long seed, long long h, int j, long long M) {
+    unsigned long long x = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(8 * h + j + 1);
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return (int)(((x >> 32) * (unsigned long long)M) >> 32);
+}
+
+// |T s - t|^2 with fused multiply-adds, the one form every stage uses (the distance checker, the score and the winner's mask see
+// the same bits).  Inlier and checker tests compare this against the squared threshold: it differs from comparing the rooted
+// distance only within a few ulps of the threshold, far inside the 1e-8 band the tests treat as sensitive.
+__device__ __forceinline__ double ransac_d2(const double *__restrict__ T, double sx, double sy, double sz, double tx, double ty, double tz) {
+    const double dx = fma(T[0], sx, fma(T[1], sy, fma(T[2], sz, T[3]))) - tx;
+    const double dy = fma(T[4], sx, fma(T[5], sy, fma(T[6], sz, T[7]))) - ty;
+    const double dz = fma(T[8], sx, fma(T[9], sy, fma(T[10], sz, T[11]))) - tz;
+    return fma(dz, dz, fma(dy, dy, dx * dx));
+}
+
+// pairs[i] = (s, t) of correspondence i, so nothing downstream chases indices; an index outside its cloud is not followed: it
+// raises *bad and the row is zeros
+__global__ void __launch_bounds__(256) k_ransac_gather(const double *__restrict__ src, int64_t ns, const double *__restrict__ tgt, int64_t nt,
+                                                       const int *__restrict__ corres, int64_t M, double *__restrict__ pairs, int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const int a = corres[i * 2], b = corres[i * 2 + 1];
+    const bool ok = a >= 0 && a < ns && b >= 0 && b < nt;
+    if (!ok) *bad = 1;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        pairs[i * 6 + c] = ok ? src[(int64_t)a * 3 + c] : 0.0;
+        pairs[i * 6 + 3 + c] = ok ? tgt[(int64_t)b * 3 + c] : 0.0;
+    }
+}
+
+// k_ransac_propose: one thread per hypothesis of the batch: sample, edge-length checker (a failing thread leaves here), the
+// Umeyama sums over the 3-4 pairs, the solve, the distance checker.  Every local array is indexed with constants after
+// unrolling (a dynamically indexed one would live in scratch, see umeyama_from_sums).  T is [12][cap]: entry e of slot i at
+// T[e * cap + i], coalesced here and in k_ransac_score.  flags: bit 0 edge ok, bit 1 distance ok; valid = both.
+__global__ void __launch_bounds__(RANSAC_BLOCK) k_ransac_propose(const double *__restrict__ pairs, int64_t M, RansacDev p, int cap,
+                                                                 int *__restrict__ samples /* [count][4] or null */, int *__restrict__ flags,
+                                                                 int *__restrict__ valid /* [count + 1] */, double *__restrict__ T) {
+    const int i = blockIdx.x * RANSAC_BLOCK + threadIdx.x;
+    if (i == 0) valid[p.count] = 0;         // the scan runs over count + 1 entries: its last output is the number of survivors
+    if (i >= p.count) return;
+    const long long h = p.h0 + i;
+    int c[4];
+    double P[4][6];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        c[j] = j < p.n ? ransac_sample(p.seed, h, j, M) : -1;
+        const int64_t row = c[j < p.n ? j : 0];
+#pragma unroll
+        for (int q = 0; q < 6; q++) P[j][q] = pairs[row * 6 + q];
+    }
+    if (samples) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) samples[(int64_t)i * 4 + j] = c[j];
+    }
+    bool edge = true;
+    if (p.sim > 0.0) {
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+#pragma unroll
+            for (int b = a + 1; b < 4; b++) {
+                if (b >= p.n) continue;
+                const double sx = P[a][0] - P[b][0], sy = P[a][1] - P[b][1], sz = P[a][2] - P[b][2];
+                const double tx = P[a][3] - P[b][3], ty = P[a][4] - P[b][4], tz = P[a][5] - P[b][5];
+                const double ds = sqrt((sx * sx + sy * sy) + sz * sz), dt = sqrt((tx * tx + ty * ty) + tz * tz);
+                if (!(ds >= p.sim * dt && dt >= p.sim * ds)) edge = false;
+            }
+    }
+    if (!edge) { flags[i] = 0; valid[i] = 0; return; }
+    double s[17];
+#pragma unroll
+    for (int q = 0; q < 17; q++) s[q] = 0.0;
+    s[0] = (double)p.n;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (j >= p.n) continue;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            s[2 + a] += P[j][a];
+            s[5 + a] += P[j][3 + a];
+#pragma unroll
+            for (int b = 0; b < 3; b++) s[8 + a * 3 + b] += P[j][a] * P[j][3 + b];
+        }
+    }
+    double U[16];
+    umeyama_from_sums(s, U, RANSAC_RANK_TOL);
+    umeyama_polish(s, U);
+    bool dist = true;
+    if (p.cd2 > 0.0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (j < p.n && ransac_d2(U, P[j][0], P[j][1], P[j][2], P[j][3], P[j][4], P[j][5]) > p.cd2) dist = false;
+    }
+#pragma unroll
+    for (int e = 0; e < 12; e++) T[(int64_t)e * cap + i] = U[e];
+    flags[i] = dist ? 3 : 1;
+    valid[i] = dist ? 1 : 0;
+}
+
+// survivors in h order: surv[rank] = batch slot (the ranks come from the exclusive scan of valid)
+__global__ void __launch_bounds__(256) k_ransac_compact(const int *__restrict__ valid, const int *__restrict__ scan, int count, int *__restrict__ surv) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count && valid[i]) surv[scan[i]] = i;
+}
+
+// k_ransac_score: one surviving hypothesis per thread, its 12 transform entries in registers; the pairs of this block's share
+// (blockIdx.y of gridDim.y equal groups of runs) are staged RANSAC_TILE at a time in LDS and read by every lane at one address
+// (a broadcast, the shape of k_match_features).  Inside a run the count and the squared distances of the inliers are summed in
+// pair order.  DIRECT (one share): the thread folds its runs in ascending order itself and writes the result; otherwise it
+// leaves (count, err2) per run in part_*[run * nsurv + k] and k_ransac_reduce folds them in the same order, so both give the
+// same bits whatever the grid.
+template <bool DIRECT>
+__global__ void __launch_bounds__(RANSAC_BLOCK) k_ransac_score(const double *__restrict__ pairs, int64_t M, const double *__restrict__ T, int cap,
+                                                               const int *__restrict__ surv, int nsurv, int runs_per_share, int nruns, double max2,
+                                                               int *__restrict__ out_cnt, double *__restrict__ out_err) {
+    __shared__ double tile[RANSAC_TILE * 6];
+    const int k = blockIdx.x * RANSAC_BLOCK + threadIdx.x;
+    const int slot = surv[k < nsurv ? k : nsurv - 1];   // a lane past the end works on the last survivor (it takes part in the staging) and writes nothing
+    double t[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) t[e] = T[(int64_t)e * cap + slot];
+    const int r0 = blockIdx.y * runs_per_share, r1 = min(nruns, r0 + runs_per_share);
+    int tot_c = 0;
+    double tot_e = 0.0;
+    for (int run = r0; run < r1; run++) {
+        const int64_t b0 = (int64_t)run * RANSAC_RUN, b1 = b0 + RANSAC_RUN < M ? b0 + RANSAC_RUN : M;
+        int cnt = 0;
+        double err = 0.0;
+        for (int64_t tb = b0; tb < b1; tb += RANSAC_TILE) {
+            const int rows = (int)(b1 - tb < RANSAC_TILE ? b1 - tb : RANSAC_TILE);
+            __syncthreads();
+            for (int e = threadIdx.x; e < rows * 6; e += RANSAC_BLOCK) tile[e] = pairs[tb * 6 + e];
+            __syncthreads();
+#pragma unroll 4
+            for (int r = 0; r < rows; r++) {
+                const double *__restrict__ q = tile + r * 6;
+                const double d2 = ransac_d2(t, q[0], q[1], q[2], q[3], q[4], q[5]);
+                const bool in = d2 < max2;
+                cnt += in ? 1 : 0;
+                err += in ? d2 : 0.0;       // adding +0 leaves the sum as it is: no branch, same bits
+            }
+        }
+        if (DIRECT) { tot_c += cnt; tot_e += err; }
+        else if (k < nsurv) { out_cnt[(int64_t)run * nsurv + k] = cnt; out_err[(int64_t)run * nsurv + k] = err; }
+    }
+    if (DIRECT && k < nsurv) { out_cnt[k] = tot_c; out_err[k] = tot_e; }
+}
+__global__ void __launch_bounds__(256) k_ransac_reduce(const int *__restrict__ part_cnt, const double *__restrict__ part_err, int nsurv, int nruns,
+                                                       int *__restrict__ cnt, double *__restrict__ err) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nsurv) return;
+    int c = 0;
+    double e = 0.0;
+    for (int run = 0; run < nruns; run++) { c += part_cnt[(int64_t)run * nsurv + k]; e += part_err[(int64_t)run * nsurv + k]; }
+    cnt[k] = c;
+    err[k] = e;
+}
+// the transform of one batch slot as 12 consecutive doubles (the host's read-back of a new best)
+__global__ void __launch_bounds__(64) k_ransac_fetch_T(const double *__restrict__ T, int cap, int slot, double *__restrict__ out12) {
+    if (threadIdx.x < 12) out12[threadIdx.x] = T[(int64_t)threadIdx.x * cap + slot];
+}
+// the winner's inlier mask, with the arithmetic of the score
+__global__ void __launch_bounds__(256) k_ransac_mask(const double *__restrict__ pairs, int64_t M, RansacT T, double max2, unsigned char *__restrict__ mask) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const double *__restrict__ q = pairs + i * 6;
+    mask[i] = ransac_d2(T.m, q[0], q[1], q[2], q[3], q[4], q[5]) < max2 ? 1 : 0;
+}
+
+// ---- RANSAC over correspondences: the host side
+struct RansacWork {
+    double *pairs = nullptr, *T = nullptr, *res_err = nullptr, *part_err = nullptr, *T12 = nullptr;
+    int *samples = nullptr, *flags = nullptr, *valid = nullptr, *scan = nullptr, *surv = nullptr, *res_cnt = nullptr, *part_cnt = nullptr, *bad = nullptr,
+        *scan_part = nullptr;               // the scan's tile sums, taken once: every batch scans on the same stream
+    int cap = 0, nruns = 0;
+    size_t part_elems = 0;
+};
+
+// the pairs gathered and their indices checked (one read-back, before any hypothesis reads a pair), the batch buffers reserved
+int ransac_setup(r3d_ctx *ctx, DevArena &ar, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt, const int *d_corres, int64_t M,
+                 int cap, bool want_samples, RansacWork &W) {
+    W.cap = cap;
+    W.nruns = (int)((M + RANSAC_RUN - 1) / RANSAC_RUN);
+    size_t part_cap = RANSAC_PART_ELEMS;
+    if (const char *e = getenv("R3D_RANSAC_PART_ELEMS")) part_cap = (size_t)std::max<long long>(atoll(e), 0);   // diagnostic: 0 forces the one-share path
+    W.part_elems = std::min<size_t>((size_t)W.nruns * cap, part_cap);
+    W.pairs = (double *)ar.get((size_t)M * 48);
+    W.T = (double *)ar.get((size_t)cap * 96);
+    W.res_err = (double *)ar.get((size_t)cap * 8);
+    W.part_err = (double *)ar.get(W.part_elems * 8);
+    W.T12 = (double *)ar.get(96);
+    W.samples = want_samples ? (int *)ar.get((size_t)cap * 16) : nullptr;
+    W.flags = (int *)ar.get((size_t)cap * 4);
+    W.valid = (int *)ar.get((size_t)(cap + 1) * 4);
+    W.scan = (int *)ar.get((size_t)(cap + 1) * 4);
+    W.surv = (int *)ar.get((size_t)cap * 4);
+    W.res_cnt = (int *)ar.get((size_t)cap * 4);
+    W.part_cnt = (int *)ar.get(W.part_elems * 4);
+    W.bad = (int *)ar.get(4);
+    W.scan_part = (int *)ar.get((size_t)((cap + 1 + SCAN_TILE - 1) / SCAN_TILE) * 4);
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemsetAsync(W.bad, 0, 4, ctx->stream));
+    k_ransac_gather<<<(unsigned)((M + 255) / 256), 256, 0, ctx->stream>>>(d_src, ns, d_tgt, nt, d_corres, M, W.pairs, W.bad);
+    R3D_HIP(ctx, hipGetLastError());
+    int bad = 0;
+    PinRead rd(ctx);
+    int rc;
+    if ((rc = rd.add(&bad, W.bad, 4)) || (rc = rd.wait())) return rc;
+    if (bad) return r3d_fail(ctx, R3D_E_BADARG, "ransac: a correspondence index lies outside its cloud (ns = %lld, nt = %lld)", (long long)ns, (long long)nt);
+    return R3D_OK;
+}
+
+// hypotheses pd.h0 .. pd.h0 + pd.count - 1: proposed, compacted in h order and scored; leaves surv / res_cnt / res_err [nsurv]
+int ransac_batch(r3d_ctx *ctx, DevArena &ar, const RansacWork &W, int64_t M, const RansacDev &pd, int *nsurv_out) {
+    const int count = pd.count;
+    k_ransac_propose<<<(unsigned)((count + RANSAC_BLOCK - 1) / RANSAC_BLOCK), RANSAC_BLOCK, 0, ctx->stream>>>(W.pairs, M, pd, W.cap, W.samples, W.flags,
+                                                                                                             W.valid, W.T);
+    R3D_HIP(ctx, hipGetLastError());
+    int rc;
+    if ((rc = dev_exclusive_scan<int>(ctx, ar, W.valid, W.scan, (int64_t)count + 1, nullptr, nullptr, W.scan_part))) return rc;
+    k_ransac_compact<<<(unsigned)((count + 255) / 256), 256, 0, ctx->stream>>>(W.valid, W.scan, count, W.surv);
+    R3D_HIP(ctx, hipGetLastError());
+    int nsurv = 0;
+    {
+        PinRead rd(ctx);
+        if ((rc = rd.add(&nsurv, W.scan + count, 4)) || (rc = rd.wait())) return rc;
+    }
+    *nsurv_out = nsurv;
+    if (nsurv <= 0) return R3D_OK;
+    // few survivors: the runs are split over gridDim.y so that the chip is still filled (about 2048 workgroups)
+    const int nbx = (nsurv + RANSAC_BLOCK - 1) / RANSAC_BLOCK;
+    int shares = std::max(1, std::min(W.nruns, 2048 / nbx));
+    if ((size_t)W.nruns * nsurv > W.part_elems) shares = 1;
+    const int per = (W.nruns + shares - 1) / shares;
+    shares = (W.nruns + per - 1) / per;
+    if (shares == 1) {
+        k_ransac_score<true><<<dim3(nbx, 1), RANSAC_BLOCK, 0, ctx->stream>>>(W.pairs, M, W.T, W.cap, W.surv, nsurv, W.nruns, W.nruns, pd.max2, W.res_cnt,
+                                                                          W.res_err);
+    } else {
+        k_ransac_score<false><<<dim3(nbx, shares), RANSAC_BLOCK, 0, ctx->stream>>>(W.pairs, M, W.T, W.cap, W.surv, nsurv, per, W.nruns, pd.max2,
+                                                                                W.part_cnt, W.part_err);
+        k_ransac_reduce<<<(unsigned)((nsurv + 255) / 256), 256, 0, ctx->stream>>>(W.part_cnt, W.part_err, nsurv, W.nruns, W.res_cnt, W.res_err);
+    }
+    R3D_HIP(ctx, hipGetLastError());
+    return R3D_OK;
+}
+
+// surv / res_cnt / res_err of the last batch on the host: through the pinned buffer when they fit, a plain copy otherwise
+int ransac_read_results(r3d_ctx *ctx, const RansacWork &W, int nsurv, std::vector<int> &surv, std::vector<int> &cnt, std::vector<double> &err) {
+    surv.resize(nsurv); cnt.resize(nsurv); err.resize(nsurv);
+    if (nsurv <= RANSAC_PIN_SURV) {
+        PinRead rd(ctx);
+        int rc;
+        if ((rc = rd.add(surv.data(), W.surv, (size_t)nsurv * 4)) || (rc = rd.add(cnt.data(), W.res_cnt, (size_t)nsurv * 4)) ||
+            (rc = rd.add(err.data(), W.res_err, (size_t)nsurv * 8)) || (rc = rd.wait()))
+            return rc;
+        return R3D_OK;
+    }
+    R3D_HIP(ctx, hipMemcpyAsync(surv.data(), W.surv, (size_t)nsurv * 4, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipMemcpyAsync(cnt.data(), W.res_cnt, (size_t)nsurv * 4, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipMemcpyAsync(err.data(), W.res_err, (size_t)nsurv * 8, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+RansacDev ransac_dev_params(const r3d_ransac_params *p) {
+    RansacDev pd;
+    pd.seed = p->seed;
+    pd.h0 = 0;
+    pd.count = 0;
+    pd.n = p->ransac_n;
+    pd.sim = p->edge_length_similarity > 0 ? p->edge_length_similarity : 0.0;
+    pd.cd2 = p->checker_distance > 0 ? p->checker_distance * p->checker_distance : 0.0;
+    pd.max2 = p->max_correspondence_distance * p->max_correspondence_distance;
+    return pd;
+}
+
+int ransac_check(r3d_ctx *ctx, const char *who, const r3d_ransac_params *p, const void *src, int64_t ns, const void *tgt, int64_t nt, const void *corres,
+                 int64_t M) {
+    if (!p || !src || !tgt || !corres || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument (null array or empty cloud)", who);
+    if (p->ransac_n < 3 || p->ransac_n > 4) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: ransac_n = %d not supported (3 or 4)", who, p->ransac_n);
+    if (M < p->ransac_n) return r3d_fail(ctx, R3D_E_BADARG, "%s: %lld correspondences, fewer than ransac_n = %d", who, (long long)M, p->ransac_n);
+    if (!(p->max_correspondence_distance > 0) || !(p->confidence > 0) || p->max_iteration < 1)
+        return r3d_fail(ctx, R3D_E_BADARG, "%s: max_correspondence_distance and confidence must be > 0, max_iteration >= 1", who);
+    if (p->max_iteration > 0x7fffffff || M > 0x7fffffff || ns > 0x7fffffff || nt > 0x7fffffff)
+        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: max_iteration, M, ns and nt must stay below 2^31", who);
+    return R3D_OK;
+}
+
+// rule 6 of the contract: how many hypotheses a best of this fitness still asks for (host double arithmetic with libm, which the
+// restatement repeats through Python's math module)
+int64_t ransac_est_k(double fitness, int n, double confidence, int64_t max_iteration) {
+    if (confidence >= 1.0) return max_iteration;
+    const double pw = std::pow(fitness, (double)n);
+    if (pw >= 1.0) return 0;
+    if (!(pw > 0.0)) return max_iteration;
+    const double k = std::ceil(std::log(1.0 - confidence) / std::log1p(-pw));
+    return k < (double)max_iteration ? (int64_t)k : max_iteration;
+}
+
+// the loop over device arrays.  mask_dev / mask_host: where the winner's mask goes (either may be null).
+int ransac_core(r3d_ctx *ctx, DevArena &ar, const r3d_ransac_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                const int *d_corres, int64_t M, double *T4x4, unsigned char *mask_dev, unsigned char *mask_host, r3d_ransac_stats *stats,
+                std::chrono::steady_clock::time_point t_begin) {
+    const int64_t max_it = p->max_iteration;
+    const int batch = (int)std::min<int64_t>(std::max<int64_t>(p->batch > 0 ? p->batch : RANSAC_DEFAULT_BATCH, 1), std::min<int64_t>(RANSAC_MAX_BATCH, max_it));
+    RansacWork W;
+    int rc;
+    if ((rc = ransac_setup(ctx, ar, d_src, ns, d_tgt, nt, d_corres, M, batch, false, W))) return rc;
+    unsigned char *d_mask = mask_dev ? mask_dev : (mask_host ? (unsigned char *)ar.get((size_t)M) : nullptr);
+    if (ar.rc) return ar.rc;
+    const auto t_loop = std::chrono::steady_clock::now();
+    RansacDev pd = ransac_dev_params(p);
+    int64_t limit = max_it, h0 = 0, validated = 0, best_h = -1, best_cnt = 0;
+    double best_rmse = 0.0, bestT[12];
+    std::vector<int> surv, cnt;
+    std::vector<double> err;
+    while (h0 < limit) {
+        pd.h0 = h0;
+        pd.count = (int)std::min<int64_t>(batch, limit - h0);
+        int nsurv = 0;
+        if ((rc = ransac_batch(ctx, ar, W, M, pd, &nsurv))) return rc;
+        if (nsurv > 0) {
+            if ((rc = ransac_read_results(ctx, W, nsurv, surv, cnt, err))) return rc;
+            int new_best_slot = -1;
+            for (int k = 0; k < nsurv; k++) {
+                const int64_t h = h0 + surv[k];
+                if (h >= limit) break;      // the sequential walk has stopped: the rest of the batch was wasted work
+                validated++;
+                if (cnt[k] <= 0) continue;
+                const double rmse = std::sqrt(err[k] / (double)cnt[k]);
+                if (cnt[k] > best_cnt || (cnt[k] == best_cnt && rmse < best_rmse)) {
+                    best_cnt = cnt[k]; best_rmse = rmse; best_h = h; new_best_slot = surv[k];
+                    const int64_t est = ransac_est_k((double)cnt[k] / (double)M, p->ransac_n, p->confidence, max_it);
+                    limit = std::max<int64_t>(std::min<int64_t>(max_it, est), h + 1);
+                }
+            }
+            if (new_best_slot >= 0) {       // the arena's T is overwritten by the next batch
+                k_ransac_fetch_T<<<1, 64, 0, ctx->stream>>>(W.T, W.cap, new_best_slot, W.T12);
+                R3D_HIP(ctx, hipGetLastError());
+                PinRead rd(ctx);
+                if ((rc = rd.add(bestT, W.T12, 96)) || (rc = rd.wait())) return rc;
+            }
+        }
+        h0 += pd.count;
+    }
+    for (int i = 0; i < 16; i++) T4x4[i] = (i % 5 == 0);
+    if (best_h >= 0) memcpy(T4x4, bestT, 96);
+    if (d_mask) {
+        if (best_h >= 0) {
+            RansacT Tm;
+            memcpy(Tm.m, bestT, 96);
+            k_ransac_mask<<<(unsigned)((M + 255) / 256), 256, 0, ctx->stream>>>(W.pairs, M, Tm, pd.max2, d_mask);
+            R3D_HIP(ctx, hipGetLastError());
+        } else {
+            R3D_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)M, ctx->stream));
+        }
+        if (mask_host) R3D_HIP(ctx, hipMemcpyAsync(mask_host, d_mask, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) {
+        stats->fitness = best_h >= 0 ? (double)best_cnt / (double)M : 0.0;
+        stats->inlier_rmse = best_h >= 0 ? best_rmse : 0.0;
+        stats->iterations = limit;
+        stats->validated = validated;
+        stats->best_hypothesis = best_h;
+        stats->inliers = best_cnt;
+        const auto t_end = std::chrono::steady_clock::now();
+        stats->setup_ms = std::chrono::duration<double, std::milli>(t_loop - t_begin).count();
+        stats->loop_ms = std::chrono::duration<double, std::milli>(t_end - t_loop).count();
+    }
     return R3D_OK;
 }
 
@@ -5128,6 +5587,83 @@ int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_nor
     for (auto &x : ev) (void)hipEventDestroy(x);
     if (rc) return rc;
     if (e != hipSuccess) return r3d_fail(ctx, R3D_E_HIP, "debug_fpfh_stages: %s", hipGetErrorString(e));
+    return R3D_OK;
+}
+
+// ---- feature-matching RANSAC over given correspondences (Open3D registration_ransac_based_on_correspondence)
+int r3d_ransac_correspondence_dev(r3d_ctx *ctx, const r3d_ransac_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                                  const int32_t *d_corres, int64_t M, double *T4x4, uint8_t *d_inlier_mask, r3d_ransac_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_ransac_correspondence_dev");
+    if (!ctx) return R3D_E_BADARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!T4x4) return r3d_fail(ctx, R3D_E_BADARG, "ransac_correspondence_dev: T4x4 is NULL");
+    if (int rc = ransac_check(ctx, "ransac_correspondence_dev", p, d_src, ns, d_tgt, nt, d_corres, M)) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return ransac_core(ctx, ar, p, d_src, ns, d_tgt, nt, d_corres, M, T4x4, d_inlier_mask, nullptr, stats, t_begin);
+}
+
+int r3d_ransac_correspondence(r3d_ctx *ctx, const r3d_ransac_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                              const int32_t *corres, int64_t M, double *T4x4, uint8_t *inlier_mask, r3d_ransac_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_ransac_correspondence");
+    if (!ctx) return R3D_E_BADARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc;
+    if (!T4x4) return r3d_fail(ctx, R3D_E_BADARG, "ransac_correspondence: T4x4 is NULL");
+    if ((rc = ransac_check(ctx, "ransac_correspondence", p, src, ns, tgt, nt, corres, M))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    int *d_c = (int *)ar.get((size_t)M * 8);
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    return ransac_core(ctx, ar, p, d_s, ns, d_t, nt, d_c, M, T4x4, nullptr, inlier_mask, stats, t_begin);
+}
+
+int r3d_debug_ransac_hypotheses(r3d_ctx *ctx, const r3d_ransac_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                                const int32_t *corres, int64_t M, int64_t h0, int64_t count, int32_t *samples, int32_t *flags, double *T,
+                                int32_t *inliers, double *err2) {
+    R3D_ROCTX_RANGE("r3d_debug_ransac_hypotheses");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = ransac_check(ctx, "debug_ransac_hypotheses", p, src, ns, tgt, nt, corres, M))) return rc;
+    if (h0 < 0 || count < 1 || count > RANSAC_MAX_BATCH || h0 + count > 0x7fffffff)
+        return r3d_fail(ctx, R3D_E_BADARG, "debug_ransac_hypotheses: h0 >= 0, 1 <= count <= %d, h0 + count < 2^31", RANSAC_MAX_BATCH);
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    int *d_c = (int *)ar.get((size_t)M * 8);
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    RansacWork W;
+    const int n = (int)count;
+    if ((rc = ransac_setup(ctx, ar, d_s, ns, d_t, nt, d_c, M, n, true, W))) return rc;
+    RansacDev pd = ransac_dev_params(p);
+    pd.h0 = h0;
+    pd.count = n;
+    int nsurv = 0;
+    if ((rc = ransac_batch(ctx, ar, W, M, pd, &nsurv))) return rc;
+    std::vector<int> surv, cnt, fl(n);
+    std::vector<double> err, Ts((size_t)n * 12);
+    if (nsurv > 0 && (rc = ransac_read_results(ctx, W, nsurv, surv, cnt, err))) return rc;
+    if (samples) R3D_HIP(ctx, hipMemcpyAsync(samples, W.samples, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipMemcpyAsync(fl.data(), W.flags, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipMemcpyAsync(Ts.data(), W.T, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n; i++) {
+        if (flags) flags[i] = fl[i];
+        if (T) for (int e = 0; e < 12; e++) T[(size_t)i * 12 + e] = (fl[i] & 1) ? Ts[(size_t)e * n + i] : 0.0;   // slots of rejected samples hold an earlier call's values
+        if (inliers) inliers[i] = 0;
+        if (err2) err2[i] = 0.0;
+    }
+    for (int k = 0; k < nsurv; k++) {
+        if (inliers) inliers[surv[k]] = cnt[k];
+        if (err2) err2[surv[k]] = err[k];
+    }
     return R3D_OK;
 }
 

@@ -336,6 +336,52 @@ int r3d_match_features_dev(r3d_ctx *ctx, const double *d_src_feat, int64_t ns, c
 int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_normals, int64_t n, double radius, int32_t max_nn,
                           double *d_fpfh, float *ms3);
 
+/* replaces: o3d.pipelines.registration.registration_ransac_based_on_correspondence / ..._on_feature_matching with
+ *           TransformationEstimationPointToPoint(False), CorrespondenceCheckerBasedOnEdgeLength / ...OnDistance and
+ *           RANSACConvergenceCriteria(max_iteration, confidence) (test/check_lama1.py:246-281, mini1.py, check8.py)
+ *           [recalled, Open3D 0.18 Registration.cpp / CorrespondenceChecker.cpp; DESIGN.md section 4 ("RANSAC") states the contract,
+ *           tests/ransac_ref.py executes it].
+ * Open3D's sampler and stopping rule are racy; this one is a pure function of (inputs, seed): hypothesis h = 0, 1, ... draws its
+ * ransac_n pairs from a counter-based generator, passes the edge-length checker, gets Eigen::umeyama's transform, passes the
+ * distance checker, is scored over all M pairs, and the best / stop rule is applied in h order on the host, whatever `batch` is. */
+typedef struct r3d_ransac_params {
+    double max_correspondence_distance; /* > 0; a pair is an inlier when |T s - t| < this */
+    double edge_length_similarity;      /* <= 0: no edge-length checker */
+    double checker_distance;            /* <= 0: no distance checker */
+    double confidence;                  /* > 0; >= 1: never stop before max_iteration */
+    int64_t max_iteration;              /* 1 .. 2^31 - 1 */
+    uint64_t seed;
+    int32_t ransac_n;                   /* 3 or 4 */
+    int32_t batch;                      /* hypotheses per launch, 0: the library's choice; never changes the result */
+} r3d_ransac_params;
+typedef struct r3d_ransac_stats {
+    double fitness;     /* inliers / M of the best hypothesis (0 if none survived) */
+    double inlier_rmse;
+    int64_t iterations; /* the sequential stop: hypotheses h < iterations count */
+    int64_t validated;  /* of those, how many passed their checkers */
+    int64_t best_hypothesis; /* -1 if none survived */
+    int64_t inliers;
+    double setup_ms;    /* host wall time: uploads, gather, index check */
+    double loop_ms;     /* host wall time of the batches and the winner's mask */
+} r3d_ransac_stats;
+/* src [ns][3], tgt [nt][3], corres [M][2] int32 rows (source index, target index); T4x4 row-major (identity if nothing survived);
+ * inlier_mask (optional) uint8 [M].  R3D_E_BADARG: a missing array, M < ransac_n, a pair index outside its cloud,
+ * max_correspondence_distance <= 0, confidence <= 0, max_iteration < 1.  R3D_E_UNSUPPORTED: ransac_n outside 3..4,
+ * max_iteration or M above 2^31 - 1.  batch is clamped to 1 .. 262144.
+ * _dev: d_src, d_tgt, d_corres and d_inlier_mask are DEVICE arrays (T4x4 and stats stay host memory); the pair indices are checked
+ * on the device before any hypothesis reads them; returns when the loop has finished, like r3d_icp_dev. */
+int r3d_ransac_correspondence(r3d_ctx *ctx, const r3d_ransac_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                              const int32_t *corres, int64_t M, double *T4x4, uint8_t *inlier_mask, r3d_ransac_stats *stats);
+int r3d_ransac_correspondence_dev(r3d_ctx *ctx, const r3d_ransac_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                                  const int32_t *d_corres, int64_t M, double *T4x4, uint8_t *d_inlier_mask, r3d_ransac_stats *stats);
+/* stage parity: hypotheses h0 .. h0 + count - 1 (count <= 262144) evaluated without the best / stop rule, host arrays.
+ * samples int32 [count][4] (unused entries -1); flags int32 [count]: bit 0 the edge-length checker passed (or is off), bit 1 the
+ * distance checker passed (or is off; 0 when bit 0 is 0: the transform is not computed then); T [count][12], rows 0..2 of the 4x4
+ * (zeros when bit 0 is 0); inliers int32 [count] and err2 [count] (0 unless both bits are set).  Any output may be NULL. */
+int r3d_debug_ransac_hypotheses(r3d_ctx *ctx, const r3d_ransac_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                                const int32_t *corres, int64_t M, int64_t h0, int64_t count, int32_t *samples, int32_t *flags, double *T,
+                                int32_t *inliers, double *err2);
+
 /* replaces: the whole body of PointCloudAlignment.align_point_clouds (pointcloud_alignment.py:6-43; caller main.py:48) in ONE
  * call, device-resident between the stages: voxel_down_sample(voxel_size) of both clouds (:22-23) ->
  * estimate_normals(KDTreeSearchParamHybrid(normal_radius, normal_max_nn)) on both (:27-28) -> registration (:35-39) ->
