@@ -40,19 +40,10 @@ struct GridView {
     const int *dense;
     const double *pts;     // [n][3] points in cell-sorted order
     const int *idx;        // [n] sorted slot -> original index
-    // optional float32 structure-of-arrays copy of pts (n + 4 entries each) for the two-stage 1-NN search of the
-    // registration loop; fe = 2 x (bound on |float distance - exact distance|), see nn_block_top4
-    const float *fx, *fy, *fz;
-    float fe;
-    // optional packed copy for the default search (nn_block_q10): one dword per sorted point = 10-bit offsets inside its own
-    // cell (x | y << 10 | z << 20) and the low two bits of its cell x index (<< 30); n + 4 entries
+    // optional packed copy for the registration loop's default search (nn_block_q10): one dword per sorted point = 10-bit offsets
+    // inside its own cell (x | y << 12 | z << 22) and the low two bits of its cell x index (<< 10); n + 4 entries
     const unsigned *q10;
-    // optional (registration loop): reach[coarse cell] != 0 iff some point lies in the 3x3x3 block of COARSE cells (rs fine cells
-    // on a side) around it.  A query whose coarse cell reads 0 has no point within rs fine cells in any direction, i.e. none within
-    // the correspondence radius (rs >= ceil(radius / cell)): its search is skipped outright, with the result it would have had.
-    const unsigned char *reach;
-    int rs, rnx, rny, rnz;
-    int pool;              // registration loop: the packed search pools the lanes' row lists per wave (nn_block_q10's pooled walk)
+    int pool;              // 1 whenever q10 is set (k_icp_eval<*, SEARCH_Q10> tests it; why it stays a field: DESIGN.md section 7)
 };
 
 __device__ __forceinline__ int cell_coord(double v, double o, double inv) { return (int)floor((v - o) * inv); }
@@ -1446,114 +1437,15 @@ __device__ __forceinline__ void nn_block_global(const GridView &g, double px, do
     }
 }
 
-// Two-stage form of the same search.  The loop is bound by the texture-addresser / L1 path (PMC: 4.4 M gather instructions
-// per iteration at 1 M points, the L2 sees only 4.6 M requests), and a float64 candidate costs two gather instructions
-// (24 bytes = dwordx4 + dwordx2).  Stage 1 scans float32 structure-of-arrays copies (three 16-byte gathers per FOUR
-// candidates) and keeps the four smallest float distances with their slots -- branch-free, so no lane waits for another
-// lane's exact arithmetic.  Stage 2 evaluates the best three exactly (float64, the update rule and tie order of
-// nn_block_global), every lane doing the same three steps.  With |d_float - d_exact| <= fe/2 for every candidate (coordinate
-// rounding of target and query; bound from the bounding box, computed on the host) every candidate that can be the exact
-// nearest point, or tie with it, has a float distance within fe of the smallest float distance; if the FOURTH smallest is
-// within that margin too, the three may not contain them all and the lane falls back to the all-float64 scan (rare: four
-// candidates within micrometres of the same distance).  Result: identical to nn_block_global.
-__device__ __forceinline__ void nn_block_top4(const GridView &g, double px, double py, double pz, int cx, int cy, int cz, double &best,
-                                              int &bi) {
-    const int xa = cx - 1, xb = cx + 1;
-    const bool xok = xb >= 0 && xa <= g.nx - 1;
-    const int x0 = min(max(xa, 0), g.nx - 1), x1 = min(max(xb, 0), g.nx - 1);
-    typedef float float4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-    int rb[9], re[9];
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-        const int z = cz + r / 3 - 1, y = cy + r % 3 - 1;
-        const bool ok = xok && z >= 0 && z < g.nz && y >= 0 && y < g.ny;
-        const int64_t row = ((int64_t)min(max(z, 0), g.nz - 1) * g.ny + min(max(y, 0), g.ny - 1)) * g.nx;
-        const cs_int4 cs = cs4(g, row + x0);
-        const int b = cs.x, de = x1 + 1 - x0, e = de == 3 ? cs.w : de == 2 ? cs.z : cs.y;
-        rb[r] = b;
-        re[r] = b + ((e - b) & (ok ? -1 : 0));
-    }
-    const float qx = (float)px, qy = (float)py, qz = (float)pz;
-    const float INF = __builtin_huge_valf();
-    float t1 = INF, t2 = INF, t3 = INF, t4 = INF;
-    int i1 = -1, i2 = -1, i3 = -1;
-#pragma unroll
-    for (int r = 0; r < 9; r++) {
-        const int e = re[r];
-        for (int j0 = rb[r]; j0 < e; j0 += 4) {
-            const float4_a4 X = *(const float4_a4 *)(g.fx + j0), Y = *(const float4_a4 *)(g.fy + j0), Z = *(const float4_a4 *)(g.fz + j0);
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int j = j0 + u;
-                const float fdx = X[u] - qx, fdy = Y[u] - qy, fdz = Z[u] - qz;
-                float f = fdx * fdx + fdy * fdy + fdz * fdz;
-                f = j < e ? f : INF;
-                // insert (f, j) into the ascending quadruple; the slot of the fourth is never needed
-                const bool c3 = f < t3, c2 = f < t2, c1 = f < t1;
-                t4 = c3 ? t3 : fminf(t4, f);
-                i3 = c2 ? i2 : (c3 ? j : i3);
-                t3 = c2 ? t2 : (c3 ? f : t3);
-                i2 = c1 ? i1 : (c2 ? j : i2);
-                t2 = c1 ? t1 : (c2 ? f : t2);
-                i1 = c1 ? j : i1;
-                t1 = c1 ? f : t1;
-            }
-        }
-    }
-    if (!(t1 < INF)) return;                       // empty block: nothing to evaluate (the caller goes on to the outer shells)
-    const float tt = sqrtf(t1) * 1.000001f + g.fe;  // the relative term covers the float32 evaluation of the distance itself
-    const float thr2 = tt * tt * 1.000001f;
-    if (t4 <= thr2) {                              // a fourth contender: the triple may be incomplete
-        nn_block_global(g, px, py, pz, cx, cy, cz, best, bi);
-        return;
-    }
-    const int cand[3] = {i1, i2, i3};
-    const float ct[3] = {t1, t2, t3};
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const int j = max(cand[q], 0);             // clamped slot: no branch around the loads
-        const double dx = g.pts[(int64_t)j * 3] - px, dy = g.pts[(int64_t)j * 3 + 1] - py, dz = g.pts[(int64_t)j * 3 + 2] - pz;
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (cand[q] >= 0 && ct[q] <= thr2 && d2 <= best) {
-            if (d2 < best || (bi >= 0 && g.idx[j] < g.idx[bi])) { best = d2; bi = j; }
-        }
-    }
-}
-
-// reach bitmap of a search grid (GridView::reach): coarse occupancy, then a 3-tap maximum along x, y and z
-__global__ void __launch_bounds__(256) k_reach_mark(GridView g, int64_t n, int rs, int rnx, int rny, int rnz, unsigned char *__restrict__ occ) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int cx = min(max(cell_coord(g.pts[i * 3], g.ox, g.inv_cell), 0), g.nx - 1) / rs;
-    const int cy = min(max(cell_coord(g.pts[i * 3 + 1], g.oy, g.inv_cell), 0), g.ny - 1) / rs;
-    const int cz = min(max(cell_coord(g.pts[i * 3 + 2], g.oz, g.inv_cell), 0), g.nz - 1) / rs;
-    occ[((int64_t)cz * rny + cy) * rnx + cx] = 1;
-}
-__global__ void __launch_bounds__(256) k_reach_dilate(const unsigned char *__restrict__ in, unsigned char *__restrict__ out, int64_t n, int64_t stride, int dim) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t pos = (i / stride) % dim;            // coordinate along the filtered axis
-    unsigned char v = in[i];
-    if (pos > 0) v |= in[i - stride];
-    if (pos + 1 < dim) v |= in[i + stride];
-    out[i] = v;
-}
-
-__global__ void __launch_bounds__(256) k_soa_f32(const double *__restrict__ pts, int64_t n, float *__restrict__ fx, float *__restrict__ fy,
-                                                 float *__restrict__ fz) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n + 4) return;
-    const bool in = i < n;
-    const int64_t ic = in ? i : n - 1;
-    fx[i] = in ? (float)pts[ic * 3] : 0.f;
-    fy[i] = in ? (float)pts[ic * 3 + 1] : 0.f;
-    fz[i] = in ? (float)pts[ic * 3 + 2] : 0.f;
-}
-
-// Packed form of the two-stage search (the default).  PMC on the float32 form: 51 M VALU wave-instructions per evaluation
-// at 1 M points (3 300 per 64 queries) against 0.5 M gathers -- the search is bound by the vector ALU, not by memory: 37
-// instructions per candidate (most of them the sorted insertion of (distance, slot) into a quadruple), every one of the nine
-// rows walked by the whole wave for as long as its longest lane.  Here
+// Two-stage, packed form of the same search (the default).  The all-float64 loop is bound by the texture-addresser / L1 path
+// (a float64 candidate costs two gather instructions, 24 bytes = dwordx4 + dwordx2), and a float32 scan that keeps (distance,
+// slot) pairs is bound by the vector ALU: 37 instructions per candidate, most of them the sorted insertion into a quadruple,
+// every one of the nine rows walked by the whole wave for as long as its longest lane.  Here STAGE 1 scans a packed copy of
+// the candidates and keeps the four smallest approximate distances, branch-free, and STAGE 2 evaluates the best three exactly
+// (float64, the update rule and tie order of nn_block_global).  With |d_stage1 - d_exact| <= FEQ / 2 for every candidate,
+// every candidate that can be the exact nearest point, or tie with it, has a stage-1 distance within FEQ of the smallest one;
+// if the FOURTH smallest is within that margin too, the three may not contain them all and the lane falls back to
+// nn_block_global (rare: four candidates within a fraction of a cell of the same distance).  In stage 1
 //  (1) a candidate is ONE dword: its position inside its own cell quantised to 10 bits per axis, x together with the low two
 //      bits of its cell x index (k_pack_q10): one 16-byte gather brings four candidates, and the query is expressed in the
 //      same unit (cell / 1024) relative to the corner of its 3x3x3 block, where every coordinate is below 4096 and float32
@@ -1568,13 +1460,12 @@ __global__ void __launch_bounds__(256) k_soa_f32(const double *__restrict__ pts,
 //      rows of the per-row maximum.
 // Error budget of stage 1 in units: reconstruction of a candidate 0.5 per axis (0.867 in distance), the query's float
 // coordinates 2.5e-4, key truncation 2^-13 relative in d^2 (<= 0.22 at the far corner of the block): |d_stage1 - d_exact| <=
-// 1.1, FEQ ("fe" of nn_block_top4) = 2.25 units = cell / 455.  Stage 2 (exact float64 evaluation of the best three, fallback
-// to nn_block_global on a fourth contender within the margin) is unchanged, and so is the result: bit-identical to the
-// all-float64 search (tests/test_cloud_gpu.py).  Queries whose nine rows hold more than 1024 candidates use the fallback.
+// 1.1, so the margin FEQ = 2.25 units = cell / 455.  The result is bit-identical to the all-float64 search
+// (tests/test_cloud_gpu.py).  Queries whose nine rows hold more than 1024 candidates use the fallback.
 constexpr float FEQ = 2.25f;
 // pooled walk (nn_block_q10<1>): queue capacity per wave, and words per wave of the pool buffer: keys [Q][4], items [Q][2], the
 // lanes' query parameters [4][64], the queue length
-constexpr int POOL_Q = 256, POOL_Q_SEARCH = 176 /* k_icp_search: four workgroups' LDS still fit a CU */;
+constexpr int POOL_Q = 256;
 constexpr int pool_words(int q) { return 6 * q + 256 + 4; }
 
 __global__ void __launch_bounds__(256) k_pack_q10(GridView g, int64_t n, unsigned *__restrict__ out) {
@@ -1603,19 +1494,10 @@ __device__ __forceinline__ int med3_i32(int a, int b, int c) { return max(min(a,
 // large clouds, where three waves per SIMD hide the gathers; 3: for clouds so small that a SIMD holds one wave -- a scanning-loop
 // frame of 40 k points is 160 workgroups on 256 CUs -- and every dependent gather is a full memory round trip: the same candidates
 // in the same order, so the same keys and the same result)
-#ifdef R3D_ICP_STATS   // diagnostic build only (csrc/build.sh -DR3D_ICP_STATS, tools/gpu_icp_stats.py): trip counts of the packed search per
-                       // wave, as the maximum over lanes (what the wave executes) and the sum over lanes (what its lanes need)
-__device__ unsigned long long g_icp_stats[16];
-__device__ __forceinline__ void icp_stat(int slot, int v) {
-    int m = v, sum = v;
-    for (int o = 32; o > 0; o >>= 1) { m = max(m, __shfl_xor(m, o)); sum += __shfl_xor(sum, o); }
-    if ((threadIdx.x & 63) == 0) { atomicAdd(&g_icp_stats[slot], (unsigned long long)m); atomicAdd(&g_icp_stats[slot + 1], (unsigned long long)sum); }
-}
-#endif
-template <int G, int PQ = POOL_Q>
+template <int G>
 __device__ __forceinline__ void nn_block_q10(const GridView &g, double px, double py, double pz, int cx, int cy, int cz, double r2,
                                              double &best, int &bi, int *__restrict__ sRun /* [18][ICP_BLOCK] */,
-                                             int *__restrict__ sPool = nullptr /* G == 1: [ICP_BLOCK / 64][pool_words(PQ)], 16-byte aligned */) {
+                                             int *__restrict__ sPool = nullptr /* G == 1: [ICP_BLOCK / 64][pool_words(POOL_Q)], 16-byte aligned */) {
     constexpr int B = 256;   // = ICP_BLOCK (declared below)
     const int tid = threadIdx.x;
     const int xa = cx - 1, xb = cx + 1;
@@ -1695,16 +1577,6 @@ __device__ __forceinline__ void nn_block_q10(const GridView &g, double px, doubl
     };
     auto scan4 = [&](int j0, int e, float qyr, float qzr) { scan4w(*(const uint4_a4 *)(g.q10 + j0), e - j0, qyr, qzr); };
     // centre row first: it gives the pruning threshold for the other eight
-#ifdef R3D_ICP_STATS
-    {
-        int lg = 0, lc = 0;
-        for (int q = 1; q < 9; q++) { lg += (re[q] - rb[q] + 3) >> 2; lc += re[q] - rb[q]; }
-        icp_stat(0, (re[0] - rb[0] + 3) >> 2);      // centre-row groups
-        icp_stat(2, re[0] - rb[0]);                 // centre-row candidates
-        icp_stat(4, lg);                            // groups of the other eight rows before pruning
-        icp_stat(6, lc);
-    }
-#endif
     if (G == 1) {
         for (int j0 = rb[0]; j0 < re[0]; j0 += 4) scan4(j0, re[0], qyc - 1024.5f, qzc - 1024.5f);
     } else {
@@ -1739,27 +1611,17 @@ __device__ __forceinline__ void nn_block_q10(const GridView &g, double px, doubl
             nr++;
         }
     }
-#ifdef R3D_ICP_STATS
-    {
-        int lg = 0, lc = 0;
-        for (int k = 1; k < nr; k++) { const int len = sRun[(k * 2 + 1) * B + tid] & 0xfffff; lg += (len + 3) >> 2; lc += len; }
-        icp_stat(8, lg);                            // groups of the surviving rows (after the slab test and the end-cell trim)
-        icp_stat(10, lc);
-        icp_stat(12, nr - 1);                       // surviving rows
-        icp_stat(14, 1);                            // [14] waves, [15] queries
-    }
-#endif
     // POOLED WALK of the other rows (G == 1, large clouds).  Left to itself a wave walks its lists for as long as its longest lane:
-    // 9.3 groups on average where its average lane has 2.3 (tools/gpu_icp_stats.py) -- three quarters of the wave's lane-steps
-    // are idle.  Here the lanes put their groups into ONE queue of the wave (LDS), every lane computes the keys of every
+    // 9.3 groups on average where its average lane has 2.3 (profiles/r04_icp_search_stats.log) -- three quarters of the wave's
+    // lane-steps are idle.  Here the lanes put their groups into ONE queue of the wave (LDS), every lane computes the keys of every
     // (active-lane-count)-th group, whoever's query it belongs to -- the owner's query parameters travel through LDS, the
     // arithmetic is keys4() with the same operands, so the keys are the ones the owner would have computed -- and the owners
     // fold their groups' keys into their best four (4 instructions per candidate instead of 20).  A wave whose queue would
-    // overflow takes the per-lane walk below.  R3D_ICP_POOL=0 (host side: no pool buffer is passed) keeps the per-lane walk.
+    // overflow (tot > POOL_Q: very dense cells) takes the per-lane walk below.
     bool pooled = false;
     if (G == 1 && sPool) {
-        int *pw = sPool + (tid >> 6) * pool_words(PQ);
-        int *p_keys = pw, *p_item = pw + 4 * PQ, *p_q = pw + 6 * PQ, *p_tot = pw + 6 * PQ + 256;
+        int *pw = sPool + (tid >> 6) * pool_words(POOL_Q);
+        int *p_keys = pw, *p_item = pw + 4 * POOL_Q, *p_q = pw + 6 * POOL_Q, *p_tot = pw + 6 * POOL_Q + 256;
         const int lane = tid & 63;
         *(volatile int *)p_tot = 0;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1768,7 +1630,7 @@ __device__ __forceinline__ void nn_block_q10(const GridView &g, double px, doubl
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const int tot = *(volatile int *)p_tot;                   // the same for every lane of the wave
-        if (tot <= PQ) {
+        if (tot <= POOL_Q) {
             pooled = true;
             p_q[lane] = __float_as_int(qx);
             p_q[64 + lane] = __float_as_int(qyc);
@@ -1806,6 +1668,8 @@ __device__ __forceinline__ void nn_block_q10(const GridView &g, double px, doubl
             }
         }
     }
+    // PER-LANE WALK: every lane walks its own list.  With G == 1 this is the overflow fallback of the pooled walk (tot > POOL_Q),
+    // with G == 3 it is the walk itself.
     if (!pooled) {
         int k = 1, j0 = 0, e = 0;
         float qyr = 0.f, qzr = 0.f;
@@ -1909,15 +1773,6 @@ __device__ __forceinline__ void nn_outer_shells(const GridView &g, double px, do
         const double reach = s * g.cell;
         if (bi >= 0 && best <= reach * reach) break;
     }
-}
-
-// true when the reach bitmap proves that no target point lies within rs fine cells of the query's cell in any direction (so none
-// within the correspondence radius).  Queries outside the grid are measured from the nearest grid cell: conservative.
-__device__ __forceinline__ bool icp_out_of_reach(const GridView &g, int cx, int cy, int cz) {
-    if (!g.reach) return false;
-    if (cx < -g.rs || cy < -g.rs || cz < -g.rs || cx >= g.nx + g.rs || cy >= g.ny + g.rs || cz >= g.nz + g.rs) return true;   // beyond the grid by more than the radius
-    const int qx = min(max(cx, 0), g.nx - 1) / g.rs, qy = min(max(cy, 0), g.ny - 1) / g.rs, qz = min(max(cz, 0), g.nz - 1) / g.rs;
-    return g.reach[((int64_t)qz * g.rny + qy) * g.rnx + qx] == 0;
 }
 
 // adds one correspondence (source point i at p, target slot bi at squared distance `best`) to the accumulators
@@ -2037,7 +1892,8 @@ __device__ __forceinline__ void icp_accumulate(const GridView &g, const double *
     
 }
 
-enum { SEARCH_EXACT = 0, SEARCH_F32 = 1, SEARCH_Q10 = 2, SEARCH_Q10_DEEP = 3 /* nn_block_q10<3>: small clouds */ };
+// the three forms of the correspondence search (the values are part of the kernels' symbol names)
+enum { SEARCH_EXACT = 0 /* nn_block_global */, SEARCH_Q10 = 2 /* nn_block_q10<1>, pooled walk */, SEARCH_Q10_DEEP = 3 /* nn_block_q10<3>: small clouds */ };
 template <int MODE, int SEARCH>
 __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) k_icp_eval(GridView g, const double *__restrict__ src, const double *__restrict__ src_n,
                                                         const double *__restrict__ tgt_n /* cell-sorted order */, int64_t ns,
@@ -2076,13 +1932,10 @@ __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) 
         const int cx = cell_coord(px, g.ox, g.inv_cell), cy = cell_coord(py, g.oy, g.inv_cell), cz = cell_coord(pz, g.oz, g.inv_cell);
         double best = r2;
         int bi = -1;
-        if (!icp_out_of_reach(g, cx, cy, cz)) {
-            if (SEARCH == SEARCH_Q10_DEEP) nn_block_q10<3>(g, px, py, pz, cx, cy, cz, r2, best, bi, sRun);
-            else if (SEARCH == SEARCH_Q10) nn_block_q10<1>(g, px, py, pz, cx, cy, cz, r2, best, bi, sRun, sPool);
-            else if (SEARCH == SEARCH_F32) nn_block_top4(g, px, py, pz, cx, cy, cz, best, bi);
-            else nn_block_global(g, px, py, pz, cx, cy, cz, best, bi);
-            nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
-        }
+        if (SEARCH == SEARCH_Q10_DEEP) nn_block_q10<3>(g, px, py, pz, cx, cy, cz, r2, best, bi, sRun);
+        else if (SEARCH == SEARCH_Q10) nn_block_q10<1>(g, px, py, pz, cx, cy, cz, r2, best, bi, sRun, sPool);
+        else nn_block_global(g, px, py, pz, cx, cy, cz, best, bi);
+        nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
         if (corr) corr[i] = bi >= 0 ? g.idx[bi] : -1;
         if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, col);
     }
@@ -2101,223 +1954,16 @@ __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) 
     }
 }
 
-// R3D_ICP_SPLIT=1: the evaluation as TWO kernels.  k_icp_search is k_icp_eval's correspondence search alone -- without the 29
-// float64 accumulators and the Jacobian temporaries it is compiled for four waves per SIMD (k_icp_eval: three) -- and writes the
-// winning target slot per query (4 B; the squared distance is recomputed from it, same expression, so nothing else need travel);
-// k_icp_accum streams queries + slots and runs k_icp_eval's accumulation and reduction with the SAME query -> thread -> workgroup
-// assignment, so the 768 x 29 partial sums are bit for bit those of the fused kernel.
-template <int SEARCH>
-__global__ void __launch_bounds__(ICP_BLOCK, 4) k_icp_search(GridView g, const double *__restrict__ src, int64_t ns, const IcpState *__restrict__ st,
-                                                             double max_dist, int *__restrict__ nn) {
-    __shared__ int sRun[SEARCH >= SEARCH_Q10 ? 18 * ICP_BLOCK : 1];
-    // a smaller queue than k_icp_eval's (176 groups per wave: 21 KB): with the 18 KB of row lists four workgroups still fit a CU
-    __shared__ __attribute__((aligned(16))) int sPoolBuf[SEARCH == SEARCH_Q10 ? (ICP_BLOCK / 64) * pool_words(POOL_Q_SEARCH) : 4];
-    int *const sPool = SEARCH == SEARCH_Q10 && g.pool ? sPoolBuf : nullptr;
-    if (st->done) return;
-    const Rigid T = load_rigid(st);
-    const double r2 = max_dist * max_dist;
-    const int smax = (int)ceil(max_dist * g.inv_cell);
-    const int64_t nchunk = (ns + ICP_BLOCK - 1) / ICP_BLOCK;
-    int64_t c_begin = blockIdx.x, c_end = nchunk, c_step = gridDim.x;
-    if ((gridDim.x & 7) == 0) {                    // XCD-aware shares: see k_icp_eval
-        const int x = blockIdx.x & 7;
-        c_begin = x * nchunk / 8 + (blockIdx.x >> 3);
-        c_end = (x + 1) * nchunk / 8;
-        c_step = gridDim.x >> 3;
-    }
-    for (int64_t c = c_begin; c < c_end; c += c_step) {
-        const int64_t i = c * ICP_BLOCK + threadIdx.x;
-        if (i >= ns) continue;
-        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
-        const double px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
-        const double py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
-        const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
-        const int cx = cell_coord(px, g.ox, g.inv_cell), cy = cell_coord(py, g.oy, g.inv_cell), cz = cell_coord(pz, g.oz, g.inv_cell);
-        double best = r2;
-        int bi = -1;
-        if (!icp_out_of_reach(g, cx, cy, cz)) {
-            if (SEARCH == SEARCH_Q10_DEEP) nn_block_q10<3>(g, px, py, pz, cx, cy, cz, r2, best, bi, sRun);
-            else if (SEARCH == SEARCH_Q10) nn_block_q10<1, POOL_Q_SEARCH>(g, px, py, pz, cx, cy, cz, r2, best, bi, sRun, sPool);
-            else if (SEARCH == SEARCH_F32) nn_block_top4(g, px, py, pz, cx, cy, cz, best, bi);
-            else nn_block_global(g, px, py, pz, cx, cy, cz, best, bi);
-            nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
-        }
-        nn[i] = bi;
-    }
-}
-template <int MODE>
-__global__ void __launch_bounds__(ICP_BLOCK, 3) k_icp_accum(GridView g, const double *__restrict__ src, const double *__restrict__ src_n,
-                                                            const double *__restrict__ tgt_n, int64_t ns, const IcpState *__restrict__ st, double eps,
-                                                            const int *__restrict__ nn, double *__restrict__ partial) {
-    if (st->done) return;
-    const Rigid T = load_rigid(st);
-    double acc[ICP_SLOTS];
-#pragma unroll
-    for (int q = 0; q < ICP_SLOTS; q++) acc[q] = 0;
-    const int64_t nchunk = (ns + ICP_BLOCK - 1) / ICP_BLOCK;
-    int64_t c_begin = blockIdx.x, c_end = nchunk, c_step = gridDim.x;
-    if ((gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        c_begin = x * nchunk / 8 + (blockIdx.x >> 3);
-        c_end = (x + 1) * nchunk / 8;
-        c_step = gridDim.x >> 3;
-    }
-    for (int64_t c = c_begin; c < c_end; c += c_step) {
-        const int64_t i = c * ICP_BLOCK + threadIdx.x;
-        if (i >= ns) continue;
-        const int bi = nn[i];
-        if (bi < 0) continue;
-        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
-        const double px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
-        const double py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
-        const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
-        const double dx = g.pts[(int64_t)bi * 3] - px, dy = g.pts[(int64_t)bi * 3 + 1] - py, dz = g.pts[(int64_t)bi * 3 + 2] - pz;
-        const double best = dx * dx + dy * dy + dz * dz;   // the search's own expression for the winner
-        icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, IcpColor{});
-    }
-    __shared__ double sm[ICP_BLOCK / 64][ICP_SLOTS];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < ICP_SLOTS; q++) {
-        double v = wave_sum(acc[q]);
-        if (lane == 0) sm[wv][q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_SLOTS) {
-        double v = 0;
-        for (int w2 = 0; w2 < ICP_BLOCK / 64; w2++) v += sm[w2][threadIdx.x];
-        partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = v;   // [slot][workgroup]: the step kernel reads a slot's sums as one contiguous run
-    }
-}
-
-// LDS-tiled variant (R3D_ICP_IMPL=tiled; slower than the global path, see r3d_icp): one wave per 64 consecutive source points.  The source is Morton-ordered, so the cells of a
-// wave's queries form a small box; the wave stages the box's cell-start entries and all target points of the box (+-1 cell)
-// into LDS with coalesced loads, and every lane then walks its own nine runs out of LDS in the same order as
-// nn_block_global (identical results).  Boxes that do not fit (spread-out chunks) use the global path for that chunk.
-constexpr int TL_MAXROWS = 64, TL_MAXW = 15, TL_MAXPTS = 512, TL_CSP = TL_MAXW + 2;
-
-template <int MODE>
-__global__ void __launch_bounds__(64) k_icp_eval_t(GridView g, const double *__restrict__ src, const double *__restrict__ src_n,
-                                                   const double *__restrict__ tgt_n, int64_t ns, const IcpState *__restrict__ st, double max_dist, double eps,
-                                                   double *__restrict__ partial, int *__restrict__ corr) {
-    __shared__ double lx[TL_MAXPTS], ly[TL_MAXPTS], lz[TL_MAXPTS];
-    __shared__ int lcs[TL_MAXROWS * TL_CSP];  // cell starts of each box row: bw + 1 entries
-    __shared__ int lbase[TL_MAXROWS + 1];     // LDS offset of each box row's points
-    if (st->done) return;
-    const Rigid T = load_rigid(st);
-    const int lane = threadIdx.x;
-    double acc[ICP_SLOTS];
-#pragma unroll
-    for (int q = 0; q < ICP_SLOTS; q++) acc[q] = 0;
-    const double r2 = max_dist * max_dist;
-    const int smax = (int)ceil(max_dist * g.inv_cell);
-    for (int64_t i0 = (int64_t)blockIdx.x * 64; i0 < ns; i0 += (int64_t)gridDim.x * 64) {
-        const int64_t i = i0 + lane;
-        const bool live = i < ns;
-        const int64_t ic = live ? i : ns - 1;
-        const double sx = src[ic * 3], sy = src[ic * 3 + 1], sz = src[ic * 3 + 2];
-        const double px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
-        const double py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
-        const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
-        const int cx = cell_coord(px, g.ox, g.inv_cell), cy = cell_coord(py, g.oy, g.inv_cell), cz = cell_coord(pz, g.oz, g.inv_cell);
-        // box of the (clamped) query cells, +-1
-        int mnx = min(max(cx, 0), g.nx - 1), mny = min(max(cy, 0), g.ny - 1), mnz = min(max(cz, 0), g.nz - 1);
-        int mxx = mnx, mxy = mny, mxz = mnz;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mnx = min(mnx, __shfl_xor(mnx, o)); mny = min(mny, __shfl_xor(mny, o)); mnz = min(mnz, __shfl_xor(mnz, o));
-            mxx = max(mxx, __shfl_xor(mxx, o)); mxy = max(mxy, __shfl_xor(mxy, o)); mxz = max(mxz, __shfl_xor(mxz, o));
-        }
-        const int bx0 = max(mnx - 1, 0), bx1 = min(mxx + 1, g.nx - 1), by0 = max(mny - 1, 0), by1 = min(mxy + 1, g.ny - 1);
-        const int bz0 = max(mnz - 1, 0), bz1 = min(mxz + 1, g.nz - 1);
-        const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1, nrows = bh * (bz1 - bz0 + 1);
-        bool tiled = nrows <= TL_MAXROWS && bw <= TL_MAXW;  // wave-uniform
-        int total = 0;
-        if (tiled) {
-            for (int e = lane; e < nrows * (bw + 1); e += 64) {
-                const int r = e / (bw + 1), c = e - r * (bw + 1);
-                const int z = bz0 + r / bh, y = by0 + r % bh;
-                lcs[r * TL_CSP + c] = cs1(g, ((int64_t)z * g.ny + y) * g.nx + bx0 + c);
-            }
-            __syncthreads();
-            const int len = lane < nrows ? lcs[lane * TL_CSP + bw] - lcs[lane * TL_CSP] : 0;
-            int incl = len;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o);
-                if (lane >= o) incl += t;
-            }
-            total = __shfl(incl, 63);
-            if (lane < nrows) lbase[lane] = incl - len;
-            if (lane == 0) lbase[nrows] = total;
-            tiled = total <= TL_MAXPTS;
-        }
-        if (tiled) {
-            __syncthreads();
-            for (int t = lane; t < total; t += 64) {
-                int lo = 0, hi = nrows;  // row with lbase[lo] <= t < lbase[lo + 1]
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (lbase[mid] <= t) lo = mid;
-                    else hi = mid;
-                }
-                const int64_t j = lcs[lo * TL_CSP] + (t - lbase[lo]);
-                lx[t] = g.pts[j * 3]; ly[t] = g.pts[j * 3 + 1]; lz[t] = g.pts[j * 3 + 2];
-            }
-            __syncthreads();
-        }
-        double best = r2;
-        int bi = -1;
-        if (live) {
-            if (tiled) {
-                const int xa = cx - 1, xb = cx + 1;
-                const bool xok = xb >= 0 && xa <= g.nx - 1;
-                const int x0 = min(max(xa, 0), g.nx - 1) - bx0, x1 = min(max(xb, 0), g.nx - 1) - bx0;
-#pragma unroll
-                for (int r = 0; r < 9; r++) {
-                    const int z = cz + r / 3 - 1, y = cy + r % 3 - 1;
-                    if (!(xok && z >= 0 && z < g.nz && y >= 0 && y < g.ny)) continue;
-                    const int row = (z - bz0) * bh + (y - by0);
-                    const int *cs = lcs + row * TL_CSP;
-                    const int gb = cs[0], off = lbase[row] - gb;  // LDS slot = global slot + off
-                    const int te = cs[x1 + 1] + off;
-                    for (int t = cs[x0] + off; t < te; t++) {
-                        const double dx = lx[t] - px, dy = ly[t] - py, dz = lz[t] - pz;
-                        const double d2 = dx * dx + dy * dy + dz * dz;
-                        if (d2 <= best) {
-                            const int j = t - off;
-                            if (d2 < best || (bi >= 0 && g.idx[j] < g.idx[bi])) { best = d2; bi = j; }
-                        }
-                    }
-                }
-            } else {
-                nn_block_global(g, px, py, pz, cx, cy, cz, best, bi);
-            }
-            nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
-            if (corr) corr[i] = bi >= 0 ? g.idx[bi] : -1;
-            if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, IcpColor{});
-        }
-        __syncthreads();  // the next chunk overwrites the tile
-    }
-#pragma unroll
-    for (int q = 0; q < ICP_SLOTS; q++) {
-        const double v = wave_sum(acc[q]);
-        if (lane == 0) partial[(size_t)q * gridDim.x + blockIdx.x] = v;
-    }
-}
-
 // r3d_debug_icp_correspondences: brings one evaluation's correspondences back to the caller's numbering.  `corr` is indexed by the
-// Morton-sorted source and holds target slots (k_icp_search's output, from_slots) or target original indices (k_icp_eval's corr);
-// `perm` is the source sort.  The squared distance is recomputed with the search's own expression, as k_icp_accum does.
-__global__ void __launch_bounds__(256) k_icp_corr_readout(GridView g, const double *__restrict__ src, const int *__restrict__ perm, int64_t ns,
+// Morton-sorted source and holds target original indices (k_icp_eval's corr); `perm` is the source sort.  The squared distance
+// is recomputed with the search's own expression.
+__global__ void __launch_bounds__(256) k_icp_corr_readout(const double *__restrict__ src, const int *__restrict__ perm, int64_t ns,
                                                           const IcpState *__restrict__ st, const double *__restrict__ tgt /* caller's order */,
-                                                          const int *__restrict__ corr, int from_slots, int *__restrict__ corr_out,
-                                                          double *__restrict__ d2_out) {
+                                                          const int *__restrict__ corr, int *__restrict__ corr_out, double *__restrict__ d2_out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= ns) return;
     const Rigid T = load_rigid(st);
-    int c = corr[i];
-    if (from_slots && c >= 0) c = g.idx[c];
+    const int c = corr[i];
     double d2 = 1e300;
     if (c >= 0) {
         const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
@@ -3021,7 +2667,7 @@ int grid_build(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, doubl
             k_cell_counts2<unsigned long long><<<nbd, 256, 0, ctx->stream>>>((const unsigned long long *)G.keys, n, rs, cnt);
         }
         if ((rc = dev_exclusive_scan<int>(ctx, ar, cnt, cs, G.ncells + 1))) return rc;
-        G.v = GridView{G.mn[0], G.mn[1], G.mn[2], cell, 1.0 / cell, dims[0], dims[1], dims[2], nullptr, nullptr, cs, sorted, idx, nullptr, nullptr, nullptr, 0.f, nullptr};
+        G.v = GridView{G.mn[0], G.mn[1], G.mn[2], cell, 1.0 / cell, dims[0], dims[1], dims[2], nullptr, nullptr, cs, sorted, idx, nullptr};
         return R3D_OK;
     }
     // two-level cell table from the sorted keys (GridView::l1 / l2); sized for the worst case, only materialised lines are touched
@@ -3043,7 +2689,7 @@ int grid_build(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, doubl
     if (G.keys32) k_line_fill<unsigned><<<(unsigned)((n + 256) / 256), 256, 0, ctx->stream>>>((const unsigned *)G.keys, n, l1, nl, l2);
     else k_line_fill<unsigned long long><<<(unsigned)((n + 256) / 256), 256, 0, ctx->stream>>>((const unsigned long long *)G.keys, n, l1, nl, l2);
     R3D_HIP(ctx, hipGetLastError());
-    G.v = GridView{G.mn[0], G.mn[1], G.mn[2], cell, 1.0 / cell, dims[0], dims[1], dims[2], l1, l2, nullptr, sorted, idx, nullptr, nullptr, nullptr, 0.f, nullptr};
+    G.v = GridView{G.mn[0], G.mn[1], G.mn[2], cell, 1.0 / cell, dims[0], dims[1], dims[2], l1, l2, nullptr, sorted, idx, nullptr};
     return R3D_OK;
 }
 
@@ -4084,56 +3730,22 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     double occ = 3.0;   // points per occupied cell the search grid aims at (R3D_ICP_OCC: A/B)
     if (const char *oe = getenv("R3D_ICP_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 64) occ = v; }
     if ((rc = grid_build(ctx, ar, d_t, nt, p->max_correspondence_distance, occ, G, true, tgt_enclosing, tgt_spacing))) return rc;   // dense table: one load per row in the loop
-    // float32 copy for the two-stage search (R3D_ICP_IMPL=exact: all-float64 search, for A/B).  fe = 2 x bound on
-    // |float distance - exact distance|: both end points are rounded to float (relative 2^-24 per coordinate), times a
-    // safety factor of 2; skipped (exact search) when the coordinates are so large that the margin stops filtering.
+    // packed copy of the target for the default search (nn_block_q10).  Its cell-relative quantisation needs (p - origin) / cell
+    // exact to well below 1/1024: a cloud whose coordinates are that large against its cell keeps the all-float64 search
+    // (nn_block_global), and R3D_ICP_IMPL=exact asks for it on any cloud (the tests' oracle); any other value is ignored
     {
         const char *ie = getenv("R3D_ICP_IMPL");
+        const bool want_exact = ie && strcmp(ie, "exact") == 0;
         double M = 0;
         for (int a = 0; a < 3; a++) M = std::max(M, std::max(std::fabs(G.mn[a]), std::fabs(G.mx[a])));
         const double Mq = M + 2.0 * p->max_correspondence_distance + G.v.cell;
-        const double e = std::sqrt(3.0) * (M + Mq) * std::ldexp(1.0, -24);
-        const bool want_f32 = ie && strcmp(ie, "f32") == 0, want_exact = ie && (strcmp(ie, "exact") == 0 || strcmp(ie, "tiled") == 0);
-        // packed search (default): the cell-relative quantisation needs (p - origin) / cell exact to well below 1/1024
-        if (!want_f32 && !want_exact && Mq / G.v.cell < 1e9) {
+        if (!want_exact && Mq / G.v.cell < 1e9) {
             unsigned *q = (unsigned *)ar.get((size_t)(nt + 4) * sizeof(unsigned));
             if (ar.rc) return ar.rc;
             G.v.q10 = q;
-            // R3D_ICP_POOL=0: every lane walks its own row lists (rounds 2-3; A/B)
-            static const bool pool_env = [] { const char *e = getenv("R3D_ICP_POOL"); return !(e && !strcmp(e, "0")); }();
-            G.v.pool = pool_env ? 1 : 0;
+            G.v.pool = 1;
             k_pack_q10<<<(unsigned)((nt + 4 + 255) / 256), 256, 0, ctx->stream>>>(G.v, nt, q);
             R3D_HIP(ctx, hipGetLastError());
-        } else if (!want_exact && 4.0 * e < 0.25 * G.v.cell && M < 1e30) {
-            float *f = (float *)ar.get((size_t)(nt + 4) * 3 * sizeof(float));
-            if (ar.rc) return ar.rc;
-            k_soa_f32<<<(unsigned)((nt + 4 + 255) / 256), 256, 0, ctx->stream>>>(G.v.pts, nt, f, f + (nt + 4), f + 2 * (nt + 4));
-            R3D_HIP(ctx, hipGetLastError());
-            G.v.fx = f; G.v.fy = f + (nt + 4); G.v.fz = f + 2 * (nt + 4);
-            G.v.fe = (float)(4.0 * e);
-        }
-    }
-    // reach bitmap (GridView::reach): where the search walks outer shells (cell < radius) a query with NO target point within the
-    // radius pays for the whole (2 s + 1)^3 neighbourhood, and the bitmap lets it leave at once.  MEASURED on the 76-frame scan:
-    // no effect (397 vs 397 ms of loops) -- there the walkers are queries whose nearest point lies between one cell and the radius,
-    // not queries far from the model; what helped is a cell as large as the radius (grid_build's spacing_hint: 390 -> 252 ms).
-    // Off by default (R3D_ICP_REACH=1 builds it: three small kernels per registration).
-    {
-        static const bool reach_on = [] { const char *e = getenv("R3D_ICP_REACH"); return e && !strcmp(e, "1"); }();
-        const int rs = (int)std::ceil(p->max_correspondence_distance * G.v.inv_cell);   // = the kernels' smax
-        if (reach_on && rs >= 2) {
-            const int rnx = (G.v.nx + rs - 1) / rs, rny = (G.v.ny + rs - 1) / rs, rnz = (G.v.nz + rs - 1) / rs;
-            const int64_t rn = (int64_t)rnx * rny * rnz;
-            unsigned char *ra = (unsigned char *)ar.get((size_t)rn), *rb = (unsigned char *)ar.get((size_t)rn);
-            if (ar.rc) return ar.rc;
-            R3D_HIP(ctx, hipMemsetAsync(ra, 0, (size_t)rn, ctx->stream));
-            k_reach_mark<<<(unsigned)((nt + 255) / 256), 256, 0, ctx->stream>>>(G.v, nt, rs, rnx, rny, rnz, ra);
-            const unsigned nbr = (unsigned)((rn + 255) / 256);
-            k_reach_dilate<<<nbr, 256, 0, ctx->stream>>>(ra, rb, rn, 1, rnx);
-            k_reach_dilate<<<nbr, 256, 0, ctx->stream>>>(rb, ra, rn, rnx, rny);
-            k_reach_dilate<<<nbr, 256, 0, ctx->stream>>>(ra, rb, rn, (int64_t)rnx * rny, rnz);
-            R3D_HIP(ctx, hipGetLastError());
-            G.v.reach = rb; G.v.rs = rs; G.v.rnx = rnx; G.v.rny = rny; G.v.rnz = rnz;
         }
     }
     double *d_tns = nullptr;
@@ -4182,55 +3794,34 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
             colk.src_i = d_si;
         }
     }
-    // default: per-lane search straight from global memory (L1/L2-cached gathers), two-stage (float32 top-4, exact top-3:
-    // nn_block_top4; R3D_ICP_IMPL=exact keeps every distance in float64); R3D_ICP_IMPL=tiled selects the LDS-tiled
-    // kernel, kept for A/B: measured 0.31 vs 0.26 ms per GICP iteration at 1M points (staging + barriers cost more than
-    // the gathers they replace once the source is Morton-ordered)
-    const char *impl_env = getenv("R3D_ICP_IMPL");
-    const bool tiled_impl = impl_env && strcmp(impl_env, "tiled") == 0;
     // one residency of the chip (3 workgroups per CU at the kernel's register count): every wave starts at once, walks its share
     // of the queries in a grid-stride loop and pays the 29-slot reduction once
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const int nblocks = tiled_impl ? (int)std::min<int64_t>((ns + 63) / 64, 8192)
-                                   : (int)std::min<int64_t>((ns + ICP_BLOCK - 1) / ICP_BLOCK, (int64_t)std::max(cus, 1) * 3);
+    const int nblocks = (int)std::min<int64_t>((ns + ICP_BLOCK - 1) / ICP_BLOCK, (int64_t)std::max(cus, 1) * 3);
     double *d_part = (double *)ar.get((size_t)nblocks * ICP_SLOTS * 8);
     IcpState *d_st = (IcpState *)ar.get(sizeof(IcpState));
+    if (ar.rc) return ar.rc;
     // small source clouds (at most two workgroups per CU: every gather of the scan is a full round trip) take the search form
     // that keeps three candidate groups in flight; R3D_ICP_DEEP=0 / 1 forces either form (A/B)
     static const int deep_env = [] { const char *e = getenv("R3D_ICP_DEEP"); return !e ? -1 : atoi(e) != 0; }();
     const bool deep_search = deep_env >= 0 ? deep_env == 1 : ns <= (int64_t)ICP_BLOCK * std::max(cus, 1) * 2;
-    // R3D_ICP_SPLIT=1: search and accumulation as two kernels (A/B; same partial sums bit for bit)
-    static const bool split_env = [] { const char *e = getenv("R3D_ICP_SPLIT"); return e && !strcmp(e, "1"); }();
-    const bool split_impl = split_env && !tiled_impl;
-    if (color && tiled_impl) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "icp_colored: the LDS-tiled kernel (R3D_ICP_IMPL=tiled) has no coloured mode");
-    if (color && split_impl) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "icp_colored: the two-kernel evaluation (R3D_ICP_SPLIT=1) has no coloured mode");
-    int *d_nn = split_impl ? (int *)ar.get((size_t)ns * 4) : nullptr;
-    if (ar.rc) return ar.rc;
+    const int search = !G.v.q10 ? SEARCH_EXACT : deep_search ? SEARCH_Q10_DEEP : SEARCH_Q10;
     static_assert(sizeof(IcpState) <= ICP_SLOTS * sizeof(double), "the pinned landing buffer holds one IcpState");
-    if (!ctx->icp_ev) R3D_HIP(ctx, hipEventCreateWithFlags(&ctx->icp_ev, hipEventDisableTiming));
     if (!ctx->icp_host) R3D_HIP(ctx, hipHostMalloc((void **)&ctx->icp_host, ICP_SLOTS * sizeof(double), hipHostMallocMapped));
     IcpState *hst = (IcpState *)ctx->icp_host;   // pinned and mapped: k_icp_step publishes the state here, the host polls it
-    // R3D_ICP_WAIT=event: the round-1/2 form (D2H copy of the state + an event polled with hipEventQuery), kept for A/B
-    static const bool wait_event = [] { const char *e = getenv("R3D_ICP_WAIT"); return e && !strcmp(e, "event"); }();
     IcpState *d_mirror = nullptr;
-    if (!wait_event) R3D_HIP(ctx, hipHostGetDevicePointer((void **)&d_mirror, hst, 0));
+    R3D_HIP(ctx, hipHostGetDevicePointer((void **)&d_mirror, hst, 0));
     memset(hst, 0, sizeof *hst);
     memcpy(hst->T, T, sizeof T);
     R3D_HIP(ctx, hipMemcpyAsync(d_st, hst, sizeof *hst, hipMemcpyHostToDevice, ctx->stream));
     const int max_it = p->max_iteration;
     // one evaluation + one step of the loop, enqueued without waiting (both return at once when the loop has ended)
-    // (`corr`: the read-out's one evaluation -- the kernels' optional output, and no step behind it; the loop passes nullptr)
+    // (`corr`: the read-out's one evaluation -- the kernel's optional output, and no step behind it; the loop passes nullptr)
     auto enqueue_eval = [&](bool publish, int *corr = nullptr) {
         const double eps = p->gicp_epsilon > 0 ? p->gicp_epsilon : 1e-3;
         const double md = p->max_correspondence_distance;
-        if (tiled_impl) {
-            switch (p->mode) {
-                case MODE_P2P: k_icp_eval_t<MODE_P2P><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
-                case MODE_P2PLANE: k_icp_eval_t<MODE_P2PLANE><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
-                default: k_icp_eval_t<MODE_GICP><<<nblocks, 64, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr); break;
-            }
-        } else {
+        // one kernel per search form x mode
 #define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr, colk)
 #define R3D_ICP_MODES(S)                                            \
     switch (p->mode) {                                              \
@@ -4239,25 +3830,13 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
         case MODE_COLORED: R3D_ICP_LAUNCH(MODE_COLORED, S); break;  \
         default: R3D_ICP_LAUNCH(MODE_GICP, S); break;               \
     }
-            if (split_impl) {
-                // the search writes one slot per query, so its grid is free: one residency at ITS occupancy (4 workgroups per CU)
-                const int nsearch = (int)std::min<int64_t>((ns + ICP_BLOCK - 1) / ICP_BLOCK, (int64_t)std::max(cus, 1) * 4);
-                if (G.v.q10) k_icp_search<SEARCH_Q10><<<nsearch, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, ns, d_st, md, d_nn);
-                else if (G.v.fx) k_icp_search<SEARCH_F32><<<nsearch, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, ns, d_st, md, d_nn);
-                else k_icp_search<SEARCH_EXACT><<<nsearch, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, ns, d_st, md, d_nn);
-                switch (p->mode) {
-                    case MODE_P2P: k_icp_accum<MODE_P2P><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, eps, d_nn, d_part); break;
-                    case MODE_P2PLANE: k_icp_accum<MODE_P2PLANE><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, eps, d_nn, d_part); break;
-                    default: k_icp_accum<MODE_GICP><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, eps, d_nn, d_part); break;
-                }
-            } else
-            if (G.v.q10 && deep_search) { R3D_ICP_MODES(SEARCH_Q10_DEEP) }
-            else if (G.v.q10) { R3D_ICP_MODES(SEARCH_Q10) }
-            else if (G.v.fx) { R3D_ICP_MODES(SEARCH_F32) }
-            else { R3D_ICP_MODES(SEARCH_EXACT) }
+        switch (search) {
+            case SEARCH_Q10_DEEP: R3D_ICP_MODES(SEARCH_Q10_DEEP) break;
+            case SEARCH_Q10: R3D_ICP_MODES(SEARCH_Q10) break;
+            default: R3D_ICP_MODES(SEARCH_EXACT) break;
+        }
 #undef R3D_ICP_MODES
 #undef R3D_ICP_LAUNCH
-        }
         if (corr) return;
         k_icp_step<<<1, 1024, 0, ctx->stream>>>(d_part, nblocks, d_st, ns, p->mode, max_it, p->relative_fitness, p->relative_rmse, d_mirror,
                                                 publish ? 1 : 0);
@@ -4267,9 +3846,7 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
         double *d_d2_out = (double *)ar.get((size_t)ns * 8);
         if (ar.rc) return ar.rc;
         enqueue_eval(false, d_corr);
-        // the split form's search writes target slots to d_nn (and leaves `corr` alone): converted through g.idx here
-        k_icp_corr_readout<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(G.v, d_s, sidx, ns, d_st, d_t, split_impl ? d_nn : d_corr,
-                                                                                  split_impl ? 1 : 0, d_corr_out, d_d2_out);
+        k_icp_corr_readout<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(d_s, sidx, ns, d_st, d_t, d_corr, d_corr_out, d_d2_out);
         R3D_HIP(ctx, hipGetLastError());
         R3D_HIP(ctx, hipMemcpyAsync(readout->corr, d_corr_out, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (readout->d2) R3D_HIP(ctx, hipMemcpyAsync(readout->d2, d_d2_out, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -4280,8 +3857,8 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     const auto t_loop = std::chrono::steady_clock::now();
     // The loop of RegistrationICP (evaluate, test, update) runs on the device; the host enqueues ICP_BATCH evaluations at a
     // time and reads the state back once per batch (a host round trip per iteration cost ~50 us of a 0.22 ms iteration).
-    // Polling an event instead of a blocking stream synchronise: the blocking wait may put the thread to sleep for a
-    // scheduler tick (occasional 40-50 ms waits).
+    // The host polls the state that k_icp_step publishes in a mapped host buffer instead of a blocking stream synchronise: the
+    // blocking wait may put the thread to sleep for a scheduler tick (occasional 40-50 ms waits).
     // A WINDOW of evaluations stays enqueued: ICP_BATCH at first, then ICP_STRIDE more whenever all but ICP_STRIDE of them have
     // been consumed -- the device never runs dry while the host notices a batch's end and enqueues the next (that hand-over
     // left the GPU idle for ~40 us per 8 iterations: profiles/r04_icp_timeline.txt).  k_icp_step publishes its state to the
@@ -4302,36 +3879,24 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
             // evaluations remain to be enqueued behind them); a step that ENDS the loop publishes by itself
             const int sno = enq + 1, first_need = ICP_BATCH - ICP_STRIDE;
             const bool awaited = sno == total || (sno >= first_need && (sno - first_need) % ICP_STRIDE == 0 && sno + ICP_STRIDE < total);
-            enqueue_eval(wait_event || awaited);
+            enqueue_eval(awaited);
         }
         R3D_HIP(ctx, hipGetLastError());
-        if (wait_event) {
-            R3D_HIP(ctx, hipMemcpyAsync(hst, d_st, sizeof *hst, hipMemcpyDeviceToHost, ctx->stream));
-            R3D_HIP(ctx, hipEventRecord(ctx->icp_ev, ctx->stream));
-        }
-        // evaluations that must have been consumed before the host goes on: everything at the end (and in event mode, where
-        // the copy is ordered behind the whole batch), all but the last ICP_STRIDE otherwise
-        const int need = (enq >= total || wait_event) ? enq : enq - ICP_STRIDE;
-        // Bounded wait: either the state k_icp_step publishes in the mapped host buffer (`seq` reaches `need`, or the DONE bit),
-        // or (R3D_ICP_WAIT=event) the event behind a D2H copy of the state.  A tight spin for
-        // the first 200 us (a batch of a small cloud is shorter than a sleep), then the thread yields between polls (a bare
-        // hipEventQuery spin hammers the runtime's stream lock, which a profiler's completion handlers also need).  The deadline
-        // scales with the work enqueued (serialised counter passes are ~100x slower than a plain run); on expiry the call fails
-        // with the last state read so the caller exits non-zero.
+        // evaluations that must have been consumed before the host goes on: everything at the end, all but the last ICP_STRIDE
+        // otherwise
+        const int need = enq >= total ? enq : enq - ICP_STRIDE;
+        // Bounded wait for the state k_icp_step publishes in the mapped host buffer (`seq` reaches `need`, or the DONE bit).  A
+        // tight spin for the first 200 us (a batch of a small cloud is shorter than a sleep), then the thread yields between
+        // polls.  The deadline scales with the work enqueued (serialised counter passes are ~100x slower than a plain run); on
+        // expiry the call fails with the last state read so the caller exits non-zero.
         const auto t_poll = std::chrono::steady_clock::now();
         const double deadline_s = 20.0 + 2e-6 * (double)(ns + nt) * ICP_BATCH;
         for (unsigned spins = 0;; spins++) {
-            if (wait_event) {
-                const hipError_t q = hipEventQuery(ctx->icp_ev);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) return r3d_fail(ctx, R3D_E_HIP, "hipEventQuery failed: %s", hipGetErrorString(q));
-            } else {
-                // `seq` is the last word k_icp_step stores, behind a system-scope fence: once it shows the awaited step, or the
-                // DONE bit, every other field of that step is visible
-                const int seq = *(volatile int *)&hst->seq;
-                std::atomic_thread_fence(std::memory_order_acquire);
-                if ((seq & ~ICP_SEQ_DONE) >= need || (seq & ICP_SEQ_DONE)) { loop_done = (seq & ICP_SEQ_DONE) != 0; break; }
-            }
+            // `seq` is the last word k_icp_step stores, behind a system-scope fence: once it shows the awaited step, or the
+            // DONE bit, every other field of that step is visible
+            const int seq = *(volatile int *)&hst->seq;
+            std::atomic_thread_fence(std::memory_order_acquire);
+            if ((seq & ~ICP_SEQ_DONE) >= need || (seq & ICP_SEQ_DONE)) { loop_done = (seq & ICP_SEQ_DONE) != 0; break; }
             if ((spins & 63) != 63) continue;
             const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count();
             if (waited > deadline_s) {
@@ -4341,11 +3906,10 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
             }
             if (waited > 2e-4) std::this_thread::sleep_for(std::chrono::microseconds(waited > 5e-3 ? 200 : 20));
         }
-        if (wait_event) loop_done = hst->done != 0;   // (the copy behind the event is complete: all fields are of one step)
         if (loop_done) break;
     }
     if (!loop_done) return r3d_fail(ctx, R3D_E_HIP, "registration loop did not finish (%d evaluations)", hst->evals);
-    // (in mirror mode evaluations enqueued behind the step that ended the loop may still be in flight: they return at their first
+    // (evaluations enqueued behind the step that ended the loop may still be in flight: they return at their first
     // instruction (`done`), and everything this call or the next enqueues is ordered behind them on the same stream)
     memcpy(T, hst->T, sizeof T);
     const int it = hst->iterations, converged = hst->converged;
@@ -5715,13 +5279,6 @@ int r3d_transform_blocks_dev(r3d_ctx *ctx, int32_t n_blocks, const double *const
 }  // extern "C"
 
 // diagnostic: the cell sort on its own (tests compare both implementations with a host lexsort)
-#ifdef R3D_ICP_STATS
-extern "C" int r3d_debug_icp_stats(uint64_t *out16, int reset) {
-    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_icp_stats), 16 * 8) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[16] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_icp_stats), z, 16 * 8) != hipSuccess) return -1; }
-    return 0;
-}
-#endif
 extern "C" int r3d_debug_sort_by_cell(r3d_ctx *ctx, const double *xyz, int64_t n, const double *org3, double cell, const int32_t *dims3, int32_t key_order,
                                       int32_t impl, int32_t *idx_out, uint64_t *keys_out) {
     R3D_ROCTX_RANGE("r3d_debug_sort_by_cell");

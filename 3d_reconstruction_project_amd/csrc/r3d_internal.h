@@ -73,7 +73,6 @@ struct r3d_ctx {
     int n_acc = 0;
     // cloud workspace (cloud.hip)
     std::vector<r3d_buf> cloud_bufs;
-    hipEvent_t icp_ev = nullptr;   // polled once per registration iteration
     double *icp_host = nullptr;    // pinned landing buffer of the per-iteration sums
     unsigned pin_seq = 0;          // sequence number of the latest PinRead
     void *pin = nullptr;           // pinned landing buffer of the small device -> host reads between kernels (R3D_PIN_BYTES)

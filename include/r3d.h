@@ -56,7 +56,7 @@ int r3d_debug_sort_by_cell(r3d_ctx *ctx, const double *xyz, int64_t n, const dou
  * (values >= 0).  out[i] = op over in[0 .. i-1], out[0] = 0. */
 int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t n, int32_t op, int32_t *out);
 /* diagnostic: the registration's correspondence search on its own.  Runs r3d_icp's set-up in the point-to-point mode (target grid,
- * packed / float32 / exact candidate selection, Morton sort of the source; the same R3D_ICP_* and R3D_CELL_TABLE switches) and ONE
+ * packed / exact candidate selection, Morton sort of the source; the same R3D_ICP_* and R3D_CELL_TABLE switches) and ONE
  * evaluation at pose T4x4 (NULL: identity).  corr_out[i]: index into tgt of the target nearest to T * src[i] under (squared
  * distance, index), or -1 when that distance is not below max_correspondence_distance; d2_out (may be NULL): the squared
  * distance, 1e300 where there is none. */
@@ -302,7 +302,7 @@ int r3d_color_gradients(r3d_ctx *ctx, const double *xyz, const double *normals, 
                         int32_t max_nn, double *out_intensity, double *out_gradient);
 /* Required: source colours, target colours, target normals (no source normals).  R3D_E_BADARG: one of them missing,
  * lambda_geometric outside [0, 1], gradient_max_nn > 128.  The _dev form takes DEVICE clouds and, like r3d_icp_dev, returns when
- * the loop has finished.  The A/B kernel forms (R3D_ICP_IMPL=tiled, R3D_ICP_SPLIT=1) have no coloured mode: R3D_E_UNSUPPORTED. */
+ * the loop has finished. */
 int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *src, const double *src_colors, int64_t ns,
                     const double *tgt, const double *tgt_normals, const double *tgt_colors, int64_t nt, const double *init4x4,
                     double *T4x4, r3d_icp_stats *stats);

@@ -133,8 +133,8 @@ def _run_child(table, env_add):
     return dict(ln.split()[1:3] for ln in o.stdout.splitlines() if ln.startswith("DIG "))
 
 
-NN_VARIANTS = [{}, {"R3D_ICP_DEEP": "0"}, {"R3D_ICP_DEEP": "0", "R3D_ICP_POOL": "0"}, {"R3D_ICP_IMPL": "exact"}, {"R3D_ICP_IMPL": "f32"},
-               {"R3D_ICP_IMPL": "tiled"}, {"R3D_ICP_SPLIT": "1"}, {"R3D_ICP_REACH": "1"}]
+# the three shipping forms: three candidate groups in flight (what sources this small take by default), the pooled walk, all-float64
+NN_VARIANTS = [{}, {"R3D_ICP_DEEP": "0"}, {"R3D_ICP_IMPL": "exact"}]
 
 
 @pytest.mark.parametrize("env_add", NN_VARIANTS, ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()) or "default")
@@ -144,6 +144,54 @@ def test_icp_search_variant_equals_brute_force(env_add):
     assert set(got) == set(want)
     wrong = [cid for cid in want if got[cid] != want[cid]]
     assert not wrong, f"{len(wrong)} of {len(want)} cases differ from the brute-force reference: {wrong}"
+
+
+# the switches of the retired search, kernel and wait forms, each at the value that used to select the form
+RETIRED_SWITCHES = {"R3D_ICP_IMPL": "tiled", "R3D_ICP_SPLIT": "1", "R3D_ICP_REACH": "1", "R3D_ICP_POOL": "0", "R3D_ICP_WAIT": "event"}
+
+
+def retired_child_main(with_table):
+    """runs in a child process: the digests of the nn table if asked, then one coloured registration on the scene of
+    tests/test_colored_icp_gpu.py (4 000 source points on 6 000), as the bytes of its result"""
+    import importlib
+    from tests import colored_icp_ref as cr
+    if with_table:
+        child_main("nn")
+    r3d = importlib.import_module("3d_reconstruction_project_amd")
+    s, sc, t, tn, tc, _ = cr.scene(relief=1e-3, tint=(1.1, 1.0, 0.9))
+    res = r3d.cloud_ops.registration_colored(s, sc, t, tn, tc, 0.02)
+    print("COL", res["T"].tobytes().hex(), res["iterations"], res["correspondences"], flush=True)
+
+
+def test_left_over_values_of_retired_switches_change_nothing():
+    """R3D_ICP_IMPL=tiled, R3D_ICP_SPLIT, R3D_ICP_REACH, R3D_ICP_POOL and R3D_ICP_WAIT used to select search, kernel and wait forms
+    that are gone, and the first two made the coloured mode fail with R3D_E_UNSUPPORTED.  With all five left over in the
+    environment the correspondences still equal the brute-force reference, and a coloured registration returns, with the bytes
+    it returns without them.  In child processes, since the switches were read once per process."""
+    code = f"import sys; sys.path.insert(0, {ROOT!r}); from tests import test_neighbor_search_gpu as t; t.retired_child_main(%s)"
+    clean = {k: v for k, v in os.environ.items() if k not in RETIRED_SWITCHES}
+    # (the two children run side by side: most of a child's time is its start-up)
+    children = [subprocess.Popen([sys.executable, "-c", code % with_table], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
+                for with_table, env in ((True, dict(clean, **RETIRED_SWITCHES)), (False, clean))]
+    outs = []
+    try:
+        for c in children:
+            out, err = c.communicate(timeout=600)
+            assert c.returncode == 0, f"child exited {c.returncode}\n{out[-2000:]}\n{err[-4000:]}"
+            outs.append(out.splitlines())
+    finally:
+        for c in children:
+            if c.poll() is None:
+                c.kill()
+                c.wait()
+    got = dict(ln.split()[1:3] for ln in outs[0] if ln.startswith("DIG "))
+    want = {cid: nr.digest(*nr.nn_reference(cid)) for cid, *_ in nr.nn_table()}
+    assert set(got) == set(want)
+    wrong = [cid for cid in want if got[cid] != want[cid]]
+    assert not wrong, f"{len(wrong)} of {len(want)} cases differ from the brute-force reference: {wrong}"
+    col = [[ln.split() for ln in out if ln.startswith("COL ")] for out in outs]
+    assert len(col[0]) == 1 and col[0] == col[1], col
+    assert int(col[0][0][2]) > 0 and int(col[0][0][3]) > 2000        # the loop iterated on most of the 4 000 source points
 
 
 def test_knn_with_the_dense_cell_table_equals_brute_force():
