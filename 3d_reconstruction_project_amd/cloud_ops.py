@@ -179,6 +179,8 @@ _lib.register({
     "r3d_model_clear": ([_vp], ctypes.c_int),
     "r3d_model_size": ([_vp, _i64p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "r3d_model_voxel_table_stats": ([_vp, _i64p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "r3d_model_debug_voxel_table": ([_vp, ctypes.c_double, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _i64p, ctypes.POINTER(ctypes.c_int32)],
+                                    ctypes.c_int),
     "r3d_model_append": ([_vp, _vp, _vp, _vp, ctypes.c_int64], ctypes.c_int),
     "r3d_model_align_append": ([_vp, ctypes.POINTER(AlignParams), _vp, _vp, ctypes.c_int64, _vp, ctypes.POINTER(_lib.IcpStats), _i64p],
                                ctypes.c_int),
@@ -599,6 +601,23 @@ class ResidentModel:
         v, r, u = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
         self._call("r3d_model_voxel_table_stats", ctypes.byref(v), ctypes.byref(r), ctypes.byref(u))
         return v.value, r.value, u.value
+
+    def debug_voxel_table(self, voxel, cap=None):
+        """r3d_model_debug_voxel_table: the model's legacy voxel grid as the next align_append(voxel_size=voxel) would see it,
+        entry by entry in ascending (kx, ky, kz) order: keys (uint64, kx << 42 | ky << 21 | kz), sums [n,3], counts, means [n,3],
+        box [6] and resident.  Without a resident table keys / sums / counts are None; with more than `cap` voxels (default: room
+        for any table) every array is None and only n and resident are reported."""
+        cap = self.size()[0] if cap is None else int(cap)
+        keys, sums, counts = np.empty(cap, np.uint64), np.empty((cap, 3)), np.empty(cap, np.int32)
+        means, box = np.empty((cap, 3)), np.empty(6)
+        n, res = ctypes.c_int64(), ctypes.c_int32()
+        self._call("r3d_model_debug_voxel_table", float(voxel), cap, _ptr(keys), _ptr(sums), _ptr(counts), _ptr(means), _ptr(box),
+                   ctypes.byref(n), ctypes.byref(res))
+        n, res = n.value, bool(res.value)
+        if n > cap:
+            return dict(n=n, resident=res, keys=None, sums=None, counts=None, means=None, box=None)
+        tab = (keys[:n].copy(), sums[:n].copy(), counts[:n].copy()) if res else (None, None, None)
+        return dict(n=n, resident=res, keys=tab[0], sums=tab[1], counts=tab[2], means=means[:n].copy(), box=box)
 
     def clear(self):
         self._call("r3d_model_clear")

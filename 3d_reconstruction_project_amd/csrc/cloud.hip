@@ -2110,7 +2110,8 @@ __global__ void __launch_bounds__(256) k_backproject(const unsigned short *__res
 // the table keeps, per occupied voxel in lexicographic (kx, ky, kz) order, the packed key, the running float64 sums and the
 // count; a new frame's points are sorted by (voxel, index), every run is added member by member onto its voxel's running sum
 // (or starts a new voxel from zero), and the new voxels are merged into the sorted table.  means = sums / count are then bit for
-// bit those of a full re-voxelisation (tests/test_pipeline_gpu.py asserts it; R3D_MODEL_IMPL=rebuild keeps the full pass).
+// bit those of a full re-voxelisation (tests/test_pipeline_gpu.py asserts it on a recorded scan, tests/test_voxel_edges_gpu.py
+// entry by entry through r3d_model_debug_voxel_table; R3D_MODEL_IMPL=rebuild keeps the full pass).
 __device__ __forceinline__ unsigned long long vt_key_of(const double *__restrict__ p, double ox, double oy, double oz, double voxel) {
     const long long kx = (long long)floor((p[0] - ox) / voxel), ky = (long long)floor((p[1] - oy) / voxel), kz = (long long)floor((p[2] - oz) / voxel);
     return (unsigned long long)kx << 42 | (unsigned long long)ky << 21 | (unsigned long long)kz;   // each index < 2^21 (checked on the host)
@@ -4586,10 +4587,14 @@ int vt_reserve(r3d_model *m, r3d_buf &b, int64_t rows, size_t elem) {
 // pointcloud_alignment.py:23 for the resident model: the legacy voxel grid of ALL model points, as means in lexicographic voxel
 // order in a fresh arena buffer.  Default: the incremental table above (full rebuild whenever the model's minimum corner moved, the
 // voxel size changed or the table does not exist); R3D_MODEL_IMPL=rebuild: the full sort of every model point, every frame.
-int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_out, int64_t *mt_out, double *box_out /* [6]: the model's box */) {
+// table_out (r3d_model_debug_voxel_table): the resident table's device arrays behind the means, all null when there is none
+struct VtView { const unsigned long long *keys = nullptr; const double *sums = nullptr; const int *cnt = nullptr; };
+int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_out, int64_t *mt_out, double *box_out /* [6]: the model's box */,
+                        VtView *table_out = nullptr) {
     r3d_ctx *ctx = m->ctx;
     int rc;
     double *d_t = (double *)m->pts.p;
+    if (table_out) *table_out = VtView();
     static const bool always_rebuild = [] { const char *e = getenv("R3D_MODEL_IMPL"); return e && !strcmp(e, "rebuild"); }();
     if (always_rebuild) {
         VoxelSegs Vt;
@@ -4615,7 +4620,6 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
         for (int a = 0; a < 3; a++) if (!((mx[a] - (mn[a] - 0.5 * voxel)) / voxel < 2097000.0)) return false;
         return true;
     };
-    const unsigned long long *tkeys = nullptr;
     if (rebuild) {
         VoxelSegs Vt;
         double bounds[6];
@@ -4644,7 +4648,7 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
     } else if (ns > 0) {
         double nmx[3], org[3];
         for (int a = 0; a < 3; a++) { nmx[a] = std::max(m->vt_max[a], smx[a]); org[a] = m->vt_min[a] - 0.5 * voxel; }
-        if (!key_space_ok(m->vt_min, nmx)) { m->vt_valid = false; return model_target_voxels(m, ar, voxel, d_tv_out, mt_out, box_out); }
+        if (!key_space_ok(m->vt_min, nmx)) { m->vt_valid = false; return model_target_voxels(m, ar, voxel, d_tv_out, mt_out, box_out, table_out); }
         VoxelSegs V;
         if ((rc = voxel_segments(ctx, ar, d_t + m->vt_pts * 3, ns, voxel, V, false, org, nmx))) return rc;
         const int c = m->vt_cur, o = c ^ 1;
@@ -4678,8 +4682,7 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
         m->vt_updates++;
     }
     m->vt_pts = m->n;
-    tkeys = (const unsigned long long *)m->vt_keys[m->vt_cur].p;
-    (void)tkeys;
+    if (table_out) *table_out = VtView{(const unsigned long long *)m->vt_keys[m->vt_cur].p, (const double *)m->vt_sums[m->vt_cur].p, (const int *)m->vt_cnt[m->vt_cur].p};
     double *d_tv = (double *)ar.get((size_t)m->vt_n * 24);
     if (ar.rc) return ar.rc;
     k_vt_means<<<(unsigned)((m->vt_n + 255) / 256), 256, 0, ctx->stream>>>((const double *)m->vt_sums[m->vt_cur].p, (const int *)m->vt_cnt[m->vt_cur].p, m->vt_n, d_tv);
@@ -4775,6 +4778,38 @@ int r3d_model_align_append(r3d_model *m, const r3d_align_params *p, const double
     if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
     if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
     return model_align_core(m, ar, p, d_s, d_c, ns, T4x4, stats, appended, t_begin);
+}
+
+// diagnostic: the model's voxel grid as the next r3d_model_align_append with this voxel size would see it -- the same
+// model_target_voxels call (the table is brought up to date with every model row, the statistics advance), then the table read out
+// entry by entry (tests/test_voxel_edges_gpu.py compares it with tests/voxel_ref.py)
+int r3d_model_debug_voxel_table(r3d_model *m, double voxel, int64_t cap, uint64_t *keys, double *sums, int32_t *counts, double *means,
+                                double *box6, int64_t *n_out, int32_t *resident) {
+    R3D_ROCTX_RANGE("r3d_model_debug_voxel_table");
+    if (!m) return R3D_E_BADARG;
+    r3d_ctx *ctx = m->ctx;
+    if (m->n <= 0) return r3d_fail(ctx, R3D_E_BADARG, "model_debug_voxel_table: the model is empty");
+    if (!(voxel > 0)) return r3d_fail(ctx, R3D_E_BADARG, "model_debug_voxel_table: voxel must be > 0");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    int rc;
+    double *d_tv = nullptr, box[6];
+    int64_t n = 0;
+    VtView vt;
+    if ((rc = model_target_voxels(m, ar, voxel, &d_tv, &n, box, &vt))) return rc;
+    if (n_out) *n_out = n;
+    if (resident) *resident = vt.keys != nullptr;
+    if (n <= cap) {
+        if (box6) memcpy(box6, box, sizeof box);
+        if (means) R3D_HIP(ctx, hipMemcpyAsync(means, d_tv, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
+        if (vt.keys) {
+            if (keys) R3D_HIP(ctx, hipMemcpyAsync(keys, vt.keys, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (sums) R3D_HIP(ctx, hipMemcpyAsync(sums, vt.sums, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
+            if (counts) R3D_HIP(ctx, hipMemcpyAsync(counts, vt.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
 }
 
 // The same two steps of main.py:34-49 for a frame that is still a DEPTH IMAGE (the recorded frames of test/output84, a RealSense

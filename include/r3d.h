@@ -417,6 +417,15 @@ int r3d_model_size(r3d_model *m, int64_t *n, int32_t *has_colors, int32_t *has_n
  * from all points otherwise (same means bit for bit either way).  Diagnostics: voxels in the table, full rebuilds and incremental
  * updates so far.  Any pointer may be NULL. */
 int r3d_model_voxel_table_stats(r3d_model *m, int64_t *voxels, int32_t *rebuilds, int32_t *updates);
+/* diagnostic: the model's voxel grid entry by entry.  Brings the table up to date with every model row exactly as the next
+ * r3d_model_align_append with this voxel size would (the statistics above advance as they would there), then copies to host
+ * buffers (NULL = skip), one entry per voxel in ascending (kx, ky, kz) order: the packed keys kx << 42 | ky << 21 | kz, the
+ * running sums [n][3], the member counts, the means handed to the registration [n][3] and the model's box (min, max).
+ * *n_out = voxels; when it exceeds cap nothing is copied and the call still succeeds.  *resident = 1 when a table
+ * exists afterwards; 0 (more than 2^21 voxels along an axis, or R3D_MODEL_IMPL=rebuild) leaves keys / sums / counts untouched.
+ * An empty model or voxel <= 0: R3D_E_BADARG. */
+int r3d_model_debug_voxel_table(r3d_model *m, double voxel, int64_t cap, uint64_t *keys, double *sums, int32_t *counts, double *means,
+                                double *box6, int64_t *n_out, int32_t *resident);
 /* combined.points = frame.points ... (main.py:42-45) and `combined += cloud` for host clouds; colors / normals may be NULL */
 int r3d_model_append(r3d_model *m, const double *xyz, const double *colors, const double *normals, int64_t n);
 /* main.py:48-49: aligned = align_point_clouds(frame, combined, threshold, voxel_size, max_iter); combined += aligned.
