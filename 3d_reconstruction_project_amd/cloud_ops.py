@@ -76,6 +76,36 @@ _lib.register({
                                      ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
 })
 
+class FgrParams(ctypes.Structure):
+    """r3d_fgr_params"""
+    _fields_ = [("division_factor", ctypes.c_double), ("maximum_correspondence_distance", ctypes.c_double),
+                ("tuple_scale", ctypes.c_double), ("seed", ctypes.c_uint64), ("iteration_number", ctypes.c_int32),
+                ("maximum_tuple_count", ctypes.c_int32), ("use_absolute_scale", ctypes.c_int32), ("decrease_mu", ctypes.c_int32),
+                ("tuple_test", ctypes.c_int32), ("batch", ctypes.c_int32)]
+
+
+class FgrStats(ctypes.Structure):
+    """r3d_fgr_stats"""
+    _fields_ = [(n, ctypes.c_double) for n in ("fitness", "inlier_rmse", "scale_global", "scale_start", "final_par", "setup_ms",
+                                               "loop_ms")] + \
+               [(n, ctypes.c_int64) for n in ("correspondences", "matched", "trials", "tuples", "pairs")]
+
+
+_fgr_corr_sig = ([_vp, ctypes.POINTER(FgrParams), _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp,
+                  ctypes.POINTER(FgrStats)], ctypes.c_int)
+_fgr_feat_sig = ([_vp, ctypes.POINTER(FgrParams), _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int32, _vp,
+                  ctypes.POINTER(FgrStats)], ctypes.c_int)
+_lib.register({
+    "r3d_fgr_correspondence": _fgr_corr_sig,
+    "r3d_fgr_correspondence_dev": _fgr_corr_sig,
+    "r3d_fgr_feature_matching": _fgr_feat_sig,
+    "r3d_fgr_feature_matching_dev": _fgr_feat_sig,
+    "r3d_debug_fgr_tuples": ([_vp, ctypes.POINTER(FgrParams), _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64,
+                              ctypes.c_int64, _vp, _vp], ctypes.c_int),
+    "r3d_debug_fgr_optimize": ([_vp, ctypes.POINTER(FgrParams), _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp],
+                               ctypes.c_int),
+})
+
 _lib.register({
     "r3d_debug_sort_by_cell": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
     "r3d_debug_exclusive_scan": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp], ctypes.c_int),
@@ -506,6 +536,86 @@ def debug_ransac_hypotheses(source, target, corres, h0, count, max_correspondenc
     return dict(samples=samples, flags=flags, T=T, inliers=inl, err2=err2)
 
 
+def _fgr_params(division_factor=1.4, use_absolute_scale=False, decrease_mu=True, maximum_correspondence_distance=0.025, iteration_number=64,
+                tuple_scale=0.95, maximum_tuple_count=1000, tuple_test=True, seed=0, batch=0):
+    """o3d.pipelines.registration.FastGlobalRegistrationOption's names and defaults, plus seed and batch"""
+    return FgrParams(float(division_factor), float(maximum_correspondence_distance), float(tuple_scale), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                     int(iteration_number), int(maximum_tuple_count), int(bool(use_absolute_scale)), int(bool(decrease_mu)),
+                     int(bool(tuple_test)), int(batch))
+
+
+def _fgr_dict(T, st, **extra):
+    return dict(T=T, fitness=st.fitness, inlier_rmse=st.inlier_rmse, correspondences=st.correspondences, matched=st.matched,
+                trials=st.trials, tuples=st.tuples, pairs=st.pairs, scale_global=st.scale_global, scale_start=st.scale_start,
+                final_par=st.final_par, setup_ms=st.setup_ms, loop_ms=st.loop_ms, **extra)
+
+
+def _evaluation_set(s, t, T, max_distance, ctx):
+    """the correspondence set of the registration loop's evaluation at pose T: (source index, nearest target index) rows"""
+    corr, _ = debug_icp_correspondences(s, t, max_distance, T, False, ctx)
+    hit = np.nonzero(corr >= 0)[0]
+    return np.stack([hit.astype(np.int32), corr[hit]], 1)
+
+
+def registration_fgr_based_on_correspondence(source, target, corres, ctx=None, **option):
+    """o3d.pipelines.registration.registration_fgr_based_on_correspondence(source, target, corres, FastGlobalRegistrationOption(
+    **option)) as a pure function of (inputs, option, seed): DESIGN.md section 4 ("FGR").  `option`: division_factor,
+    use_absolute_scale, decrease_mu, maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count,
+    tuple_test (Open3D's names and defaults), seed (the tuple sampler's) and batch (trials per launch; never changes the result).
+    Returns dict(T, fitness, inlier_rmse, correspondence_set [K, 2] int32, correspondences, matched, trials, tuples, pairs,
+    scale_global, scale_start, final_par, setup_ms, loop_ms); fitness, inlier_rmse and the set are the registration loop's
+    evaluation at T with maximum_correspondence_distance.  Fewer than 10 rows: T is the centroid-to-centroid translation."""
+    ctx = ctx or _lib.default_context()
+    s, t, c = _c(source), _c(target), _corres_rows(corres)
+    prm = _fgr_params(**option)
+    T, st = np.empty((4, 4)), FgrStats()
+    ctx.call("r3d_fgr_correspondence", ctypes.byref(prm), _ptr(s), len(s), _ptr(t), len(t), c.ctypes.data_as(_vp), len(c), _ptr(T),
+             ctypes.byref(st))
+    return _fgr_dict(T, st, correspondence_set=_evaluation_set(s, t, T, prm.maximum_correspondence_distance, ctx))
+
+
+def registration_fgr_based_on_feature_matching(source, target, source_features, target_features, ctx=None, **option):
+    """o3d's function of that name: the mutual pairs of the two nearest-feature searches (the plain cross-check, in ascending
+    source index; not correspondences_from_features' mutual_consistent_ratio fall-back), then the tuple test and the loop of
+    registration_fgr_based_on_correspondence, all on the device.  Features are (33, N) arrays."""
+    ctx = ctx or _lib.default_context()
+    s, t, sf, tf = _c(source), _c(target), _feat_rows(source_features), _feat_rows(target_features)
+    if len(sf) != len(s) or len(tf) != len(t):
+        raise _lib.R3DError(-1, "registration_fgr_based_on_feature_matching: one feature column per point")
+    prm = _fgr_params(**option)
+    T, st = np.empty((4, 4)), FgrStats()
+    ctx.call("r3d_fgr_feature_matching", ctypes.byref(prm), _ptr(s), len(s), _ptr(t), len(t), _ptr(sf), _ptr(tf), FPFH_DIM, _ptr(T),
+             ctypes.byref(st))
+    return _fgr_dict(T, st, correspondence_set=_evaluation_set(s, t, T, prm.maximum_correspondence_distance, ctx))
+
+
+def debug_fgr_tuples(source, target, corres, t0, count, ctx=None, **option):
+    """r3d_debug_fgr_tuples: trials t0 .. t0 + count - 1 of the tuple test over the normalised pairs, without the cut:
+    dict(samples [count, 3] int32, flags [count] int32)"""
+    ctx = ctx or _lib.default_context()
+    s, t, c = _c(source), _c(target), _corres_rows(corres)
+    prm = _fgr_params(**option)
+    n = max(int(count), 0)
+    samples, flags = np.empty((n, 3), np.int32), np.empty(n, np.int32)
+    ctx.call("r3d_debug_fgr_tuples", ctypes.byref(prm), _ptr(s), len(s), _ptr(t), len(t), c.ctypes.data_as(_vp), len(c), int(t0), int(count),
+             samples.ctypes.data_as(_vp), flags.ctypes.data_as(_vp))
+    return dict(samples=samples, flags=flags)
+
+
+def debug_fgr_optimize(source, target, pairs, ctx=None, **option):
+    """r3d_debug_fgr_optimize: the loop alone on the given pairs: dict(trace_T [iteration_number, 4, 4], trace_par
+    [iteration_number]), the composed transform (target -> source) and the annealing parameter after every iteration, in
+    normalised units; fewer than 10 pairs: the start state"""
+    ctx = ctx or _lib.default_context()
+    s, t, c = _c(source), _c(target), _corres_rows(pairs)
+    prm = _fgr_params(**option)
+    it = max(prm.iteration_number, 0)
+    trace_T, trace_par = np.empty((it, 4, 4)), np.empty(it)
+    ctx.call("r3d_debug_fgr_optimize", ctypes.byref(prm), _ptr(s), len(s), _ptr(t), len(t), c.ctypes.data_as(_vp), len(c), _ptr(trace_T),
+             _ptr(trace_par))
+    return dict(trace_T=trace_T, trace_par=trace_par)
+
+
 def _colored_params(max_correspondence_distance, lambda_geometric, max_iteration, relative_fitness, relative_rmse, gradient_radius,
                     gradient_max_nn):
     return _lib.ColoredIcpParams(_lib.IcpParams(COLORED, int(max_iteration), float(max_correspondence_distance), float(relative_fitness),
@@ -813,6 +923,28 @@ def registration_ransac_based_on_feature_matching_device(d_source, ns, d_target,
         ctx.free(d_m)
     res["correspondence_set"] = corres[mask != 0]
     return res
+
+
+def registration_fgr_based_on_correspondence_device(d_source, ns, d_target, nt, d_corres, m, ctx=None, **option):
+    """r3d_fgr_correspondence_dev: clouds ([n][3] float64) and pairs ([m][2] int32) already in HBM (device pointers as int).
+    Returns when the result is ready; the dict of registration_fgr_based_on_correspondence without correspondence_set."""
+    ctx = ctx or _lib.default_context()
+    prm = _fgr_params(**option)
+    T, st = np.empty((4, 4)), FgrStats()
+    ctx.call("r3d_fgr_correspondence_dev", ctypes.byref(prm), _vp(d_source), int(ns), _vp(d_target), int(nt), _vp(d_corres), int(m), _ptr(T),
+             ctypes.byref(st))
+    return _fgr_dict(T, st)
+
+
+def registration_fgr_based_on_feature_matching_device(d_source, ns, d_target, nt, d_source_features, d_target_features, ctx=None, **option):
+    """r3d_fgr_feature_matching_dev: clouds and [n][33] float64 feature rows already in HBM; searches, cross-check, tuple test and
+    loop without a host copy of any of them.  The dict of the host form without correspondence_set."""
+    ctx = ctx or _lib.default_context()
+    prm = _fgr_params(**option)
+    T, st = np.empty((4, 4)), FgrStats()
+    ctx.call("r3d_fgr_feature_matching_dev", ctypes.byref(prm), _vp(d_source), int(ns), _vp(d_target), int(nt), _vp(d_source_features),
+             _vp(d_target_features), FPFH_DIM, _ptr(T), ctypes.byref(st))
+    return _fgr_dict(T, st)
 
 
 def transform_points_device(d_points, n, T, d_out, rotate_only=False, ctx=None):

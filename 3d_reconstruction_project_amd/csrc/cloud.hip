@@ -2872,8 +2872,10 @@ __host__ __device__ void umeyama_polish(const double *s /*ICP slots*/, double U[
     }
 }
 
-// SolveJacobianSystemAndObtainExtrinsicMatrix: x = LDLT(JTJ) \ (-JTr); identity when |det| < 1e-6
-__host__ __device__ bool solve6_to_matrix(const double *s, double U[16]) {
+// SolveJacobianSystemAndObtainExtrinsicMatrix: x = LDLT(JTJ) \ (-JTr); identity when |det| < det_tol (the registration loop's
+// 1e-6).  det_tol < 0 (FGR: Open3D's SolveLinearSystemPSD has no such rule): no determinant test; the identity only for a zero
+// pivot or a non-finite x.
+__host__ __device__ bool solve6_to_matrix(const double *s, double U[16], double det_tol = 1e-6) {
     double A[6][6], b[6];
     for (int a = 0, q = 2; a < 6; a++)
         for (int c = a; c < 6; c++, q++) A[a][c] = A[c][a] = s[q];
@@ -2895,11 +2897,18 @@ __host__ __device__ bool solve6_to_matrix(const double *s, double U[16]) {
         }
     }
     for (int i = 0; i < 16; i++) U[i] = (i % 5 == 0);
-    if (!isfinite(det) || fabs(det) < 1e-6) return false;
+    if (det_tol >= 0) {
+        if (!isfinite(det) || fabs(det) < det_tol) return false;
+    } else {
+        for (int j = 0; j < 6; j++) if (Dg[j] == 0) return false;
+    }
     double y[6], x[6];
     for (int i = 0; i < 6; i++) { y[i] = b[i]; for (int k = 0; k < i; k++) y[i] -= L[i][k] * y[k]; }
     for (int i = 0; i < 6; i++) y[i] /= Dg[i];
     for (int i = 5; i >= 0; i--) { x[i] = y[i]; for (int k = i + 1; k < 6; k++) x[i] -= L[k][i] * x[k]; }
+    if (det_tol < 0) {
+        for (int i = 0; i < 6; i++) if (!isfinite(x[i])) return false;
+    }
     // TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0)
     double ca, sa, cb, sb, cc, sc;   // one range reduction per angle (the update runs in a single GPU thread)
     sincos(x[0], &sa, &ca);
@@ -3403,6 +3412,279 @@ int ransac_core(r3d_ctx *ctx, DevArena &ar, const r3d_ransac_params *p, const do
         stats->loop_ms = std::chrono::duration<double, std::milli>(t_end - t_loop).count();
     }
     return R3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ Fast Global Registration
+// The contract is stated in DESIGN.md section 4 ("FGR") [recalled, Open3D 0.18 FastGlobalRegistration.cpp] and executed in
+// tests/fgr_ref.py: both clouds centred and scaled, the pairs (given, or the mutual ones of two feature searches), the tuple test
+// with RANSAC's counter-based sampler, the graduated-non-convexity Gauss-Newton loop, the result in the clouds' own units.
+// Every sum below has one fixed order that depends on the sizes alone: the same bits on every run, whatever `batch` is.
+constexpr int FGR_MIN_PAIRS = 10;           // fewer rows: the loop does not run (Open3D's OptimizePairwiseRegistration)
+constexpr int FGR_TRIALS_PER_PAIR = 100;
+constexpr int FGR_OPT_BLOCK = 1024, FGR_OPT_WAVES = FGR_OPT_BLOCK / 64;
+constexpr int FGR_SUMS = 16;                // the distinct ones of the 21 + 6 sums, see k_fgr_optimize
+constexpr int FGR_MOM_BLOCKS = 1024;
+
+struct FgrNorm { double mean_s[3], mean_t[3], scale_global; };
+
+// sums of the coordinates of both clouds (blockIdx.y: 0 source, 1 target): thread-strided partial sums, then a fixed tree in LDS;
+// part[(y * gridDim.x + b) * 3 + a]
+__global__ void __launch_bounds__(256) k_fgr_moments(const double *__restrict__ src, int64_t ns, const double *__restrict__ tgt, int64_t nt,
+                                                     double *__restrict__ part) {
+    const double *__restrict__ p = blockIdx.y ? tgt : src;
+    const int64_t n = blockIdx.y ? nt : ns;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        for (int a = 0; a < 3; a++) s[a] += p[i * 3 + a];
+    __shared__ double sm[3][256];
+    for (int a = 0; a < 3; a++) sm[a][threadIdx.x] = s[a];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h)
+            for (int a = 0; a < 3; a++) sm[a][threadIdx.x] += sm[a][threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = sm[threadIdx.x][0];
+}
+// the finish: the partial sums folded the same way, divided by n; mom[0..2] mean_s, mom[3..5] mean_t
+__global__ void __launch_bounds__(256) k_fgr_moments_final(const double *__restrict__ part, int nb, int64_t ns, int64_t nt, double *__restrict__ mom) {
+    __shared__ double sm[6][256];
+    for (int c = 0; c < 2; c++) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int b = threadIdx.x; b < nb; b += 256)
+            for (int a = 0; a < 3; a++) s[a] += part[((int64_t)c * nb + b) * 3 + a];
+        for (int a = 0; a < 3; a++) sm[c * 3 + a][threadIdx.x] = s[a];
+    }
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h)
+            for (int a = 0; a < 6; a++) sm[a][threadIdx.x] += sm[a][threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) mom[threadIdx.x] = sm[threadIdx.x][0] / (double)(threadIdx.x < 3 ? ns : nt);
+}
+// the largest norm of the centred points, per workgroup (a maximum: any order gives the same value)
+__global__ void __launch_bounds__(256) k_fgr_maxnorm(const double *__restrict__ src, int64_t ns, const double *__restrict__ tgt, int64_t nt,
+                                                     const double *__restrict__ mom, double *__restrict__ part) {
+    const double *__restrict__ p = blockIdx.y ? tgt : src;
+    const int64_t n = blockIdx.y ? nt : ns;
+    const double mx = mom[blockIdx.y * 3], my = mom[blockIdx.y * 3 + 1], mz = mom[blockIdx.y * 3 + 2];
+    double m = 0.0;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double x = p[i * 3] - mx, y = p[i * 3 + 1] - my, z = p[i * 3 + 2] - mz;
+        const double l = sqrt((x * x + y * y) + z * z);
+        bad |= !isfinite(l);                // fmax drops a NaN: it is carried separately
+        m = fmax(m, l);
+    }
+    __shared__ double sm[256];
+    sm[threadIdx.x] = bad ? INFINITY : m;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
+}
+__global__ void __launch_bounds__(256) k_fgr_maxnorm_final(const double *__restrict__ part, int nb2, double *__restrict__ mom) {
+    __shared__ double sm[256];
+    double m = 0.0;
+    for (int b = threadIdx.x; b < nb2; b += 256) m = fmax(m, part[b]);
+    sm[threadIdx.x] = m;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { mom[6] = sm[0]; mom[7] = 0.0; }
+}
+
+// the plain cross-check of the two feature searches: flag[i] = nn_ts[nn_st[i]] == i (flag[ns] = 0: the scan's last output is the
+// count); an index outside its table is not followed
+__global__ void __launch_bounds__(256) k_fgr_mutual(const int *__restrict__ nn_st, int64_t ns, const int *__restrict__ nn_ts, int64_t nt,
+                                                    int *__restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > ns) return;
+    int f = 0;
+    if (i < ns) {
+        const int j = nn_st[i];
+        if (j >= 0 && j < nt) f = nn_ts[j] == (int)i ? 1 : 0;
+    }
+    flag[i] = f;
+}
+// the mutual pairs in ascending i
+__global__ void __launch_bounds__(256) k_fgr_mutual_compact(const int *__restrict__ nn_st, int64_t ns, const int *__restrict__ flag,
+                                                            const int *__restrict__ scan, int *__restrict__ corres) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ns || !flag[i]) return;
+    corres[(int64_t)scan[i] * 2] = (int)i;
+    corres[(int64_t)scan[i] * 2 + 1] = nn_st[i];
+}
+
+// rows[i] = (p, q) of pair i, centred and divided by scale_global; an index outside its cloud is not followed: it raises *bad
+// and the row is zeros
+__global__ void __launch_bounds__(256) k_fgr_gather(const double *__restrict__ src, int64_t ns, const double *__restrict__ tgt, int64_t nt,
+                                                    const int *__restrict__ corres, int64_t M, FgrNorm nm, double *__restrict__ rows,
+                                                    int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const int a = corres[i * 2], b = corres[i * 2 + 1];
+    const bool ok = a >= 0 && a < ns && b >= 0 && b < nt;
+    if (!ok) *bad = 1;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        rows[i * 6 + c] = ok ? (src[(int64_t)a * 3 + c] - nm.mean_s[c]) / nm.scale_global : 0.0;
+        rows[i * 6 + 3 + c] = ok ? (tgt[(int64_t)b * 3 + c] - nm.mean_t[c]) / nm.scale_global : 0.0;
+    }
+}
+
+// one trial of the tuple test per thread: the three pair indices from RANSAC's sampler (no distinctness test: a repeated index
+// gives a zero edge, and 0 < 0 fails), then li * tuple_scale < lj < li / tuple_scale on the three edges.  flags[count] = 0: the
+// scan's last output is the number of accepted trials of the batch.
+__global__ void __launch_bounds__(256) k_fgr_tuples(const double *__restrict__ rows, int64_t ncorr, unsigned long long seed, long long t0, int count,
+                                                    double tuple_scale, int *__restrict__ samples /* [count][3] or null */,
+                                                    int *__restrict__ flags /* [count + 1] */, int *__restrict__ cut /* or null: set to -1 */) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) { flags[count] = 0; if (cut) *cut = -1; }
+    if (i >= count) return;
+    int c[3];
+    double P[3][6];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        c[j] = ransac_sample(seed, t0 + i, j, ncorr);
+#pragma unroll
+        for (int q = 0; q < 6; q++) P[j][q] = rows[(int64_t)c[j] * 6 + q];
+    }
+    if (samples) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) samples[(int64_t)i * 3 + j] = c[j];
+    }
+    bool ok = true;
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+        const int a = e, b = (e + 1) % 3;   // (r0, r1), (r1, r2), (r2, r0)
+        const double sx = P[a][0] - P[b][0], sy = P[a][1] - P[b][1], sz = P[a][2] - P[b][2];
+        const double tx = P[a][3] - P[b][3], ty = P[a][4] - P[b][4], tz = P[a][5] - P[b][5];
+        const double li = sqrt((sx * sx + sy * sy) + sz * sz), lj = sqrt((tx * tx + ty * ty) + tz * tz);
+        if (!(li * tuple_scale < lj && lj < li / tuple_scale)) ok = false;
+    }
+    flags[i] = ok ? 1 : 0;
+}
+// the accepted trials of a batch in t order behind the `have` accepted before it, the cut at `max_count`: trial rank r < max_count
+// leaves its three rows at out[3 r ..]; the one that fills the last place leaves its batch slot in *cut (set to -1 before)
+__global__ void __launch_bounds__(256) k_fgr_tuple_compact(const double *__restrict__ rows, int64_t ncorr, unsigned long long seed, long long t0,
+                                                           int count, const int *__restrict__ flags, const int *__restrict__ scan, int64_t have,
+                                                           int64_t max_count, double *__restrict__ out, int *__restrict__ cut) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count || !flags[i]) return;
+    const int64_t r = have + scan[i];
+    if (r >= max_count) return;
+    if (r == max_count - 1) *cut = i;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int64_t c = ransac_sample(seed, t0 + i, j, ncorr);
+#pragma unroll
+        for (int q = 0; q < 6; q++) out[(r * 3 + j) * 6 + q] = rows[c * 6 + q];
+    }
+}
+
+// k_fgr_optimize: the whole graduated-non-convexity loop in one launch by one workgroup; no launch and no host read between its
+// iterations.  Per iteration every thread walks the rows tid, tid + 1024, ... in ascending order: q = trans q0, rpq = p - q,
+// s = (par / (rpq . rpq + par))^2, and the sums of s J^T J and s J^T r with the three Jacobian rows [0, -qz, qy, -1, 0, 0],
+// [qz, 0, -qx, 0, -1, 0], [-qy, qx, 0, 0, 0, -1].  Of those 21 + 6 sums only 16 differ: six of the rotation block, S s q (the
+// rotation-translation block holds it and its exact negative), S s (the translation block's diagonal) and the six right-hand
+// sides; the others are sums of exact zeros.  The 16 are reduced per wave by wave_sum's fixed tree and across the 16 waves
+// through LDS in wave order; thread 0 then expands them into solve6_to_matrix's slots, solves without the determinant rule,
+// forms trans = delta trans and publishes it in LDS for the next iteration.
+// out17: the final trans and par; trace_T [iterations][16] / trace_par [iterations] (both or neither): the state after every
+// iteration (r3d_debug_fgr_optimize).
+__global__ void __launch_bounds__(FGR_OPT_BLOCK) k_fgr_optimize(const double *__restrict__ rows, int64_t M, int iterations, double par0, double limit,
+                                                                double division_factor, int decrease_mu, double *__restrict__ out17,
+                                                                double *__restrict__ trace_T, double *__restrict__ trace_par) {
+    __shared__ double wsum[FGR_OPT_WAVES][FGR_SUMS];
+    __shared__ double sh_state[13];         // rows 0..2 of trans, par
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    double T[16], par = par0;               // thread 0's copy is the state
+#pragma unroll
+    for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0);
+    if (tid < 12) sh_state[tid] = (tid % 5 == 0) ? 1.0 : 0.0;
+    if (tid == 12) sh_state[12] = par0;
+    __syncthreads();
+    for (int itr = 0; itr < iterations; itr++) {
+        double t[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) t[i] = sh_state[i];
+        const double pr = sh_state[12];
+        double acc[FGR_SUMS];
+#pragma unroll
+        for (int e = 0; e < FGR_SUMS; e++) acc[e] = 0.0;
+#pragma unroll 2
+        for (int64_t i = tid; i < M; i += FGR_OPT_BLOCK) {
+            const double *__restrict__ r = rows + i * 6;
+            const double px = r[0], py = r[1], pz = r[2], x0 = r[3], y0 = r[4], z0 = r[5];
+            const double qx = ((t[0] * x0 + t[1] * y0) + t[2] * z0) + t[3];
+            const double qy = ((t[4] * x0 + t[5] * y0) + t[6] * z0) + t[7];
+            const double qz = ((t[8] * x0 + t[9] * y0) + t[10] * z0) + t[11];
+            const double rx = px - qx, ry = py - qy, rz = pz - qz;
+            const double wt = pr / (((rx * rx + ry * ry) + rz * rz) + pr);
+            const double s = wt * wt;
+            acc[0] += s * (qy * qy + qz * qz);
+            acc[1] += s * -(qx * qy);
+            acc[2] += s * -(qx * qz);
+            acc[3] += s * (qx * qx + qz * qz);
+            acc[4] += s * -(qy * qz);
+            acc[5] += s * (qx * qx + qy * qy);
+            acc[6] += s * qx;
+            acc[7] += s * qy;
+            acc[8] += s * qz;
+            acc[9] += s;
+            acc[10] += s * (qz * ry - qy * rz);
+            acc[11] += s * (qx * rz - qz * rx);
+            acc[12] += s * (qy * rx - qx * ry);
+            acc[13] += s * -rx;
+            acc[14] += s * -ry;
+            acc[15] += s * -rz;
+        }
+#pragma unroll
+        for (int e = 0; e < FGR_SUMS; e++) {
+            const double v = wave_sum(acc[e]);
+            if (lane == 0) wsum[w][e] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double v[FGR_SUMS];
+            for (int e = 0; e < FGR_SUMS; e++) {
+                double a = 0.0;
+                for (int k = 0; k < FGR_OPT_WAVES; k++) a += wsum[k][e];
+                v[e] = a;
+            }
+            // solve6_to_matrix's slots: [2 .. 22] the upper triangle of JTJ row by row, [23 .. 28] JTr
+            const double sx = v[6], sy = v[7], sz = v[8], ss = v[9];
+            const double sl[29] = {0.0, 0.0,
+                                   v[0], v[1], v[2], 0.0, -sz, sy,
+                                   v[3], v[4], sz, 0.0, -sx,
+                                   v[5], -sy, sx, 0.0,
+                                   ss, 0.0, 0.0,
+                                   ss, 0.0,
+                                   ss,
+                                   v[10], v[11], v[12], v[13], v[14], v[15]};
+            double U[16];
+            solve6_to_matrix(sl, U, -1.0);  // a failed solve leaves the identity: the loop goes on
+            mat4_mul(U, T, T);
+            if (decrease_mu && itr % 4 == 0 && par > limit) par /= division_factor;
+            for (int i = 0; i < 12; i++) sh_state[i] = T[i];
+            sh_state[12] = par;
+            if (trace_T) {
+                for (int i = 0; i < 16; i++) trace_T[(int64_t)itr * 16 + i] = T[i];
+                trace_par[itr] = par;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        for (int i = 0; i < 16; i++) out17[i] = T[i];
+        out17[16] = par;
+    }
 }
 
 }  // namespace
@@ -3938,6 +4220,256 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     }
     return R3D_OK;
 }
+
+// ---- Fast Global Registration: the host side (the kernels stand next to the RANSAC block)
+namespace {
+
+int fgr_check(r3d_ctx *ctx, const char *who, const r3d_fgr_params *p, const void *src, int64_t ns, const void *tgt, int64_t nt) {
+    if (!p || !src || !tgt || ns < 1 || nt < 1) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument (null array or empty cloud)", who);
+    if (!(p->division_factor > 1) || !(p->maximum_correspondence_distance > 0) || !(p->tuple_scale > 0) || !(p->tuple_scale <= 1) ||
+        !std::isfinite(p->division_factor) || !std::isfinite(p->maximum_correspondence_distance) || p->iteration_number < 0 ||
+        p->maximum_tuple_count < 1 || p->batch < 0)
+        return r3d_fail(ctx, R3D_E_BADARG, "%s: division_factor > 1, maximum_correspondence_distance > 0, 0 < tuple_scale <= 1, iteration_number >= 0, "
+                                           "maximum_tuple_count >= 1 and batch >= 0 are required", who);
+    if (ns > 0x7fffffff || nt > 0x7fffffff) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: ns and nt must stay below 2^31", who);
+    return R3D_OK;
+}
+
+// step 1 of the contract: the means and the largest centred norm of both clouds in two fixed-order two-level passes, one read-back
+int fgr_normalise(r3d_ctx *ctx, DevArena &ar, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt, bool absolute, FgrNorm &nm,
+                  double *scale_start) {
+    const int nb = (int)std::min<int64_t>((std::max(ns, nt) + 255) / 256, FGR_MOM_BLOCKS);
+    double *part = (double *)ar.get((size_t)nb * 6 * 8), *part2 = (double *)ar.get((size_t)nb * 2 * 8), *mom = (double *)ar.get(64);
+    if (ar.rc) return ar.rc;
+    k_fgr_moments<<<dim3(nb, 2), 256, 0, ctx->stream>>>(d_src, ns, d_tgt, nt, part);
+    k_fgr_moments_final<<<1, 256, 0, ctx->stream>>>(part, nb, ns, nt, mom);
+    k_fgr_maxnorm<<<dim3(nb, 2), 256, 0, ctx->stream>>>(d_src, ns, d_tgt, nt, mom, part2);
+    k_fgr_maxnorm_final<<<1, 256, 0, ctx->stream>>>(part2, nb * 2, mom);
+    R3D_HIP(ctx, hipGetLastError());
+    double h[8];
+    PinRead rd(ctx);
+    int rc;
+    if ((rc = rd.add(h, mom, sizeof h)) || (rc = rd.wait())) return rc;
+    const double scale = h[6];
+    if (!(scale > 0) || !std::isfinite(scale))
+        return r3d_fail(ctx, R3D_E_BADARG, "fgr: the clouds have no extent or non-finite coordinates (largest centred norm %g)", scale);
+    for (int a = 0; a < 3; a++) { nm.mean_s[a] = h[a]; nm.mean_t[a] = h[3 + a]; }
+    nm.scale_global = absolute ? 1.0 : scale;
+    *scale_start = absolute ? scale : 1.0;
+    return R3D_OK;
+}
+
+// the normalised [M][6] rows of the pairs, their indices checked on the device before anything reads a row
+int fgr_gather(r3d_ctx *ctx, DevArena &ar, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt, const int *d_corres, int64_t M,
+               const FgrNorm &nm, double **rows_out) {
+    double *rows = (double *)ar.get((size_t)M * 48);
+    int *d_bad = (int *)ar.get(4);
+    if (ar.rc) return ar.rc;
+    *rows_out = rows;
+    if (M == 0) return R3D_OK;
+    R3D_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
+    k_fgr_gather<<<(unsigned)((M + 255) / 256), 256, 0, ctx->stream>>>(d_src, ns, d_tgt, nt, d_corres, M, nm, rows, d_bad);
+    R3D_HIP(ctx, hipGetLastError());
+    int bad = 0, rc;
+    PinRead rd(ctx);
+    if ((rc = rd.add(&bad, d_bad, 4)) || (rc = rd.wait())) return rc;
+    if (bad) return r3d_fail(ctx, R3D_E_BADARG, "fgr: a correspondence index lies outside its cloud (ns = %lld, nt = %lld)", (long long)ns, (long long)nt);
+    return R3D_OK;
+}
+
+// step 2, feature form: both searches, the cross-check, the pairs compacted in ascending source index; one read-back (the count)
+int fgr_mutual(r3d_ctx *ctx, DevArena &ar, const double *d_sf, int64_t ns, const double *d_tf, int64_t nt, int **corres_out, int64_t *M_out,
+               double ms[2] /* matching, filter: filled when timing */, bool timing) {
+    int *nn_st = (int *)ar.get((size_t)ns * 4), *nn_ts = (int *)ar.get((size_t)nt * 4);
+    int *flag = (int *)ar.get((size_t)(ns + 1) * 4), *scan = (int *)ar.get((size_t)(ns + 1) * 4), *corres = (int *)ar.get((size_t)ns * 8);
+    if (ar.rc) return ar.rc;
+    int rc;
+    auto t0 = std::chrono::steady_clock::now();
+    if ((rc = match_core(ctx, ar, d_sf, ns, d_tf, nt, nn_st, nullptr))) return rc;
+    if ((rc = match_core(ctx, ar, d_tf, nt, d_sf, ns, nn_ts, nullptr))) return rc;
+    if (timing) {
+        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const auto t1 = std::chrono::steady_clock::now();
+        ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+    }
+    k_fgr_mutual<<<(unsigned)((ns + 1 + 255) / 256), 256, 0, ctx->stream>>>(nn_st, ns, nn_ts, nt, flag);
+    R3D_HIP(ctx, hipGetLastError());
+    if ((rc = dev_exclusive_scan<int>(ctx, ar, flag, scan, ns + 1))) return rc;
+    k_fgr_mutual_compact<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(nn_st, ns, flag, scan, corres);
+    R3D_HIP(ctx, hipGetLastError());
+    int count = 0;
+    PinRead rd(ctx);
+    if ((rc = rd.add(&count, scan + ns, 4)) || (rc = rd.wait())) return rc;
+    if (timing) ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *corres_out = corres;
+    *M_out = count;
+    return R3D_OK;
+}
+
+// step 3: trials in batches, compacted in t order, until maximum_tuple_count are accepted or 100 ncorr have been evaluated; one
+// read-back per batch.  The rows of the accepted trials, three per trial.
+int fgr_tuple_stage(r3d_ctx *ctx, DevArena &ar, const r3d_fgr_params *p, const double *rows, int64_t ncorr, double **out_rows, int64_t *trials_out,
+                    int64_t *tuples_out) {
+    *out_rows = nullptr; *trials_out = 0; *tuples_out = 0;
+    if (ncorr == 0) return R3D_OK;
+    const int64_t total = FGR_TRIALS_PER_PAIR * ncorr, maxc = std::min<int64_t>(p->maximum_tuple_count, total);
+    if (maxc * 3 > 0x7fffffff) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "fgr: up to %lld tuples give more than 2^31 - 1 rows", (long long)maxc);
+    const int batch = (int)std::min<int64_t>(p->batch > 0 ? p->batch : RANSAC_DEFAULT_BATCH, std::min<int64_t>(RANSAC_MAX_BATCH, total));
+    double *out = (double *)ar.get((size_t)maxc * 3 * 48);
+    int *flags = (int *)ar.get((size_t)(batch + 1) * 4), *scan = (int *)ar.get((size_t)(batch + 1) * 4), *cut = (int *)ar.get(4);
+    int *scan_part = (int *)ar.get((size_t)((batch + 1 + SCAN_TILE - 1) / SCAN_TILE) * 4);
+    if (ar.rc) return ar.rc;
+    int64_t have = 0, t0 = 0, trials = total;
+    while (t0 < total && have < maxc) {
+        const int count = (int)std::min<int64_t>(batch, total - t0);
+        const unsigned nb = (unsigned)((count + 255) / 256);
+        k_fgr_tuples<<<nb, 256, 0, ctx->stream>>>(rows, ncorr, p->seed, t0, count, p->tuple_scale, nullptr, flags, cut);
+        R3D_HIP(ctx, hipGetLastError());
+        int rc;
+        if ((rc = dev_exclusive_scan<int>(ctx, ar, flags, scan, (int64_t)count + 1, nullptr, nullptr, scan_part))) return rc;
+        k_fgr_tuple_compact<<<nb, 256, 0, ctx->stream>>>(rows, ncorr, p->seed, t0, count, flags, scan, have, maxc, out, cut);
+        R3D_HIP(ctx, hipGetLastError());
+        int acc = 0, cutv = -1;
+        PinRead rd(ctx);
+        if ((rc = rd.add(&acc, scan + count, 4)) || (rc = rd.add(&cutv, cut, 4)) || (rc = rd.wait())) return rc;
+        if (have + acc >= maxc) {
+            if (cutv < 0 || cutv >= count) return r3d_fail(ctx, R3D_E_HIP, "fgr: the tuple cut was not recorded (batch at trial %lld)", (long long)t0);
+            trials = t0 + cutv + 1;
+            have = maxc;
+            break;
+        }
+        have += acc;
+        t0 += count;
+    }
+    *out_rows = out;
+    *trials_out = trials;
+    *tuples_out = have;
+    return R3D_OK;
+}
+
+// step 4: the loop in one launch.  trace_T / trace_par (host, optional): the state after every iteration; with fewer than
+// FGR_MIN_PAIRS rows the loop does not run and they hold the start state.
+int fgr_optimise_stage(r3d_ctx *ctx, DevArena &ar, const r3d_fgr_params *p, const double *rows, int64_t M, double par0, double trans[16],
+                       double *final_par, double *trace_T, double *trace_par) {
+    const int it = p->iteration_number;
+    for (int i = 0; i < 16; i++) trans[i] = (i % 5 == 0);
+    *final_par = par0;
+    if (M < FGR_MIN_PAIRS || it == 0) {
+        for (int k = 0; k < it && trace_T; k++) { memcpy(trace_T + (size_t)k * 16, trans, 128); trace_par[k] = par0; }
+        return R3D_OK;
+    }
+    double *d_out = (double *)ar.get(17 * 8), *d_tr = trace_T ? (double *)ar.get((size_t)it * 17 * 8) : nullptr;
+    if (ar.rc) return ar.rc;
+    // QUIRK_UNSCALED_DISTANCE (tests/fgr_ref.py): par, in normalised units, is compared with the distance as the caller gave it
+    k_fgr_optimize<<<1, FGR_OPT_BLOCK, 0, ctx->stream>>>(rows, M, it, par0, p->maximum_correspondence_distance, p->division_factor,
+                                                         p->decrease_mu ? 1 : 0, d_out, d_tr, d_tr ? d_tr + (size_t)it * 16 : nullptr);
+    R3D_HIP(ctx, hipGetLastError());
+    double h[17];
+    int rc;
+    PinRead rd(ctx);
+    if ((rc = rd.add(h, d_out, sizeof h)) || (rc = rd.wait())) return rc;
+    memcpy(trans, h, 128);
+    *final_par = h[16];
+    if (trace_T) {
+        R3D_HIP(ctx, hipMemcpyAsync(trace_T, d_tr, (size_t)it * 128, hipMemcpyDeviceToHost, ctx->stream));
+        R3D_HIP(ctx, hipMemcpyAsync(trace_par, d_tr + (size_t)it * 16, (size_t)it * 8, hipMemcpyDeviceToHost, ctx->stream));
+        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return R3D_OK;
+}
+
+// step 5: T_ts = [R | -R mean_t + t scale_global + mean_s] maps target to source; the result is its rigid inverse
+void fgr_original_scale(const double trans[16], const FgrNorm &nm, double T[16]) {
+    double tt[3];
+    for (int i = 0; i < 3; i++)
+        tt[i] = (trans[i * 4 + 3] * nm.scale_global -
+                 ((trans[i * 4] * nm.mean_t[0] + trans[i * 4 + 1] * nm.mean_t[1]) + trans[i * 4 + 2] * nm.mean_t[2])) + nm.mean_s[i];
+    for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) T[i * 4 + j] = trans[j * 4 + i];
+        T[i * 4 + 3] = -((trans[i] * tt[0] + trans[4 + i] * tt[1]) + trans[8 + i] * tt[2]);
+    }
+}
+
+// everything over device arrays: d_corres [M][2] (correspondence form) or the feature rows (feature form, d_corres null)
+int fgr_core(r3d_ctx *ctx, DevArena &ar, const r3d_fgr_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+             const int *d_corres, int64_t M, const double *d_sf, const double *d_tf, double *T4x4, r3d_fgr_stats *stats,
+             std::chrono::steady_clock::time_point t_begin) {
+    // R3D_FGR_TIMING=1 (tools/gpu_bench_fgr.py): the stream is drained after every stage and the stage times go to stderr
+    static const bool timing = [] { const char *e = getenv("R3D_FGR_TIMING"); return e && *e == '1'; }();
+    double ms[6] = {0, 0, 0, 0, 0, 0};      // matching, mutual filter, normalise + gather, tuples, optimisation, evaluation
+    auto tick = std::chrono::steady_clock::now();
+    auto lap = [&](int slot) -> int {
+        if (!timing) return R3D_OK;
+        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const auto now = std::chrono::steady_clock::now();
+        ms[slot] = std::chrono::duration<double, std::milli>(now - tick).count();
+        tick = now;
+        return R3D_OK;
+    };
+    int rc;
+    FgrNorm nm;
+    double scale_start = 1.0;
+    int *corres = const_cast<int *>(d_corres);
+    if (!d_corres) {
+        if ((rc = fgr_mutual(ctx, ar, d_sf, ns, d_tf, nt, &corres, &M, ms, timing))) return rc;
+        tick = std::chrono::steady_clock::now();
+    }
+    if ((rc = fgr_normalise(ctx, ar, d_src, ns, d_tgt, nt, p->use_absolute_scale != 0, nm, &scale_start))) return rc;
+    double *rows = nullptr;
+    if ((rc = fgr_gather(ctx, ar, d_src, ns, d_tgt, nt, corres, M, nm, &rows))) return rc;
+    if ((rc = lap(2))) return rc;
+    int64_t trials = 0, tuples = 0, pairs = M;
+    if (p->tuple_test) {
+        double *trows = nullptr;
+        if ((rc = fgr_tuple_stage(ctx, ar, p, rows, M, &trows, &trials, &tuples))) return rc;
+        rows = trows;
+        pairs = tuples * 3;
+    }
+    if ((rc = lap(3))) return rc;
+    const auto t_loop = std::chrono::steady_clock::now();
+    double trans[16], final_par = scale_start;
+    if ((rc = fgr_optimise_stage(ctx, ar, p, rows, pairs, scale_start, trans, &final_par, nullptr, nullptr))) return rc;
+    if ((rc = lap(4))) return rc;
+    // QUIRK_FEW_PAIRS (tests/fgr_ref.py): with fewer than FGR_MIN_PAIRS rows trans is the identity, and the result is still taken
+    // back to the clouds' units: the centroid-to-centroid translation
+    fgr_original_scale(trans, nm, T4x4);
+    const auto t_eval = std::chrono::steady_clock::now();
+    // fitness, inlier_rmse and the correspondence count: one evaluation of the registration loop at that pose, no update
+    r3d_icp_params ip = {};
+    ip.mode = MODE_P2P;
+    ip.max_iteration = 0;
+    ip.max_correspondence_distance = p->maximum_correspondence_distance;
+    ip.relative_fitness = ip.relative_rmse = 1e-6;
+    r3d_icp_stats ist = {};
+    double Tsame[16];
+    if ((rc = icp_core(ctx, ar, &ip, const_cast<double *>(d_src), ns, nullptr, const_cast<double *>(d_tgt), nt, nullptr, T4x4, Tsame, &ist, t_eval)))
+        return rc;
+    if ((rc = lap(5))) return rc;
+    if (stats) {
+        stats->fitness = ist.fitness;
+        stats->inlier_rmse = ist.inlier_rmse;
+        stats->scale_global = nm.scale_global;
+        stats->scale_start = scale_start;
+        stats->final_par = final_par;
+        stats->correspondences = ist.correspondences;
+        stats->matched = M;
+        stats->trials = trials;
+        stats->tuples = tuples;
+        stats->pairs = pairs;
+        const auto t_end = std::chrono::steady_clock::now();
+        stats->setup_ms = std::chrono::duration<double, std::milli>(t_loop - t_begin).count();
+        stats->loop_ms = std::chrono::duration<double, std::milli>(t_end - t_loop).count();
+    }
+    if (timing)
+        fprintf(stderr, "[r3d fgr] matching %.3f ms, mutual filter %.3f ms, normalise+gather %.3f ms, tuples %.3f ms, optimisation %.3f ms, "
+                        "evaluation %.3f ms (matched %lld, trials %lld, rows %lld)\n", ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], (long long)M,
+                (long long)trials, (long long)pairs);
+    return R3D_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -5264,6 +5796,134 @@ int r3d_debug_ransac_hypotheses(r3d_ctx *ctx, const r3d_ransac_params *p, const 
         if (err2) err2[surv[k]] = err[k];
     }
     return R3D_OK;
+}
+
+// ---- Fast Global Registration (Open3D registration_fgr_based_on_correspondence / ..._on_feature_matching)
+static int fgr_pairs_check(r3d_ctx *ctx, const char *who, const void *corres, int64_t M) {
+    if (!corres || M < 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument (no correspondences)", who);
+    if (M > 0x7fffffff) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: M must stay below 2^31", who);
+    return R3D_OK;
+}
+
+int r3d_fgr_correspondence_dev(r3d_ctx *ctx, const r3d_fgr_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                               const int32_t *d_corres, int64_t M, double *T4x4, r3d_fgr_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_fgr_correspondence_dev");
+    if (!ctx) return R3D_E_BADARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc;
+    if (!T4x4) return r3d_fail(ctx, R3D_E_BADARG, "fgr_correspondence_dev: T4x4 is NULL");
+    if ((rc = fgr_check(ctx, "fgr_correspondence_dev", p, d_src, ns, d_tgt, nt)) || (rc = fgr_pairs_check(ctx, "fgr_correspondence_dev", d_corres, M)))
+        return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return fgr_core(ctx, ar, p, d_src, ns, d_tgt, nt, d_corres, M, nullptr, nullptr, T4x4, stats, t_begin);
+}
+
+int r3d_fgr_correspondence(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                           const int32_t *corres, int64_t M, double *T4x4, r3d_fgr_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_fgr_correspondence");
+    if (!ctx) return R3D_E_BADARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc;
+    if (!T4x4) return r3d_fail(ctx, R3D_E_BADARG, "fgr_correspondence: T4x4 is NULL");
+    if ((rc = fgr_check(ctx, "fgr_correspondence", p, src, ns, tgt, nt)) || (rc = fgr_pairs_check(ctx, "fgr_correspondence", corres, M))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    int *d_c = (int *)ar.get((size_t)M * 8);
+    if (ar.rc) return ar.rc;
+    if (M > 0) R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    return fgr_core(ctx, ar, p, d_s, ns, d_t, nt, d_c, M, nullptr, nullptr, T4x4, stats, t_begin);
+}
+
+int r3d_fgr_feature_matching_dev(r3d_ctx *ctx, const r3d_fgr_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                                 const double *d_src_feat, const double *d_tgt_feat, int32_t dim, double *T4x4, r3d_fgr_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_fgr_feature_matching_dev");
+    if (!ctx) return R3D_E_BADARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc;
+    if (!T4x4) return r3d_fail(ctx, R3D_E_BADARG, "fgr_feature_matching_dev: T4x4 is NULL");
+    if ((rc = fgr_check(ctx, "fgr_feature_matching_dev", p, d_src, ns, d_tgt, nt))) return rc;
+    if ((rc = match_check(ctx, "fgr_feature_matching_dev", d_src_feat, ns, d_tgt_feat, nt, dim, T4x4))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return fgr_core(ctx, ar, p, d_src, ns, d_tgt, nt, nullptr, 0, d_src_feat, d_tgt_feat, T4x4, stats, t_begin);
+}
+
+int r3d_fgr_feature_matching(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                             const double *src_feat, const double *tgt_feat, int32_t dim, double *T4x4, r3d_fgr_stats *stats) {
+    R3D_ROCTX_RANGE("r3d_fgr_feature_matching");
+    if (!ctx) return R3D_E_BADARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc;
+    if (!T4x4) return r3d_fail(ctx, R3D_E_BADARG, "fgr_feature_matching: T4x4 is NULL");
+    if ((rc = fgr_check(ctx, "fgr_feature_matching", p, src, ns, tgt, nt))) return rc;
+    if ((rc = match_check(ctx, "fgr_feature_matching", src_feat, ns, tgt_feat, nt, dim, T4x4))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t, *d_sf, *d_tf;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    if ((rc = upload(ctx, ar, src_feat, ns * FPFH_DIM, &d_sf))) return rc;
+    if ((rc = upload(ctx, ar, tgt_feat, nt * FPFH_DIM, &d_tf))) return rc;
+    return fgr_core(ctx, ar, p, d_s, ns, d_t, nt, nullptr, 0, d_sf, d_tf, T4x4, stats, t_begin);
+}
+
+// stage parity: trials t0 .. t0 + count - 1 of the tuple test over the normalised pairs, without the cut
+int r3d_debug_fgr_tuples(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt, const int32_t *corres,
+                         int64_t M, int64_t t0, int64_t count, int32_t *samples, int32_t *flags) {
+    R3D_ROCTX_RANGE("r3d_debug_fgr_tuples");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = fgr_check(ctx, "debug_fgr_tuples", p, src, ns, tgt, nt)) || (rc = fgr_pairs_check(ctx, "debug_fgr_tuples", corres, M))) return rc;
+    if (M < 1 || t0 < 0 || count < 1 || count > RANSAC_MAX_BATCH || t0 > (int64_t)1 << 60)
+        return r3d_fail(ctx, R3D_E_BADARG, "debug_fgr_tuples: M >= 1, t0 >= 0, 1 <= count <= %d", RANSAC_MAX_BATCH);
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    int *d_c = (int *)ar.get((size_t)M * 8);
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    FgrNorm nm;
+    double scale_start, *rows;
+    if ((rc = fgr_normalise(ctx, ar, d_s, ns, d_t, nt, p->use_absolute_scale != 0, nm, &scale_start))) return rc;
+    if ((rc = fgr_gather(ctx, ar, d_s, ns, d_t, nt, d_c, M, nm, &rows))) return rc;
+    const int n = (int)count;
+    int *d_samples = (int *)ar.get((size_t)n * 12), *d_flags = (int *)ar.get((size_t)(n + 1) * 4);
+    if (ar.rc) return ar.rc;
+    k_fgr_tuples<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(rows, M, p->seed, t0, n, p->tuple_scale, d_samples, d_flags, nullptr);
+    R3D_HIP(ctx, hipGetLastError());
+    if (samples) R3D_HIP(ctx, hipMemcpyAsync(samples, d_samples, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (flags) R3D_HIP(ctx, hipMemcpyAsync(flags, d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+// stage parity: step 4 alone on the given pairs (no tuple test), the state after every iteration in normalised units
+int r3d_debug_fgr_optimize(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt, const int32_t *pairs,
+                           int64_t M, double *trace_T, double *trace_par) {
+    R3D_ROCTX_RANGE("r3d_debug_fgr_optimize");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = fgr_check(ctx, "debug_fgr_optimize", p, src, ns, tgt, nt)) || (rc = fgr_pairs_check(ctx, "debug_fgr_optimize", pairs, M))) return rc;
+    if (p->iteration_number > 0 && (!trace_T || !trace_par)) return r3d_fail(ctx, R3D_E_BADARG, "debug_fgr_optimize: trace_T or trace_par is NULL");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_s, *d_t;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    int *d_c = (int *)ar.get((size_t)M * 8);
+    if (ar.rc) return ar.rc;
+    if (M > 0) R3D_HIP(ctx, hipMemcpyAsync(d_c, pairs, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    FgrNorm nm;
+    double scale_start, *rows, trans[16], final_par;
+    if ((rc = fgr_normalise(ctx, ar, d_s, ns, d_t, nt, p->use_absolute_scale != 0, nm, &scale_start))) return rc;
+    if ((rc = fgr_gather(ctx, ar, d_s, ns, d_t, nt, d_c, M, nm, &rows))) return rc;
+    return fgr_optimise_stage(ctx, ar, p, rows, M, scale_start, trans, &final_par, trace_T, trace_par);
 }
 
 int r3d_transform_points_dev(r3d_ctx *ctx, const double *d_xyz, int64_t n, const double *T4x4, int32_t rotate_only, double *d_out) {

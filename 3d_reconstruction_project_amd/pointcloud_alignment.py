@@ -81,13 +81,18 @@ def multi_scale_icp(source, target, voxel_size, init=None, scales=(15.0, 5.0, 1.
     return T, results
 
 
-def global_registration(source, target, voxel_size, seed=0, max_iteration=4_000_000, confidence=0.999):
+def global_registration(source, target, voxel_size, seed=0, max_iteration=4_000_000, confidence=0.999, method="ransac"):
     """The global-registration recipe of test/check_lama1.py:246-281 (mini1.py, check8.py): voxel_down_sample(voxel_size) of both
     clouds, estimate_normals(Hybrid(2 * voxel, 30)), compute_fpfh_feature(Hybrid(5 * voxel, 100)), then
     registration_ransac_based_on_feature_matching(mutual_filter=True, 1.5 * voxel, PointToPoint, ransac_n = 3,
     [EdgeLength(0.9), Distance(1.5 * voxel)], RANSACConvergenceCriteria(max_iteration, confidence)).
     Returns (T, result): T is ready for multi_scale_icp(init=T); result is the estimator's dict plus the down-sampled clouds and
-    their normals (source_down, target_down, source_normals, target_normals)."""
+    their normals (source_down, target_down, source_normals, target_normals).
+    method="fgr": the same preparation, then registration_fgr_based_on_feature_matching with FastGlobalRegistrationOption(
+    maximum_correspondence_distance = 0.5 * voxel_size) -- check8.py:244-248's value, recalled -- and `seed` for the tuple
+    sampler; max_iteration and confidence are RANSAC's and do not apply."""
+    if method not in ("ransac", "fgr"):
+        raise ValueError(f"global_registration: method must be 'ransac' or 'fgr', got {method!r}")
     sp, _, _ = as_arrays(source)
     tp, _, _ = as_arrays(target)
     downs = []
@@ -96,6 +101,10 @@ def global_registration(source, target, voxel_size, seed=0, max_iteration=4_000_
         nrm = cloud_ops.estimate_normals(down, voxel_size * 2, 30)
         downs.append((down, nrm, cloud_ops.compute_fpfh_feature(down, nrm, voxel_size * 5, 100)))
     (sd, sn, sf), (td, tn, tf) = downs
+    if method == "fgr":
+        res = cloud_ops.registration_fgr_based_on_feature_matching(sd, td, sf, tf, maximum_correspondence_distance=voxel_size * 0.5, seed=seed)
+        res.update(source_down=sd, target_down=td, source_normals=sn, target_normals=tn)
+        return res["T"], res
     dist = voxel_size * 1.5
     res = cloud_ops.registration_ransac_based_on_feature_matching(sd, td, sf, tf, True, dist, ransac_n=3, edge_length=0.9,
                                                                   checker_distance=dist, max_iteration=max_iteration,

@@ -382,6 +382,58 @@ int r3d_debug_ransac_hypotheses(r3d_ctx *ctx, const r3d_ransac_params *p, const 
                                 const int32_t *corres, int64_t M, int64_t h0, int64_t count, int32_t *samples, int32_t *flags, double *T,
                                 int32_t *inliers, double *err2);
 
+/* replaces: o3d.pipelines.registration.registration_fgr_based_on_feature_matching / ..._on_correspondence with
+ *           FastGlobalRegistrationOption (check8.py:244-248)   [recalled, Open3D 0.18 FastGlobalRegistration.cpp; DESIGN.md section 4
+ *           ("FGR") states the contract, tests/fgr_ref.py executes it].
+ * Both clouds are centred and scaled, the pairs (given, or the mutual ones of two r3d_match_features searches) go through the
+ * tuple test, and a graduated-non-convexity Gauss-Newton loop runs over the surviving rows in ONE kernel launch.  Open3D's tuple
+ * sampler draws from a process-wide generator; this one is a pure function of (inputs, options, seed): trial t draws its three
+ * pairs from the RANSAC entry points' counter-based generator, and the first maximum_tuple_count accepted trials count in t order,
+ * whatever `batch` is.  Every sum has a fixed order: the same bits on every run. */
+typedef struct r3d_fgr_params {          /* 56 bytes */
+    double division_factor;                  /* 1.4; > 1 */
+    double maximum_correspondence_distance;  /* 0.025; > 0.  Compared with the annealing parameter as given, as Open3D does */
+    double tuple_scale;                      /* 0.95; in (0, 1] */
+    uint64_t seed;
+    int32_t iteration_number;                /* 64; >= 0 */
+    int32_t maximum_tuple_count;             /* 1000; >= 1 */
+    int32_t use_absolute_scale, decrease_mu, tuple_test;   /* 0, 1, 1 */
+    int32_t batch;                           /* trials per launch, 0: the library's choice; never changes the result */
+} r3d_fgr_params;
+typedef struct r3d_fgr_stats {           /* 96 bytes */
+    double fitness, inlier_rmse;    /* the registration loop's evaluation at the result with maximum_correspondence_distance */
+    double scale_global, scale_start, final_par;
+    double setup_ms;                /* host wall time up to the optimisation: uploads, matching, normalisation, tuple test */
+    double loop_ms;                 /* host wall time of the optimisation and the evaluation */
+    int64_t correspondences;        /* of that evaluation */
+    int64_t matched;                /* pairs after step 2: M given, or the mutual pairs */
+    int64_t trials;                 /* tuple trials evaluated up to the cut (100 matched when the count is never reached) */
+    int64_t tuples;                 /* accepted trials used */
+    int64_t pairs;                  /* rows the optimisation ran on: 3 tuples, or matched with tuple_test off */
+} r3d_fgr_stats;
+/* src [ns][3], tgt [nt][3], corres [M][2] int32 rows (source index, target index; duplicates kept); T4x4 row-major, source ->
+ * target.  With fewer than 10 rows the loop does not run and T is the centroid-to-centroid translation (Open3D's behaviour).
+ * R3D_E_BADARG: a missing array, ns or nt < 1, an option outside its domain, a pair index outside its cloud (checked on the
+ * device before any read), clouds without extent.  R3D_E_UNSUPPORTED: counts above 2^31 - 1; feature form: dim != 33 or a size
+ * r3d_match_features refuses.  _dev: the clouds, pairs and feature rows are DEVICE arrays (T4x4 and stats stay host memory);
+ * returns when the result is ready, like r3d_icp_dev. */
+int r3d_fgr_correspondence(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                           const int32_t *corres, int64_t M, double *T4x4, r3d_fgr_stats *stats);
+int r3d_fgr_correspondence_dev(r3d_ctx *ctx, const r3d_fgr_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                               const int32_t *d_corres, int64_t M, double *T4x4, r3d_fgr_stats *stats);
+int r3d_fgr_feature_matching(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                             const double *src_feat, const double *tgt_feat, int32_t dim, double *T4x4, r3d_fgr_stats *stats);
+int r3d_fgr_feature_matching_dev(r3d_ctx *ctx, const r3d_fgr_params *p, const double *d_src, int64_t ns, const double *d_tgt, int64_t nt,
+                                 const double *d_src_feat, const double *d_tgt_feat, int32_t dim, double *T4x4, r3d_fgr_stats *stats);
+/* stage parity, host arrays.  r3d_debug_fgr_tuples normalises, then evaluates trials t0 .. t0 + count - 1 (count <= 262144, M >= 1)
+ * without the cut: samples int32 [count][3], flags int32 [count] (either may be NULL).  r3d_debug_fgr_optimize normalises, skips
+ * the tuple test, runs the loop on the given pairs and returns the composed transform ([iteration_number][16]) and the annealing
+ * parameter ([iteration_number]) after every iteration, in normalised units; with fewer than 10 pairs: the start state. */
+int r3d_debug_fgr_tuples(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                         const int32_t *corres, int64_t M, int64_t t0, int64_t count, int32_t *samples, int32_t *flags);
+int r3d_debug_fgr_optimize(r3d_ctx *ctx, const r3d_fgr_params *p, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                           const int32_t *pairs, int64_t M, double *trace_T, double *trace_par);
+
 /* replaces: the whole body of PointCloudAlignment.align_point_clouds (pointcloud_alignment.py:6-43; caller main.py:48) in ONE
  * call, device-resident between the stages: voxel_down_sample(voxel_size) of both clouds (:22-23) ->
  * estimate_normals(KDTreeSearchParamHybrid(normal_radius, normal_max_nn)) on both (:27-28) -> registration (:35-39) ->
