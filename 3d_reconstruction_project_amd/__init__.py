@@ -7,7 +7,7 @@ or through the `r3d` alias module at the repository root (`import r3d`).
 from . import (_lib, cloud_ops, distributed, io_formats, pipeline, normal_estimation, orientation, pointcloud, pointcloud_alignment,  # noqa: F401
                pointcloud_processing, stereo_prepost, stereo_sgbm, synth)
 from ._lib import Context, R3DError, default_context  # noqa: F401
-from .cloud_ops import (compute_fpfh_feature, correspondences_from_features, registration_fgr_based_on_correspondence,  # noqa: F401
+from .cloud_ops import (compute_fpfh_feature, compute_rgbd_odometry, correspondences_from_features, registration_fgr_based_on_correspondence,  # noqa: F401
                         registration_fgr_based_on_feature_matching, registration_ransac_based_on_correspondence,
                         registration_ransac_based_on_feature_matching)
 from .stereo_sgbm import (STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_SGBM_3WAY, StereoSGBM, StereoSGBM_create, createRightMatcher, depth,  # noqa: F401

@@ -983,3 +983,195 @@ def backproject_depth(depth, camera, color=None, want_pixels=False, ctx=None):
     n = m.value
     out = (pts[:n].copy(), col[:n].copy() if col is not None else None)
     return out + (pix[:n].copy(),) if want_pixels else out
+
+
+# ---- RGB-D odometry ("RGB-D odometry") ----------------------------------------------------------------------
+ODOMETRY_HYBRID, ODOMETRY_COLOR = 0, 1
+_JACOBIANS = {"hybrid": ODOMETRY_HYBRID, "color": ODOMETRY_COLOR, "colour": ODOMETRY_COLOR, ODOMETRY_HYBRID: ODOMETRY_HYBRID,
+              ODOMETRY_COLOR: ODOMETRY_COLOR}
+
+
+class OdometryParams(ctypes.Structure):
+    """r3d_odometry_params: Open3D's OdometryOption + the Jacobian term."""
+    _fields_ = [("depth_diff_max", ctypes.c_double), ("depth_min", ctypes.c_double), ("depth_max", ctypes.c_double),
+                ("iterations", ctypes.c_int32 * 4), ("levels", ctypes.c_int32), ("jacobian", ctypes.c_int32)]
+
+
+class OdometryStats(ctypes.Structure):
+    _fields_ = [("success", ctypes.c_int32), ("failed_level", ctypes.c_int32), ("failed_iteration", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("correspondences_init", ctypes.c_int64), ("correspondences", ctypes.c_int64),
+                ("r2", ctypes.c_double), ("setup_ms", ctypes.c_double), ("loop_ms", ctypes.c_double)]
+
+
+_i32, _dbl = ctypes.c_int32, ctypes.c_double
+_odo_f32_sig = ([_vp, ctypes.POINTER(OdometryParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp,
+                 ctypes.POINTER(OdometryStats), _vp], ctypes.c_int)
+_lib.register({
+    "r3d_rgbd_odometry": ([_vp, ctypes.POINTER(OdometryParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                           ctypes.POINTER(DepthCamera), _vp, _vp, _vp, ctypes.POINTER(OdometryStats), _vp], ctypes.c_int),
+    "r3d_rgbd_odometry_f32": _odo_f32_sig,
+    "r3d_rgbd_odometry_f32_dev": _odo_f32_sig,
+    "r3d_debug_rgbd_convert": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(DepthCamera), _vp, _vp], ctypes.c_int),
+    "r3d_debug_rgbd_prepare": ([_vp, ctypes.POINTER(OdometryParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp,
+                                _vp, _vp, _vp, _vp, _i32, _vp, _i64p, _vp], ctypes.c_int),
+    "r3d_debug_rgbd_iteration": ([_vp, ctypes.POINTER(OdometryParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp,
+                                  _i32, _vp, _vp, _i64p, _vp, _vp, ctypes.POINTER(_i32)], ctypes.c_int),
+})
+
+
+def odometry_params(jacobian="hybrid", depth_diff_max=0.03, depth_min=0.0, depth_max=4.0, iteration_number_per_pyramid_level=(20, 10, 5),
+                    levels=None):
+    """OdometryOption's fields as keywords.  iteration_number_per_pyramid_level: coarsest level first, as in Open3D; its length
+    is the number of pyramid levels unless `levels` says otherwise (missing counts are 0)."""
+    its = [int(i) for i in iteration_number_per_pyramid_level]
+    levels = len(its) if levels is None else int(levels)
+    if len(its) > 4 or jacobian not in _JACOBIANS:
+        raise ValueError("at most 4 pyramid levels; jacobian is 'hybrid' or 'color'")
+    return OdometryParams(float(depth_diff_max), float(depth_min), float(depth_max), (ctypes.c_int32 * 4)(*(its + [0] * 4)[:4]), levels,
+                          _JACOBIANS[jacobian])
+
+
+class RGBDImage:
+    """create_from_color_and_depth(color, depth, depth_scale, depth_trunc, convert_rgb_to_intensity=True): the raw images and how
+    to read them.  color: uint8 [H,W,3] or [H,W]; depth: uint16 [H,W].  The conversion itself runs on the device."""
+
+    def __init__(self, color, depth, depth_scale=1000.0, depth_trunc=3.0, bgr=False):
+        self.depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        self.color = np.ascontiguousarray(color, dtype=np.uint8)
+        if self.depth.ndim != 2 or self.color.shape[:2] != self.depth.shape or self.color.ndim not in (2, 3) or \
+                (self.color.ndim == 3 and self.color.shape[2] not in (1, 3)):
+            raise ValueError(f"colour image {self.color.shape} and depth image {self.depth.shape} do not make an RGB-D image")
+        self.channels = 1 if self.color.ndim == 2 else self.color.shape[2]
+        self.depth_scale, self.depth_trunc, self.bgr = float(depth_scale), float(depth_trunc), bool(bgr)
+
+    def planes(self, ctx=None):
+        """-> intensity, depth as float32 [H,W] (r3d_debug_rgbd_convert)"""
+        ctx = ctx or _lib.default_context()
+        H, W = self.depth.shape
+        cam = DepthCamera(1.0, 1.0, 0.0, 0.0, self.depth_scale, self.depth_trunc, 0, 0)
+        inten, z = np.empty((H, W), np.float32), np.empty((H, W), np.float32)
+        ctx.call("r3d_debug_rgbd_convert", _ptr(self.depth), _ptr(self.color), W, H, W, W * self.channels, self.channels, int(self.bgr),
+                 ctypes.byref(cam), _ptr(inten), _ptr(z))
+        return inten, z
+
+
+def rgbd_image(color, depth, depth_scale=1000.0, depth_trunc=3.0, bgr=False):
+    return RGBDImage(color, depth, depth_scale, depth_trunc, bgr)
+
+
+def _intrinsic4(intrinsic):
+    if isinstance(intrinsic, DepthCamera):
+        return intrinsic.fx, intrinsic.fy, intrinsic.ppx, intrinsic.ppy
+    if isinstance(intrinsic, dict):
+        return tuple(float(intrinsic[k]) for k in ("fx", "fy", "ppx", "ppy"))
+    a = np.asarray(intrinsic, dtype=np.float64)
+    if a.size == 4:
+        return tuple(float(v) for v in a.reshape(4))
+    K = a.reshape(3, 3)
+    return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+
+
+def _f32_frames(source, target):
+    planes = [np.ascontiguousarray(p, dtype=np.float32) for p in (source[0], source[1], target[0], target[1])]
+    if planes[0].ndim != 2 or any(p.shape != planes[0].shape for p in planes):
+        raise ValueError("the four planes (source intensity, source depth, target intensity, target depth) must be 2-D and of one size")
+    return planes
+
+
+def _odometry_result(T, info, st, trace):
+    res = dict(success=bool(st.success), T=T, info=info, failed_level=st.failed_level, failed_iteration=st.failed_iteration,
+               correspondences_init=st.correspondences_init, correspondences=st.correspondences, r2=st.r2, setup_ms=st.setup_ms,
+               loop_ms=st.loop_ms)
+    if trace is not None:
+        res["trace"] = trace
+    return res
+
+
+def rgbd_odometry(source, target, intrinsic, odo_init=None, jacobian="hybrid", want_trace=False, ctx=None, **option):
+    """compute_rgbd_odometry with its statistics as a dict (T maps source camera coordinates to target camera coordinates).
+    source / target: two RGBDImage (r3d_rgbd_odometry: the raw images go up and are converted on the device; both must share
+    depth_scale, depth_trunc and channel order) or two (intensity, depth) pairs of float32 planes (r3d_rgbd_odometry_f32).
+    intrinsic: depth_camera(...), a dict with fx / fy / ppx / ppy, a 3x3 matrix or (fx, fy, cx, cy)."""
+    ctx = ctx or _lib.default_context()
+    prm = odometry_params(jacobian, **option)
+    fx, fy, cx, cy = _intrinsic4(intrinsic)
+    init = None if odo_init is None else np.ascontiguousarray(odo_init, dtype=np.float64).reshape(4, 4)
+    T, info, st = np.empty((4, 4)), np.empty((6, 6)), OdometryStats()
+    trace = np.zeros((sum(prm.iterations[:prm.levels]) if 1 <= prm.levels <= 4 else 0, 4, 4)) if want_trace else None
+    if isinstance(source, RGBDImage) and isinstance(target, RGBDImage):
+        if (source.depth_scale, source.depth_trunc, source.bgr, source.channels, source.depth.shape) != \
+                (target.depth_scale, target.depth_trunc, target.bgr, target.channels, target.depth.shape):
+            raise ValueError("source and target RGB-D images differ in size, depth_scale, depth_trunc or channel order")
+        H, W = source.depth.shape
+        cam = DepthCamera(fx, fy, cx, cy, source.depth_scale, source.depth_trunc, 0, 0)
+        ctx.call("r3d_rgbd_odometry", ctypes.byref(prm), _ptr(source.depth), _ptr(source.color), _ptr(target.depth), _ptr(target.color), W, H,
+                 W, W * source.channels, source.channels, int(source.bgr), ctypes.byref(cam), _ptr(init), _ptr(T), _ptr(info), ctypes.byref(st),
+                 _ptr(trace))
+    else:
+        si, sd, ti, td = _f32_frames(source, target)
+        H, W = si.shape
+        ctx.call("r3d_rgbd_odometry_f32", ctypes.byref(prm), _ptr(si), _ptr(sd), _ptr(ti), _ptr(td), W, H, W, fx, fy, cx, cy, _ptr(init),
+                 _ptr(T), _ptr(info), ctypes.byref(st), _ptr(trace))
+    return _odometry_result(T, info, st, trace)
+
+
+def rgbd_odometry_device(d_source, d_target, width, height, intrinsic, odo_init=None, jacobian="hybrid", want_trace=False, ctx=None, **option):
+    """r3d_rgbd_odometry_f32_dev: d_source / d_target are (intensity, depth) pairs of device pointers (as int) to contiguous
+    float32 [height][width] planes.  Returns when the result is ready."""
+    ctx = ctx or _lib.default_context()
+    prm = odometry_params(jacobian, **option)
+    fx, fy, cx, cy = _intrinsic4(intrinsic)
+    init = None if odo_init is None else np.ascontiguousarray(odo_init, dtype=np.float64).reshape(4, 4)
+    T, info, st = np.empty((4, 4)), np.empty((6, 6)), OdometryStats()
+    trace = np.zeros((sum(prm.iterations[:prm.levels]) if 1 <= prm.levels <= 4 else 0, 4, 4)) if want_trace else None
+    ctx.call("r3d_rgbd_odometry_f32_dev", ctypes.byref(prm), _vp(d_source[0]), _vp(d_source[1]), _vp(d_target[0]), _vp(d_target[1]), int(width),
+             int(height), int(width), fx, fy, cx, cy, _ptr(init), _ptr(T), _ptr(info), ctypes.byref(st), _ptr(trace))
+    return _odometry_result(T, info, st, trace)
+
+
+def compute_rgbd_odometry(source, target, intrinsic, odo_init=None, jacobian="hybrid", want_trace=False, ctx=None, **option):
+    """o3d.pipelines.odometry.compute_rgbd_odometry(source, target, intrinsic, odo_init, jacobian, OdometryOption(**option))
+    (test/check84.py:239-241).  -> (success, T, info) as Open3D does[, trace [sum of iterations][4][4]]."""
+    res = rgbd_odometry(source, target, intrinsic, odo_init, jacobian, want_trace, ctx, **option)
+    out = (res["success"], res["T"], res["info"])
+    return out + (res["trace"],) if want_trace else out
+
+
+def debug_rgbd_prepare(source, target, intrinsic, odo_init=None, grad_level=0, ctx=None, **option):
+    """r3d_debug_rgbd_prepare on (intensity, depth) float32 pairs.  -> dict(source=[(I_l, D_l)], target=[(I_l, D_l)],
+    gradients=(dI/dx, dI/dy, dD/dx, dD/dy) of grad_level, correspondences_init, scales=(s_src, s_tgt))"""
+    ctx = ctx or _lib.default_context()
+    prm = odometry_params(**option)
+    fx, fy, cx, cy = _intrinsic4(intrinsic)
+    init = None if odo_init is None else np.ascontiguousarray(odo_init, dtype=np.float64).reshape(4, 4)
+    si, sd, ti, td = _f32_frames(source, target)
+    H, W = si.shape
+    shapes = [(H >> l, W >> l) for l in range(max(prm.levels, 1))]
+    total = sum(a * b for a, b in shapes)
+    pyr = [np.empty(total, np.float32) for _ in range(4)]
+    gl = min(max(int(grad_level), 0), len(shapes) - 1)
+    grad = np.empty(shapes[gl] + (4,), np.float32)
+    n, sc = ctypes.c_int64(), np.zeros(2)
+    ctx.call("r3d_debug_rgbd_prepare", ctypes.byref(prm), _ptr(si), _ptr(sd), _ptr(ti), _ptr(td), W, H, W, fx, fy, cx, cy, _ptr(init),
+             _ptr(pyr[0]), _ptr(pyr[1]), _ptr(pyr[2]), _ptr(pyr[3]), int(grad_level), _ptr(grad), ctypes.byref(n), _ptr(sc))
+    offs = np.cumsum([0] + [a * b for a, b in shapes])
+    cut = lambda p: [p[offs[l]:offs[l + 1]].reshape(shapes[l]) for l in range(len(shapes))]
+    return dict(source=list(zip(cut(pyr[0]), cut(pyr[1]))), target=list(zip(cut(pyr[2]), cut(pyr[3]))),
+                gradients=tuple(np.ascontiguousarray(grad[..., k]) for k in range(4)), correspondences_init=n.value, scales=(sc[0], sc[1]))
+
+
+def debug_rgbd_iteration(source, target, intrinsic, level, pose, odo_init=None, jacobian="hybrid", ctx=None, **option):
+    """r3d_debug_rgbd_iteration.  -> dict(corr int32 [n][4] rows (u_s, v_s, u_t, v_t), sums [29], T pose after the step, ok)"""
+    ctx = ctx or _lib.default_context()
+    prm = odometry_params(jacobian, **option)
+    fx, fy, cx, cy = _intrinsic4(intrinsic)
+    init = None if odo_init is None else np.ascontiguousarray(odo_init, dtype=np.float64).reshape(4, 4)
+    pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(4, 4)
+    si, sd, ti, td = _f32_frames(source, target)
+    H, W = si.shape
+    lv = min(max(int(level), 0), 3)
+    corr = np.empty(((H >> lv) * (W >> lv), 4), np.int32)
+    n, ok, sums, T = ctypes.c_int64(), _i32(), np.empty(29), np.empty((4, 4))
+    ctx.call("r3d_debug_rgbd_iteration", ctypes.byref(prm), _ptr(si), _ptr(sd), _ptr(ti), _ptr(td), W, H, W, fx, fy, cx, cy, _ptr(init),
+             int(level), _ptr(pose), _ptr(corr), ctypes.byref(n), _ptr(sums), _ptr(T), ctypes.byref(ok))
+    return dict(corr=corr[:n.value].copy(), sums=sums, T=T, ok=bool(ok.value))

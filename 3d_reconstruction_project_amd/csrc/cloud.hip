@@ -2212,24 +2212,6 @@ __global__ void __launch_bounds__(256) k_vt_means(const double *__restrict__ sum
     out[i * 3] = sums[i * 3] / c; out[i * 3 + 1] = sums[i * 3 + 1] / c; out[i * 3 + 2] = sums[i * 3 + 2] / c;
 }
 
-struct DevArena {  // simple bump allocator over ctx->cloud_bufs (grow-only, reused across calls)
-    r3d_ctx *ctx;
-    size_t next = 0;
-    int rc = R3D_OK;
-    explicit DevArena(r3d_ctx *c) : ctx(c) {}
-    void *get(size_t bytes) {
-        if (rc) return nullptr;
-        if (ctx->poisoned) {
-            rc = r3d_fail(ctx, R3D_E_HIP, "context poisoned by an earlier timed-out call (its kernels may still use the arena): destroy it");
-            return nullptr;
-        }
-        if (next >= ctx->cloud_bufs.size()) ctx->cloud_bufs.emplace_back();
-        r3d_buf &b = ctx->cloud_bufs[next++];
-        rc = r3d_reserve(ctx, b, bytes ? bytes : 16);
-        return rc ? nullptr : b.p;
-    }
-};
-
 // Small device -> host reads between kernels (counts, bounding boxes).  k_publish copies every piece into the context's pinned,
 // device-mapped buffer and then stores a sequence number there (system-scope fence in between); the host polls that number in
 // memory.  No copy command, no marker, no runtime call in the wait: two staged 4-byte hipMemcpyAsync + a blocking synchronise
@@ -2870,57 +2852,6 @@ __host__ __device__ void umeyama_polish(const double *s /*ICP slots*/, double U[
         for (int j = 0; j < 3; j++) U[i * 4 + j] = R[i][j];
         U[i * 4 + 3] = pt[i] - (R[i][0] * ps[0] + R[i][1] * ps[1] + R[i][2] * ps[2]);
     }
-}
-
-// SolveJacobianSystemAndObtainExtrinsicMatrix: x = LDLT(JTJ) \ (-JTr); identity when |det| < det_tol (the registration loop's
-// 1e-6).  det_tol < 0 (FGR: Open3D's SolveLinearSystemPSD has no such rule): no determinant test; the identity only for a zero
-// pivot or a non-finite x.
-__host__ __device__ bool solve6_to_matrix(const double *s, double U[16], double det_tol = 1e-6) {
-    double A[6][6], b[6];
-    for (int a = 0, q = 2; a < 6; a++)
-        for (int c = a; c < 6; c++, q++) A[a][c] = A[c][a] = s[q];
-    for (int a = 0; a < 6; a++) b[a] = -s[23 + a];
-    // LDL^T
-    double L[6][6], Dg[6];
-    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) L[i][j] = 0;
-    double det = 1;
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-        for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * Dg[k];
-        Dg[j] = d;
-        det *= d;
-        L[j][j] = 1;
-        for (int i = j + 1; i < 6; i++) {
-            double v = A[i][j];
-            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * Dg[k];
-            L[i][j] = d != 0 ? v / d : 0;
-        }
-    }
-    for (int i = 0; i < 16; i++) U[i] = (i % 5 == 0);
-    if (det_tol >= 0) {
-        if (!isfinite(det) || fabs(det) < det_tol) return false;
-    } else {
-        for (int j = 0; j < 6; j++) if (Dg[j] == 0) return false;
-    }
-    double y[6], x[6];
-    for (int i = 0; i < 6; i++) { y[i] = b[i]; for (int k = 0; k < i; k++) y[i] -= L[i][k] * y[k]; }
-    for (int i = 0; i < 6; i++) y[i] /= Dg[i];
-    for (int i = 5; i >= 0; i--) { x[i] = y[i]; for (int k = i + 1; k < 6; k++) x[i] -= L[k][i] * x[k]; }
-    if (det_tol < 0) {
-        for (int i = 0; i < 6; i++) if (!isfinite(x[i])) return false;
-    }
-    // TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0)
-    double ca, sa, cb, sb, cc, sc;   // one range reduction per angle (the update runs in a single GPU thread)
-    sincos(x[0], &sa, &ca);
-    sincos(x[1], &sb, &cb);
-    sincos(x[2], &sc, &cc);
-    const double R[9] = {cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
-                         -sb, cb * sa, cb * ca};
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) U[i * 4 + j] = R[i * 3 + j];
-        U[i * 4 + 3] = x[3 + i];
-    }
-    return true;
 }
 
 // One step of the registration loop on the device.  16 waves: wave w reduces slots w and w + 16 (lane t adds the partials

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -93,6 +94,75 @@ int r3d_reserve(r3d_ctx *ctx, r3d_buf &b, size_t bytes);
             return r3d_fail((ctx), R3D_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
                             __FILE__, __LINE__);                                                    \
     } while (0)
+
+struct DevArena {  // simple bump allocator over ctx->cloud_bufs (grow-only, reused across calls)
+    r3d_ctx *ctx;
+    size_t next = 0;
+    int rc = R3D_OK;
+    explicit DevArena(r3d_ctx *c) : ctx(c) {}
+    void *get(size_t bytes) {
+        if (rc) return nullptr;
+        if (ctx->poisoned) {
+            rc = r3d_fail(ctx, R3D_E_HIP, "context poisoned by an earlier timed-out call (its kernels may still use the arena): destroy it");
+            return nullptr;
+        }
+        if (next >= ctx->cloud_bufs.size()) ctx->cloud_bufs.emplace_back();
+        r3d_buf &b = ctx->cloud_bufs[next++];
+        rc = r3d_reserve(ctx, b, bytes ? bytes : 16);
+        return rc ? nullptr : b.p;
+    }
+};
+
+// SolveJacobianSystemAndObtainExtrinsicMatrix: x = LDLT(JTJ) \ (-JTr); identity when |det| < det_tol (the registration loop's
+// 1e-6).  det_tol < 0 (FGR: Open3D's SolveLinearSystemPSD has no such rule): no determinant test; the identity only for a zero
+// pivot or a non-finite x.
+__host__ __device__ inline bool solve6_to_matrix(const double *s, double U[16], double det_tol = 1e-6) {
+    double A[6][6], b[6];
+    for (int a = 0, q = 2; a < 6; a++)
+        for (int c = a; c < 6; c++, q++) A[a][c] = A[c][a] = s[q];
+    for (int a = 0; a < 6; a++) b[a] = -s[23 + a];
+    // LDL^T
+    double L[6][6], Dg[6];
+    for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) L[i][j] = 0;
+    double det = 1;
+    for (int j = 0; j < 6; j++) {
+        double d = A[j][j];
+        for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * Dg[k];
+        Dg[j] = d;
+        det *= d;
+        L[j][j] = 1;
+        for (int i = j + 1; i < 6; i++) {
+            double v = A[i][j];
+            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * Dg[k];
+            L[i][j] = d != 0 ? v / d : 0;
+        }
+    }
+    for (int i = 0; i < 16; i++) U[i] = (i % 5 == 0);
+    if (det_tol >= 0) {
+        if (!isfinite(det) || fabs(det) < det_tol) return false;
+    } else {
+        for (int j = 0; j < 6; j++) if (Dg[j] == 0) return false;
+    }
+    double y[6], x[6];
+    for (int i = 0; i < 6; i++) { y[i] = b[i]; for (int k = 0; k < i; k++) y[i] -= L[i][k] * y[k]; }
+    for (int i = 0; i < 6; i++) y[i] /= Dg[i];
+    for (int i = 5; i >= 0; i--) { x[i] = y[i]; for (int k = i + 1; k < 6; k++) x[i] -= L[k][i] * x[k]; }
+    if (det_tol < 0) {
+        for (int i = 0; i < 6; i++) if (!isfinite(x[i])) return false;
+    }
+    // TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0)
+    double ca, sa, cb, sb, cc, sc;   // one range reduction per angle (the update runs in a single GPU thread)
+    sincos(x[0], &sa, &ca);
+    sincos(x[1], &sb, &cb);
+    sincos(x[2], &sc, &cc);
+    const double R[9] = {cc * cb, cc * sb * sa - sc * ca, cc * sb * ca + sc * sa, sc * cb, sc * sb * sa + cc * ca, sc * sb * ca - cc * sa,
+                         -sb, cb * sa, cb * ca};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) U[i * 4 + j] = R[i * 3 + j];
+        U[i * 4 + 3] = x[3 + i];
+    }
+    return true;
+}
 
 // profiling helpers: record an event before each named kernel when ctx->profiling
 void r3d_prof_harvest(r3d_ctx *ctx, r3d_prof_set &ps);

@@ -444,3 +444,16 @@ def multi_view_fuse(local_clouds, n_views, threshold=0.02, mode=cloud_ops.GICP, 
     fused, Ts = multi_view_fuse_tensors(local, n_views, threshold, mode, max_iteration, reg, tr, ctx)
     arr = fused.cpu().numpy()
     return PointCloud(arr[0], arr[2] if len(arr) == 3 else None, arr[1]), Ts
+
+
+def odometry_edges(frames, camera, ctx=None, **option):
+    """The pose-graph edges of consecutive frames (test/check84.py:236-255): frame i+1 -> frame i by RGB-D odometry from the
+    identity.  frames: (colour uint8 [H,W,3] or [H,W], depth uint16 [H,W]) pairs or cloud_ops.RGBDImage; camera:
+    cloud_ops.depth_camera(...), whose depth_scale and depth_trunc read the raw pairs.  A failed pair gives the identity and
+    uncertain=True, as the script's fallback edge.  -> [dict(source, target, T, info, uncertain)]"""
+    imgs = [f if isinstance(f, cloud_ops.RGBDImage) else cloud_ops.rgbd_image(f[0], f[1], camera.depth_scale, camera.depth_trunc) for f in frames]
+    edges = []
+    for i in range(len(imgs) - 1):
+        ok, T, info = cloud_ops.compute_rgbd_odometry(imgs[i + 1], imgs[i], camera, ctx=ctx, **option)
+        edges.append(dict(source=i + 1, target=i, T=T if ok else np.eye(4), info=info if ok else np.eye(6), uncertain=not ok))
+    return edges

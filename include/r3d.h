@@ -545,6 +545,76 @@ int r3d_transform_blocks_dev(r3d_ctx *ctx, int32_t n_blocks, const double *const
                              const int32_t *rotate_only, double *const *d_out);
 
 
+/* ---- RGB-D odometry ("RGB-D odometry") ---------------------------------------------------------------------
+ * replaces: o3d.pipelines.odometry.compute_rgbd_odometry(source, target, intrinsic, odo_init,
+ *           RGBDOdometryJacobianFromHybridTerm(), OdometryOption())   test/check84.py:239-241 -- the registration of consecutive
+ * frames, the one registration of the reference that works on images and not on clouds.  [recalled, Open3D 0.18
+ * pipelines/odometry/Odometry.cpp, RGBDOdometryJacobian.cpp, geometry/Image.cpp]: Open3D is absent and the reference recorded no
+ * poses, so parity is UNPINNED; tests/rgbd_odometry_ref.py restates the contract with its open choices as named switches.
+ * Image pyramids (Gaussian3 + 2x2 mean), a z-buffered warp of the source depth into the target (smallest float32 z' wins, then
+ * the smaller source index), a 6x6 Gauss-Newton step per iteration through the registration loop's solver (|det| < 1e-6 =>
+ * failure), no convergence test.  All iterations of all levels are enqueued without a host read; the same bits on every run. */
+#define R3D_ODOMETRY_HYBRID 0  /* RGBDOdometryJacobianFromHybridTerm: photometric + depth residual, lambda_depth 0.95 */
+#define R3D_ODOMETRY_COLOR 1   /* RGBDOdometryJacobianFromColorTerm: the photometric row alone */
+typedef struct r3d_odometry_params {   /* 48 bytes */
+    double depth_diff_max;             /* 0.03; >= 0 */
+    double depth_min, depth_max;       /* 0.0, 4.0 */
+    int32_t iterations[4];             /* coarsest level first; 20, 10, 5, 0; each >= 0 */
+    int32_t levels;                    /* 1..4; 3 */
+    int32_t jacobian;                  /* R3D_ODOMETRY_* */
+} r3d_odometry_params;
+typedef struct r3d_odometry_stats {    /* 56 bytes */
+    int32_t success, failed_level, failed_iteration, reserved;   /* -1, -1 when success; (0, -1): no correspondences at odo_init */
+    int64_t correspondences_init, correspondences;               /* at odo_init / at the result, level 0 */
+    double r2;                                                   /* sum of r^2 of the last iteration */
+    double setup_ms, loop_ms;                                    /* device time: pyramids + normalisation / iterations + information */
+} r3d_odometry_stats;
+/* source, target: frames of equal size w x h.  init4x4 (NULL: identity) and T4x4 map source camera coordinates to target camera
+ * coordinates, row-major.  info6x6 (may be NULL): the information matrix of the level-0 correspondences at the result.
+ * trace_T (may be NULL): the pose after every iteration, [sum of iterations][16], rows after a failure zero.  An odometry
+ * failure (no correspondences, a singular system) is NOT an error: the call returns 0 with stats->success = 0, T = identity and
+ * info = identity.  R3D_E_BADARG: a missing array, w or h < 2^(levels-1), levels outside 1..4, a negative iteration count or
+ * depth_diff_max, an unknown jacobian, fx or fy of 0, a stride too small, color_channels other than 1 or 3.
+ * r3d_rgbd_odometry: raw HOST images as create_from_color_and_depth(convert_rgb_to_intensity=True) takes them: depth uint16
+ * [h][depth_stride], colour uint8 [h][color_stride bytes] with 1 or 3 channels (color_bgr != 0: B, G, R order); intensity =
+ * (0.2990f R + 0.5870f G + 0.1140f B) / 255.0f, z = float32(raw) / float32(depth_scale), z > depth_trunc => 0 (cam->flip_yz is
+ * not used).  r3d_rgbd_odometry_f32: float32 HOST planes [h][stride floats], intensity in [0, 1], depth in metres (0 or NaN: no
+ * measurement).  r3d_rgbd_odometry_f32_dev: the same on DEVICE planes; returns when the result is ready, like r3d_icp_dev. */
+int r3d_rgbd_odometry(r3d_ctx *ctx, const r3d_odometry_params *p, const uint16_t *src_depth, const uint8_t *src_color,
+                      const uint16_t *tgt_depth, const uint8_t *tgt_color, int32_t w, int32_t h, int32_t depth_stride,
+                      int32_t color_stride, int32_t color_channels, int32_t color_bgr, const r3d_depth_camera *cam,
+                      const double *init4x4, double *T4x4, double *info6x6, r3d_odometry_stats *stats, double *trace_T);
+int r3d_rgbd_odometry_f32(r3d_ctx *ctx, const r3d_odometry_params *p, const float *src_intensity, const float *src_depth,
+                          const float *tgt_intensity, const float *tgt_depth, int32_t w, int32_t h, int32_t stride, double fx,
+                          double fy, double cx, double cy, const double *init4x4, double *T4x4, double *info6x6,
+                          r3d_odometry_stats *stats, double *trace_T);
+int r3d_rgbd_odometry_f32_dev(r3d_ctx *ctx, const r3d_odometry_params *p, const float *d_src_intensity, const float *d_src_depth,
+                              const float *d_tgt_intensity, const float *d_tgt_depth, int32_t w, int32_t h, int32_t stride,
+                              double fx, double fy, double cx, double cy, const double *init4x4, double *T4x4, double *info6x6,
+                              r3d_odometry_stats *stats, double *trace_T);
+/* the conversion of the raw form alone: out_intensity, out_depth float32 [h][w] on the host */
+int r3d_debug_rgbd_convert(r3d_ctx *ctx, const uint16_t *depth, const uint8_t *color, int32_t w, int32_t h, int32_t depth_stride,
+                           int32_t color_stride, int32_t color_channels, int32_t color_bgr, const r3d_depth_camera *cam,
+                           float *out_intensity, float *out_depth);
+/* the preparation alone (host float planes in, as r3d_rgbd_odometry_f32).  Each pyramid output holds the levels one after the
+ * other, level l as float32 [h >> l][w >> l], un-normalised; any of them may be NULL.  grad4 (may be NULL): the target gradient
+ * records of level grad_level, float32 [h_l][w_l][4] = Sobel dI/dx, dI/dy, dD/dx, dD/dy (not yet multiplied by 0.125, NaN kept).
+ * *corr_init: correspondences at init4x4 on level 0; scales2: s_src, s_tgt (0, 0 when there are none). */
+int r3d_debug_rgbd_prepare(r3d_ctx *ctx, const r3d_odometry_params *p, const float *src_intensity, const float *src_depth,
+                           const float *tgt_intensity, const float *tgt_depth, int32_t w, int32_t h, int32_t stride, double fx,
+                           double fy, double cx, double cy, const double *init4x4, float *src_pyr_intensity, float *src_pyr_depth,
+                           float *tgt_pyr_intensity, float *tgt_pyr_depth, int32_t grad_level, float *grad4, int64_t *corr_init,
+                           double *scales2);
+/* prepares (scales from init4x4), then one iteration at `level` from pose4x4: corr (may be NULL) int32 [w_l h_l][4] rows
+ * (u_s, v_s, u_t, v_t) in target row-major order, *n_corr of them; sums29: count, sum r^2, the upper triangle of JTJ row by row,
+ * JTr; T_after: the pose after the step; *ok = 0 when the step failed (T_after = identity).  R3D_E_BADARG also for a level
+ * outside 0..levels-1 and when the normalisation at init4x4 finds no correspondences. */
+int r3d_debug_rgbd_iteration(r3d_ctx *ctx, const r3d_odometry_params *p, const float *src_intensity, const float *src_depth,
+                             const float *tgt_intensity, const float *tgt_depth, int32_t w, int32_t h, int32_t stride, double fx,
+                             double fy, double cx, double cy, const double *init4x4, int32_t level, const double *pose4x4,
+                             int32_t *corr, int64_t *n_corr, double *sums29, double *T_after, int32_t *ok);
+
+
 /* ---- per-frame stages either side of the matcher in Calib_depth/depth*.py --------------
  * OpenCV is a dependency of the reference that is absent here, and the reference records no output of these calls:
  * parity of this group is UNPINNED (restated from OpenCV 4.x's published algorithms; see oracle/prepost_oracle.py). */
