@@ -1,0 +1,904 @@
+// tsdf.hip -- Open3D's ScalableTSDFVolume on the device: posed RGB-D frames are integrated into a sparse volume of 16^3-voxel units
+// and a point cloud is extracted from it.  The contract is DESIGN.md section 4 "TSDF volume"; tests/tsdf_ref.py restates it in
+// numpy.  Every float expression below is written in the order the contract gives (build.sh passes -ffp-contract=off), so the
+// planes, the points and the colours are bit for bit the restatement's.
+//
+// A volume owns an open-addressing hash table of packed unit keys and a pool of unit blocks kept as planes (tsdf, weight, three
+// colour planes; 4096 entries per unit, the z walk of one (x, y) column contiguous).  One frame is three launches: k_tsdf_touch
+// (one thread per sampled pixel inserts the box of units around its point, lists the table entries that are new and those seen
+// for the first time in this frame), k_tsdf_assign (new entries get the next pool slots) and k_tsdf_integrate (one workgroup
+// per touched unit, one thread per column).  Between touch and assign the host reads 16 bytes of counters: how many units are new
+// decides whether pool and table must grow first.  Which slot a unit gets depends on which thread won the race; nothing
+// observable does: extraction and the debug dump walk the units in key order.  No kernel waits for another workgroup.
+#include <cstring>
+
+#include "r3d_internal.h"
+
+namespace {
+
+constexpr int TSDF_R = 16;                    // volume_unit_resolution (the only one)
+constexpr int TSDF_UNIT = TSDF_R * TSDF_R * TSDF_R;
+constexpr int TSDF_IDX_LIMIT = 1 << 20;       // unit indices in [-2^20, 2^20): 21 bits per axis
+constexpr unsigned long long TSDF_EMPTY = ~0ull;
+constexpr int TSDF_DEFAULT_UNITS = 1024;
+
+struct TsdfCounters { int n_new, n_touched, table_full, out_of_range; };
+
+struct TsdfTable {
+    unsigned long long *keys;   // TSDF_EMPTY or a packed unit key
+    int *slot;                  // pool slot of the entry's unit
+    int *stamp;                 // number of the touch pass that last saw the entry
+    int cap;                    // a power of two, at least twice the pool capacity
+};
+
+struct TsdfCam { double fx, fy, cx, cy; };
+struct TsdfPose { double Ai[9], ti[3]; };   // camera -> world: the inverse of the extrinsic
+
+// key order = ascending (X, Y, Z)
+__host__ __device__ inline unsigned long long tsdf_pack(int X, int Y, int Z) {
+    return ((unsigned long long)(X + TSDF_IDX_LIMIT) << 42) | ((unsigned long long)(Y + TSDF_IDX_LIMIT) << 21) |
+           (unsigned long long)(Z + TSDF_IDX_LIMIT);
+}
+__host__ __device__ inline void tsdf_unpack(unsigned long long key, int &X, int &Y, int &Z) {
+    X = (int)(key >> 42) - TSDF_IDX_LIMIT;
+    Y = (int)((key >> 21) & 0x1FFFFF) - TSDF_IDX_LIMIT;
+    Z = (int)(key & 0x1FFFFF) - TSDF_IDX_LIMIT;
+}
+__device__ __forceinline__ bool tsdf_in_range(int X, int Y, int Z) {
+    return X >= -TSDF_IDX_LIMIT && X < TSDF_IDX_LIMIT && Y >= -TSDF_IDX_LIMIT && Y < TSDF_IDX_LIMIT && Z >= -TSDF_IDX_LIMIT && Z < TSDF_IDX_LIMIT;
+}
+__device__ __forceinline__ unsigned tsdf_hash(unsigned long long k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
+    return (unsigned)k;
+}
+// pool slot of the unit (X, Y, Z), -1 when the volume has no such unit
+__device__ inline int tsdf_find(const TsdfTable &t, int X, int Y, int Z) {
+    if (!tsdf_in_range(X, Y, Z)) return -1;
+    const unsigned long long key = tsdf_pack(X, Y, Z);
+    const unsigned mask = (unsigned)t.cap - 1u;
+    unsigned h = tsdf_hash(key) & mask;
+    for (int probe = 0; probe < t.cap; probe++, h = (h + 1u) & mask) {
+        const unsigned long long k = t.keys[h];
+        if (k == key) return t.slot[h];
+        if (k == TSDF_EMPTY) return -1;
+    }
+    return -1;
+}
+
+__global__ void __launch_bounds__(256) k_tsdf_depth_u16(const uint16_t *__restrict__ raw, int w, int h, float scale, float trunc, float *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= w * h) return;
+    float z = (float)raw[i] / scale;
+    if (z > trunc) z = 0.0f;
+    out[i] = z;
+}
+
+// ---- touch ------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_tsdf_touch(const float *__restrict__ depth, int dstride, int s, int nj, int ni, TsdfCam c, TsdfPose P,
+                                                    double trunc, double ul, TsdfTable t, int pass, int *__restrict__ new_list,
+                                                    int *__restrict__ touched, TsdfCounters *__restrict__ cnt) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= ni * nj) return;
+    const int i = (idx / nj) * s, j = (idx % nj) * s;
+    const float zf = depth[(size_t)i * dstride + j];
+    if (!(zf > 0.0f)) return;
+    const double z = (double)zf;
+    const double x = (((double)j - c.cx) * z) / c.fx, y = (((double)i - c.cy) * z) / c.fy;
+    int lo[3], hi[3];
+    for (int k = 0; k < 3; k++) {
+        const double p = ((P.Ai[k * 3] * x + P.Ai[k * 3 + 1] * y) + P.Ai[k * 3 + 2] * z) + P.ti[k];
+        const double l = floor((p - trunc) / ul), u = floor((p + trunc) / ul);
+        if (!(l >= (double)-TSDF_IDX_LIMIT && u < (double)TSDF_IDX_LIMIT)) {   // also a NaN or an infinity
+            cnt->out_of_range = 1;
+            return;
+        }
+        lo[k] = (int)l;
+        hi[k] = (int)u;
+    }
+    const unsigned mask = (unsigned)t.cap - 1u;
+    for (int X = lo[0]; X <= hi[0]; X++)
+        for (int Y = lo[1]; Y <= hi[1]; Y++)
+            for (int Z = lo[2]; Z <= hi[2]; Z++) {
+                const unsigned long long key = tsdf_pack(X, Y, Z);
+                unsigned h = tsdf_hash(key) & mask;
+                bool placed = false;
+                for (int probe = 0; probe < t.cap; probe++, h = (h + 1u) & mask) {
+                    unsigned long long k = t.keys[h];
+                    if (k == TSDF_EMPTY) {
+                        k = atomicCAS(&t.keys[h], TSDF_EMPTY, key);
+                        if (k == TSDF_EMPTY) {
+                            new_list[atomicAdd(&cnt->n_new, 1)] = (int)h;   // at most t.cap entries can be claimed
+                            k = key;
+                        }
+                    }
+                    if (k == key) {
+                        if (atomicExch(&t.stamp[h], pass) != pass) touched[atomicAdd(&cnt->n_touched, 1)] = (int)h;
+                        placed = true;
+                        break;
+                    }
+                }
+                if (!placed) {
+                    cnt->table_full = 1;
+                    return;
+                }
+            }
+}
+
+__global__ void __launch_bounds__(256) k_tsdf_assign(TsdfTable t, const int *__restrict__ new_list, int n_new, int base,
+                                                     unsigned long long *__restrict__ unit_keys) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_new) return;
+    const int h = new_list[i];
+    t.slot[h] = base + i;
+    unit_keys[base + i] = t.keys[h];
+}
+
+// the table from the units alone (after a growth, and to forget the entries of a touch pass that was given up)
+__global__ void __launch_bounds__(256) k_tsdf_rebuild(TsdfTable t, const unsigned long long *__restrict__ unit_keys, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = unit_keys[i];
+    const unsigned mask = (unsigned)t.cap - 1u;
+    unsigned h = tsdf_hash(key) & mask;
+    for (int probe = 0; probe < t.cap; probe++, h = (h + 1u) & mask)
+        if (atomicCAS(&t.keys[h], TSDF_EMPTY, key) == TSDF_EMPTY) {
+            t.slot[h] = i;
+            return;
+        }
+}
+
+// ---- integrate --------------------------------------------------------------------------------------------------------------------
+struct TsdfFrame {
+    const float *depth;
+    const uint8_t *color;
+    int dstride, cstride, w, h;
+    float fx, fy, cx, cy, ifx, ify;   // ifx = 1.0f / fx
+    float E[12];                      // float32 of the extrinsic's first three rows
+    float vl, trunc, itrunc, wlim, hlim;
+    double vld, ul;
+};
+
+// QUIRK_TSDF_MATVEC_ORDER: ((E0 x + E1 y) + E2 z) + E3.  QUIRK_TSDF_Z_RUNNING_SUM: the camera point of z + 1 is that of z plus
+// f32(E[k][2] * f32(vl)), a running float32 sum down the column.
+template <bool COLOR>
+__global__ void __launch_bounds__(256) k_tsdf_integrate(TsdfFrame F, TsdfTable t, const int *__restrict__ touched, float *__restrict__ tsdf,
+                                                        float *__restrict__ weight, double *__restrict__ c0, double *__restrict__ c1,
+                                                        double *__restrict__ c2) {
+    const int h = touched[blockIdx.x];
+    const int slot = t.slot[h];
+    int X, Y, Z;
+    tsdf_unpack(t.keys[h], X, Y, Z);
+    const int x = (int)threadIdx.x >> 4, y = (int)threadIdx.x & 15;
+    const double half = 0.5 * F.vld;
+    const float Px = (float)((half + F.vld * (double)x) + (double)X * F.ul);
+    const float Py = (float)((half + F.vld * (double)y) + (double)Y * F.ul);
+    const float Pz = (float)(half + (double)Z * F.ul);
+    float pc0 = ((F.E[0] * Px + F.E[1] * Py) + F.E[2] * Pz) + F.E[3];
+    float pc1 = ((F.E[4] * Px + F.E[5] * Py) + F.E[6] * Pz) + F.E[7];
+    float pc2 = ((F.E[8] * Px + F.E[9] * Py) + F.E[10] * Pz) + F.E[11];
+    const float s0 = F.E[2] * F.vl, s1 = F.E[6] * F.vl, s2 = F.E[10] * F.vl;
+    // first the walk alone: which voxels of the column update, with what value, from which pixel.  A column with none (most of
+    // them: outside the image, on a hole, far behind the surface) loads and stores nothing.  The 16 values and pixel offsets of
+    // a thread wait in LDS (its own entries, [z][thread]: no bank conflict, no barrier): held in registers, the unrolled walk
+    // took all 256 VGPRs and left one wave per SIMD.
+    __shared__ float s_tv[TSDF_R * 256];
+    __shared__ int s_pix[COLOR ? TSDF_R * 256 : 1];
+    const int tid = (int)threadIdx.x;
+    unsigned upd = 0;
+#pragma unroll 2
+    for (int z = 0; z < TSDF_R; z++) {
+        if (pc2 > 0.0f) {
+            const float uf = ((pc0 * F.fx) / pc2 + F.cx) + 0.5f, vf = ((pc1 * F.fy) / pc2 + F.cy) + 0.5f;
+            if (uf >= 0.0001f && uf < F.wlim && vf >= 0.0001f && vf < F.hlim) {
+                int u = (int)uf, v = (int)vf;
+                u = u < F.w ? u : F.w - 1;   // never taken while wlim < w; keeps the gather inside the image whatever wlim rounds to
+                v = v < F.h ? v : F.h - 1;
+                const float d = F.depth[(size_t)v * F.dstride + u];
+                if (d > 0.0f) {
+                    const float xx = ((float)u - F.cx) * F.ifx, yy = ((float)v - F.cy) * F.ify;
+                    const float mult = sqrtf((xx * xx + yy * yy) + 1.0f);
+                    const float sdf = (d - pc2) * mult;
+                    if (sdf > -F.trunc) {
+                        const float q = sdf * F.itrunc;
+                        s_tv[z * 256 + tid] = q < 1.0f ? q : 1.0f;
+                        if (COLOR) s_pix[z * 256 + tid] = v * F.cstride + u * 3;
+                        upd |= 1u << z;
+                    }
+                }
+            }
+        }
+        pc0 += s0;
+        pc1 += s1;
+        pc2 += s2;
+    }
+    if (!upd) return;
+    const size_t base = (size_t)slot * TSDF_UNIT + (size_t)threadIdx.x * TSDF_R;
+    float f[TSDF_R], w[TSDF_R];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const float4 a = reinterpret_cast<const float4 *>(tsdf + base)[q], b = reinterpret_cast<const float4 *>(weight + base)[q];
+        f[q * 4] = a.x; f[q * 4 + 1] = a.y; f[q * 4 + 2] = a.z; f[q * 4 + 3] = a.w;
+        w[q * 4] = b.x; w[q * 4 + 1] = b.y; w[q * 4 + 2] = b.z; w[q * 4 + 3] = b.w;
+    }
+    if (COLOR) {
+        double *const planes[3] = {c0, c1, c2};
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            double2 *col = reinterpret_cast<double2 *>(planes[ch] + base);
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                if (!((upd >> (2 * q)) & 3u)) continue;
+                double2 cc = col[q];
+                if ((upd >> (2 * q)) & 1u)
+                    cc.x = (cc.x * (double)w[2 * q] + (double)F.color[s_pix[2 * q * 256 + tid] + ch]) / ((double)w[2 * q] + 1.0);
+                if ((upd >> (2 * q + 1)) & 1u)
+                    cc.y = (cc.y * (double)w[2 * q + 1] + (double)F.color[s_pix[(2 * q + 1) * 256 + tid] + ch]) / ((double)w[2 * q + 1] + 1.0);
+                col[q] = cc;
+            }
+        }
+    }
+#pragma unroll
+    for (int z = 0; z < TSDF_R; z++)
+        if ((upd >> z) & 1u) {
+            f[z] = (f[z] * w[z] + s_tv[z * 256 + tid]) / (w[z] + 1.0f);
+            w[z] = w[z] + 1.0f;
+        }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        if (!((upd >> (4 * q)) & 15u)) continue;
+        reinterpret_cast<float4 *>(tsdf + base)[q] = make_float4(f[q * 4], f[q * 4 + 1], f[q * 4 + 2], f[q * 4 + 3]);
+        reinterpret_cast<float4 *>(weight + base)[q] = make_float4(w[q * 4], w[q * 4 + 1], w[q * 4 + 2], w[q * 4 + 3]);
+    }
+}
+
+// ---- key order --------------------------------------------------------------------------------------------------------------------
+// order[r] = the slot whose key has r smaller keys: keys are distinct, so this is a permutation.  n^2 / 2 comparisons out of LDS,
+// no host read; a volume has thousands of units, not millions.
+__global__ void __launch_bounds__(256) k_tsdf_rank(const unsigned long long *__restrict__ unit_keys, int n, int *__restrict__ order) {
+    __shared__ unsigned long long tile[256];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long mine = i < n ? unit_keys[i] : 0ull;
+    int r = 0;
+    for (int base = 0; base < n; base += 256) {
+        tile[threadIdx.x] = base + (int)threadIdx.x < n ? unit_keys[base + threadIdx.x] : TSDF_EMPTY;
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < 256; j++) r += tile[j] < mine;
+        __syncthreads();
+    }
+    if (i < n) order[r] = i;
+}
+
+// ---- extraction -------------------------------------------------------------------------------------------------------------------
+struct TsdfVol {
+    TsdfTable t;
+    const float *tsdf, *weight;
+    const double *c[3];
+    double vl, ul;
+};
+
+__device__ __forceinline__ bool tsdf_usable(float w, float f) { return w != 0.0f && f < 0.98f && f >= -0.98f; }
+
+// QUIRK_TSDF_NORMAL_IGNORES_WEIGHT: the trilinear value reads tsdf alone (a never-observed voxel counts as 0.0), an absent unit
+// is 0.0 throughout
+__device__ double tsdf_at(const TsdfVol &V, const double *q) {
+    const double half = 0.5 * V.vl;
+    int U[3], i0[3];
+    double r[3];
+    for (int k = 0; k < 3; k++) {
+        const double ql = q[k] - half;
+        const double u = floor(ql / V.ul);
+        if (!(u >= (double)-TSDF_IDX_LIMIT && u < (double)TSDF_IDX_LIMIT)) return 0.0;
+        U[k] = (int)u;
+        const double g = (ql - u * V.ul) / V.vl;
+        int c = (int)floor(g);
+        c = c < 0 ? 0 : (c > TSDF_R - 1 ? TSDF_R - 1 : c);
+        i0[k] = c;
+        r[k] = g - (double)c;
+    }
+    const int home = tsdf_find(V.t, U[0], U[1], U[2]);
+    if (home < 0) return 0.0;
+    double f[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {   // corner c sits at i0 + {(0,0,0),(1,0,0),(1,1,0),(0,1,0),(0,0,1),(1,0,1),(1,1,1),(0,1,1)}[c]
+        const int off[3] = {((c + 1) >> 1) & 1, (c >> 1) & 1, c >> 2};
+        int v[3], W[3];
+        bool wrap = false;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            v[k] = i0[k] + off[k];
+            W[k] = U[k];
+            if (v[k] > TSDF_R - 1) { v[k] = 0; W[k]++; wrap = true; }
+        }
+        const int slot = wrap ? tsdf_find(V.t, W[0], W[1], W[2]) : home;
+        f[c] = slot < 0 ? 0.0 : (double)V.tsdf[(size_t)slot * TSDF_UNIT + (v[0] * TSDF_R + v[1]) * TSDF_R + v[2]];
+    }
+    const double a = 1.0 - r[0], b = 1.0 - r[1], g = 1.0 - r[2];
+    return a * (b * (g * f[0] + r[2] * f[4]) + r[1] * (g * f[3] + r[2] * f[7])) +
+           r[0] * (b * (g * f[1] + r[2] * f[5]) + r[1] * (g * f[2] + r[2] * f[6]));
+}
+
+// One workgroup per unit in key order, one thread per (x, y) column: its 16 voxels are 16 consecutive flat indices, so walking
+// threads in order, z in order, axes in order is the contract's order.  EMIT = false counts (thread offsets inside the unit and
+// the unit's total), EMIT = true writes the rows at unit_off[unit] + thread_off.
+template <bool EMIT, bool COLOR>
+__global__ void __launch_bounds__(256) k_tsdf_extract(TsdfVol V, const int *__restrict__ order, const unsigned long long *__restrict__ unit_keys,
+                                                      int *__restrict__ thread_off, int *__restrict__ unit_cnt,
+                                                      const long long *__restrict__ unit_off, double *__restrict__ xyz,
+                                                      double *__restrict__ nrm, double *__restrict__ col) {
+    __shared__ int scan[256];
+    const int unit = blockIdx.x, tid = (int)threadIdx.x;
+    const int slot = order[unit];
+    int X, Y, Z;
+    tsdf_unpack(unit_keys[slot], X, Y, Z);
+    const int x = tid >> 4, y = tid & 15;
+    const int sx = x == TSDF_R - 1 ? tsdf_find(V.t, X + 1, Y, Z) : slot;
+    const int sy = y == TSDF_R - 1 ? tsdf_find(V.t, X, Y + 1, Z) : slot;
+    const int sz = tsdf_find(V.t, X, Y, Z + 1);
+    const long long own = (long long)slot * TSDF_UNIT + tid * TSDF_R;
+    const long long nbx = sx < 0 ? -1 : (long long)sx * TSDF_UNIT + ((((x + 1) & 15) * TSDF_R) + y) * TSDF_R;
+    const long long nby = sy < 0 ? -1 : (long long)sy * TSDF_UNIT + ((x * TSDF_R) + ((y + 1) & 15)) * TSDF_R;
+    const long long nbz = sz < 0 ? -1 : (long long)sz * TSDF_UNIT + tid * TSDF_R;
+    long long out = 0;
+    if (EMIT) out = unit_off[unit] + thread_off[(size_t)unit * 256 + tid];
+    int n = 0;
+    const double half = 0.5 * V.vl;
+    for (int z = 0; z < TSDF_R; z++) {
+        const float f0 = V.tsdf[own + z], w0 = V.weight[own + z];
+        if (!tsdf_usable(w0, f0)) continue;
+        for (int a = 0; a < 3; a++) {
+            long long nb;
+            if (a == 0) nb = nbx < 0 ? -1 : nbx + z;
+            else if (a == 1) nb = nby < 0 ? -1 : nby + z;
+            else nb = z < TSDF_R - 1 ? own + z + 1 : nbz;
+            if (nb < 0) continue;
+            const float f1 = V.tsdf[nb], w1 = V.weight[nb];
+            if (!(tsdf_usable(w1, f1) && f0 * f1 < 0.0f)) continue;
+            if (EMIT) {
+                const float r0f = fabsf(f0), r1f = fabsf(f1);
+                const double r0 = (double)r0f, r1 = (double)r1f, rs = (double)(r0f + r1f);
+                double p[3] = {(half + V.vl * (double)x) + (double)X * V.ul, (half + V.vl * (double)y) + (double)Y * V.ul,
+                               (half + V.vl * (double)z) + (double)Z * V.ul};
+                p[a] = (p[a] * r1 + (p[a] + V.vl) * r0) / rs;
+                double *o = xyz + (out + n) * 3;
+                o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+                if (COLOR) {
+                    double *oc = col + (out + n) * 3;
+                    for (int ch = 0; ch < 3; ch++) oc[ch] = ((V.c[ch][own + z] * r1 + V.c[ch][nb] * r0) / rs) / 255.0;
+                }
+                const double d = 0.99 * V.vl;
+                double g[3];
+                for (int k = 0; k < 3; k++) {
+                    double q[3] = {p[0], p[1], p[2]};
+                    q[k] = p[k] + d;
+                    const double fp = tsdf_at(V, q);
+                    q[k] = p[k] - d;
+                    g[k] = fp - tsdf_at(V, q);
+                }
+                const double len = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+                double *on = nrm + (out + n) * 3;
+                for (int k = 0; k < 3; k++) on[k] = len != 0.0 ? g[k] / len : g[k];
+            }
+            n++;
+        }
+    }
+    if (EMIT) return;
+    scan[tid] = n;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    thread_off[(size_t)unit * 256 + tid] = scan[tid] - n;
+    if (tid == 255) unit_cnt[unit] = scan[255];
+}
+
+// exclusive offsets of the units and the total, one workgroup: 256 counts at a time with a carry
+__global__ void __launch_bounds__(256) k_tsdf_unit_offsets(const int *__restrict__ unit_cnt, int n, long long *__restrict__ unit_off,
+                                                           long long *__restrict__ total) {
+    __shared__ long long scan[256];
+    const int tid = (int)threadIdx.x;
+    long long carry = 0;
+    for (int base = 0; base < n; base += 256) {
+        const long long mine = base + tid < n ? (long long)unit_cnt[base + tid] : 0;
+        scan[tid] = mine;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const long long v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        if (base + tid < n) unit_off[base + tid] = carry + scan[tid] - mine;
+        carry += scan[255];
+        __syncthreads();
+    }
+    if (tid == 0) *total = carry;
+}
+
+// the debug dump: unit `order[blockIdx.x]`'s planes into row blockIdx.x
+__global__ void __launch_bounds__(256) k_tsdf_gather(TsdfVol V, int color, const int *__restrict__ order, const unsigned long long *__restrict__ unit_keys,
+                                                     int32_t *__restrict__ idx3, float *__restrict__ o_tsdf, float *__restrict__ o_weight,
+                                                     double *__restrict__ o_color) {
+    const int unit = blockIdx.x, slot = order[unit];
+    if (threadIdx.x == 0) {
+        int X, Y, Z;
+        tsdf_unpack(unit_keys[slot], X, Y, Z);
+        idx3[unit * 3] = X; idx3[unit * 3 + 1] = Y; idx3[unit * 3 + 2] = Z;
+    }
+    for (int e = threadIdx.x; e < TSDF_UNIT; e += 256) {
+        const size_t s = (size_t)slot * TSDF_UNIT + e, d = (size_t)unit * TSDF_UNIT + e;
+        o_tsdf[d] = V.tsdf[s];
+        o_weight[d] = V.weight[s];
+        if (color)
+            for (int ch = 0; ch < 3; ch++) o_color[((size_t)unit * 3 + ch) * TSDF_UNIT + e] = V.c[ch][s];
+    }
+}
+
+}  // namespace
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+struct r3d_tsdf {
+    r3d_ctx *ctx = nullptr;
+    r3d_tsdf_params prm = {};
+    int cap = 0;                 // pool capacity in units
+    int n_units = 0;
+    TsdfTable t = {};
+    float *tsdf = nullptr, *weight = nullptr;
+    double *c[3] = {};
+    unsigned long long *unit_keys = nullptr;
+    int *new_list = nullptr, *touched = nullptr, *order = nullptr;
+    TsdfCounters *d_cnt = nullptr, *h_cnt = nullptr;   // h_cnt: pinned
+    int pass = 0;
+    long long frames = 0;
+    int last_touched = 0, growths = 0;
+    hipEvent_t ev[3] = {};
+    bool timed = false;
+};
+
+namespace {
+
+template <class T> void tsdf_free(T *&p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+
+void tsdf_release(r3d_tsdf *v) {
+    tsdf_free(v->t.keys); tsdf_free(v->t.slot); tsdf_free(v->t.stamp);
+    tsdf_free(v->tsdf); tsdf_free(v->weight);
+    for (auto &p : v->c) tsdf_free(p);
+    tsdf_free(v->unit_keys); tsdf_free(v->new_list); tsdf_free(v->touched); tsdf_free(v->order); tsdf_free(v->d_cnt);
+    if (v->h_cnt) (void)hipHostFree(v->h_cnt);
+    v->h_cnt = nullptr;
+    for (auto &e : v->ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+}
+
+template <class T> int tsdf_alloc(r3d_ctx *ctx, T *&p, size_t count) {
+    void *q = nullptr;
+    const hipError_t e = hipMalloc(&q, count * sizeof(T));
+    if (e != hipSuccess) return r3d_fail(ctx, R3D_E_OOM, "tsdf: hipMalloc(%zu) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    p = (T *)q;
+    return R3D_OK;
+}
+
+// a plane of `cap` units from one of `old_cap`: the first n_units blocks copied, the rest zero
+template <class T> int tsdf_grow_plane(r3d_tsdf *v, T *&p, size_t per_unit, int new_cap) {
+    r3d_ctx *ctx = v->ctx;
+    T *q = nullptr;
+    if (int rc = tsdf_alloc(ctx, q, (size_t)new_cap * per_unit)) return rc;
+    const size_t keep = (size_t)v->n_units * per_unit;
+    hipError_t e = hipSuccess;
+    if (p && keep) e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(q + keep, 0, ((size_t)new_cap * per_unit - keep) * sizeof(T), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(q);
+        return r3d_fail(ctx, R3D_E_HIP, "tsdf: growing a plane failed: %s", hipGetErrorString(e));
+    }
+    tsdf_free(p);
+    p = q;
+    return R3D_OK;
+}
+
+int tsdf_clear_table(r3d_tsdf *v) {
+    r3d_ctx *ctx = v->ctx;
+    R3D_HIP(ctx, hipMemsetAsync(v->t.keys, 0xFF, (size_t)v->t.cap * 8, ctx->stream));
+    R3D_HIP(ctx, hipMemsetAsync(v->t.stamp, 0, (size_t)v->t.cap * 4, ctx->stream));
+    R3D_HIP(ctx, hipMemsetAsync(v->t.slot, 0xFF, (size_t)v->t.cap * 4, ctx->stream));
+    v->pass = 0;
+    if (v->n_units) k_tsdf_rebuild<<<(unsigned)((v->n_units + 255) / 256), 256, 0, ctx->stream>>>(v->t, v->unit_keys, v->n_units);
+    R3D_HIP(ctx, hipGetLastError());
+    return R3D_OK;
+}
+
+// pool of new_cap units and a table of at least twice as many entries; the units kept, the table rebuilt from them
+int tsdf_resize(r3d_tsdf *v, int new_cap) {
+    r3d_ctx *ctx = v->ctx;
+    int rc;
+    if ((rc = tsdf_grow_plane(v, v->tsdf, TSDF_UNIT, new_cap)) || (rc = tsdf_grow_plane(v, v->weight, TSDF_UNIT, new_cap))) return rc;
+    if (v->prm.color_type == R3D_TSDF_COLOR_RGB8)
+        for (auto &p : v->c)
+            if ((rc = tsdf_grow_plane(v, p, TSDF_UNIT, new_cap))) return rc;
+    if ((rc = tsdf_grow_plane(v, v->unit_keys, 1, new_cap))) return rc;
+    tsdf_free(v->order);
+    if ((rc = tsdf_alloc(ctx, v->order, (size_t)new_cap))) return rc;
+    int tcap = 16;
+    while (tcap < 2 * new_cap) tcap *= 2;
+    tsdf_free(v->t.keys); tsdf_free(v->t.slot); tsdf_free(v->t.stamp); tsdf_free(v->new_list); tsdf_free(v->touched);
+    v->t.cap = tcap;
+    if ((rc = tsdf_alloc(ctx, v->t.keys, (size_t)tcap)) || (rc = tsdf_alloc(ctx, v->t.slot, (size_t)tcap)) ||
+        (rc = tsdf_alloc(ctx, v->t.stamp, (size_t)tcap)) || (rc = tsdf_alloc(ctx, v->new_list, (size_t)tcap)) ||
+        (rc = tsdf_alloc(ctx, v->touched, (size_t)tcap)))
+        return rc;
+    v->cap = new_cap;
+    return tsdf_clear_table(v);
+}
+
+int tsdf_vol_ok(r3d_ctx *ctx, const r3d_tsdf *v, const char *who) {
+    if (!v) return r3d_fail(ctx, R3D_E_BADARG, "%s: volume missing", who);
+    if (v->ctx != ctx) return r3d_fail(ctx, R3D_E_BADARG, "%s: the volume belongs to another context", who);
+    if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "%s: context poisoned by an earlier timed-out call: destroy it", who);
+    return R3D_OK;
+}
+
+// inverse of an affine 4x4 by the adjugate of its 3x3 block, every expression in the order tests/tsdf_ref.py writes it
+int tsdf_inverse(r3d_ctx *ctx, const double *E, TsdfPose &P) {
+    if (!(E[12] == 0.0 && E[13] == 0.0 && E[14] == 0.0 && E[15] == 1.0))
+        return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: the extrinsic's last row must be 0 0 0 1");
+    const double a = E[0], b = E[1], c = E[2], d = E[4], e = E[5], f = E[6], g = E[8], h = E[9], i = E[10];
+    const double det = (a * (e * i - f * h) + b * (f * g - d * i)) + c * (d * h - e * g);
+    if (!std::isfinite(det) || det == 0.0) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: the extrinsic is singular or not finite");
+    const double adj[9] = {e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d};
+    for (int k = 0; k < 9; k++) P.Ai[k] = adj[k] / det;
+    for (int k = 0; k < 3; k++) P.ti[k] = -((P.Ai[k * 3] * E[3] + P.Ai[k * 3 + 1] * E[7]) + P.Ai[k * 3 + 2] * E[11]);
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(P.ti[k])) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: the extrinsic is singular or not finite");
+    return R3D_OK;
+}
+
+int tsdf_images_ok(r3d_ctx *ctx, const r3d_tsdf *v, const void *depth, const void *color, int w, int h, int dstride, int cw, int ch, int cstride, int cn,
+                   double fx, double fy, const double *extrinsic) {
+    if (!depth || !extrinsic || w <= 0 || h <= 0 || dstride < w || (int64_t)w * h > (int64_t)1 << 28)
+        return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: a missing depth image or extrinsic, an empty image or a stride too small");
+    if (!(fx != 0) || !(fy != 0) || !std::isfinite(fx) || !std::isfinite(fy)) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: fx and fy must be non-zero");
+    if (v->prm.color_type == R3D_TSDF_COLOR_RGB8) {
+        if (!color || cn != 3) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: an RGB8 volume needs a 3-channel colour image (got %d channels)", color ? cn : 0);
+        if (cw != w || ch != h) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: colour image %d x %d and depth image %d x %d differ in size", cw, ch, w, h);
+        if ((int64_t)cstride < (int64_t)w * 3 || (int64_t)cstride * h > INT32_MAX) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: colour stride %d", cstride);
+    }
+    return R3D_OK;
+}
+
+// device planes in; everything up to and including the integrate launch
+int tsdf_integrate_dev(r3d_tsdf *v, const float *d_depth, int dstride, const uint8_t *d_color, int cstride, int w, int h, TsdfCam cam, const double *E) {
+    r3d_ctx *ctx = v->ctx;
+    hipStream_t st = ctx->stream;
+    TsdfPose P;
+    if (int rc = tsdf_inverse(ctx, E, P)) return rc;
+    const int s = v->prm.depth_sampling_stride;
+    const int ni = (h + s - 1) / s, nj = (w + s - 1) / s;
+    const double ul = v->prm.voxel_length * TSDF_R;
+    R3D_HIP(ctx, hipEventRecord(v->ev[0], st));
+    TsdfCounters cnt;
+    for (;;) {
+        v->pass++;
+        R3D_HIP(ctx, hipMemsetAsync(v->d_cnt, 0, sizeof(TsdfCounters), st));
+        k_tsdf_touch<<<(unsigned)(((size_t)ni * nj + 255) / 256), 256, 0, st>>>(d_depth, dstride, s, nj, ni, cam, P, v->prm.sdf_trunc, ul, v->t, v->pass,
+                                                                                 v->new_list, v->touched, v->d_cnt);
+        R3D_HIP(ctx, hipGetLastError());
+        // the one device -> host read of a frame: 16 bytes of counters (a frame that outgrows the pool repeats the pass and the read)
+        R3D_HIP(ctx, hipMemcpyAsync(v->h_cnt, v->d_cnt, sizeof(TsdfCounters), hipMemcpyDeviceToHost, st));
+        R3D_HIP(ctx, hipStreamSynchronize(st));
+        cnt = *v->h_cnt;
+        if (cnt.out_of_range) {
+            if (int rc = tsdf_clear_table(v)) return rc;
+            return r3d_fail(ctx, R3D_E_UNSUPPORTED, "tsdf_integrate: a depth sample falls into a unit index outside +-2^20 (or is not finite)");
+        }
+        if (!cnt.table_full && v->n_units + cnt.n_new <= v->cap) break;
+        int want = v->n_units + cnt.n_new;
+        if (want < 2 * v->cap) want = 2 * v->cap;
+        if (want > (1 << 22)) {
+            (void)tsdf_clear_table(v);
+            return r3d_fail(ctx, R3D_E_OOM, "tsdf_integrate: more than 2^22 units");
+        }
+        if (int rc = tsdf_resize(v, want)) return rc;
+        v->growths++;
+    }
+    if (cnt.n_new) k_tsdf_assign<<<(unsigned)((cnt.n_new + 255) / 256), 256, 0, st>>>(v->t, v->new_list, cnt.n_new, v->n_units, v->unit_keys);
+    v->n_units += cnt.n_new;
+    R3D_HIP(ctx, hipEventRecord(v->ev[1], st));
+    if (cnt.n_touched) {
+        TsdfFrame F;
+        F.depth = d_depth; F.color = d_color; F.dstride = dstride; F.cstride = cstride; F.w = w; F.h = h;
+        F.fx = (float)cam.fx; F.fy = (float)cam.fy; F.cx = (float)cam.cx; F.cy = (float)cam.cy;
+        F.ifx = 1.0f / F.fx; F.ify = 1.0f / F.fy;
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) F.E[r * 4 + c] = (float)E[r * 4 + c];
+        F.vl = (float)v->prm.voxel_length; F.trunc = (float)v->prm.sdf_trunc; F.itrunc = 1.0f / F.trunc;
+        F.wlim = (float)((double)w - 0.0001); F.hlim = (float)((double)h - 0.0001);
+        F.vld = v->prm.voxel_length; F.ul = ul;
+        if (v->prm.color_type == R3D_TSDF_COLOR_RGB8)
+            k_tsdf_integrate<true><<<(unsigned)cnt.n_touched, 256, 0, st>>>(F, v->t, v->touched, v->tsdf, v->weight, v->c[0], v->c[1], v->c[2]);
+        else
+            k_tsdf_integrate<false><<<(unsigned)cnt.n_touched, 256, 0, st>>>(F, v->t, v->touched, v->tsdf, v->weight, nullptr, nullptr, nullptr);
+        R3D_HIP(ctx, hipGetLastError());
+    }
+    R3D_HIP(ctx, hipEventRecord(v->ev[2], st));
+    v->timed = true;
+    v->frames++;
+    v->last_touched = cnt.n_touched;
+    return R3D_OK;
+}
+
+TsdfVol tsdf_view(const r3d_tsdf *v) {
+    TsdfVol V;
+    V.t = v->t; V.tsdf = v->tsdf; V.weight = v->weight;
+    for (int k = 0; k < 3; k++) V.c[k] = v->c[k];
+    V.vl = v->prm.voxel_length; V.ul = v->prm.voxel_length * TSDF_R;
+    return V;
+}
+
+int tsdf_sort_units(r3d_tsdf *v) {
+    if (v->n_units) k_tsdf_rank<<<(unsigned)((v->n_units + 255) / 256), 256, 0, v->ctx->stream>>>(v->unit_keys, v->n_units, v->order);
+    R3D_HIP(v->ctx, hipGetLastError());
+    return R3D_OK;
+}
+
+// count (always), then emit into device arrays when cap allows.  Returns after the count is known.
+int tsdf_extract(r3d_tsdf *v, DevArena &ar, int64_t cap, double *d_xyz, double *d_nrm, double *d_col, int64_t *out_n, bool host_out, double *xyz,
+                 double *nrm, double *col) {
+    r3d_ctx *ctx = v->ctx;
+    hipStream_t st = ctx->stream;
+    const bool color = v->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    *out_n = 0;
+    if (!v->n_units) return R3D_OK;
+    const int n = v->n_units;
+    int *thread_off = (int *)ar.get((size_t)n * 256 * 4);
+    int *unit_cnt = (int *)ar.get((size_t)n * 4);
+    long long *unit_off = (long long *)ar.get((size_t)n * 8);
+    long long *d_total = (long long *)ar.get(8);
+    if (ar.rc) return ar.rc;
+    int rc;
+    if ((rc = tsdf_sort_units(v))) return rc;
+    const TsdfVol V = tsdf_view(v);
+    k_tsdf_extract<false, false><<<(unsigned)n, 256, 0, st>>>(V, v->order, v->unit_keys, thread_off, unit_cnt, nullptr, nullptr, nullptr, nullptr);
+    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, unit_off, d_total);
+    R3D_HIP(ctx, hipGetLastError());
+    long long total = 0;
+    R3D_HIP(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipStreamSynchronize(st));
+    *out_n = total;
+    if (cap == 0 || total == 0) return R3D_OK;
+    if (cap < total) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_extract_point_cloud: %lld points do not fit a capacity of %lld", total, (long long)cap);
+    if (host_out) {
+        d_xyz = (double *)ar.get((size_t)total * 24);
+        d_nrm = (double *)ar.get((size_t)total * 24);
+        d_col = color ? (double *)ar.get((size_t)total * 24) : nullptr;
+        if (ar.rc) return ar.rc;
+    }
+    if (color)
+        k_tsdf_extract<true, true><<<(unsigned)n, 256, 0, st>>>(V, v->order, v->unit_keys, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, d_col);
+    else
+        k_tsdf_extract<true, false><<<(unsigned)n, 256, 0, st>>>(V, v->order, v->unit_keys, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, nullptr);
+    R3D_HIP(ctx, hipGetLastError());
+    if (host_out) {
+        R3D_HIP(ctx, hipMemcpyAsync(xyz, d_xyz, (size_t)total * 24, hipMemcpyDeviceToHost, st));
+        R3D_HIP(ctx, hipMemcpyAsync(nrm, d_nrm, (size_t)total * 24, hipMemcpyDeviceToHost, st));
+        if (color) R3D_HIP(ctx, hipMemcpyAsync(col, d_col, (size_t)total * 24, hipMemcpyDeviceToHost, st));
+        R3D_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return R3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int r3d_tsdf_create(r3d_ctx *ctx, const r3d_tsdf_params *p, r3d_tsdf **out) {
+    R3D_ROCTX_RANGE("r3d_tsdf_create");
+    if (!ctx) return R3D_E_BADARG;
+    if (!p || !out) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_create: params or output missing");
+    *out = nullptr;
+    if (!(p->voxel_length > 0) || !std::isfinite(p->voxel_length)) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_create: voxel_length must be positive");
+    if (!(p->sdf_trunc > 0) || !std::isfinite(p->sdf_trunc)) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_create: sdf_trunc must be positive");
+    if (p->depth_sampling_stride < 1) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_create: depth_sampling_stride %d < 1", p->depth_sampling_stride);
+    if (p->color_type != R3D_TSDF_COLOR_NONE && p->color_type != R3D_TSDF_COLOR_RGB8)
+        return r3d_fail(ctx, p->color_type == 2 ? R3D_E_UNSUPPORTED : R3D_E_BADARG, "tsdf_create: color_type %d (0 None, 1 RGB8; Gray32 is not built)", p->color_type);
+    if (p->initial_units < 0 || p->initial_units > (1 << 22)) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_create: initial_units %d", p->initial_units);
+    if (p->volume_unit_resolution != TSDF_R)
+        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "tsdf_create: volume_unit_resolution %d (only 16 is built)", p->volume_unit_resolution);
+    if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "tsdf_create: context poisoned by an earlier timed-out call: destroy it");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    r3d_tsdf *v = new r3d_tsdf;
+    v->ctx = ctx;
+    v->prm = *p;
+    int rc = tsdf_alloc(ctx, v->d_cnt, 1);
+    if (!rc && hipHostMalloc((void **)&v->h_cnt, sizeof(TsdfCounters), hipHostMallocDefault) != hipSuccess)
+        rc = r3d_fail(ctx, R3D_E_OOM, "tsdf_create: pinned allocation failed");
+    for (auto &e : v->ev)
+        if (!rc && hipEventCreate(&e) != hipSuccess) rc = r3d_fail(ctx, R3D_E_HIP, "tsdf_create: hipEventCreate failed");
+    if (!rc) rc = tsdf_resize(v, p->initial_units ? p->initial_units : TSDF_DEFAULT_UNITS);
+    if (rc) {
+        tsdf_release(v);
+        delete v;
+        return rc;
+    }
+    *out = v;
+    return R3D_OK;
+}
+
+int r3d_tsdf_destroy(r3d_ctx *ctx, r3d_tsdf *vol) {
+    R3D_ROCTX_RANGE("r3d_tsdf_destroy");
+    if (!ctx) return R3D_E_BADARG;
+    if (!vol) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_destroy: volume missing");
+    if (vol->ctx != ctx) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_destroy: the volume belongs to another context");
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    tsdf_release(vol);
+    delete vol;
+    return R3D_OK;
+}
+
+int r3d_tsdf_reset(r3d_ctx *ctx, r3d_tsdf *vol) {
+    R3D_ROCTX_RANGE("r3d_tsdf_reset");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_vol_ok(ctx, vol, "tsdf_reset")) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t used = (size_t)vol->n_units * TSDF_UNIT;
+    if (used) {
+        R3D_HIP(ctx, hipMemsetAsync(vol->tsdf, 0, used * 4, ctx->stream));
+        R3D_HIP(ctx, hipMemsetAsync(vol->weight, 0, used * 4, ctx->stream));
+        if (vol->prm.color_type == R3D_TSDF_COLOR_RGB8)
+            for (auto &p : vol->c) R3D_HIP(ctx, hipMemsetAsync(p, 0, used * 8, ctx->stream));
+    }
+    vol->n_units = 0;
+    vol->frames = 0;
+    vol->last_touched = 0;
+    vol->timed = false;
+    return tsdf_clear_table(vol);
+}
+
+int r3d_tsdf_integrate_f32_dev(r3d_ctx *ctx, r3d_tsdf *vol, const float *d_depth, const uint8_t *d_color, int32_t w, int32_t h, int32_t depth_stride,
+                               int32_t color_w, int32_t color_h, int32_t color_stride, int32_t color_channels, double fx, double fy, double cx,
+                               double cy, const double *extrinsic4x4) {
+    R3D_ROCTX_RANGE("r3d_tsdf_integrate_f32_dev");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = tsdf_vol_ok(ctx, vol, "tsdf_integrate"))) return rc;
+    if ((rc = tsdf_images_ok(ctx, vol, d_depth, d_color, w, h, depth_stride, color_w, color_h, color_stride, color_channels, fx, fy, extrinsic4x4))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    return tsdf_integrate_dev(vol, d_depth, depth_stride, d_color, color_stride, w, h, TsdfCam{fx, fy, cx, cy}, extrinsic4x4);
+}
+
+int r3d_tsdf_integrate_f32(r3d_ctx *ctx, r3d_tsdf *vol, const float *depth, const uint8_t *color, int32_t w, int32_t h, int32_t depth_stride,
+                           int32_t color_w, int32_t color_h, int32_t color_stride, int32_t color_channels, double fx, double fy, double cx, double cy,
+                           const double *extrinsic4x4) {
+    R3D_ROCTX_RANGE("r3d_tsdf_integrate_f32");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = tsdf_vol_ok(ctx, vol, "tsdf_integrate"))) return rc;
+    if ((rc = tsdf_images_ok(ctx, vol, depth, color, w, h, depth_stride, color_w, color_h, color_stride, color_channels, fx, fy, extrinsic4x4))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    const bool rgb = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    DevArena ar(ctx);
+    float *dd = (float *)ar.get((size_t)w * h * 4);
+    uint8_t *dc = rgb ? (uint8_t *)ar.get((size_t)w * h * 3) : nullptr;
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemcpy2DAsync(dd, (size_t)w * 4, depth, (size_t)depth_stride * 4, (size_t)w * 4, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    if (rgb) R3D_HIP(ctx, hipMemcpy2DAsync(dc, (size_t)w * 3, color, (size_t)color_stride, (size_t)w * 3, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = tsdf_integrate_dev(vol, dd, w, dc, w * 3, w, h, TsdfCam{fx, fy, cx, cy}, extrinsic4x4))) return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+int r3d_tsdf_integrate(r3d_ctx *ctx, r3d_tsdf *vol, const uint16_t *depth, const uint8_t *color, int32_t w, int32_t h, int32_t depth_stride,
+                       int32_t color_w, int32_t color_h, int32_t color_stride, int32_t color_channels, const r3d_depth_camera *cam,
+                       const double *extrinsic4x4) {
+    R3D_ROCTX_RANGE("r3d_tsdf_integrate");
+    if (!ctx) return R3D_E_BADARG;
+    int rc;
+    if ((rc = tsdf_vol_ok(ctx, vol, "tsdf_integrate"))) return rc;
+    if (!cam) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: camera missing");
+    if (!(cam->depth_scale > 0) || !(cam->depth_trunc > 0)) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_integrate: depth_scale and depth_trunc must be positive");
+    if ((rc = tsdf_images_ok(ctx, vol, depth, color, w, h, depth_stride, color_w, color_h, color_stride, color_channels, cam->fx, cam->fy, extrinsic4x4)))
+        return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    const bool rgb = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    DevArena ar(ctx);
+    uint16_t *raw = (uint16_t *)ar.get((size_t)w * h * 2);
+    float *dd = (float *)ar.get((size_t)w * h * 4);
+    uint8_t *dc = rgb ? (uint8_t *)ar.get((size_t)w * h * 3) : nullptr;
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemcpy2DAsync(raw, (size_t)w * 2, depth, (size_t)depth_stride * 2, (size_t)w * 2, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    if (rgb) R3D_HIP(ctx, hipMemcpy2DAsync(dc, (size_t)w * 3, color, (size_t)color_stride, (size_t)w * 3, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    k_tsdf_depth_u16<<<(unsigned)(((size_t)w * h + 255) / 256), 256, 0, ctx->stream>>>(raw, w, h, (float)cam->depth_scale, (float)cam->depth_trunc, dd);
+    R3D_HIP(ctx, hipGetLastError());
+    if ((rc = tsdf_integrate_dev(vol, dd, w, dc, w * 3, w, h, TsdfCam{cam->fx, cam->fy, cam->ppx, cam->ppy}, extrinsic4x4))) return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+int r3d_tsdf_stats(r3d_ctx *ctx, r3d_tsdf *vol, r3d_tsdf_info *out) {
+    R3D_ROCTX_RANGE("r3d_tsdf_stats");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_vol_ok(ctx, vol, "tsdf_stats")) return rc;
+    if (!out) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_stats: output missing");
+    memset(out, 0, sizeof(*out));
+    out->units = vol->n_units;
+    out->frames = vol->frames;
+    out->touched = vol->last_touched;
+    out->capacity = vol->cap;
+    out->growths = vol->growths;
+    if (vol->timed) {
+        float ms = 0;
+        R3D_HIP(ctx, hipEventSynchronize(vol->ev[2]));
+        R3D_HIP(ctx, hipEventElapsedTime(&ms, vol->ev[0], vol->ev[1]));
+        out->touch_ms = ms;
+        R3D_HIP(ctx, hipEventElapsedTime(&ms, vol->ev[1], vol->ev[2]));
+        out->integrate_ms = ms;
+    }
+    return R3D_OK;
+}
+
+int r3d_tsdf_extract_point_cloud(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, double *xyz, double *normals, double *colors, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_tsdf_extract_point_cloud");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_vol_ok(ctx, vol, "tsdf_extract_point_cloud")) return rc;
+    const bool color = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    if (!out_n || cap < 0 || (cap > 0 && (!xyz || !normals || (color && !colors))))
+        return r3d_fail(ctx, R3D_E_BADARG, "tsdf_extract_point_cloud: a missing array or a negative capacity");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return tsdf_extract(vol, ar, cap, nullptr, nullptr, nullptr, out_n, true, xyz, normals, colors);
+}
+
+int r3d_tsdf_extract_point_cloud_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, double *d_xyz, double *d_normals, double *d_colors, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_tsdf_extract_point_cloud_dev");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_vol_ok(ctx, vol, "tsdf_extract_point_cloud")) return rc;
+    const bool color = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    if (!out_n || cap < 0 || (cap > 0 && (!d_xyz || !d_normals || (color && !d_colors))))
+        return r3d_fail(ctx, R3D_E_BADARG, "tsdf_extract_point_cloud: a missing array or a negative capacity");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    int rc = tsdf_extract(vol, ar, cap, d_xyz, d_normals, d_colors, out_n, false, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the emit kernel reads arena buffers the next call may hand out again
+    return R3D_OK;
+}
+
+int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t *idx3, float *tsdf, float *weight, double *colour, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_debug_tsdf_units");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_vol_ok(ctx, vol, "debug_tsdf_units")) return rc;
+    const bool color = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    if (!out_n || cap_units < 0 || (cap_units > 0 && (!idx3 || !tsdf || !weight || (color && !colour))))
+        return r3d_fail(ctx, R3D_E_BADARG, "debug_tsdf_units: a missing array or a negative capacity");
+    const int n = vol->n_units;
+    *out_n = n;
+    if (cap_units == 0 || n == 0) return R3D_OK;
+    if (cap_units < n) return r3d_fail(ctx, R3D_E_BADARG, "debug_tsdf_units: %d units do not fit a capacity of %lld", n, (long long)cap_units);
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevArena ar(ctx);
+    int32_t *d_idx = (int32_t *)ar.get((size_t)n * 12);
+    float *d_t = (float *)ar.get((size_t)n * TSDF_UNIT * 4), *d_w = (float *)ar.get((size_t)n * TSDF_UNIT * 4);
+    double *d_c = color ? (double *)ar.get((size_t)n * TSDF_UNIT * 24) : nullptr;
+    if (ar.rc) return ar.rc;
+    if (int rc = tsdf_sort_units(vol)) return rc;
+    k_tsdf_gather<<<(unsigned)n, 256, 0, st>>>(tsdf_view(vol), color ? 1 : 0, vol->order, vol->unit_keys, d_idx, d_t, d_w, d_c);
+    R3D_HIP(ctx, hipGetLastError());
+    R3D_HIP(ctx, hipMemcpyAsync(idx3, d_idx, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipMemcpyAsync(tsdf, d_t, (size_t)n * TSDF_UNIT * 4, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipMemcpyAsync(weight, d_w, (size_t)n * TSDF_UNIT * 4, hipMemcpyDeviceToHost, st));
+    if (color) R3D_HIP(ctx, hipMemcpyAsync(colour, d_c, (size_t)n * TSDF_UNIT * 24, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipStreamSynchronize(st));
+    return R3D_OK;
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from . import cloud_ops, distributed
+from . import cloud_ops, distributed, tsdf
 from .pointcloud import PointCloud, as_arrays
 from .pointcloud_alignment import GeneralizedICPAlignment, PointCloudAlignment
 
@@ -457,3 +457,35 @@ def odometry_edges(frames, camera, ctx=None, **option):
         ok, T, info = cloud_ops.compute_rgbd_odometry(imgs[i + 1], imgs[i], camera, ctx=ctx, **option)
         edges.append(dict(source=i + 1, target=i, T=T if ok else np.eye(4), info=info if ok else np.eye(6), uncertain=not ok))
     return edges
+
+
+def poses_from_edges(edges):
+    """Camera-to-world poses of the frames from a chain of pairwise edges, the first frame being the world: the composition of
+    test/check84.py's loop, odometry = T @ odometry, node pose = inv(odometry), where T takes frame k to frame k + 1.  An edge
+    of odometry_edges runs the other way (source k + 1 -> target k), so its T enters inverted; an edge with source k and
+    target k + 1 enters as it is.  -> [4x4] of len(edges) + 1"""
+    odometry = np.eye(4)
+    poses = [np.eye(4)]
+    for k, e in enumerate(edges):
+        T = np.asarray(e["T"], dtype=np.float64).reshape(4, 4)
+        if (e["source"], e["target"]) == (k + 1, k):
+            T = np.linalg.inv(T)
+        elif (e["source"], e["target"]) != (k, k + 1):
+            raise ValueError(f"edge {k} joins frames {e['source']} -> {e['target']}: poses_from_edges composes a chain of consecutive frames")
+        odometry = T @ odometry
+        poses.append(np.linalg.inv(odometry))
+    return poses
+
+
+def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, **volume_options):
+    """test/check84.py:41-44,295,307: every frame into a ScalableTSDFVolume with extrinsic = inv(pose), then
+    extract_point_cloud().  frames: (colour, depth uint16) pairs or cloud_ops.RGBDImage, as odometry_edges takes them; camera:
+    cloud_ops.depth_camera(...); poses: camera-to-world 4x4 per frame (poses_from_edges).  -> PointCloud with normals[, colours]"""
+    if len(poses) != len(frames):
+        raise ValueError(f"{len(frames)} frames but {len(poses)} poses")
+    imgs = [f if isinstance(f, cloud_ops.RGBDImage) else cloud_ops.rgbd_image(f[0], f[1], camera.depth_scale, camera.depth_trunc) for f in frames]
+    kind = tsdf.TSDFVolumeColorType.RGB8 if color else tsdf.TSDFVolumeColorType.NoColor
+    with tsdf.ScalableTSDFVolume(voxel_length, sdf_trunc, kind, ctx=ctx, **volume_options) as volume:
+        for img, pose in zip(imgs, poses):
+            volume.integrate(img, camera, np.linalg.inv(np.asarray(pose, dtype=np.float64).reshape(4, 4)))
+        return volume.extract_point_cloud()

@@ -614,6 +614,65 @@ int r3d_debug_rgbd_iteration(r3d_ctx *ctx, const r3d_odometry_params *p, const f
                              double fy, double cx, double cy, const double *init4x4, int32_t level, const double *pose4x4,
                              int32_t *corr, int64_t *n_corr, double *sums29, double *T_after, int32_t *ok);
 
+/* ---- TSDF volume ("TSDF volume") -----------------------------------------------------------------------------
+ * replaces: volume = o3d.pipelines.integration.ScalableTSDFVolume(voxel_length, sdf_trunc, color_type); volume.integrate(rgbd,
+ *           intrinsic, np.linalg.inv(pose)); volume.extract_point_cloud()   test/check84.py:41-44,295,307 -- the stage every
+ * experiment pipeline of the reference ends in.  [recalled, Open3D 0.18 pipelines/integration/ScalableTSDFVolume.cpp,
+ * UniformTSDFVolume.cpp]: Open3D is absent and the reference recorded no volume, so parity is UNPINNED; tests/tsdf_ref.py restates
+ * the contract.  A sparse volume of 16^3-voxel units behind a device hash table; tsdf and weight float32, colour three float64 per
+ * voxel.  The same bits on every run: which pool slot a unit gets is a race, everything a caller can see is ordered by unit index
+ * (X, then Y, then Z).  extract_triangle_mesh, Gray32 and unit resolutions other than 16 are not built. */
+#define R3D_TSDF_COLOR_NONE 0
+#define R3D_TSDF_COLOR_RGB8 1
+typedef struct r3d_tsdf r3d_tsdf;
+typedef struct r3d_tsdf_params {       /* 32 bytes */
+    double voxel_length, sdf_trunc;    /* metres, both > 0 */
+    int32_t color_type;                /* R3D_TSDF_COLOR_* */
+    int32_t volume_unit_resolution;    /* 16; anything else: R3D_E_UNSUPPORTED */
+    int32_t depth_sampling_stride;     /* 4; >= 1: every stride-th pixel of every stride-th row decides which units a frame touches */
+    int32_t initial_units;             /* starting capacity of the unit pool, 0 = 1024; pool and table grow when a frame needs more */
+} r3d_tsdf_params;
+typedef struct r3d_tsdf_info {        /* 48 bytes */
+    int64_t units, frames, touched;    /* units in the volume, frames integrated, units the last frame touched */
+    int32_t capacity, growths;         /* pool capacity in units, how often it grew */
+    double touch_ms, integrate_ms;     /* device time of the last frame: touch + slot assignment / the voxel update */
+} r3d_tsdf_info;
+/* A volume belongs to the context it was made on and is used through it (any other: R3D_E_BADARG); destroy it before the context. */
+int r3d_tsdf_create(r3d_ctx *ctx, const r3d_tsdf_params *p, r3d_tsdf **out);
+int r3d_tsdf_destroy(r3d_ctx *ctx, r3d_tsdf *vol);
+int r3d_tsdf_reset(r3d_ctx *ctx, r3d_tsdf *vol);   /* no units, no frames; the pool keeps its capacity */
+/* One frame.  extrinsic4x4: world -> camera, row-major, last row 0 0 0 1.  The depth image is w x h; the colour image
+ * (color_w x color_h, color_stride BYTES per row, color_channels interleaved uint8 in the order given) is read only by an RGB8
+ * volume, which refuses (R3D_E_BADARG) a missing one, one of another size and one without exactly 3 channels; a volume without
+ * colour accepts NULL.  R3D_E_UNSUPPORTED: a sampled depth pixel lands in a unit whose index leaves +-2^20 (the volume is
+ * unchanged).  r3d_tsdf_integrate: raw HOST images, depth uint16 [h][depth_stride], z = float32(raw) / float32(cam->depth_scale),
+ * z > cam->depth_trunc => 0 -- the plane r3d_debug_rgbd_convert returns.  r3d_tsdf_integrate_f32: a float32 HOST depth plane in
+ * metres [h][depth_stride floats], 0 = no sample.  r3d_tsdf_integrate_f32_dev: the same on DEVICE images; it reads 16 bytes of
+ * counters back after the touch pass (how many units are new decides whether the pool grows), enqueues the voxel update on the
+ * context stream and returns without waiting for it: the images must stay untouched until the stream has passed. */
+int r3d_tsdf_integrate(r3d_ctx *ctx, r3d_tsdf *vol, const uint16_t *depth, const uint8_t *color, int32_t w, int32_t h,
+                       int32_t depth_stride, int32_t color_w, int32_t color_h, int32_t color_stride, int32_t color_channels,
+                       const r3d_depth_camera *cam, const double *extrinsic4x4);
+int r3d_tsdf_integrate_f32(r3d_ctx *ctx, r3d_tsdf *vol, const float *depth, const uint8_t *color, int32_t w, int32_t h,
+                           int32_t depth_stride, int32_t color_w, int32_t color_h, int32_t color_stride, int32_t color_channels,
+                           double fx, double fy, double cx, double cy, const double *extrinsic4x4);
+int r3d_tsdf_integrate_f32_dev(r3d_ctx *ctx, r3d_tsdf *vol, const float *d_depth, const uint8_t *d_color, int32_t w, int32_t h,
+                               int32_t depth_stride, int32_t color_w, int32_t color_h, int32_t color_stride,
+                               int32_t color_channels, double fx, double fy, double cx, double cy, const double *extrinsic4x4);
+int r3d_tsdf_stats(r3d_ctx *ctx, r3d_tsdf *vol, r3d_tsdf_info *out);   /* waits for the last frame when it reports its times */
+/* extract_point_cloud(): *out_n = the number of points, always.  cap = 0: the count alone.  cap < count: R3D_E_BADARG and nothing
+ * is written.  Otherwise xyz, normals and (RGB8 volumes; else ignored, may be NULL) colors receive count rows of 3 doubles; order:
+ * units by (X, Y, Z), voxels by flat index, axes x, y, z.  The _dev form writes DEVICE arrays and returns when they are complete. */
+int r3d_tsdf_extract_point_cloud(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, double *xyz, double *normals, double *colors,
+                                 int64_t *out_n);
+int r3d_tsdf_extract_point_cloud_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, double *d_xyz, double *d_normals, double *d_colors,
+                                     int64_t *out_n);
+/* the state, for the tests: *out_n units in (X, Y, Z) order; cap_units = 0: the count alone, cap_units < count: R3D_E_BADARG.
+ * idx3 int32 [n][3]; tsdf, weight float32 [n][4096] (voxel (x, y, z) at x*256 + y*16 + z); colour float64 [n][3][4096] (RGB8
+ * volumes; else ignored) */
+int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t *idx3, float *tsdf, float *weight, double *colour,
+                         int64_t *out_n);
+
 
 /* ---- per-frame stages either side of the matcher in Calib_depth/depth*.py --------------
  * OpenCV is a dependency of the reference that is absent here, and the reference records no output of these calls:
