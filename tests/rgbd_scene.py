@@ -19,6 +19,13 @@ def camera(w, h):
     return (float(f), float(f), 0.5 * w - 0.5, 0.5 * h - 0.5)
 
 
+def skewed_camera(w, h):
+    """(fx, fy, cx, cy) with fy = 0.85 fx and the principal point 11 % of the width right of and 7 % of the height above the
+    centre: a kernel that takes fx for fy, or cx for cy, or assumes a centred principal point gives another answer"""
+    f = 0.5 * w / np.tan(np.radians(30.0))
+    return (float(f), float(0.85 * f), 0.5 * w - 0.5 + 0.11 * w, 0.5 * h - 0.5 - 0.07 * h)
+
+
 def pose(rx_deg=0.0, ry_deg=0.0, rz_deg=0.0, t=(0.0, 0.0, 0.0)):
     a, b, c = np.radians([rx_deg, ry_deg, rz_deg])
     Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
@@ -30,10 +37,11 @@ def pose(rx_deg=0.0, ry_deg=0.0, rz_deg=0.0, t=(0.0, 0.0, 0.0)):
     return T
 
 
-def render(w, h, cam_to_world=None, holes=(), step=None):
+def render(w, h, cam_to_world=None, holes=(), step=None, cam=None):
     """-> intensity float32 [h][w], depth float32 [h][w] (0 in the holes).  holes: rectangles (x0, y0, x1, y1) as fractions
-    of the image.  step = (x_fraction, dz): columns left of x_fraction see a surface dz nearer (a depth step)."""
-    fx, fy, cx, cy = camera(w, h)
+    of the image.  step = (x_fraction, dz): columns left of x_fraction see a surface dz nearer (a depth step).
+    cam: (fx, fy, cx, cy), camera(w, h) when None."""
+    fx, fy, cx, cy = camera(w, h) if cam is None else cam
     C = np.eye(4) if cam_to_world is None else np.asarray(cam_to_world, dtype=np.float64)
     u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
     ray = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1)
@@ -58,7 +66,8 @@ HOLES = ((0.10, 0.15, 0.22, 0.30), (0.60, 0.55, 0.78, 0.70))
 TRUTH = pose(0.6, -0.7, 0.4, (0.010, -0.008, 0.016))       # about 1 degree and 16 mm from the identity
 
 
-def pair(w, h, truth=TRUTH, holes=HOLES):
+def pair(w, h, truth=TRUTH, holes=HOLES, cam=None):
     """-> source frame, target frame, camera, truth.  The target camera sits at the world origin, the source camera at
-    `truth` (source camera coordinates -> target camera coordinates)."""
-    return render(w, h, truth, holes), render(w, h, None, holes), camera(w, h), np.asarray(truth, dtype=np.float64)
+    `truth` (source camera coordinates -> target camera coordinates).  cam: camera(w, h) when None."""
+    cam = camera(w, h) if cam is None else tuple(cam)
+    return render(w, h, truth, holes, cam=cam), render(w, h, None, holes, cam=cam), cam, np.asarray(truth, dtype=np.float64)

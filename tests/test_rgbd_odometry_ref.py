@@ -17,6 +17,37 @@ def test_restatement_converges_on_the_height_field():
     assert np.array_equal(res["trace"][-1], res["T"])
 
 
+def test_render_with_its_default_camera_given_explicitly():
+    """render and pair take a camera; camera(w, h) given explicitly is the frame every earlier test sees, bit for bit"""
+    w, h = 67, 45
+    for kw in (dict(), dict(cam_to_world=scene.TRUTH, holes=scene.HOLES), dict(step=(0.5, 0.3))):
+        for a, b in zip(scene.render(w, h, **kw), scene.render(w, h, cam=scene.camera(w, h), **kw)):
+            assert a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    src, tgt, cam, _ = scene.pair(w, h)
+    src2, tgt2, cam2, _ = scene.pair(w, h, cam=scene.camera(w, h))
+    assert cam == cam2 and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(src + tgt, src2 + tgt2))
+    fx, fy, cx, cy = scene.skewed_camera(w, h)
+    assert fy == 0.85 * fx and (cx, cy) == (0.5 * w - 0.5 + 0.11 * w, 0.5 * h - 0.5 - 0.07 * h)
+    assert not np.array_equal(scene.render(w, h, cam=(fx, fy, cx, cy))[1], scene.render(w, h)[1])
+
+
+def test_restatement_converges_with_a_skewed_camera_and_tells_fx_from_fy():
+    """fx != fy and an off-centre principal point: the restatement still converges, and given the camera with fx and fy
+    swapped it answers 6e-3 away -- ten orders above the tolerance of a full call, so a swap inside a kernel cannot hide"""
+    for w, h in ((67, 45), (160, 120)):
+        cam = scene.skewed_camera(w, h)
+        src, tgt, cam, truth = scene.pair(w, h, cam=cam)
+        before = ref.pose_error(np.eye(4), truth)
+        res = ref.compute_rgbd_odometry(src, tgt, cam)
+        after = ref.pose_error(res["T"], truth)
+        swapped = ref.compute_rgbd_odometry(src, tgt, (cam[1], cam[0], cam[2], cam[3]))
+        moved = np.abs(res["T"] - swapped["T"]).max()
+        print(f"{w}x{h}: max-abs pose error {before:.3e} -> {after:.3e} ({before / after:.1f}-fold); fx <-> fy moves T by {moved:.2e}")
+        assert res["success"] == 1 and len(res["trace"]) == 35
+        assert after * 4 <= before
+        assert swapped["success"] == 1 and moved > 1e-3
+
+
 def test_identical_frames_keep_the_identity_exactly():
     _, tgt, cam, _ = scene.pair(67, 45)
     res = ref.compute_rgbd_odometry(tgt, tgt, cam)
