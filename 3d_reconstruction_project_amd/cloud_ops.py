@@ -110,6 +110,8 @@ _lib.register({
     "r3d_debug_sort_by_cell": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_double, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp], ctypes.c_int),
     "r3d_debug_exclusive_scan": ([_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp], ctypes.c_int),
     "r3d_debug_icp_correspondences": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp], ctypes.c_int),
+    "r3d_debug_icp_sums": ([_vp, ctypes.POINTER(_lib.IcpParams), _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
+                           ctypes.c_int),
 })
 
 
@@ -147,6 +149,18 @@ def debug_icp_correspondences(source, target, max_correspondence_distance, T=Non
     ctx.call("r3d_debug_icp_correspondences", s.ctypes.data_as(_vp), len(s), t.ctypes.data_as(_vp), len(t), float(max_correspondence_distance),
              None if T0 is None else T0.ctypes.data_as(_vp), corr.ctypes.data_as(_vp), None if d2 is None else d2.ctypes.data_as(_vp))
     return corr, d2
+
+
+def debug_icp_sums(source, target, max_distance, mode, T=None, source_normals=None, target_normals=None, gicp_epsilon=0.0, ctx=None):
+    """r3d_debug_icp_sums: (sums [29], origin [3]) of one evaluation of the registration loop in mode 0, 1 or 2 at pose T, as the
+    device reduces them for its step.  The slots' meaning, and the origin the point-to-point slots are relative to: include/r3d.h."""
+    ctx = ctx or _lib.default_context()
+    s, t, sn, tn = _c(source), _c(target), _c(source_normals), _c(target_normals)
+    T0 = None if T is None else np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+    prm = _lib.IcpParams(int(mode), 0, float(max_distance), 0.0, 0.0, float(gicp_epsilon))
+    sums, origin = np.empty(29), np.empty(3)
+    ctx.call("r3d_debug_icp_sums", ctypes.byref(prm), _ptr(s), len(s), _ptr(sn), _ptr(t), len(t), _ptr(tn), _ptr(T0), _ptr(sums), _ptr(origin))
+    return sums, origin
 
 
 class AlignParams(ctypes.Structure):

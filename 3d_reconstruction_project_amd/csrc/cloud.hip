@@ -1090,6 +1090,8 @@ struct IcpColor {
 };
 
 struct Rigid { double r[9], t[3]; };
+// the point the point-to-point slots are relative to: the centre of the target grid's box (icp_core)
+struct IcpOrigin { double x, y, z; };
 
 // Device-resident state of one registration loop: the evaluation kernels read the pose from here and k_icp_step advances it,
 // so consecutive iterations are enqueued back to back without a host round trip (the host looks at `done` once per batch).
@@ -1779,16 +1781,21 @@ __device__ __forceinline__ void nn_outer_shells(const GridView &g, double px, do
 template <int MODE>
 __device__ __forceinline__ void icp_accumulate(const GridView &g, const double *__restrict__ src_n, const double *__restrict__ tgt_n,
                                                int64_t i, const Rigid &T, double eps, double px, double py, double pz, double best, int bi,
-                                               double (&acc)[29], const IcpColor &col) {
+                                               double (&acc)[29], const IcpColor &col, const IcpOrigin &o) {
         const double tx = g.pts[(int64_t)bi * 3], ty = g.pts[(int64_t)bi * 3 + 1], tz = g.pts[(int64_t)bi * 3 + 2];
         acc[0] += 1.0;
         acc[1] += best;
         if (MODE == MODE_P2P) {
-            acc[2] += px; acc[3] += py; acc[4] += pz;
-            acc[5] += tx; acc[6] += ty; acc[7] += tz;
-            acc[8] += px * tx; acc[9] += px * ty; acc[10] += px * tz;
-            acc[11] += py * tx; acc[12] += py * ty; acc[13] += py * tz;
-            acc[14] += pz * tx; acc[15] += pz * ty; acc[16] += pz * tz;
+            // moments relative to the centre of the target grid's box (a correspondence is within max_dist of that box):
+            // sigma = E[p t^T] - mean mean^T cancels against the clouds' extent, not against their distance from the world
+            // origin.  k_icp_step restores the translation.
+            const double qx = px - o.x, qy = py - o.y, qz = pz - o.z;
+            const double ux = tx - o.x, uy = ty - o.y, uz = tz - o.z;
+            acc[2] += qx; acc[3] += qy; acc[4] += qz;
+            acc[5] += ux; acc[6] += uy; acc[7] += uz;
+            acc[8] += qx * ux; acc[9] += qx * uy; acc[10] += qx * uz;
+            acc[11] += qy * ux; acc[12] += qy * uy; acc[13] += qy * uz;
+            acc[14] += qz * ux; acc[15] += qz * uy; acc[16] += qz * uz;
         } else {
             double J[3][6], rr[3];
             int rows;
@@ -1899,7 +1906,7 @@ __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) 
                                                         const double *__restrict__ tgt_n /* cell-sorted order */, int64_t ns,
                                                         const IcpState *__restrict__ st, double max_dist, double eps, double *__restrict__ partial,
                                                         int *__restrict__ corr /* optional [ns] target original index or -1 */,
-                                                        IcpColor col /* MODE_COLORED only */) {
+                                                        IcpColor col /* MODE_COLORED only */, IcpOrigin org /* MODE_P2P only */) {
     static_assert(ICP_BLOCK == 256, "nn_block_q10 assumes 256 threads");
     __shared__ int sRun[SEARCH >= SEARCH_Q10 ? 18 * ICP_BLOCK : 1];
     __shared__ __attribute__((aligned(16))) int sPoolBuf[SEARCH == SEARCH_Q10 ? (ICP_BLOCK / 64) * pool_words(POOL_Q) : 4];
@@ -1937,7 +1944,7 @@ __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) 
         else nn_block_global(g, px, py, pz, cx, cy, cz, best, bi);
         nn_outer_shells(g, px, py, pz, cx, cy, cz, smax, best, bi);
         if (corr) corr[i] = bi >= 0 ? g.idx[bi] : -1;
-        if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, col);
+        if (bi >= 0) icp_accumulate<MODE>(g, src_n, tgt_n, i, T, eps, px, py, pz, best, bi, acc, col, org);
     }
     __shared__ double sm[ICP_BLOCK / 64][ICP_SLOTS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2725,12 +2732,13 @@ __host__ __device__ double det3(const double M[3][3]) {
 }
 // Eigen::umeyama(src, dst, false) from the accumulated sums: returns U (4x4) mapping src -> dst.
 // rank_tol: a singular value counts when it is above rank_tol x the largest.  They are roots of the eigenvalues of sigma^T sigma,
-// whose rounding noise is ~1e-16 of the largest eigenvalue, i.e. up to ~5e-8 of the largest SINGULAR value: under the
-// registration loop's 1e-14 an exactly deficient covariance (three pairs always are: rank 2) is taken for full rank whenever that
-// noise comes out positive, and the left vector made from it is not orthogonal to the others.  The registration loop keeps its
-// value (its clouds are nowhere near deficient, and its results stay bit for bit); RANSAC, whose samples are deficient by
-// construction, passes RANSAC_RANK_TOL.
-__host__ __device__ void umeyama_from_sums(const double *s /*ICP slots*/, double U[16], double rank_tol = 1e-14) {
+// whose rounding noise is ~1e-16 of the largest eigenvalue, i.e. up to ~5e-8 of the largest SINGULAR value: under a tolerance
+// below that (the registration loop once passed 1e-14) an exactly deficient covariance (three pairs always are: rank 2; so is a
+// wall) is taken for full rank whenever that noise comes out positive, and the left vector made from it is not orthogonal to the
+// others.  Both callers pass 1e-6 (RANSAC_RANK_TOL, ICP_RANK_TOL) and follow with umeyama_polish.
+// The means and products in `s` may be relative to any common origin: R does not depend on it, and the translation written
+// here is the one between the relative frames (icp_p2p_update moves it back).
+__host__ __device__ void umeyama_from_sums(const double *s /*ICP slots*/, double U[16], double rank_tol) {
     const double n = s[0];
     const double ps[3] = {s[2] / n, s[3] / n, s[4] / n}, pt[3] = {s[5] / n, s[6] / n, s[7] / n};
     double sigma[3][3];  // (1/n) sum (t - mt)(p - mp)^T  = E[t p^T] - mt mp^T ; slots hold p_i t_j
@@ -2874,12 +2882,84 @@ __device__ __forceinline__ void icp_publish(const IcpState *st, IcpState *mirror
     // above, and the host would copy a stale iteration count / fitness (the fields share one 64-byte line)
     *(volatile int *)&mirror->seq = st->evals | (st->done ? ICP_SEQ_DONE : 0);
 }
+// The reduction of k_icp_eval's partial sums, by a 1024-thread workgroup: 16 waves, wave w reduces slots w and w + 16 into
+// sums[]; the caller places the barrier.  k_icp_step and the read-out of r3d_debug_icp_sums share it.
+__device__ __forceinline__ void icp_reduce_partials(const double *__restrict__ partial, int nblocks, double *sums /* shared, [32] */) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // wave w owns slots w and w + 16; the partial sums are stored [slot][workgroup], so lane t reads t, t + 64, ... of a
+    // contiguous run, twelve requests per slot in flight (768 workgroups = one round), added in ascending order: the same
+    // sum, bit for bit, as one lane walking them one dependent load at a time (that walk was 2 x 12 L2 round trips of the
+    // 12 us this kernel took)
+    constexpr int U = 12;
+    const int s0 = w, s1 = w + 16;
+    const bool two = s1 < ICP_SLOTS;
+    const double *p0 = partial + (size_t)s0 * nblocks, *p1 = partial + (size_t)(two ? s1 : s0) * nblocks;
+    double v0 = 0, v1 = 0;
+    for (int b0 = 0; b0 < nblocks; b0 += 64 * U) {
+        double a0[U], a1[U];
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            const int b = b0 + j * 64 + lane, bc = min(b, nblocks - 1);   // clamped address + select: no branch around a load
+            const double x0 = p0[bc], x1 = p1[bc];
+            a0[j] = b < nblocks ? x0 : 0.0;
+            a1[j] = b < nblocks ? x1 : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < U; j++) { v0 += a0[j]; v1 += a1[j]; }
+    }
+    v0 = wave_sum(v0);
+    v1 = wave_sum(v1);
+    if (lane == 0) { sums[s0] = v0; if (two) sums[s1] = v1; }
+}
+
+// r3d_debug_icp_sums: the 29 slots of one evaluation as k_icp_step would see them (its reduction, nothing else)
+__global__ void __launch_bounds__(1024) k_icp_sums_readout(const double *__restrict__ partial, int nblocks, double *__restrict__ out) {
+    __shared__ double sums[32];
+    icp_reduce_partials(partial, nblocks, sums);
+    __syncthreads();
+    if (threadIdx.x < ICP_SLOTS) out[threadIdx.x] = sums[threadIdx.x];
+}
+
+// The point-to-point update from the slots k_icp_eval accumulates relative to the origin o (the centre of the target grid's
+// box): Umeyama on the relative moments, then the translation back in world coordinates, t = (o + mu) - R (o + mq) with mq, mu
+// the relative means.
+// The rank rule is RANSAC's (see umeyama_from_sums): walls and floors give rank-2 covariances, whose third singular value is
+// rounding noise; under the 1e-14 this loop used to pass that noise counted as a direction and the rotation came out
+// non-orthonormal (1e-3 on a flat patch).  umeyama_polish then takes the rotation from the eigenvector route's ~1e-13 to the
+// least-squares rotation of sigma itself.
+// The translation is summed in double-double (error-free products and sums, one rounding at the end): its terms are as large
+// as the clouds' distance from the world origin, the result as small as the motion, and a plain sum would round at the former.
+constexpr double ICP_RANK_TOL = 1e-6;
+__host__ __device__ inline void dd_add(double &hi, double &lo, double x) {   // (hi, lo) += x, hi + lo exact to the sum's second order
+    const double s = hi + x, b = s - hi;
+    lo += (hi - (s - b)) + (x - b);
+    hi = s;
+}
+__host__ __device__ void icp_p2p_update(const double *sums, const IcpOrigin &org, double U[16]) {
+    umeyama_from_sums(sums, U, ICP_RANK_TOL);
+    umeyama_polish(sums, U);
+    const double n = sums[0], o[3] = {org.x, org.y, org.z};
+    const double mq[3] = {sums[2] / n, sums[3] / n, sums[4] / n}, mu[3] = {sums[5] / n, sums[6] / n, sums[7] / n};
+    for (int i = 0; i < 3; i++) {
+        double hi = o[i], lo = 0;
+        dd_add(hi, lo, mu[i]);
+        for (int j = 0; j < 3; j++) {
+            const double r = -U[i * 4 + j];
+            const double a = r * o[j], b = r * mq[j];
+            lo += fma(r, o[j], -a) + fma(r, mq[j], -b);   // what the two products rounded away
+            dd_add(hi, lo, a);
+            dd_add(hi, lo, b);
+        }
+        U[i * 4 + 3] = hi + lo;
+    }
+}
+
 __global__ void __launch_bounds__(1024) k_icp_step(const double *__restrict__ partial, int nblocks, IcpState *__restrict__ st, int64_t ns,
                                                    int mode, int max_it, double rel_fit, double rel_rmse, IcpState *__restrict__ mirror,
-                                                   int publish /* this step is one the host waits for (the last step always is) */) {
+                                                   int publish /* this step is one the host waits for (the last step always is) */,
+                                                   IcpOrigin org /* origin of the point-to-point slots */) {
     __shared__ double sums[32];
     if (st->done) return;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     // the state the one deciding thread needs, requested BEFORE the reduction so that its round trips run under the partial sums'
     // (they were a chain of dependent loads after the barrier)
     int k = 0;
@@ -2891,32 +2971,7 @@ __global__ void __launch_bounds__(1024) k_icp_step(const double *__restrict__ pa
 #pragma unroll
         for (int i = 0; i < 16; i++) T[i] = st->T[i];
     }
-    {
-        // wave w owns slots w and w + 16; the partial sums are stored [slot][workgroup], so lane t reads t, t + 64, ... of a
-        // contiguous run, twelve requests per slot in flight (768 workgroups = one round), added in ascending order: the same
-        // sum, bit for bit, as one lane walking them one dependent load at a time (that walk was 2 x 12 L2 round trips of the
-        // 12 us this kernel took)
-        constexpr int U = 12;
-        const int s0 = w, s1 = w + 16;
-        const bool two = s1 < ICP_SLOTS;
-        const double *p0 = partial + (size_t)s0 * nblocks, *p1 = partial + (size_t)(two ? s1 : s0) * nblocks;
-        double v0 = 0, v1 = 0;
-        for (int b0 = 0; b0 < nblocks; b0 += 64 * U) {
-            double a0[U], a1[U];
-#pragma unroll
-            for (int j = 0; j < U; j++) {
-                const int b = b0 + j * 64 + lane, bc = min(b, nblocks - 1);   // clamped address + select: no branch around a load
-                const double x0 = p0[bc], x1 = p1[bc];
-                a0[j] = b < nblocks ? x0 : 0.0;
-                a1[j] = b < nblocks ? x1 : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < U; j++) { v0 += a0[j]; v1 += a1[j]; }
-        }
-        v0 = wave_sum(v0);
-        v1 = wave_sum(v1);
-        if (lane == 0) { sums[s0] = v0; if (two) sums[s1] = v1; }
-    }
+    icp_reduce_partials(partial, nblocks, sums);
     __syncthreads();
     if (threadIdx.x != 0) return;
     const unsigned long long now = wall_clock64();
@@ -2932,7 +2987,7 @@ __global__ void __launch_bounds__(1024) k_icp_step(const double *__restrict__ pa
     double U[16];
     for (int i = 0; i < 16; i++) U[i] = (i % 5 == 0);
     if (sums[0] > 0) {
-        if (mode == MODE_P2P) umeyama_from_sums(sums, U);
+        if (mode == MODE_P2P) icp_p2p_update(sums, org, U);
         else solve6_to_matrix(sums, U);
     }
     mat4_mul(U, T, T);
@@ -3924,7 +3979,8 @@ int match_core(r3d_ctx *ctx, DevArena &ar, const double *d_src, int64_t ns, cons
 }
 
 // r3d_debug_icp_correspondences' output (host arrays, the caller's numbering)
-struct IcpReadout { int32_t *corr; double *d2; };
+// r3d_debug_icp_sums' output: `sums` set (host, [29]) selects that read-out instead, `origin` (host, [3]) goes with it
+struct IcpReadout { int32_t *corr; double *d2; double *sums; double *origin; };
 // the coloured mode's extra inputs (device colours of both clouds) and parameters, resolved by the entry point
 struct IcpColorInput { const double *d_sc, *d_tc; double lambda, radius; int max_nn; };
 
@@ -4030,13 +4086,16 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     memcpy(hst->T, T, sizeof T);
     R3D_HIP(ctx, hipMemcpyAsync(d_st, hst, sizeof *hst, hipMemcpyHostToDevice, ctx->stream));
     const int max_it = p->max_iteration;
+    // what the point-to-point moments are relative to: a fixed point both clouds are near (the paired sources lie within the
+    // distance of the target's box)
+    const IcpOrigin org = {0.5 * (G.mn[0] + G.mx[0]), 0.5 * (G.mn[1] + G.mx[1]), 0.5 * (G.mn[2] + G.mx[2])};
     // one evaluation + one step of the loop, enqueued without waiting (both return at once when the loop has ended)
     // (`corr`: the read-out's one evaluation -- the kernel's optional output, and no step behind it; the loop passes nullptr)
     auto enqueue_eval = [&](bool publish, int *corr = nullptr) {
         const double eps = p->gicp_epsilon > 0 ? p->gicp_epsilon : 1e-3;
         const double md = p->max_correspondence_distance;
         // one kernel per search form x mode
-#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr, colk)
+#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr, colk, org)
 #define R3D_ICP_MODES(S)                                            \
     switch (p->mode) {                                              \
         case MODE_P2P: R3D_ICP_LAUNCH(MODE_P2P, S); break;          \
@@ -4053,8 +4112,21 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
 #undef R3D_ICP_LAUNCH
         if (corr) return;
         k_icp_step<<<1, 1024, 0, ctx->stream>>>(d_part, nblocks, d_st, ns, p->mode, max_it, p->relative_fitness, p->relative_rmse, d_mirror,
-                                                publish ? 1 : 0);
+                                                publish ? 1 : 0, org);
     };
+    if (readout && readout->sums) {
+        // the loop's own evaluation (no correspondence output), then k_icp_step's reduction of its partial sums
+        int *d_corr = (int *)ar.get((size_t)ns * 4);   // enqueue_eval skips the step only when it is given this buffer
+        double *d_sums = (double *)ar.get(ICP_SLOTS * 8);
+        if (ar.rc) return ar.rc;
+        enqueue_eval(false, d_corr);
+        k_icp_sums_readout<<<1, 1024, 0, ctx->stream>>>(d_part, nblocks, d_sums);
+        R3D_HIP(ctx, hipGetLastError());
+        R3D_HIP(ctx, hipMemcpyAsync(readout->sums, d_sums, ICP_SLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
+        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (readout->origin) { readout->origin[0] = org.x; readout->origin[1] = org.y; readout->origin[2] = org.z; }
+        return R3D_OK;
+    }
     if (readout) {
         int *d_corr = (int *)ar.get((size_t)ns * 4), *d_corr_out = (int *)ar.get((size_t)ns * 4);
         double *d_d2_out = (double *)ar.get((size_t)ns * 8);
@@ -5954,6 +6026,31 @@ extern "C" int r3d_debug_icp_correspondences(r3d_ctx *ctx, const double *src, in
     double T[16];
     const IcpReadout ro = {corr_out, d2_out};
     return icp_core(ctx, ar, &p, d_s, ns, nullptr, d_t, nt, nullptr, T4x4, T, nullptr, std::chrono::steady_clock::now(), nullptr, 0, &ro);
+}
+
+// diagnostic: what one evaluation of the registration loop accumulates -- icp_core's set-up in the given mode, one k_icp_eval at
+// pose T through the loop's own launch, then k_icp_step's reduction of the partial sums
+extern "C" int r3d_debug_icp_sums(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns, const double *src_normals,
+                                  const double *tgt, int64_t nt, const double *tgt_normals, const double *T4x4, double *sums_out,
+                                  double *origin_out) {
+    R3D_ROCTX_RANGE("r3d_debug_icp_sums");
+    if (!ctx) return R3D_E_BADARG;
+    if (!p || !src || !tgt || !sums_out || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: bad argument");
+    if (p->mode < 0 || p->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)");
+    if (!(p->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: max_correspondence_distance must be > 0");
+    if (p->mode != MODE_P2P && !tgt_normals) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: target normals required for this mode");
+    if (p->mode == MODE_GICP && !src_normals) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: source normals required for GICP");
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    int rc;
+    double *d_t, *d_s, *d_tn = nullptr, *d_sn = nullptr;
+    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    if (p->mode != MODE_P2P && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if (p->mode == MODE_GICP && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
+    double T[16];
+    const IcpReadout ro = {nullptr, nullptr, sums_out, origin_out};
+    return icp_core(ctx, ar, p, d_s, ns, d_sn, d_t, nt, d_tn, T4x4, T, nullptr, std::chrono::steady_clock::now(), nullptr, 0, &ro);
 }
 
 extern "C" int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t n, int32_t op, int32_t *out) {

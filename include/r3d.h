@@ -276,9 +276,33 @@ typedef struct {
 /* src_normals: GICP only (covariances C = I - (1-eps) n n^T, as Open3D derives them from normals);
  * tgt_normals: point-to-plane and GICP.  init4x4 may be NULL (identity).  T4x4: row-major result.
  * The loop (correspondences, statistics, convergence test, update) runs on the device; the host enqueues evaluations in batches
- * and reads the loop state once per batch, so `iterations` / `converged` are exactly those of the sequential loop. */
+ * and reads the loop state once per batch, so `iterations` / `converged` are exactly those of the sequential loop.
+ * The point-to-point update is Eigen's umeyama(src, dst, false) of the correspondences.  Its moments are accumulated relative to
+ * the centre of the target grid's box (r3d_debug_icp_sums), so the result does not degrade with the clouds' distance from the world origin.
+ * A singular value of the covariance below 1e-6 of the largest counts as zero: planar correspondences (a wall, three pairs) give
+ * the proper rotation that completes the plane's, collinear ones the smallest rotation that maps the line, one pair a pure
+ * translation.  The plane and GICP updates solve the 6x6 system and keep the pose when |det J^T J| < 1e-6. */
 int r3d_icp(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns, const double *src_normals, const double *tgt,
             int64_t nt, const double *tgt_normals, const double *init4x4, double *T4x4, r3d_icp_stats *stats);
+/* diagnostic: what one evaluation of the registration loop accumulates.  Runs r3d_icp's set-up for p->mode (0, 1 or 2) and ONE
+ * evaluation at pose T4x4 (NULL: identity) through the loop's own launch: the same search form, the same number of workgroups and
+ * the same layout of partial sums.  sums_out[29] is the DEVICE's reduction of those partial sums, by the code k_icp_step runs (a
+ * kernel of its own stores them; no host sum is involved); no step is taken.  p->max_iteration and the relative criteria are unused.
+ * Refuses like r3d_icp: missing normals for the mode, ns / nt <= 0, distance <= 0, mode outside 0..2.
+ * Slots, over the correspondences (source i, its nearest target j within the distance; p = T * src[i], t = tgt[j]):
+ *   [0] their count   [1] sum of the squared distances, as the search formed them
+ *   point-to-point: with q = p - o, u = t - o,  [2..4] sum q   [5..7] sum u   [8 + 3a + b] sum q_a u_b;  [17..28] zero.
+ *     o is the centre of the box the target's search grid is laid out in (the target's bounding box for this call), written to
+ *     origin_out[3] (may be NULL).  The means are o + [2..4] / n and o + [5..7] / n, and sigma_ab = [8 + 3b + a] / n - ([5 + a] / n) ([2 + b] / n) is the
+ *     covariance (1/n) sum (t - mean t)_a (p - mean p)_b that Umeyama decomposes: it does not depend on o.
+ *   point-to-plane and GICP: [2..22] the upper triangle of J^T J (6x6, row by row: 00 01 .. 05 11 12 ..), [23..28] J^T r, in
+ *     ABSOLUTE coordinates like Open3D (origin_out is still written, and means nothing here).  Point-to-plane: the row
+ *     J = [p x n, n], r = (p - t) . n with n the target normal.  GICP: J^T J = sum Jb^T M^-1 Jb and J^T r = sum Jb^T M^-1 (p - t)
+ *     with Jb = [-[p]x | I], M = C_t + R C_s R^T, C = I - (1 - eps) n n^T, R the rotation of T, and a normal with n_x < -0.99
+ *     replaced by e1 (Open3D's GetRotationFromE1ToX) on both sides; eps = p->gicp_epsilon, <= 0 selecting 1e-3. */
+int r3d_debug_icp_sums(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns, const double *src_normals,
+                       const double *tgt, int64_t nt, const double *tgt_normals, const double *T4x4, double *sums_out,
+                       double *origin_out);
 
 /* replaces: o3d.pipelines.registration.registration_colored_icp(source, target, max_dist, init,
  *           TransformationEstimationForColoredICP(lambda_geometric), ICPConvergenceCriteria(...))   [recalled, Open3D 0.18

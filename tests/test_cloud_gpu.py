@@ -412,6 +412,22 @@ def test_fused_align_call_equals_chained_entry_points(r3d, mode):
             ops.align_point_clouds(sp, tp, 0.02, None, 10, mode, None, 0)             # this mode needs normals
 
 
+def _one_step_against_the_reference(r3d, src, tgt, md, sn, tn):
+    """One registration step of every mode against tests/icp_step_ref.py (slots, pose, statistics: tests/test_icp_step_gpu.py),
+    wherever the answer is determined: point-to-point always (a rank-1 covariance in its mapped means and line), the 6x6 modes
+    when the reference's determinant is clear of the |det| < 1e-6 rule on either side."""
+    from tests import icp_step_cases as cs
+    from tests import icp_step_ref as ref
+    from tests.test_icp_step_gpu import check_case
+    c = cs._case("degenerate", "degenerate", src, tgt, md, sn=sn, tn=tn)
+    for mode in (0, 1, 2):
+        ev = ref.evaluate(c["src"], c["tgt"], md, mode, None, c["sn"], c["tn"], c["eps"])
+        if mode and 1e-9 <= abs(ref.step(ev, mode)[1]["det"]) <= 1e-3:
+            continue
+        fails = check_case(r3d, c, mode)
+        assert not fails, f"mode {mode}: " + "\n".join(fails)
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 17])
 def test_tiny_clouds_stay_finite(r3d, n):
     """Clouds of one to a few points: every cloud entry point returns finite results.  One correspondence pair (or coincident
@@ -433,6 +449,7 @@ def test_tiny_clouds_stay_finite(r3d, n):
     for mode in (1, 2):
         res = ops.registration(p, p + shift, 0.05, mode=mode, max_iteration=5, source_normals=nr, target_normals=nr)
         assert np.isfinite(res["T"]).all()
+    _one_step_against_the_reference(r3d, p, p + shift, 0.05, nr, nr)
     a = ops.align_point_clouds(p, p + shift, 0.05, 0.1, 5, 0, 0.2, 10)
     assert np.isfinite(a["T"]).all()
 
@@ -447,9 +464,12 @@ def test_degenerate_geometry_stays_finite(r3d):
         assert np.isfinite(res["T"]).all(), mode
     res = ops.registration(p, p + np.array([0.0, 0.001, 0.0]), 0.05, mode=0, max_iteration=1)
     np.testing.assert_allclose(res["T"][:3, :3], np.eye(3), atol=1e-12)          # smallest rotation for rank-1 pairs: none
+    _one_step_against_the_reference(r3d, p, p + np.array([0.0, 0.001, 0.0]), 0.05, nr, nr)
     d = np.ones((50, 3))                                                          # all points coincident
-    assert np.isfinite(ops.estimate_normals(d, 0.2, 20)).all()
+    dn = ops.estimate_normals(d, 0.2, 20)
+    assert np.isfinite(dn).all()
     assert np.isfinite(ops.registration(d, d, 0.05, mode=0, max_iteration=3)["T"]).all()
+    _one_step_against_the_reference(r3d, d, d, 0.05, dn, dn)
 
 
 # ------------------------------------------------------------------------------- normal orientation (rows c2 / f-3)
