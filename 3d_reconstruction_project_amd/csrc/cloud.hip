@@ -2109,7 +2109,6 @@ __global__ void __launch_bounds__(256) k_backproject(const unsigned short *__res
     if (pix) pix[o] = (int)i;
 }
 
-// ------------------------------------------------------------------------------------------------ host side
 // ------------------------------------------------------------------------------------------------ incremental model voxel table
 // The scanning loop re-down-samples the WHOLE model every frame (pointcloud_alignment.py:23; main.py:48).  The legacy grid's voxel
 // of a point depends only on the model's minimum corner (origin = min_bound - voxel / 2) and a voxel's mean is its members summed
@@ -2282,6 +2281,16 @@ struct PinRead {
         return R3D_OK;
     }
 };
+// Count of a compaction -- n flags and their exclusive scan -- which is the scan's last entry plus the last flag.  d_scan / d_flag
+// are those two device words, for kernels enqueued before the host knows the count; add_to puts them into a read-back the caller
+// owns, so whatever else it wants from the device (a bounding box, a deferred sort's test) travels in the same round trip.
+struct CompactCount {
+    const int *d_scan, *d_flag;
+    int h_scan = 0, h_flag = 0;
+    CompactCount(const int *scan, const int *flags, int64_t n) : d_scan(scan + (n - 1)), d_flag(flags + (n - 1)) {}
+    int add_to(PinRead &rd) { if (int rc = rd.add(&h_scan, d_scan, 4)) return rc; return rd.add(&h_flag, d_flag, 4); }
+    int64_t count() const { return (int64_t)h_scan + h_flag; }   // after the read-back's wait()
+};
 
 // means of the members `ld` loads through the index list: voxels up to VM_BIG members by a thread each, the listed rest by a wave
 // each; scratch: (nseg + 16) ints (the counter, then the list)
@@ -2309,6 +2318,13 @@ static inline int launch_voxel_mean(r3d_ctx *ctx, DevArena &ar, bool f32, const 
     }
     if (f32) return launch_voxel_mean_ld<float>(ctx, ar, MemberXyz{a}, idx, starts, nseg, n, out);
     return launch_voxel_mean_ld<double>(ctx, ar, MemberXyz{a}, idx, starts, nseg, n, out);
+}
+
+// Sorted cell keys are 32-bit whenever the key space allows, else 64-bit: calls the generic `f` with the pointer in its real type
+// (where the keys are yet to be made, a null one: `decltype(+*k)` is the key type).
+template <class F>
+static inline auto with_keys(bool keys32, const void *keys, F &&f) {
+    return keys32 ? f((const unsigned *)keys) : f((const unsigned long long *)keys);
 }
 
 struct Grid {
@@ -2576,12 +2592,14 @@ int sort_by_cell(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, con
     }
     if (!force_radix && nbuckets <= CS_MAX_BUCKETS && n < 0x7fffffff) {
         bool done = false;
-        const int rc = *keys32 ? counting_sort_by_cell_t<unsigned>(ctx, ar, d_pts, n, g, nbuckets, keys_sorted, idx_sorted, sorted_pts, &done, defer)
-                               : counting_sort_by_cell_t<unsigned long long>(ctx, ar, d_pts, n, g, nbuckets, keys_sorted, idx_sorted, sorted_pts, &done, defer);
+        const int rc = with_keys(*keys32, nullptr, [&](auto *k) {
+            return counting_sort_by_cell_t<decltype(+*k)>(ctx, ar, d_pts, n, g, nbuckets, keys_sorted, idx_sorted, sorted_pts, &done, defer);
+        });
         if (rc || done) return rc;
     }
-    const int rc = *keys32 ? radix_sort_by_cell_t<unsigned>(ctx, ar, d_pts, n, org, cell, dims, key_order, bits, keys_sorted, idx_sorted)
-                           : radix_sort_by_cell_t<unsigned long long>(ctx, ar, d_pts, n, org, cell, dims, key_order, bits, keys_sorted, idx_sorted);
+    const int rc = with_keys(*keys32, nullptr, [&](auto *k) {
+        return radix_sort_by_cell_t<decltype(+*k)>(ctx, ar, d_pts, n, org, cell, dims, key_order, bits, keys_sorted, idx_sorted);
+    });
     if (rc) return rc;
     if (sorted_pts) {
         k_gather3<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_pts, *idx_sorted, n, sorted_pts);
@@ -2649,13 +2667,10 @@ int grid_build(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, doubl
         if (ar.rc) return ar.rc;
         R3D_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)(G.ncells + 1) * 4, ctx->stream));
         const int nbd = (int)((n + 255) / 256);
-        if (G.keys32) {
-            k_cell_counts<unsigned><<<nbd, 256, 0, ctx->stream>>>((const unsigned *)G.keys, n, rs, cnt);
-            k_cell_counts2<unsigned><<<nbd, 256, 0, ctx->stream>>>((const unsigned *)G.keys, n, rs, cnt);
-        } else {
-            k_cell_counts<unsigned long long><<<nbd, 256, 0, ctx->stream>>>((const unsigned long long *)G.keys, n, rs, cnt);
-            k_cell_counts2<unsigned long long><<<nbd, 256, 0, ctx->stream>>>((const unsigned long long *)G.keys, n, rs, cnt);
-        }
+        with_keys(G.keys32, G.keys, [&](auto *keys) {
+            k_cell_counts<<<nbd, 256, 0, ctx->stream>>>(keys, n, rs, cnt);
+            k_cell_counts2<<<nbd, 256, 0, ctx->stream>>>(keys, n, rs, cnt);
+        });
         if ((rc = dev_exclusive_scan<int>(ctx, ar, cnt, cs, G.ncells + 1))) return rc;
         G.v = GridView{G.mn[0], G.mn[1], G.mn[2], cell, 1.0 / cell, dims[0], dims[1], dims[2], nullptr, nullptr, cs, sorted, idx, nullptr};
         return R3D_OK;
@@ -2671,13 +2686,11 @@ int grid_build(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, doubl
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemsetAsync(mark, 0, (size_t)(nl4 + nl) * 4, ctx->stream));
     const int nb = (int)((n + 255) / 256), nlb = (int)((nl + 255) / 256);
-    if (G.keys32) k_line_mark<unsigned><<<nb, 256, 0, ctx->stream>>>((const unsigned *)G.keys, n, mark, last1);
-    else k_line_mark<unsigned long long><<<nb, 256, 0, ctx->stream>>>((const unsigned long long *)G.keys, n, mark, last1);
+    with_keys(G.keys32, G.keys, [&](auto *keys) { k_line_mark<<<nb, 256, 0, ctx->stream>>>(keys, n, mark, last1); });
     if ((rc = dev_exclusive_scan<int>(ctx, ar, mark, ids, nl))) return rc;
     if ((rc = dev_exclusive_scan<int, true>(ctx, ar, last1, before, nl))) return rc;
     k_line_l1<<<nlb, 256, 0, ctx->stream>>>(mark, ids, before, nl, l1);
-    if (G.keys32) k_line_fill<unsigned><<<(unsigned)((n + 256) / 256), 256, 0, ctx->stream>>>((const unsigned *)G.keys, n, l1, nl, l2);
-    else k_line_fill<unsigned long long><<<(unsigned)((n + 256) / 256), 256, 0, ctx->stream>>>((const unsigned long long *)G.keys, n, l1, nl, l2);
+    with_keys(G.keys32, G.keys, [&](auto *keys) { k_line_fill<<<(unsigned)((n + 256) / 256), 256, 0, ctx->stream>>>(keys, n, l1, nl, l2); });
     R3D_HIP(ctx, hipGetLastError());
     G.v = GridView{G.mn[0], G.mn[1], G.mn[2], cell, 1.0 / cell, dims[0], dims[1], dims[2], l1, l2, nullptr, sorted, idx, nullptr};
     return R3D_OK;
@@ -2999,6 +3012,31 @@ int upload(r3d_ctx *ctx, DevArena &ar, const double *h, int64_t n3, double **d) 
     *d = (double *)ar.get((size_t)n3 * 8);
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemcpyAsync(*d, h, (size_t)n3 * 8, hipMemcpyHostToDevice, ctx->stream));
+    return R3D_OK;
+}
+// the (source, target) pair of a registration problem: ns / nt rows of `width` doubles (3: points, FPFH_DIM: features)
+int upload_pair(r3d_ctx *ctx, DevArena &ar, const double *src, int64_t ns, const double *tgt, int64_t nt, double **d_s, double **d_t, int width = 3) {
+    if (int rc = upload(ctx, ar, src, ns * width, d_s)) return rc;
+    return upload(ctx, ar, tgt, nt * width, d_t);
+}
+// ... and the M index pairs (source row, target row) of a correspondence problem; M may be 0
+int upload_corres_problem(r3d_ctx *ctx, DevArena &ar, const double *src, int64_t ns, const double *tgt, int64_t nt, const int32_t *corres, int64_t M,
+                          double **d_s, double **d_t, int **d_c) {
+    if (int rc = upload_pair(ctx, ar, src, ns, tgt, nt, d_s, d_t)) return rc;
+    *d_c = (int *)ar.get((size_t)M * 8);
+    if (ar.rc) return ar.rc;
+    if (M > 0) R3D_HIP(ctx, hipMemcpyAsync(*d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    return R3D_OK;
+}
+// source.transform(T) of a registered cloud into fresh arena buffers: the points moved, the normals (d_n may be null, *d_on then is) rotated
+int transform_cloud(r3d_ctx *ctx, DevArena &ar, const double T[16], const double *d_p, const double *d_n, int64_t n, double **d_o, double **d_on) {
+    *d_o = (double *)ar.get((size_t)n * 24);
+    *d_on = d_n ? (double *)ar.get((size_t)n * 24) : nullptr;
+    if (ar.rc) return ar.rc;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    k_transform<<<nb, 256, 0, ctx->stream>>>(d_p, n, to_rigid(T), 0, *d_o);
+    if (d_n) k_transform<<<nb, 256, 0, ctx->stream>>>(d_n, n, to_rigid(T), 1, *d_on);
+    R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
 }
 
@@ -3693,50 +3731,41 @@ int reproject_core(r3d_ctx *ctx, DevArena &ar, const int16_t *d_d, int w, int h,
     if (max_depth > 0) k_disp_flags_depth<<<nb, 256, 0, ctx->stream>>>(d_d, w, n, min_valid_x16, Q, max_depth, flags);
     else k_disp_flags<<<nb, 256, 0, ctx->stream>>>(d_d, n, min_valid_x16, flags);
     if (int src = dev_exclusive_scan<int>(ctx, ar, flags, scan, n)) return src;
-    int ls = 0, lf = 0;
-    if (bounds_out) {
-        // arrays sized for the upper bound (every pixel valid); reprojection, pose and bounding box enqueued without a host read
-        double *d_xyz = (double *)ar.get((size_t)n * 24);
-        int *d_pix = want_pix ? (int *)ar.get((size_t)n * 4) : nullptr;
-        if (ar.rc) return ar.rc;
-        k_reproject<<<nb, 256, 0, ctx->stream>>>(d_d, flags, scan, w, n, Q, d_xyz, d_pix);
-        if (pose4x4) {
-            double *d_t = (double *)ar.get((size_t)n * 24);
-            if (ar.rc) return ar.rc;
-            k_transform_dn<<<nb, 256, 0, ctx->stream>>>(d_xyz, scan + (n - 1), flags + (n - 1), to_rigid(pose4x4), d_t);
-            d_xyz = d_t;
-        }
-        const double *d_box = nullptr;
-        if (int brc = cloud_bbox_enqueue_dn(ctx, ar, d_xyz, n, scan + (n - 1), flags + (n - 1), &d_box)) return brc;
-        {
-            PinRead rd(ctx);
-            int prc;
-            if ((prc = rd.add(&ls, scan + (n - 1), 4)) || (prc = rd.add(&lf, flags + (n - 1), 4)) || (prc = rd.add(bounds_out, d_box, 48)) || (prc = rd.wait())) return prc;
-        }
-        const int64_t m = (int64_t)ls + lf;
-        *m_out = m;
-        *d_xyz_out = m ? d_xyz : nullptr;
-        if (d_pix_out) *d_pix_out = m ? d_pix : nullptr;
-        return m ? bbox_check(ctx, bounds_out, bounds_out + 3) : R3D_OK;
-    }
-    {
-        PinRead rd(ctx);
-        int prc;
-        if ((prc = rd.add(&ls, scan + (n - 1), 4)) || (prc = rd.add(&lf, flags + (n - 1), 4)) || (prc = rd.wait())) return prc;
-    }
-    const int64_t m = (int64_t)ls + lf;
-    *m_out = m;
+    // With bounds_out the arrays are sized for the upper bound (every pixel valid) and reprojection, pose and bounding box are
+    // enqueued before the one read-back; without it the count is read first and the arrays hold exactly the valid pixels.
+    const bool upper = bounds_out != nullptr;
+    CompactCount cc(scan, flags, n);
+    PinRead rd(ctx);
+    int rc;
+    *m_out = 0;
     *d_xyz_out = nullptr;
     if (d_pix_out) *d_pix_out = nullptr;
-    if (m == 0) return R3D_OK;
-    double *d_xyz = (double *)ar.get((size_t)m * 24);
-    int *d_pix = want_pix ? (int *)ar.get((size_t)m * 4) : nullptr;
+    if (!upper) {
+        if ((rc = cc.add_to(rd)) || (rc = rd.wait())) return rc;
+        if (cc.count() == 0) return R3D_OK;
+    }
+    const int64_t rows = upper ? n : cc.count();
+    double *d_xyz = (double *)ar.get((size_t)rows * 24);
+    int *d_pix = want_pix ? (int *)ar.get((size_t)rows * 4) : nullptr;
     if (ar.rc) return ar.rc;
     k_reproject<<<nb, 256, 0, ctx->stream>>>(d_d, flags, scan, w, n, Q, d_xyz, d_pix);
     R3D_HIP(ctx, hipGetLastError());
+    if (upper) {
+        if (pose4x4) {
+            double *d_t = (double *)ar.get((size_t)n * 24);
+            if (ar.rc) return ar.rc;
+            k_transform_dn<<<nb, 256, 0, ctx->stream>>>(d_xyz, cc.d_scan, cc.d_flag, to_rigid(pose4x4), d_t);
+            d_xyz = d_t;
+        }
+        const double *d_box = nullptr;
+        if ((rc = cloud_bbox_enqueue_dn(ctx, ar, d_xyz, n, cc.d_scan, cc.d_flag, &d_box))) return rc;
+        if ((rc = cc.add_to(rd)) || (rc = rd.add(bounds_out, d_box, 48)) || (rc = rd.wait())) return rc;
+        if (cc.count() == 0) return R3D_OK;
+    }
+    *m_out = cc.count();
     *d_xyz_out = d_xyz;
     if (d_pix_out) *d_pix_out = d_pix;
-    return R3D_OK;
+    return upper ? bbox_check(ctx, bounds_out, bounds_out + 3) : R3D_OK;
 }
 
 // depth image (host) -> compacted xyz / colours (device); everything below r3d_backproject_depth's argument checks
@@ -3757,53 +3786,54 @@ int backproject_core(r3d_ctx *ctx, DevArena &ar, const uint16_t *depth, int w, i
     const int nb = (int)((n + 255) / 256);
     k_depth_flags<<<nb, 256, 0, ctx->stream>>>(d_d, w, stride, n, c, flags);
     if (int src = dev_exclusive_scan<int>(ctx, ar, flags, scan, n)) return src;
-    int ls = 0, lf = 0;
-    if (bounds_out) {   // as reproject_core: arrays for the upper bound, back-projection and bounding box enqueued, ONE read-back
-        double *d_xyz = (double *)ar.get((size_t)n * 24), *d_rgb = color ? (double *)ar.get((size_t)n * 24) : nullptr;
-        int *d_pix = want_pix ? (int *)ar.get((size_t)n * 4) : nullptr;
-        if (ar.rc) return ar.rc;
-        k_backproject<<<nb, 256, 0, ctx->stream>>>(d_d, d_c, flags, scan, w, stride, cstride, n, c, d_xyz, d_rgb, d_pix);
-        const double *d_box = nullptr;
-        if (int brc = cloud_bbox_enqueue_dn(ctx, ar, d_xyz, n, scan + (n - 1), flags + (n - 1), &d_box)) return brc;
-        {
-            PinRead rd(ctx);
-            int prc;
-            if ((prc = rd.add(&ls, scan + (n - 1), 4)) || (prc = rd.add(&lf, flags + (n - 1), 4)) || (prc = rd.add(bounds_out, d_box, 48)) ||
-                (extra && extra->host && (prc = rd.add(extra->host, extra->dev, extra->bytes))) || (prc = rd.wait())) return prc;
-        }
-        const int64_t m = (int64_t)ls + lf;
-        *m_out = m;
-        *d_xyz_out = m ? d_xyz : nullptr;
-        if (d_rgb_out) *d_rgb_out = m ? d_rgb : nullptr;
-        if (d_pix_out) *d_pix_out = m ? d_pix : nullptr;
-        return m ? bbox_check(ctx, bounds_out, bounds_out + 3) : R3D_OK;
-    }
-    {
-        PinRead rd(ctx);
-        int prc;
-        if ((prc = rd.add(&ls, scan + (n - 1), 4)) || (prc = rd.add(&lf, flags + (n - 1), 4)) || (prc = rd.wait())) return prc;
-    }
-    const int64_t m = (int64_t)ls + lf;
-    *m_out = m;
+    // as reproject_core: with bounds_out, arrays for the upper bound and back-projection and bounding box enqueued before the ONE
+    // read-back; without it, the count first
+    const bool upper = bounds_out != nullptr;
+    CompactCount cc(scan, flags, n);
+    PinRead rd(ctx);
+    int rc;
+    *m_out = 0;
     *d_xyz_out = nullptr;
     if (d_rgb_out) *d_rgb_out = nullptr;
     if (d_pix_out) *d_pix_out = nullptr;
-    if (m == 0) return R3D_OK;
-    double *d_xyz = (double *)ar.get((size_t)m * 24), *d_rgb = color ? (double *)ar.get((size_t)m * 24) : nullptr;
-    int *d_pix = want_pix ? (int *)ar.get((size_t)m * 4) : nullptr;
+    if (!upper) {
+        if ((rc = cc.add_to(rd)) || (rc = rd.wait())) return rc;
+        if (cc.count() == 0) return R3D_OK;
+    }
+    const int64_t rows = upper ? n : cc.count();
+    double *d_xyz = (double *)ar.get((size_t)rows * 24), *d_rgb = color ? (double *)ar.get((size_t)rows * 24) : nullptr;
+    int *d_pix = want_pix ? (int *)ar.get((size_t)rows * 4) : nullptr;
     if (ar.rc) return ar.rc;
     k_backproject<<<nb, 256, 0, ctx->stream>>>(d_d, d_c, flags, scan, w, stride, cstride, n, c, d_xyz, d_rgb, d_pix);
     R3D_HIP(ctx, hipGetLastError());
+    if (upper) {
+        const double *d_box = nullptr;
+        if ((rc = cloud_bbox_enqueue_dn(ctx, ar, d_xyz, n, cc.d_scan, cc.d_flag, &d_box))) return rc;
+        if ((rc = cc.add_to(rd)) || (rc = rd.add(bounds_out, d_box, 48)) ||
+            (extra && extra->host && (rc = rd.add(extra->host, extra->dev, extra->bytes))) || (rc = rd.wait())) return rc;
+        if (cc.count() == 0) return R3D_OK;
+    }
+    *m_out = cc.count();
     *d_xyz_out = d_xyz;
     if (d_rgb_out) *d_rgb_out = d_rgb;
     if (d_pix_out) *d_pix_out = d_pix;
-    return R3D_OK;
+    return upper ? bbox_check(ctx, bounds_out, bounds_out + 3) : R3D_OK;
 }
 static int depth_args_ok(r3d_ctx *ctx, const uint16_t *depth, int w, int h, int stride, const r3d_depth_camera *cam, const uint8_t *color,
                          int cstride, const char *who) {
     if (!depth || !cam || w <= 0 || h <= 0 || stride < w || (color && cstride < 3 * w)) return r3d_fail(ctx, R3D_E_BADARG, "%s: bad argument", who);
     if (!(cam->fx != 0) || !(cam->fy != 0) || !(cam->depth_scale > 0) || !(cam->depth_trunc > 0))
         return r3d_fail(ctx, R3D_E_BADARG, "%s: focal lengths must be non-zero, depth_scale and depth_trunc positive", who);
+    return R3D_OK;
+}
+// argument checks of the registration modes P2P / P2PLANE / GICP.  have_tn / have_sn: the caller has, or will compute, target /
+// source normals; no_tn: what to say where the plane and GICP modes find none for the target
+static int icp_mode_check(r3d_ctx *ctx, const char *who, const r3d_icp_params *p, bool have_tn, bool have_sn,
+                          const char *no_tn = "target normals required for this mode") {
+    if (p->mode < 0 || p->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "%s: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)", who);
+    if (!(p->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "%s: max_correspondence_distance must be > 0", who);
+    if (p->mode != MODE_P2P && !have_tn) return r3d_fail(ctx, R3D_E_BADARG, "%s: %s", who, no_tn);
+    if (p->mode == MODE_GICP && !have_sn) return r3d_fail(ctx, R3D_E_BADARG, "%s: source normals required for GICP", who);
     return R3D_OK;
 }
 
@@ -3863,23 +3893,52 @@ int voxel_segments(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t n, dou
         SortDefer df;
         if ((rc = sort_by_cell(ctx, ar, d_p, n, org, voxel, dims, tensor_grid ? 3 : 1, &keys, &keys32, &V.idx, V.sorted, attempt ? 1 : -1,
                                attempt ? nullptr : &df))) return rc;
-        if (keys32) k_seg_flags<unsigned><<<nb, 256, 0, ctx->stream>>>((const unsigned *)keys, n, flags);
-        else k_seg_flags<unsigned long long><<<nb, 256, 0, ctx->stream>>>((const unsigned long long *)keys, n, flags);
+        with_keys(keys32, keys, [&](auto *k) { k_seg_flags<<<nb, 256, 0, ctx->stream>>>(k, n, flags); });
         if (int src = dev_exclusive_scan<int>(ctx, ar, flags, scan, n)) return src;
         k_seg_starts<<<nb, 256, 0, ctx->stream>>>(flags, scan, n, V.starts);
-        int last_scan = 0, last_flag = 0;
-        {
-            PinRead rd(ctx);
-            int prc;
-            if ((prc = rd.add(&last_scan, scan + (n - 1), 4)) || (prc = rd.add(&last_flag, flags + (n - 1), 4)) || (prc = df.add_to(rd)) || (prc = rd.wait())) return prc;
-        }
-        V.nseg = (int64_t)last_scan + last_flag;
+        CompactCount cc(scan, flags, n);
+        PinRead rd(ctx);
+        if ((rc = cc.add_to(rd)) || (rc = df.add_to(rd)) || (rc = rd.wait())) return rc;
+        V.nseg = cc.count();
         if (df.ok()) return R3D_OK;
         static const bool dbg = [] { const char *e = getenv("R3D_SORT_DEBUG"); return e && *e == '1'; }();
         if (dbg) fprintf(stderr, "[r3d sort] voxel grid: deferred test failed (n=%lld runs=%d max_runs_per_bucket=%d): sorting again with the radix sort\n",
                          (long long)n, (int)(df.h_total >> 32), df.h_maxruns);
     }
     return r3d_fail(ctx, R3D_E_HIP, "voxel grid: the fallback sort did not complete");
+}
+// Voxel-down-sampled points of a device cloud: the means of the voxels' members, V.nseg rows in a fresh arena buffer.
+// tensor_grid / bounds_out / known_bounds: voxel_segments'.  V stays valid for voxel_attr_means and for readers of the sorted points.
+int voxel_means(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t n, double voxel, VoxelSegs &V, double **d_means, bool tensor_grid = false,
+                double *bounds_out = nullptr, const double *known_bounds = nullptr) {
+    if (int rc = voxel_segments(ctx, ar, d_p, n, voxel, V, tensor_grid, nullptr, nullptr, bounds_out, known_bounds)) return rc;
+    *d_means = (double *)ar.get((size_t)V.nseg * 24);
+    if (ar.rc) return ar.rc;
+    return launch_voxel_mean(ctx, ar, tensor_grid, d_p, V.idx, V.starts, V.nseg, n, *d_means, V.sorted);
+}
+// a further attribute of the same n points (colours, normals: [n][3], the cloud's order) averaged over the same voxels
+int voxel_attr_means(r3d_ctx *ctx, DevArena &ar, const VoxelSegs &V, const double *d_a, int64_t n, double **d_means, bool f32 = false) {
+    *d_means = (double *)ar.get((size_t)V.nseg * 24);
+    if (ar.rc) return ar.rc;
+    return launch_voxel_mean(ctx, ar, f32, d_a, V.idx, V.starts, V.nseg, n, *d_means);
+}
+
+// Launch of a kernel that keeps its k nearest neighbours in LDS columns (knn_collect): one thread per point, k * 12 bytes of dynamic
+// LDS each.  Every such kernel's parameters begin (grid, n, k, radius); `rest` are the others.
+template <class... P, class... A>
+int launch_knn(r3d_ctx *ctx, void (*kernel)(GridView, int64_t, int, double, P...), const Grid &G, int64_t n, int k, double radius, A... rest) {
+    const size_t lds = (size_t)k * KNN_BLOCK * 12;
+    R3D_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kernel<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, rest...);
+    R3D_HIP(ctx, hipGetLastError());
+    return R3D_OK;
+}
+// occupied cells of a k-NN search grid should hold about this many points (grid_build's target_occ)
+inline double knn_target_occ(int k) { return std::max(2.0, k / 5.0); }
+// ... unless R3D_KNN_OCC says otherwise (normals and colour gradients only)
+inline double knn_target_occ_env(int k) {
+    if (const char *oe = getenv("R3D_KNN_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 256) return v; }
+    return knn_target_occ(k);
 }
 
 // normals of a device cloud into a fresh device buffer
@@ -3888,17 +3947,11 @@ int normals_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t n, doubl
     Grid G;
     const int k = (int)std::min<int64_t>(max_nn, n);
     int rc;
-    double occ = std::max(2.0, k / 5.0);
-    if (const char *oe = getenv("R3D_KNN_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 256) occ = v; }
-    if ((rc = grid_build(ctx, ar, d_p, n, radius, occ, G, false, enclosing))) return rc;
+    if ((rc = grid_build(ctx, ar, d_p, n, radius, knn_target_occ_env(k), G, false, enclosing))) return rc;
     double *d_n = (double *)ar.get((size_t)n * 24);
     if (ar.rc) return ar.rc;
-    const size_t lds = (size_t)k * KNN_BLOCK * 12;
-    R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_normals, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_normals<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, d_prev, d_n, nullptr);
-    R3D_HIP(ctx, hipGetLastError());
     *d_n_out = d_n;
-    return R3D_OK;
+    return launch_knn(ctx, k_normals, G, n, k, radius, d_prev, d_n, nullptr);
 }
 
 // intensity + colour gradient of a device cloud (k_color_gradient's 4-double records, the caller's numbering) into a fresh device
@@ -3908,18 +3961,12 @@ int color_gradients_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, int64_t 
     Grid G;
     const int k = (int)std::min<int64_t>(max_nn, n);
     int rc;
-    double occ = std::max(2.0, k / 5.0);
-    if (const char *oe = getenv("R3D_KNN_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 256) occ = v; }
-    if ((rc = grid_build(ctx, ar, d_p, n, radius, occ, G, false))) return rc;
+    if ((rc = grid_build(ctx, ar, d_p, n, radius, knn_target_occ_env(k), G, false))) return rc;
     double *d_i = (double *)ar.get((size_t)n * 8), *d_rec = (double *)ar.get((size_t)n * 32);
     if (ar.rc) return ar.rc;
     k_intensity<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_c, G.v.idx, n, d_i);
-    const size_t lds = (size_t)k * KNN_BLOCK * 12;
-    R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_color_gradient, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_color_gradient<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, d_n, d_i, d_rec);
-    R3D_HIP(ctx, hipGetLastError());
     *d_rec_out = d_rec;
-    return R3D_OK;
+    return launch_knn(ctx, k_color_gradient, G, n, k, radius, d_n, d_i, d_rec);
 }
 
 // FPFH of a device cloud into the caller's device arrays d_fpfh / d_spfh_out ([n][33], the caller's numbering; d_spfh_out may be
@@ -3932,29 +3979,23 @@ int fpfh_core(r3d_ctx *ctx, DevArena &ar, const double *d_p, const double *d_n, 
     Grid G;
     const int k = (int)std::min<int64_t>(max_nn, n);
     int rc;
-    if ((rc = grid_build(ctx, ar, d_p, n, radius, std::max(2.0, k / 5.0), G))) return rc;
+    if ((rc = grid_build(ctx, ar, d_p, n, radius, knn_target_occ(k), G))) return rc;
     const size_t slots = (size_t)std::max(k - 1, 1);
     int *l_cnt = (int *)ar.get((size_t)n * 4), *l_idx = (int *)ar.get(slots * n * 4);
     double *l_d2 = (double *)ar.get(slots * n * 8), *spfh_s = (double *)ar.get((size_t)n * FPFH_DIM * 8);
     double *nrm_s = d_n ? (double *)ar.get((size_t)n * 24) : nullptr;
     if (ar.rc) return ar.rc;
-    const size_t lds = (size_t)k * KNN_BLOCK * 12;
-    const unsigned nbq = (unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK);
-    int *li = l_idx;
-    double *ld = l_d2;
     if (ev) R3D_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     if (d_n) {
         k_gather3<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_n, G.v.idx, n, nrm_s);
-        R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_spfh, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_spfh<<<nbq, KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, nrm_s, l_cnt, li, ld, spfh_s, d_spfh_out);
+        rc = launch_knn(ctx, k_spfh, G, n, k, radius, nrm_s, l_cnt, l_idx, l_d2, spfh_s, d_spfh_out);
     } else {
         k_gather_rows33<<<(unsigned)((n * FPFH_DIM + 255) / 256), 256, 0, ctx->stream>>>(d_spfh_in, G.v.idx, n, spfh_s);
-        R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_fpfh_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_fpfh_lists<<<nbq, KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, l_cnt, li, ld);
+        rc = launch_knn(ctx, k_fpfh_lists, G, n, k, radius, l_cnt, l_idx, l_d2);
     }
-    R3D_HIP(ctx, hipGetLastError());
+    if (rc) return rc;
     if (ev) R3D_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-    k_fpfh<<<nbq, 64, 0, ctx->stream>>>(n, l_cnt, li, ld, spfh_s, G.v.idx, d_fpfh);
+    k_fpfh<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), 64, 0, ctx->stream>>>(n, l_cnt, l_idx, l_d2, spfh_s, G.v.idx, d_fpfh);
     R3D_HIP(ctx, hipGetLastError());
     if (ev) R3D_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
     return R3D_OK;
@@ -4477,21 +4518,6 @@ int fgr_core(r3d_ctx *ctx, DevArena &ar, const r3d_fgr_params *p, const double *
 extern "C" {
 
 static int voxel_downsample_impl(r3d_ctx *ctx, const double *xyz, const double *colors, const double *normals, int64_t n, double voxel,
-                                 double *out_xyz, double *out_colors, double *out_normals, int64_t *out_n, bool tensor_grid);
-
-int r3d_voxel_downsample(r3d_ctx *ctx, const double *xyz, const double *colors, const double *normals, int64_t n, double voxel,
-                         double *out_xyz, double *out_colors, double *out_normals, int64_t *out_n) {
-    R3D_ROCTX_RANGE("r3d_voxel_downsample");
-    return voxel_downsample_impl(ctx, xyz, colors, normals, n, voxel, out_xyz, out_colors, out_normals, out_n, false);
-}
-
-int r3d_voxel_downsample_tensor(r3d_ctx *ctx, const double *xyz, const double *colors, const double *normals, int64_t n, double voxel,
-                                double *out_xyz, double *out_colors, double *out_normals, int64_t *out_n) {
-    R3D_ROCTX_RANGE("r3d_voxel_downsample_tensor");
-    return voxel_downsample_impl(ctx, xyz, colors, normals, n, voxel, out_xyz, out_colors, out_normals, out_n, true);
-}
-
-static int voxel_downsample_impl(r3d_ctx *ctx, const double *xyz, const double *colors, const double *normals, int64_t n, double voxel,
                                  double *out_xyz, double *out_colors, double *out_normals, int64_t *out_n, bool tensor_grid) {
     if (!ctx) return R3D_E_BADARG;
     if (!xyz || !out_xyz || !out_n || n <= 0 || !(voxel > 0)) return r3d_fail(ctx, R3D_E_BADARG, "voxel_downsample: bad argument");
@@ -4504,21 +4530,29 @@ static int voxel_downsample_impl(r3d_ctx *ctx, const double *xyz, const double *
     if (colors && (rc = upload(ctx, ar, colors, n * 3, &d_c))) return rc;
     if (normals && (rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
     VoxelSegs V;
-    if ((rc = voxel_segments(ctx, ar, d_p, n, voxel, V, tensor_grid))) return rc;
-    const int64_t nseg = V.nseg;
-    double *d_out = (double *)ar.get((size_t)nseg * 24);
-    if (ar.rc) return ar.rc;
+    double *d_out;
     const double *ins[3] = {d_p, d_c, d_n};
     double *outs[3] = {out_xyz, out_colors, out_normals};
     for (int a = 0; a < 3; a++) {
         if (!ins[a]) continue;
-        if ((rc = launch_voxel_mean(ctx, ar, tensor_grid, ins[a], V.idx, V.starts, nseg, n, d_out, a == 0 ? V.sorted : nullptr))) return rc;
-        R3D_HIP(ctx, hipGetLastError());
-        R3D_HIP(ctx, hipMemcpyAsync(outs[a], d_out, (size_t)nseg * 24, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = a == 0 ? voxel_means(ctx, ar, d_p, n, voxel, V, &d_out, tensor_grid) : voxel_attr_means(ctx, ar, V, ins[a], n, &d_out, tensor_grid))) return rc;
+        R3D_HIP(ctx, hipMemcpyAsync(outs[a], d_out, (size_t)V.nseg * 24, hipMemcpyDeviceToHost, ctx->stream));
         R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    *out_n = nseg;
+    *out_n = V.nseg;
     return R3D_OK;
+}
+
+int r3d_voxel_downsample(r3d_ctx *ctx, const double *xyz, const double *colors, const double *normals, int64_t n, double voxel,
+                         double *out_xyz, double *out_colors, double *out_normals, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_voxel_downsample");
+    return voxel_downsample_impl(ctx, xyz, colors, normals, n, voxel, out_xyz, out_colors, out_normals, out_n, false);
+}
+
+int r3d_voxel_downsample_tensor(r3d_ctx *ctx, const double *xyz, const double *colors, const double *normals, int64_t n, double voxel,
+                                double *out_xyz, double *out_colors, double *out_normals, int64_t *out_n) {
+    R3D_ROCTX_RANGE("r3d_voxel_downsample_tensor");
+    return voxel_downsample_impl(ctx, xyz, colors, normals, n, voxel, out_xyz, out_colors, out_normals, out_n, true);
 }
 
 int r3d_estimate_normals(r3d_ctx *ctx, const double *xyz, int64_t n, double radius, int32_t max_nn, const double *prev_normals,
@@ -4551,13 +4585,10 @@ int r3d_neighbor_score(r3d_ctx *ctx, const double *xyz, int64_t n, int32_t k, do
     if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
     Grid G;
     const int kk = (int)std::min<int64_t>(std::max(k, 1), n);
-    if ((rc = grid_build(ctx, ar, d_p, n, count_radius > 0 ? count_radius : -1.0, std::max(2.0, kk / 5.0), G))) return rc;
+    if ((rc = grid_build(ctx, ar, d_p, n, count_radius > 0 ? count_radius : -1.0, knn_target_occ(kk), G))) return rc;
     double *d_s = (double *)ar.get((size_t)n * 8);
     if (ar.rc) return ar.rc;
-    const size_t lds = (size_t)kk * KNN_BLOCK * 12;
-    R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_score, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_knn_score<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, kk, count_radius, d_s);
-    R3D_HIP(ctx, hipGetLastError());
+    if ((rc = launch_knn(ctx, k_knn_score, G, n, kk, count_radius, d_s))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync(score, d_s, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
@@ -4626,11 +4657,8 @@ static int disparity_to_cloud_impl(r3d_ctx *ctx, const int16_t *d_disp, int32_t 
     if (m == 0) return R3D_OK;
     if (voxel > 0) {
         VoxelSegs V;
-        if ((rc = voxel_segments(ctx, ar, d_p, m, voxel, V, false, nullptr, nullptr, nullptr, box))) return rc;
-        double *d_v = (double *)ar.get((size_t)V.nseg * 24);
-        if (ar.rc) return ar.rc;
-        if ((rc = launch_voxel_mean(ctx, ar, false, d_p, V.idx, V.starts, V.nseg, m, d_v, V.sorted))) return rc;
-        R3D_HIP(ctx, hipGetLastError());
+        double *d_v;
+        if ((rc = voxel_means(ctx, ar, d_p, m, voxel, V, &d_v, false, nullptr, box))) return rc;
         if (color) {   // voxel colours straight from the image bytes, in the members' order (the pose does not touch colours)
             d_c = (double *)ar.get((size_t)V.nseg * 24);
             if (ar.rc) return ar.rc;
@@ -4706,40 +4734,28 @@ int r3d_align_point_clouds(r3d_ctx *ctx, const r3d_align_params *p, const double
     if (!p || !src || !tgt || !out_xyz || !out_n || !T4x4 || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "align: bad argument");
     if (src_colors && !out_colors) return r3d_fail(ctx, R3D_E_BADARG, "align: colours given without an output array");
     const r3d_icp_params *ip = &p->icp;
-    if (ip->mode < 0 || ip->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "align: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)");
-    if (!(ip->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "align: max_correspondence_distance must be > 0");
+    int rc;
+    if ((rc = icp_mode_check(ctx, "align", ip, p->normal_max_nn > 0, true, "this mode needs normals (normal_max_nn > 0)"))) return rc;
     if (p->normal_max_nn > 128) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "align: normal_max_nn > 128 not supported");
-    if (ip->mode != MODE_P2P && p->normal_max_nn <= 0) return r3d_fail(ctx, R3D_E_BADARG, "align: this mode needs normals (normal_max_nn > 0)");
     if (p->normal_max_nn > 0 && !out_normals) return r3d_fail(ctx, R3D_E_BADARG, "align: normals requested without an output array");
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
-    int rc;
     double *d_s, *d_t, *d_c = nullptr;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
     int64_t ms = ns, mt = nt;
     double tbox[6];
     const double *tgt_box = nullptr;
     if (p->voxel_size > 0) {  // pointcloud_alignment.py:22-23
-        VoxelSegs V;
-        if ((rc = voxel_segments(ctx, ar, d_s, ns, p->voxel_size, V))) return rc;
-        double *d_sv = (double *)ar.get((size_t)V.nseg * 24), *d_cv = d_c ? (double *)ar.get((size_t)V.nseg * 24) : nullptr;
-        if (ar.rc) return ar.rc;
-        if ((rc = launch_voxel_mean(ctx, ar, false, d_s, V.idx, V.starts, V.nseg, ns, d_sv, V.sorted))) return rc;
-        if (d_c) if ((rc = launch_voxel_mean(ctx, ar, false, d_c, V.idx, V.starts, V.nseg, ns, d_cv))) return rc;
-        R3D_HIP(ctx, hipGetLastError());
+        VoxelSegs V, Vt;
+        double *d_sv, *d_tv;
+        if ((rc = voxel_means(ctx, ar, d_s, ns, p->voxel_size, V, &d_sv))) return rc;
+        if (d_c && (rc = voxel_attr_means(ctx, ar, V, d_c, ns, &d_c))) return rc;
         d_s = d_sv;
-        d_c = d_cv;
         ms = V.nseg;
-        VoxelSegs Vt;
-        if ((rc = voxel_segments(ctx, ar, d_t, nt, p->voxel_size, Vt, false, nullptr, nullptr, tbox))) return rc;
+        if ((rc = voxel_means(ctx, ar, d_t, nt, p->voxel_size, Vt, &d_tv, false, tbox))) return rc;
         tgt_box = tbox;   // the search grid of the down-sampled target is laid out in the box of the target's own points (as the resident model does)
-        double *d_tv = (double *)ar.get((size_t)Vt.nseg * 24);
-        if (ar.rc) return ar.rc;
-        if ((rc = launch_voxel_mean(ctx, ar, false, d_t, Vt.idx, Vt.starts, Vt.nseg, nt, d_tv, Vt.sorted))) return rc;
-        R3D_HIP(ctx, hipGetLastError());
         d_t = d_tv;
         mt = Vt.nseg;
     }
@@ -4751,12 +4767,8 @@ int r3d_align_point_clouds(r3d_ctx *ctx, const r3d_align_params *p, const double
     double T[16];
     if ((rc = icp_core(ctx, ar, ip, d_s, ms, d_sn, d_t, mt, d_tn, init4x4, T, stats, t_begin, tgt_box, p->voxel_size > 0 ? p->voxel_size : 0))) return rc;  // :35-39
     memcpy(T4x4, T, sizeof T);
-    double *d_o = (double *)ar.get((size_t)ms * 24), *d_on = d_sn ? (double *)ar.get((size_t)ms * 24) : nullptr;
-    if (ar.rc) return ar.rc;
-    const unsigned nb = (unsigned)((ms + 255) / 256);
-    k_transform<<<nb, 256, 0, ctx->stream>>>(d_s, ms, to_rigid(T), 0, d_o);  // :42 source.transform
-    if (d_sn) k_transform<<<nb, 256, 0, ctx->stream>>>(d_sn, ms, to_rigid(T), 1, d_on);
-    R3D_HIP(ctx, hipGetLastError());
+    double *d_o, *d_on;
+    if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ms, &d_o, &d_on))) return rc;  // :42 source.transform
     R3D_HIP(ctx, hipMemcpyAsync(out_xyz, d_o, (size_t)ms * 24, hipMemcpyDeviceToHost, ctx->stream));
     if (d_sn) R3D_HIP(ctx, hipMemcpyAsync(out_normals, d_on, (size_t)ms * 24, hipMemcpyDeviceToHost, ctx->stream));
     if (d_c) R3D_HIP(ctx, hipMemcpyAsync(out_colors, d_c, (size_t)ms * 24, hipMemcpyDeviceToHost, ctx->stream));
@@ -4776,14 +4788,11 @@ int r3d_knn_graph(r3d_ctx *ctx, const double *xyz, int64_t n, int32_t k, double 
     int rc;
     if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
     Grid G;
-    if ((rc = grid_build(ctx, ar, d_p, n, radius, std::max(2.0, k / 5.0), G))) return rc;
+    if ((rc = grid_build(ctx, ar, d_p, n, radius, knn_target_occ(k), G))) return rc;
     int *d_nb = (int *)ar.get((size_t)n * k * 4);
     double *d_d2 = d2 ? (double *)ar.get((size_t)n * k * 8) : nullptr;
     if (ar.rc) return ar.rc;
-    const size_t lds = (size_t)k * KNN_BLOCK * 12;
-    R3D_HIP(ctx, hipFuncSetAttribute((const void *)k_knn_graph, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_knn_graph<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, d_nb, d_d2);
-    R3D_HIP(ctx, hipGetLastError());
+    if ((rc = launch_knn(ctx, k_knn_graph, G, n, k, radius, d_nb, d_d2))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync(nbr, d_nb, (size_t)n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (d2) R3D_HIP(ctx, hipMemcpyAsync(d2, d_d2, (size_t)n * k * 8, hipMemcpyDeviceToHost, ctx->stream));
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -4964,17 +4973,13 @@ int r3d_icp(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns
     R3D_ROCTX_RANGE("r3d_icp");
     if (!ctx) return R3D_E_BADARG;
     if (!p || !src || !tgt || !T4x4 || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "icp: bad argument");
-    if (p->mode < 0 || p->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "icp: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)");
-    if (!(p->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "icp: max_correspondence_distance must be > 0");
-    if (p->mode != MODE_P2P && !tgt_normals) return r3d_fail(ctx, R3D_E_BADARG, "icp: target normals required for this mode");
-    if (p->mode == MODE_GICP && !src_normals) return r3d_fail(ctx, R3D_E_BADARG, "icp: source normals required for GICP");
+    int rc;
+    if ((rc = icp_mode_check(ctx, "icp", p, tgt_normals != nullptr, src_normals != nullptr))) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
-    int rc;
     double *d_t, *d_tn = nullptr, *d_s, *d_sn = nullptr;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     if (src_normals && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
     if (tgt_normals && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
     return icp_core(ctx, ar, p, d_s, ns, d_sn, d_t, nt, d_tn, init4x4, T4x4, stats, t_begin);
@@ -5133,11 +5138,7 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
     static const bool always_rebuild = [] { const char *e = getenv("R3D_MODEL_IMPL"); return e && !strcmp(e, "rebuild"); }();
     if (always_rebuild) {
         VoxelSegs Vt;
-        if ((rc = voxel_segments(ctx, ar, d_t, m->n, voxel, Vt, false, nullptr, nullptr, box_out))) return rc;
-        double *d_tv = (double *)ar.get((size_t)Vt.nseg * 24);
-        if (ar.rc) return ar.rc;
-        if ((rc = launch_voxel_mean(ctx, ar, false, d_t, Vt.idx, Vt.starts, Vt.nseg, m->n, d_tv, Vt.sorted))) return rc;
-        *d_tv_out = d_tv;
+        if ((rc = voxel_means(ctx, ar, d_t, m->n, voxel, Vt, d_tv_out, false, box_out))) return rc;
         *mt_out = Vt.nseg;
         return R3D_OK;
     }
@@ -5158,17 +5159,15 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
     if (rebuild) {
         VoxelSegs Vt;
         double bounds[6];
-        if ((rc = voxel_segments(ctx, ar, d_t, m->n, voxel, Vt, false, nullptr, nullptr, bounds))) return rc;
+        if ((rc = cloud_bbox(ctx, ar, d_t, m->n, bounds, bounds + 3))) return rc;   // (the pass voxel_segments would make itself)
         for (int a = 0; a < 6; a++) box_out[a] = bounds[a];
         if (!key_space_ok(bounds, bounds + 3)) {          // more than 2^21 voxels along an axis: no table, the plain full pass
+            if ((rc = voxel_means(ctx, ar, d_t, m->n, voxel, Vt, d_tv_out, false, nullptr, bounds))) return rc;
             m->vt_valid = false;
-            double *d_tv = (double *)ar.get((size_t)Vt.nseg * 24);
-            if (ar.rc) return ar.rc;
-            if ((rc = launch_voxel_mean(ctx, ar, false, d_t, Vt.idx, Vt.starts, Vt.nseg, m->n, d_tv, Vt.sorted))) return rc;
-            *d_tv_out = d_tv;
             *mt_out = Vt.nseg;
             return R3D_OK;
         }
+        if ((rc = voxel_segments(ctx, ar, d_t, m->n, voxel, Vt, false, nullptr, nullptr, nullptr, bounds))) return rc;
         const int c = m->vt_cur;
         if ((rc = vt_reserve(m, m->vt_keys[c], Vt.nseg, 8)) || (rc = vt_reserve(m, m->vt_sums[c], Vt.nseg, 24)) || (rc = vt_reserve(m, m->vt_cnt[c], Vt.nseg, 4))) return rc;
         k_vt_build<8><<<(unsigned)((Vt.nseg + 255) / 256), 256, 0, ctx->stream>>>(Vt.sorted, Vt.starts, Vt.nseg, m->n, bounds[0] - 0.5 * voxel,
@@ -5198,13 +5197,10 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
         k_vt_update<<<nbs, 256, 0, ctx->stream>>>(V.sorted, V.starts, V.nseg, ns, org[0], org[1], org[2], voxel, (const unsigned long long *)m->vt_keys[c].p,
                                                   m->vt_n, (double *)m->vt_sums[c].p, (int *)m->vt_cnt[c].p, segkey, is_new, ins, nsum, ncnt);
         if (int src = dev_exclusive_scan<int>(ctx, ar, is_new, rank, V.nseg)) return src;
-        int last_rank = 0, last_flag = 0;
-        {
-            PinRead rd(ctx);
-            int prc;
-            if ((prc = rd.add(&last_rank, rank + (V.nseg - 1), 4)) || (prc = rd.add(&last_flag, is_new + (V.nseg - 1), 4)) || (prc = rd.wait())) return prc;
-        }
-        const int total_new = last_rank + last_flag;
+        CompactCount cc(rank, is_new, V.nseg);
+        PinRead rd(ctx);
+        if ((rc = cc.add_to(rd)) || (rc = rd.wait())) return rc;
+        const int total_new = (int)cc.count();
         if (total_new > 0) {
             k_vt_merge<<<(unsigned)((m->vt_n + V.nseg + 255) / 256), 256, 0, ctx->stream>>>(
                 (const unsigned long long *)m->vt_keys[c].p, (const double *)m->vt_sums[c].p, (const int *)m->vt_cnt[c].p, m->vt_n, segkey, is_new, rank, ins, nsum,
@@ -5230,11 +5226,8 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
 int model_align_checks(r3d_model *m, const r3d_align_params *p, const char *who) {
     r3d_ctx *ctx = m->ctx;
     if (m->n <= 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: the model is empty (append the first frame)", who);
-    const r3d_icp_params *ip = &p->icp;
-    if (ip->mode < 0 || ip->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "%s: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)", who);
-    if (!(ip->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "%s: max_correspondence_distance must be > 0", who);
+    if (int rc = icp_mode_check(ctx, who, &p->icp, p->normal_max_nn > 0, true, "this mode needs normals (normal_max_nn > 0)")) return rc;
     if (p->normal_max_nn > 128) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: normal_max_nn > 128 not supported", who);
-    if (ip->mode != MODE_P2P && p->normal_max_nn <= 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: this mode needs normals (normal_max_nn > 0)", who);
     return R3D_OK;
 }
 // the frame (d_s, optional colours d_c, ns points) is already on the device in arena `ar`
@@ -5250,14 +5243,10 @@ int model_align_core(r3d_model *m, DevArena &ar, const r3d_align_params *p, doub
     double tbox[6];
     if (p->voxel_size > 0) {  // pointcloud_alignment.py:22-23 on the frame and on the WHOLE resident model
         VoxelSegs V;
-        if ((rc = voxel_segments(ctx, ar, d_s, ns, p->voxel_size, V, false, nullptr, nullptr, nullptr, frame_box))) return rc;
-        double *d_sv = (double *)ar.get((size_t)V.nseg * 24), *d_cv = d_c ? (double *)ar.get((size_t)V.nseg * 24) : nullptr;
-        if (ar.rc) return ar.rc;
-        if ((rc = launch_voxel_mean(ctx, ar, false, d_s, V.idx, V.starts, V.nseg, ns, d_sv, V.sorted))) return rc;
-        if (d_c) if ((rc = launch_voxel_mean(ctx, ar, false, d_c, V.idx, V.starts, V.nseg, ns, d_cv))) return rc;
-        R3D_HIP(ctx, hipGetLastError());
+        double *d_sv;
+        if ((rc = voxel_means(ctx, ar, d_s, ns, p->voxel_size, V, &d_sv, false, nullptr, frame_box))) return rc;
+        if (d_c && (rc = voxel_attr_means(ctx, ar, V, d_c, ns, &d_c))) return rc;
         d_s = d_sv;
-        d_c = d_cv;
         ms = V.nseg;
         double *d_tv = nullptr;
         if ((rc = model_target_voxels(m, ar, p->voxel_size, &d_tv, &mt, tbox))) return rc;
@@ -5274,12 +5263,8 @@ int model_align_core(r3d_model *m, DevArena &ar, const r3d_align_params *p, doub
     double T[16];
     if ((rc = icp_core(ctx, ar, ip, d_s, ms, d_sn, d_t, mt, d_tn, nullptr, T, stats, t_begin, tgt_box, p->voxel_size > 0 ? p->voxel_size : 0))) return rc;  // :35-39, from identity
     memcpy(T4x4, T, sizeof T);
-    double *d_o = (double *)ar.get((size_t)ms * 24), *d_on = d_sn ? (double *)ar.get((size_t)ms * 24) : nullptr;
-    if (ar.rc) return ar.rc;
-    const unsigned nb = (unsigned)((ms + 255) / 256);
-    k_transform<<<nb, 256, 0, ctx->stream>>>(d_s, ms, to_rigid(T), 0, d_o);  // :42 source.transform
-    if (d_sn) k_transform<<<nb, 256, 0, ctx->stream>>>(d_sn, ms, to_rigid(T), 1, d_on);
-    R3D_HIP(ctx, hipGetLastError());
+    double *d_o, *d_on;
+    if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ms, &d_o, &d_on))) return rc;  // :42 source.transform
     const int64_t n_before = m->n;
     if ((rc = model_append(m, d_o, d_c, d_on, ms, hipMemcpyDeviceToDevice))) return rc;   // main.py:49 combined += aligned
     if (appended) *appended = ms;
@@ -5426,14 +5411,12 @@ int r3d_model_register_append(r3d_model *m, const r3d_icp_params *p, const doubl
     r3d_ctx *ctx = m->ctx;
     if (!p || !src || !T4x4 || ns <= 0) return r3d_fail(ctx, R3D_E_BADARG, "model_register_append: bad argument");
     if (m->n <= 0) return r3d_fail(ctx, R3D_E_BADARG, "model_register_append: the model is empty (append the first frame)");
-    if (p->mode < 0 || p->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "model_register_append: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)");
-    if (!(p->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "model_register_append: max_correspondence_distance must be > 0");
-    if (p->mode != MODE_P2P && !m->has_normals) return r3d_fail(ctx, R3D_E_BADARG, "model_register_append: the model has no normals (r3d_model_estimate_normals)");
-    if (p->mode == MODE_GICP && !src_normals) return r3d_fail(ctx, R3D_E_BADARG, "model_register_append: source normals required for GICP");
+    int rc;
+    if ((rc = icp_mode_check(ctx, "model_register_append", p, m->has_normals, src_normals != nullptr, "the model has no normals (r3d_model_estimate_normals)")))
+        return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
-    int rc;
     double *d_s, *d_c = nullptr, *d_sn = nullptr;
     if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
     if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
@@ -5442,12 +5425,8 @@ int r3d_model_register_append(r3d_model *m, const r3d_icp_params *p, const doubl
     if ((rc = icp_core(ctx, ar, p, d_s, ns, d_sn, (double *)m->pts.p, m->n, m->has_normals ? (double *)m->nrms.p : nullptr, nullptr, T, stats, t_begin)))
         return rc;                                                                     // test/GICP1.py:99-102, from identity
     memcpy(T4x4, T, sizeof T);
-    double *d_o = (double *)ar.get((size_t)ns * 24), *d_on = d_sn ? (double *)ar.get((size_t)ns * 24) : nullptr;
-    if (ar.rc) return ar.rc;
-    const unsigned nb = (unsigned)((ns + 255) / 256);
-    k_transform<<<nb, 256, 0, ctx->stream>>>(d_s, ns, to_rigid(T), 0, d_o);            // :103 source.transform
-    if (d_sn) k_transform<<<nb, 256, 0, ctx->stream>>>(d_sn, ns, to_rigid(T), 1, d_on);
-    R3D_HIP(ctx, hipGetLastError());
+    double *d_o, *d_on;
+    if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ns, &d_o, &d_on))) return rc;    // :103 source.transform
     return model_append(m, d_o, d_c, d_on, ns, hipMemcpyDeviceToDevice);               // :146 combined += aligned
 }
 
@@ -5493,10 +5472,7 @@ int r3d_icp_dev(r3d_ctx *ctx, const r3d_icp_params *p, const double *d_src, int6
     R3D_ROCTX_RANGE("r3d_icp_dev");
     if (!ctx) return R3D_E_BADARG;
     if (!p || !d_src || !d_tgt || !T4x4 || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "icp_dev: bad argument");
-    if (p->mode < 0 || p->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "icp_dev: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)");
-    if (!(p->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "icp_dev: max_correspondence_distance must be > 0");
-    if (p->mode != MODE_P2P && !d_tgt_normals) return r3d_fail(ctx, R3D_E_BADARG, "icp_dev: target normals required for this mode");
-    if (p->mode == MODE_GICP && !d_src_normals) return r3d_fail(ctx, R3D_E_BADARG, "icp_dev: source normals required for GICP");
+    if (int rc = icp_mode_check(ctx, "icp_dev", p, d_tgt_normals != nullptr, d_src_normals != nullptr)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
@@ -5561,8 +5537,7 @@ int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double 
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     double *d_t, *d_tn, *d_tc, *d_s, *d_sc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     if ((rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
     if ((rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc))) return rc;
     if ((rc = upload(ctx, ar, src_colors, ns * 3, &d_sc))) return rc;
@@ -5668,8 +5643,7 @@ int r3d_match_features(r3d_ctx *ctx, const double *src_feat, int64_t ns, const d
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t;
-    if ((rc = upload(ctx, ar, src_feat, ns * FPFH_DIM, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt_feat, nt * FPFH_DIM, &d_t))) return rc;
+    if ((rc = upload_pair(ctx, ar, src_feat, ns, tgt_feat, nt, &d_s, &d_t, FPFH_DIM))) return rc;
     int *d_nn = (int *)ar.get((size_t)ns * 4);
     double *d_d2 = d2_out ? (double *)ar.get((size_t)ns * 8) : nullptr;
     if (ar.rc) return ar.rc;
@@ -5700,14 +5674,12 @@ int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_nor
         DevArena ar(ctx);
         Grid G;
         const int k = (int)std::min<int64_t>(max_nn, n);
-        if (!(rc = grid_build(ctx, ar, d_xyz, n, radius, std::max(2.0, k / 5.0), G))) {
+        if (!(rc = grid_build(ctx, ar, d_xyz, n, radius, knn_target_occ(k), G))) {
             int *d_nb = (int *)ar.get((size_t)n * k * 4);
             double *d_d2 = (double *)ar.get((size_t)n * k * 8);
             if (!(rc = ar.rc)) {
-                const size_t lds = (size_t)k * KNN_BLOCK * 12;
-                (void)hipFuncSetAttribute((const void *)k_knn_graph, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 (void)hipEventRecord(ev[3], ctx->stream);
-                k_knn_graph<<<(unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK), KNN_BLOCK, lds, ctx->stream>>>(G.v, n, k, radius, d_nb, d_d2);
+                rc = launch_knn(ctx, k_knn_graph, G, n, k, radius, d_nb, d_d2);
                 (void)hipEventRecord(ev[4], ctx->stream);
             }
         }
@@ -5748,11 +5720,8 @@ int r3d_ransac_correspondence(r3d_ctx *ctx, const r3d_ransac_params *p, const do
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    int *d_c = (int *)ar.get((size_t)M * 8);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    int *d_c;
+    if ((rc = upload_corres_problem(ctx, ar, src, ns, tgt, nt, corres, M, &d_s, &d_t, &d_c))) return rc;
     return ransac_core(ctx, ar, p, d_s, ns, d_t, nt, d_c, M, T4x4, nullptr, inlier_mask, stats, t_begin);
 }
 
@@ -5768,11 +5737,8 @@ int r3d_debug_ransac_hypotheses(r3d_ctx *ctx, const r3d_ransac_params *p, const 
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    int *d_c = (int *)ar.get((size_t)M * 8);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    int *d_c;
+    if ((rc = upload_corres_problem(ctx, ar, src, ns, tgt, nt, corres, M, &d_s, &d_t, &d_c))) return rc;
     RansacWork W;
     const int n = (int)count;
     if ((rc = ransac_setup(ctx, ar, d_s, ns, d_t, nt, d_c, M, n, true, W))) return rc;
@@ -5833,11 +5799,8 @@ int r3d_fgr_correspondence(r3d_ctx *ctx, const r3d_fgr_params *p, const double *
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    int *d_c = (int *)ar.get((size_t)M * 8);
-    if (ar.rc) return ar.rc;
-    if (M > 0) R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    int *d_c;
+    if ((rc = upload_corres_problem(ctx, ar, src, ns, tgt, nt, corres, M, &d_s, &d_t, &d_c))) return rc;
     return fgr_core(ctx, ar, p, d_s, ns, d_t, nt, d_c, M, nullptr, nullptr, T4x4, stats, t_begin);
 }
 
@@ -5867,10 +5830,8 @@ int r3d_fgr_feature_matching(r3d_ctx *ctx, const r3d_fgr_params *p, const double
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t, *d_sf, *d_tf;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    if ((rc = upload(ctx, ar, src_feat, ns * FPFH_DIM, &d_sf))) return rc;
-    if ((rc = upload(ctx, ar, tgt_feat, nt * FPFH_DIM, &d_tf))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
+    if ((rc = upload_pair(ctx, ar, src_feat, ns, tgt_feat, nt, &d_sf, &d_tf, FPFH_DIM))) return rc;
     return fgr_core(ctx, ar, p, d_s, ns, d_t, nt, nullptr, 0, d_sf, d_tf, T4x4, stats, t_begin);
 }
 
@@ -5886,11 +5847,8 @@ int r3d_debug_fgr_tuples(r3d_ctx *ctx, const r3d_fgr_params *p, const double *sr
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    int *d_c = (int *)ar.get((size_t)M * 8);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    int *d_c;
+    if ((rc = upload_corres_problem(ctx, ar, src, ns, tgt, nt, corres, M, &d_s, &d_t, &d_c))) return rc;
     FgrNorm nm;
     double scale_start, *rows;
     if ((rc = fgr_normalise(ctx, ar, d_s, ns, d_t, nt, p->use_absolute_scale != 0, nm, &scale_start))) return rc;
@@ -5917,11 +5875,8 @@ int r3d_debug_fgr_optimize(r3d_ctx *ctx, const r3d_fgr_params *p, const double *
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    int *d_c = (int *)ar.get((size_t)M * 8);
-    if (ar.rc) return ar.rc;
-    if (M > 0) R3D_HIP(ctx, hipMemcpyAsync(d_c, pairs, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
+    int *d_c;
+    if ((rc = upload_corres_problem(ctx, ar, src, ns, tgt, nt, pairs, M, &d_s, &d_t, &d_c))) return rc;
     FgrNorm nm;
     double scale_start, *rows, trans[16], final_par;
     if ((rc = fgr_normalise(ctx, ar, d_s, ns, d_t, nt, p->use_absolute_scale != 0, nm, &scale_start))) return rc;
@@ -6018,8 +5973,7 @@ extern "C" int r3d_debug_icp_correspondences(r3d_ctx *ctx, const double *src, in
     DevArena ar(ctx);
     int rc;
     double *d_t, *d_s;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     r3d_icp_params p = {};
     p.mode = MODE_P2P;
     p.max_correspondence_distance = max_correspondence_distance;
@@ -6036,17 +5990,13 @@ extern "C" int r3d_debug_icp_sums(r3d_ctx *ctx, const r3d_icp_params *p, const d
     R3D_ROCTX_RANGE("r3d_debug_icp_sums");
     if (!ctx) return R3D_E_BADARG;
     if (!p || !src || !tgt || !sums_out || ns <= 0 || nt <= 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: bad argument");
-    if (p->mode < 0 || p->mode > 2) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: mode must be 0 (P2P), 1 (P2PLANE) or 2 (GICP)");
-    if (!(p->max_correspondence_distance > 0)) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: max_correspondence_distance must be > 0");
-    if (p->mode != MODE_P2P && !tgt_normals) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: target normals required for this mode");
-    if (p->mode == MODE_GICP && !src_normals) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums: source normals required for GICP");
+    int rc;
+    if ((rc = icp_mode_check(ctx, "debug_icp_sums", p, tgt_normals != nullptr, src_normals != nullptr))) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    int rc;
     double *d_t, *d_s, *d_tn = nullptr, *d_sn = nullptr;
-    if ((rc = upload(ctx, ar, tgt, nt * 3, &d_t))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     if (p->mode != MODE_P2P && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
     if (p->mode == MODE_GICP && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
     double T[16];
     const IcpReadout ro = {nullptr, nullptr, sums_out, origin_out};
