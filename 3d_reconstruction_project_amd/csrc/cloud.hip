@@ -1090,7 +1090,13 @@ struct IcpColor {
 };
 
 struct Rigid { double r[9], t[3]; };
-// the point the point-to-point slots are relative to: the centre of the target grid's box (icp_core)
+// p = T s as the registration forms it: ((r0 sx + r1 sy) + r2 sz) + t per row
+__device__ __forceinline__ void rigid_apply(const Rigid &T, double sx, double sy, double sz, double &px, double &py, double &pz) {
+    px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
+    py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
+    pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
+}
+// the point the point-to-point slots are relative to: the centre of the target grid's box (icp_setup)
 struct IcpOrigin { double x, y, z; };
 
 // Device-resident state of one registration loop: the evaluation kernels read the pose from here and k_icp_step advances it,
@@ -1932,10 +1938,8 @@ __global__ void __launch_bounds__(ICP_BLOCK, SEARCH == SEARCH_Q10_DEEP ? 2 : 3) 
     for (int64_t c = c_begin; c < c_end; c += c_step) {
         const int64_t i = c * ICP_BLOCK + threadIdx.x;
         if (i >= ns) continue;
-        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
-        const double px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
-        const double py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
-        const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
+        double px, py, pz;
+        rigid_apply(T, src[i * 3], src[i * 3 + 1], src[i * 3 + 2], px, py, pz);
         const int cx = cell_coord(px, g.ox, g.inv_cell), cy = cell_coord(py, g.oy, g.inv_cell), cz = cell_coord(pz, g.oz, g.inv_cell);
         double best = r2;
         int bi = -1;
@@ -1973,10 +1977,8 @@ __global__ void __launch_bounds__(256) k_icp_corr_readout(const double *__restri
     const int c = corr[i];
     double d2 = 1e300;
     if (c >= 0) {
-        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
-        const double px = T.r[0] * sx + T.r[1] * sy + T.r[2] * sz + T.t[0];
-        const double py = T.r[3] * sx + T.r[4] * sy + T.r[5] * sz + T.t[1];
-        const double pz = T.r[6] * sx + T.r[7] * sy + T.r[8] * sz + T.t[2];
+        double px, py, pz;
+        rigid_apply(T, src[i * 3], src[i * 3 + 1], src[i * 3 + 2], px, py, pz);
         const double dx = tgt[(int64_t)c * 3] - px, dy = tgt[(int64_t)c * 3 + 1] - py, dz = tgt[(int64_t)c * 3 + 2] - pz;
         d2 = dx * dx + dy * dy + dz * dz;
     }
@@ -2000,10 +2002,7 @@ __global__ void __launch_bounds__(256) k_transform_dn(const double *__restrict__
                                                       double *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)*c0 + *c1) return;
-    const double x = in[i * 3], y = in[i * 3 + 1], z = in[i * 3 + 2];
-    out[i * 3] = T.r[0] * x + T.r[1] * y + T.r[2] * z + T.t[0];
-    out[i * 3 + 1] = T.r[3] * x + T.r[4] * y + T.r[5] * z + T.t[1];
-    out[i * 3 + 2] = T.r[6] * x + T.r[7] * y + T.r[8] * z + T.t[2];
+    rigid_apply(T, in[i * 3], in[i * 3 + 1], in[i * 3 + 2], out[i * 3], out[i * 3 + 1], out[i * 3 + 2]);
 }
 
 // several blocks of triplets, each with its own rigid transform, in ONE launch (the fuse step of the multi-view exchange: eight
@@ -2325,6 +2324,15 @@ static inline int launch_voxel_mean(r3d_ctx *ctx, DevArena &ar, bool f32, const 
 template <class F>
 static inline auto with_keys(bool keys32, const void *keys, F &&f) {
     return keys32 ? f((const unsigned *)keys) : f((const unsigned long long *)keys);
+}
+// A run-time value as a template argument: calls the generic `f` with std::integral_constant<int, V> for the first V of the list
+// that equals v, with the last one if none does
+template <int V, int... Vs, class F>
+static inline void with_const(int v, F &&f) {
+    if constexpr (sizeof...(Vs) > 0) {
+        if (v != V) return with_const<Vs...>(v, f);
+    }
+    f(std::integral_constant<int, V>{});
 }
 
 struct Grid {
@@ -4019,167 +4027,205 @@ int match_core(r3d_ctx *ctx, DevArena &ar, const double *d_src, int64_t ns, cons
     return R3D_OK;
 }
 
-// r3d_debug_icp_correspondences' output (host arrays, the caller's numbering)
-// r3d_debug_icp_sums' output: `sums` set (host, [29]) selects that read-out instead, `origin` (host, [3]) goes with it
-struct IcpReadout { int32_t *corr; double *d2; double *sums; double *origin; };
 // the coloured mode's extra inputs (device colours of both clouds) and parameters, resolved by the entry point
 struct IcpColorInput { const double *d_sc, *d_tc; double lambda, radius; int max_nn; };
+// What a registration runs on: clouds that are already in device memory (d_sn / d_tn may be null where the mode allows it).
+// The call sites name what they set; the rest is zero.
+struct IcpInput {
+    const double *d_s; int64_t ns; const double *d_sn;   // the source and its normals
+    const double *d_t; int64_t nt; const double *d_tn;   // the target and its normals
+    const double *init4x4;         // the initial pose (null: the identity)
+    const double *tgt_enclosing;   // optional: grid_build's `enclosing`
+    double tgt_spacing;            // optional: grid_build's `spacing_hint`, the voxel size the target was down-sampled with
+    const IcpColorInput *color;    // MODE_COLORED (and only then)
+};
+// What icp_setup leaves for the evaluations, the loop and the two read-outs (the device buffers belong to the call's arena)
+struct IcpWork {
+    Grid G;                            // the target's search grid (G.v) and its box
+    IcpOrigin org;                     // the point the point-to-point slots are relative to: the centre of that box
+    int64_t ns;
+    double *d_s, *d_sn, *d_tns;        // the source and its normals in Morton order, the target's normals in cell-sorted order
+    int *sidx;                         // the permutation that sorted the source
+    IcpColor colk;
+    double *d_part;
+    IcpState *d_st, *hst, *d_mirror;   // hst is pinned and mapped: k_icp_step publishes the state there (d_mirror), the host polls it
+    int nblocks, search;
+};
 
-// ICP / point-to-plane / GICP loop on clouds that are already in device memory (d_sn / d_tn may be null where the mode
-// allows it); everything below r3d_icp's argument checks and uploads
-static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double *d_s, int64_t ns, double *d_sn, double *d_t, int64_t nt,
-                    double *d_tn, const double *init4x4, double *T4x4, r3d_icp_stats *stats,
-                    std::chrono::steady_clock::time_point t_begin, const double *tgt_enclosing = nullptr /* grid_build's `enclosing` */,
-                    double tgt_spacing = 0 /* grid_build's `spacing_hint`: voxel size the target was down-sampled with */,
-                    const IcpReadout *readout = nullptr /* r3d_debug_icp_correspondences: one evaluation at the initial pose, no loop */,
-                    const IcpColorInput *color = nullptr /* MODE_COLORED (and only then) */) {
+// The search form of a registration's evaluations.  The default is the packed search (nn_block_q10).  Its cell-relative
+// quantisation needs (p - origin) / cell exact to well below 1/1024: a cloud whose coordinates are that large against its cell
+// keeps the all-float64 search (nn_block_global), and R3D_ICP_IMPL=exact asks for it on any cloud (the tests' oracle); any other
+// value is ignored.  Of the packed forms, small source clouds (at most two workgroups per CU: every gather of the scan is a full
+// round trip) take the one that keeps three candidate groups in flight; R3D_ICP_DEEP=0 / 1 forces either form (A/B)
+static int icp_search_form(const Grid &G, double max_dist, int64_t ns, int cus) {
+    static const int deep_env = [] { const char *e = getenv("R3D_ICP_DEEP"); return !e ? -1 : atoi(e) != 0; }();
+    const char *ie = getenv("R3D_ICP_IMPL");
+    const bool want_exact = ie && strcmp(ie, "exact") == 0;
+    double M = 0;
+    for (int a = 0; a < 3; a++) M = std::max(M, std::max(std::fabs(G.mn[a]), std::fabs(G.mx[a])));
+    const double Mq = M + 2.0 * max_dist + G.v.cell;
+    if (want_exact || !(Mq / G.v.cell < 1e9)) return SEARCH_EXACT;
+    const bool deep_search = deep_env >= 0 ? deep_env == 1 : ns <= (int64_t)ICP_BLOCK * std::max(cus, 1) * 2;
+    return deep_search ? SEARCH_Q10_DEEP : SEARCH_Q10;
+}
+
+// Set-up of a registration: everything between the entry point's argument checks and uploads and the first evaluation
+static int icp_setup(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, const IcpInput &in, IcpWork &w) {
+    const int64_t ns = in.ns, nt = in.nt;
+    const IcpColorInput *const color = in.color;
+    Grid &G = w.G;
     int rc;
     // coloured mode: the target's intensities and gradients, once per call (a search grid of its own: the radius differs)
     double *d_trec = nullptr;
-    if (color && (rc = color_gradients_core(ctx, ar, d_t, nt, d_tn, color->d_tc, color->radius, color->max_nn, &d_trec))) return rc;
-    Grid G;
+    if (color && (rc = color_gradients_core(ctx, ar, in.d_t, nt, in.d_tn, color->d_tc, color->radius, color->max_nn, &d_trec))) return rc;
     double occ = 3.0;   // points per occupied cell the search grid aims at (R3D_ICP_OCC: A/B)
     if (const char *oe = getenv("R3D_ICP_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 64) occ = v; }
-    if ((rc = grid_build(ctx, ar, d_t, nt, p->max_correspondence_distance, occ, G, true, tgt_enclosing, tgt_spacing))) return rc;   // dense table: one load per row in the loop
-    // packed copy of the target for the default search (nn_block_q10).  Its cell-relative quantisation needs (p - origin) / cell
-    // exact to well below 1/1024: a cloud whose coordinates are that large against its cell keeps the all-float64 search
-    // (nn_block_global), and R3D_ICP_IMPL=exact asks for it on any cloud (the tests' oracle); any other value is ignored
-    {
-        const char *ie = getenv("R3D_ICP_IMPL");
-        const bool want_exact = ie && strcmp(ie, "exact") == 0;
-        double M = 0;
-        for (int a = 0; a < 3; a++) M = std::max(M, std::max(std::fabs(G.mn[a]), std::fabs(G.mx[a])));
-        const double Mq = M + 2.0 * p->max_correspondence_distance + G.v.cell;
-        if (!want_exact && Mq / G.v.cell < 1e9) {
-            unsigned *q = (unsigned *)ar.get((size_t)(nt + 4) * sizeof(unsigned));
-            if (ar.rc) return ar.rc;
-            G.v.q10 = q;
-            G.v.pool = 1;
-            k_pack_q10<<<(unsigned)((nt + 4 + 255) / 256), 256, 0, ctx->stream>>>(G.v, nt, q);
-            R3D_HIP(ctx, hipGetLastError());
-        }
-    }
-    double *d_tns = nullptr;
-    if (d_tn) {
-        d_tns = (double *)ar.get((size_t)nt * 24);
+    if ((rc = grid_build(ctx, ar, in.d_t, nt, p->max_correspondence_distance, occ, G, true, in.tgt_enclosing, in.tgt_spacing))) return rc;   // dense table: one load per row in the loop
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    w.search = icp_search_form(G, p->max_correspondence_distance, ns, cus);
+    if (w.search != SEARCH_EXACT) {   // packed copy of the target for nn_block_q10
+        unsigned *q = (unsigned *)ar.get((size_t)(nt + 4) * sizeof(unsigned));
         if (ar.rc) return ar.rc;
-        k_gather3<<<(unsigned)((nt + 255) / 256), 256, 0, ctx->stream>>>(d_tn, G.v.idx, nt, d_tns);
+        G.v.q10 = q;
+        G.v.pool = 1;
+        k_pack_q10<<<(unsigned)((nt + 4 + 255) / 256), 256, 0, ctx->stream>>>(G.v, nt, q);
+        R3D_HIP(ctx, hipGetLastError());
     }
-    IcpColor colk = {};
+    w.d_tns = nullptr;
+    if (in.d_tn) {
+        w.d_tns = (double *)ar.get((size_t)nt * 24);
+        if (ar.rc) return ar.rc;
+        k_gather3<<<(unsigned)((nt + 255) / 256), 256, 0, ctx->stream>>>(in.d_tn, G.v.idx, nt, w.d_tns);
+    }
+    w.colk = {};
     if (color) {
         double *d_trecs = (double *)ar.get((size_t)nt * 32);
         if (ar.rc) return ar.rc;
         k_gather4<<<(unsigned)((nt + 255) / 256), 256, 0, ctx->stream>>>(d_trec, G.v.idx, nt, d_trecs);
-        colk.tgt_ig = d_trecs;
-        colk.sg = std::sqrt(color->lambda);
-        colk.sp = std::sqrt(1.0 - color->lambda);
+        w.colk.tgt_ig = d_trecs;
+        w.colk.sg = std::sqrt(color->lambda);
+        w.colk.sp = std::sqrt(1.0 - color->lambda);
     }
     // spatially sort the source once (Morton order of the target-grid cell of its initial pose) so that neighbouring threads
     // walk the same cells; sums are order-dependent only at the 1e-16 level and stay deterministic
     double T[16];
-    if (init4x4) memcpy(T, init4x4, sizeof T);
+    if (in.init4x4) memcpy(T, in.init4x4, sizeof T);
     else for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0);
-    int *sidx;
-    {
-        double *d_s0 = (double *)ar.get((size_t)ns * 24);
+    double *d_s0 = (double *)ar.get((size_t)ns * 24);
+    if (ar.rc) return ar.rc;
+    k_transform<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(in.d_s, ns, to_rigid(T), 0, d_s0);
+    int dims[3] = {G.v.nx, G.v.ny, G.v.nz};
+    void *sk;
+    bool sk32;
+    if ((rc = sort_by_cell(ctx, ar, d_s0, ns, G.mn, G.v.cell, dims, 2, &sk, &sk32, &w.sidx))) return rc;
+    w.d_s = (double *)ar.get((size_t)ns * 24);
+    if (ar.rc) return ar.rc;
+    k_gather3<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(in.d_s, w.sidx, ns, w.d_s);
+    w.d_sn = nullptr;
+    if (in.d_sn) {
+        w.d_sn = (double *)ar.get((size_t)ns * 24);
         if (ar.rc) return ar.rc;
-        k_transform<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(d_s, ns, to_rigid(T), 0, d_s0);
-        int dims[3] = {G.v.nx, G.v.ny, G.v.nz};
-        void *sk;
-        bool sk32;
-        if ((rc = sort_by_cell(ctx, ar, d_s0, ns, G.mn, G.v.cell, dims, 2, &sk, &sk32, &sidx))) return rc;
-        double *d_ss = (double *)ar.get((size_t)ns * 24);
+        k_gather3<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(in.d_sn, w.sidx, ns, w.d_sn);
+    }
+    if (color) {
+        double *d_si = (double *)ar.get((size_t)ns * 8);
         if (ar.rc) return ar.rc;
-        k_gather3<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(d_s, sidx, ns, d_ss);
-        d_s = d_ss;
-        if (d_sn) {
-            double *d_sns = (double *)ar.get((size_t)ns * 24);
-            if (ar.rc) return ar.rc;
-            k_gather3<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(d_sn, sidx, ns, d_sns);
-            d_sn = d_sns;
-        }
-        if (color) {
-            double *d_si = (double *)ar.get((size_t)ns * 8);
-            if (ar.rc) return ar.rc;
-            k_intensity<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(color->d_sc, sidx, ns, d_si);
-            colk.src_i = d_si;
-        }
+        k_intensity<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(color->d_sc, w.sidx, ns, d_si);
+        w.colk.src_i = d_si;
     }
     // one residency of the chip (3 workgroups per CU at the kernel's register count): every wave starts at once, walks its share
     // of the queries in a grid-stride loop and pays the 29-slot reduction once
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const int nblocks = (int)std::min<int64_t>((ns + ICP_BLOCK - 1) / ICP_BLOCK, (int64_t)std::max(cus, 1) * 3);
-    double *d_part = (double *)ar.get((size_t)nblocks * ICP_SLOTS * 8);
-    IcpState *d_st = (IcpState *)ar.get(sizeof(IcpState));
+    w.ns = ns;
+    w.nblocks = (int)std::min<int64_t>((ns + ICP_BLOCK - 1) / ICP_BLOCK, (int64_t)std::max(cus, 1) * 3);
+    w.d_part = (double *)ar.get((size_t)w.nblocks * ICP_SLOTS * 8);
+    w.d_st = (IcpState *)ar.get(sizeof(IcpState));
     if (ar.rc) return ar.rc;
-    // small source clouds (at most two workgroups per CU: every gather of the scan is a full round trip) take the search form
-    // that keeps three candidate groups in flight; R3D_ICP_DEEP=0 / 1 forces either form (A/B)
-    static const int deep_env = [] { const char *e = getenv("R3D_ICP_DEEP"); return !e ? -1 : atoi(e) != 0; }();
-    const bool deep_search = deep_env >= 0 ? deep_env == 1 : ns <= (int64_t)ICP_BLOCK * std::max(cus, 1) * 2;
-    const int search = !G.v.q10 ? SEARCH_EXACT : deep_search ? SEARCH_Q10_DEEP : SEARCH_Q10;
     static_assert(sizeof(IcpState) <= ICP_SLOTS * sizeof(double), "the pinned landing buffer holds one IcpState");
     if (!ctx->icp_host) R3D_HIP(ctx, hipHostMalloc((void **)&ctx->icp_host, ICP_SLOTS * sizeof(double), hipHostMallocMapped));
-    IcpState *hst = (IcpState *)ctx->icp_host;   // pinned and mapped: k_icp_step publishes the state here, the host polls it
-    IcpState *d_mirror = nullptr;
-    R3D_HIP(ctx, hipHostGetDevicePointer((void **)&d_mirror, hst, 0));
-    memset(hst, 0, sizeof *hst);
-    memcpy(hst->T, T, sizeof T);
-    R3D_HIP(ctx, hipMemcpyAsync(d_st, hst, sizeof *hst, hipMemcpyHostToDevice, ctx->stream));
-    const int max_it = p->max_iteration;
+    w.hst = (IcpState *)ctx->icp_host;   // pinned and mapped: k_icp_step publishes the state here, the host polls it
+    w.d_mirror = nullptr;
+    R3D_HIP(ctx, hipHostGetDevicePointer((void **)&w.d_mirror, w.hst, 0));
+    memset(w.hst, 0, sizeof *w.hst);
+    memcpy(w.hst->T, T, sizeof T);
+    R3D_HIP(ctx, hipMemcpyAsync(w.d_st, w.hst, sizeof *w.hst, hipMemcpyHostToDevice, ctx->stream));
     // what the point-to-point moments are relative to: a fixed point both clouds are near (the paired sources lie within the
     // distance of the target's box)
-    const IcpOrigin org = {0.5 * (G.mn[0] + G.mx[0]), 0.5 * (G.mn[1] + G.mx[1]), 0.5 * (G.mn[2] + G.mx[2])};
-    // one evaluation + one step of the loop, enqueued without waiting (both return at once when the loop has ended)
-    // (`corr`: the read-out's one evaluation -- the kernel's optional output, and no step behind it; the loop passes nullptr)
-    auto enqueue_eval = [&](bool publish, int *corr = nullptr) {
-        const double eps = p->gicp_epsilon > 0 ? p->gicp_epsilon : 1e-3;
-        const double md = p->max_correspondence_distance;
-        // one kernel per search form x mode
-#define R3D_ICP_LAUNCH(M, S) k_icp_eval<M, S><<<nblocks, ICP_BLOCK, 0, ctx->stream>>>(G.v, d_s, d_sn, d_tns, ns, d_st, md, eps, d_part, corr, colk, org)
-#define R3D_ICP_MODES(S)                                            \
-    switch (p->mode) {                                              \
-        case MODE_P2P: R3D_ICP_LAUNCH(MODE_P2P, S); break;          \
-        case MODE_P2PLANE: R3D_ICP_LAUNCH(MODE_P2PLANE, S); break;  \
-        case MODE_COLORED: R3D_ICP_LAUNCH(MODE_COLORED, S); break;  \
-        default: R3D_ICP_LAUNCH(MODE_GICP, S); break;               \
-    }
-        switch (search) {
-            case SEARCH_Q10_DEEP: R3D_ICP_MODES(SEARCH_Q10_DEEP) break;
-            case SEARCH_Q10: R3D_ICP_MODES(SEARCH_Q10) break;
-            default: R3D_ICP_MODES(SEARCH_EXACT) break;
+    w.org = {0.5 * (G.mn[0] + G.mx[0]), 0.5 * (G.mn[1] + G.mx[1]), 0.5 * (G.mn[2] + G.mx[2])};
+    return R3D_OK;
+}
+
+// one evaluation of the loop, enqueued without waiting (it returns at once when the loop has ended): one kernel per search form x
+// mode.  `corr`: the kernel's optional output (the read-outs'; the loop passes nullptr)
+static void icp_enqueue_eval(r3d_ctx *ctx, const r3d_icp_params *p, const IcpWork &w, int *corr) {
+    const double eps = p->gicp_epsilon > 0 ? p->gicp_epsilon : 1e-3;
+    const double md = p->max_correspondence_distance;
+    with_const<SEARCH_Q10_DEEP, SEARCH_Q10, SEARCH_EXACT>(w.search, [&](auto search) {
+        with_const<MODE_P2P, MODE_P2PLANE, MODE_COLORED, MODE_GICP>(p->mode, [&](auto mode) {
+            k_icp_eval<decltype(mode)::value, decltype(search)::value><<<w.nblocks, ICP_BLOCK, 0, ctx->stream>>>(
+                w.G.v, w.d_s, w.d_sn, w.d_tns, w.ns, w.d_st, md, eps, w.d_part, corr, w.colk, w.org);
+        });
+    });
+}
+
+// r3d_debug_icp_sums' read-out (host: sums [29], origin [3] or null): the loop's own evaluation, then k_icp_step's reduction of
+// its partial sums
+static int icp_read_sums(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, const IcpWork &w, double *sums, double *origin) {
+    int *d_corr = (int *)ar.get((size_t)w.ns * 4);
+    double *d_sums = (double *)ar.get(ICP_SLOTS * 8);
+    if (ar.rc) return ar.rc;
+    icp_enqueue_eval(ctx, p, w, d_corr);
+    k_icp_sums_readout<<<1, 1024, 0, ctx->stream>>>(w.d_part, w.nblocks, d_sums);
+    R3D_HIP(ctx, hipGetLastError());
+    R3D_HIP(ctx, hipMemcpyAsync(sums, d_sums, ICP_SLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (origin) { origin[0] = w.org.x; origin[1] = w.org.y; origin[2] = w.org.z; }
+    return R3D_OK;
+}
+// r3d_debug_icp_correspondences' read-out (host arrays in the caller's numbering, d2 may be null): one evaluation at the initial
+// pose; d_t is the target in the caller's order
+static int icp_read_correspondences(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, const IcpWork &w, const double *d_t, int32_t *corr,
+                                    double *d2) {
+    const int64_t ns = w.ns;
+    int *d_corr = (int *)ar.get((size_t)ns * 4), *d_corr_out = (int *)ar.get((size_t)ns * 4);
+    double *d_d2_out = (double *)ar.get((size_t)ns * 8);
+    if (ar.rc) return ar.rc;
+    icp_enqueue_eval(ctx, p, w, d_corr);
+    k_icp_corr_readout<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(w.d_s, w.sidx, ns, w.d_st, d_t, d_corr, d_corr_out, d_d2_out);
+    R3D_HIP(ctx, hipGetLastError());
+    R3D_HIP(ctx, hipMemcpyAsync(corr, d_corr_out, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (d2) R3D_HIP(ctx, hipMemcpyAsync(d2, d_d2_out, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+// Bounded wait for the state k_icp_step publishes in the mapped host buffer (`seq` reaches `need`, or the DONE bit: `loop_done`).  A
+// tight spin for the first 200 us (a batch of a small cloud is shorter than a sleep), then the thread yields between
+// polls.  The deadline scales with the work enqueued (serialised counter passes are ~100x slower than a plain run); on
+// expiry the call fails with the last state read so the caller exits non-zero.
+static int icp_poll(r3d_ctx *ctx, const IcpState *hst, int need, int enq, double deadline_s, bool &loop_done) {
+    const auto t_poll = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; spins++) {
+        // `seq` is the last word k_icp_step stores, behind a system-scope fence: once it shows the awaited step, or the
+        // DONE bit, every other field of that step is visible
+        const int seq = *(volatile const int *)&hst->seq;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if ((seq & ~ICP_SEQ_DONE) >= need || (seq & ICP_SEQ_DONE)) { loop_done = (seq & ICP_SEQ_DONE) != 0; return R3D_OK; }
+        if ((spins & 63) != 63) continue;
+        const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count();
+        if (waited > deadline_s) {
+            ctx->poisoned = true;   // the batch is still queued on arena buffers: no later call may reuse them
+            return r3d_fail(ctx, R3D_E_HIP, "registration loop: no completion after %.0f s (%d evaluations enqueued, last state read: %d evaluations, done=%d)",
+                            waited, enq, hst->evals, hst->done);
         }
-#undef R3D_ICP_MODES
-#undef R3D_ICP_LAUNCH
-        if (corr) return;
-        k_icp_step<<<1, 1024, 0, ctx->stream>>>(d_part, nblocks, d_st, ns, p->mode, max_it, p->relative_fitness, p->relative_rmse, d_mirror,
-                                                publish ? 1 : 0, org);
-    };
-    if (readout && readout->sums) {
-        // the loop's own evaluation (no correspondence output), then k_icp_step's reduction of its partial sums
-        int *d_corr = (int *)ar.get((size_t)ns * 4);   // enqueue_eval skips the step only when it is given this buffer
-        double *d_sums = (double *)ar.get(ICP_SLOTS * 8);
-        if (ar.rc) return ar.rc;
-        enqueue_eval(false, d_corr);
-        k_icp_sums_readout<<<1, 1024, 0, ctx->stream>>>(d_part, nblocks, d_sums);
-        R3D_HIP(ctx, hipGetLastError());
-        R3D_HIP(ctx, hipMemcpyAsync(readout->sums, d_sums, ICP_SLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
-        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (readout->origin) { readout->origin[0] = org.x; readout->origin[1] = org.y; readout->origin[2] = org.z; }
-        return R3D_OK;
+        if (waited > 2e-4) std::this_thread::sleep_for(std::chrono::microseconds(waited > 5e-3 ? 200 : 20));
     }
-    if (readout) {
-        int *d_corr = (int *)ar.get((size_t)ns * 4), *d_corr_out = (int *)ar.get((size_t)ns * 4);
-        double *d_d2_out = (double *)ar.get((size_t)ns * 8);
-        if (ar.rc) return ar.rc;
-        enqueue_eval(false, d_corr);
-        k_icp_corr_readout<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(d_s, sidx, ns, d_st, d_t, d_corr, d_corr_out, d_d2_out);
-        R3D_HIP(ctx, hipGetLastError());
-        R3D_HIP(ctx, hipMemcpyAsync(readout->corr, d_corr_out, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (readout->d2) R3D_HIP(ctx, hipMemcpyAsync(readout->d2, d_d2_out, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
-        R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return R3D_OK;
-    }
+}
+
+// The loop of a registration on icp_setup's work record: the final pose to T4x4, the loop's figures to `stats` (may be null)
+static int icp_loop(r3d_ctx *ctx, const r3d_icp_params *p, const IcpWork &w, int64_t nt, double *T4x4, r3d_icp_stats *stats,
+                    std::chrono::steady_clock::time_point t_begin) {
+    const IcpState *const hst = w.hst;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const auto t_loop = std::chrono::steady_clock::now();
     // The loop of RegistrationICP (evaluate, test, update) runs on the device; the host enqueues ICP_BATCH evaluations at a
@@ -4195,59 +4241,38 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
     // served" loops of shared boxes were the device running dry behind a descheduled host; evaluations behind the step that ends
     // the loop return at their first instruction (at most 24 x ~8 us).  R3D_ICP_WINDOW=<batch> overrides (stride = batch / 2).
     static const int win_env = [] { const char *e = getenv("R3D_ICP_WINDOW"); const int v = e ? atoi(e) : 0; return v < 2 ? 0 : (v > 256 ? 256 : v); }();
-    const bool big = ns >= 500000;
+    const bool big = w.ns >= 500000;
     const int ICP_BATCH = win_env ? win_env : big ? 24 : 8, ICP_STRIDE = win_env ? std::max(win_env / 2, 1) : big ? 8 : 4;
+    const double deadline_s = 20.0 + 2e-6 * (double)(w.ns + nt) * ICP_BATCH;
     bool loop_done = false;
-    const int total = max_it + 1;
-    for (int enq = 0; enq < total;) {
+    const int total = p->max_iteration + 1;
+    for (int enq = 0; enq < total && !loop_done;) {
         for (int b = 0, nb = enq == 0 ? ICP_BATCH : ICP_STRIDE; b < nb && enq < total; b++, enq++) {
             // a step publishes its state to the host mirror (~20 posted writes and a system-scope fence) only if the host will WAIT
             // for it: the last one, and the steps `need` below names (ICP_BATCH - ICP_STRIDE, then every ICP_STRIDE-th, while more
             // evaluations remain to be enqueued behind them); a step that ENDS the loop publishes by itself
             const int sno = enq + 1, first_need = ICP_BATCH - ICP_STRIDE;
             const bool awaited = sno == total || (sno >= first_need && (sno - first_need) % ICP_STRIDE == 0 && sno + ICP_STRIDE < total);
-            enqueue_eval(awaited);
+            icp_enqueue_eval(ctx, p, w, nullptr);   // the evaluation and its step both return at once when the loop has ended
+            k_icp_step<<<1, 1024, 0, ctx->stream>>>(w.d_part, w.nblocks, w.d_st, w.ns, p->mode, p->max_iteration, p->relative_fitness, p->relative_rmse,
+                                                    w.d_mirror, awaited ? 1 : 0, w.org);
         }
         R3D_HIP(ctx, hipGetLastError());
         // evaluations that must have been consumed before the host goes on: everything at the end, all but the last ICP_STRIDE
         // otherwise
         const int need = enq >= total ? enq : enq - ICP_STRIDE;
-        // Bounded wait for the state k_icp_step publishes in the mapped host buffer (`seq` reaches `need`, or the DONE bit).  A
-        // tight spin for the first 200 us (a batch of a small cloud is shorter than a sleep), then the thread yields between
-        // polls.  The deadline scales with the work enqueued (serialised counter passes are ~100x slower than a plain run); on
-        // expiry the call fails with the last state read so the caller exits non-zero.
-        const auto t_poll = std::chrono::steady_clock::now();
-        const double deadline_s = 20.0 + 2e-6 * (double)(ns + nt) * ICP_BATCH;
-        for (unsigned spins = 0;; spins++) {
-            // `seq` is the last word k_icp_step stores, behind a system-scope fence: once it shows the awaited step, or the
-            // DONE bit, every other field of that step is visible
-            const int seq = *(volatile int *)&hst->seq;
-            std::atomic_thread_fence(std::memory_order_acquire);
-            if ((seq & ~ICP_SEQ_DONE) >= need || (seq & ICP_SEQ_DONE)) { loop_done = (seq & ICP_SEQ_DONE) != 0; break; }
-            if ((spins & 63) != 63) continue;
-            const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count();
-            if (waited > deadline_s) {
-                ctx->poisoned = true;   // the batch is still queued on arena buffers: no later call may reuse them
-                return r3d_fail(ctx, R3D_E_HIP, "registration loop: no completion after %.0f s (%d evaluations enqueued, last state read: %d evaluations, done=%d)",
-                                waited, enq, hst->evals, hst->done);
-            }
-            if (waited > 2e-4) std::this_thread::sleep_for(std::chrono::microseconds(waited > 5e-3 ? 200 : 20));
-        }
-        if (loop_done) break;
+        if (int rc = icp_poll(ctx, hst, need, enq, deadline_s, loop_done)) return rc;
     }
     if (!loop_done) return r3d_fail(ctx, R3D_E_HIP, "registration loop did not finish (%d evaluations)", hst->evals);
     // (evaluations enqueued behind the step that ended the loop may still be in flight: they return at their first
     // instruction (`done`), and everything this call or the next enqueues is ordered behind them on the same stream)
-    memcpy(T, hst->T, sizeof T);
-    const int it = hst->iterations, converged = hst->converged;
-    const double fit = hst->fit, rmse = hst->rmse, ncorr = hst->corr;
-    memcpy(T4x4, T, sizeof T);
+    memcpy(T4x4, hst->T, sizeof hst->T);
     if (stats) {
-        stats->iterations = it;
-        stats->converged = converged;
-        stats->correspondences = (int64_t)ncorr;
-        stats->fitness = fit;
-        stats->inlier_rmse = rmse;
+        stats->iterations = hst->iterations;
+        stats->converged = hst->converged;
+        stats->correspondences = (int64_t)hst->corr;
+        stats->fitness = hst->fit;
+        stats->inlier_rmse = hst->rmse;
         const auto t_end = std::chrono::steady_clock::now();
         stats->setup_ms = std::chrono::duration<double, std::milli>(t_loop - t_begin).count();
         stats->loop_ms = std::chrono::duration<double, std::milli>(t_end - t_loop).count();
@@ -4263,6 +4288,15 @@ static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, double 
         }
     }
     return R3D_OK;
+}
+
+// ICP / point-to-plane / GICP / coloured loop on clouds that are already in device memory: everything below r3d_icp's argument
+// checks and uploads
+static int icp_core(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, const IcpInput &in, double *T4x4, r3d_icp_stats *stats,
+                    std::chrono::steady_clock::time_point t_begin) {
+    IcpWork w;
+    if (int rc = icp_setup(ctx, ar, p, in, w)) return rc;
+    return icp_loop(ctx, p, w, in.nt, T4x4, stats, t_begin);
 }
 
 // ---- Fast Global Registration: the host side (the kernels stand next to the RANSAC block)
@@ -4488,8 +4522,7 @@ int fgr_core(r3d_ctx *ctx, DevArena &ar, const r3d_fgr_params *p, const double *
     ip.relative_fitness = ip.relative_rmse = 1e-6;
     r3d_icp_stats ist = {};
     double Tsame[16];
-    if ((rc = icp_core(ctx, ar, &ip, const_cast<double *>(d_src), ns, nullptr, const_cast<double *>(d_tgt), nt, nullptr, T4x4, Tsame, &ist, t_eval)))
-        return rc;
+    if ((rc = icp_core(ctx, ar, &ip, {.d_s = d_src, .ns = ns, .d_t = d_tgt, .nt = nt, .init4x4 = T4x4}, Tsame, &ist, t_eval))) return rc;
     if ((rc = lap(5))) return rc;
     if (stats) {
         stats->fitness = ist.fitness;
@@ -4765,7 +4798,9 @@ int r3d_align_point_clouds(r3d_ctx *ctx, const r3d_align_params *p, const double
         if ((rc = normals_core(ctx, ar, d_t, mt, p->normal_radius, p->normal_max_nn, nullptr, &d_tn))) return rc;
     }
     double T[16];
-    if ((rc = icp_core(ctx, ar, ip, d_s, ms, d_sn, d_t, mt, d_tn, init4x4, T, stats, t_begin, tgt_box, p->voxel_size > 0 ? p->voxel_size : 0))) return rc;  // :35-39
+    const IcpInput in = {.d_s = d_s, .ns = ms, .d_sn = d_sn, .d_t = d_t, .nt = mt, .d_tn = d_tn, .init4x4 = init4x4,
+                         .tgt_enclosing = tgt_box, .tgt_spacing = p->voxel_size > 0 ? p->voxel_size : 0};
+    if ((rc = icp_core(ctx, ar, ip, in, T, stats, t_begin))) return rc;  // :35-39
     memcpy(T4x4, T, sizeof T);
     double *d_o, *d_on;
     if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ms, &d_o, &d_on))) return rc;  // :42 source.transform
@@ -4982,7 +5017,7 @@ int r3d_icp(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns
     if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     if (src_normals && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
     if (tgt_normals && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
-    return icp_core(ctx, ar, p, d_s, ns, d_sn, d_t, nt, d_tn, init4x4, T4x4, stats, t_begin);
+    return icp_core(ctx, ar, p, {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = init4x4}, T4x4, stats, t_begin);
 }
 
 // ---- resident scan-loop model (main.py:34-54, test/GICP1.py:134-155) ---------------------------------
@@ -5261,7 +5296,9 @@ int model_align_core(r3d_model *m, DevArena &ar, const r3d_align_params *p, doub
     if (want_sn && (rc = normals_core(ctx, ar, d_s, ms, p->normal_radius, p->normal_max_nn, nullptr, &d_sn))) return rc;
     if (ip->mode != MODE_P2P && (rc = normals_core(ctx, ar, d_t, mt, p->normal_radius, p->normal_max_nn, nullptr, &d_tn))) return rc;
     double T[16];
-    if ((rc = icp_core(ctx, ar, ip, d_s, ms, d_sn, d_t, mt, d_tn, nullptr, T, stats, t_begin, tgt_box, p->voxel_size > 0 ? p->voxel_size : 0))) return rc;  // :35-39, from identity
+    const IcpInput in = {.d_s = d_s, .ns = ms, .d_sn = d_sn, .d_t = d_t, .nt = mt, .d_tn = d_tn,
+                         .tgt_enclosing = tgt_box, .tgt_spacing = p->voxel_size > 0 ? p->voxel_size : 0};
+    if ((rc = icp_core(ctx, ar, ip, in, T, stats, t_begin))) return rc;  // :35-39, from identity
     memcpy(T4x4, T, sizeof T);
     double *d_o, *d_on;
     if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ms, &d_o, &d_on))) return rc;  // :42 source.transform
@@ -5422,8 +5459,9 @@ int r3d_model_register_append(r3d_model *m, const r3d_icp_params *p, const doubl
     if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
     if (src_normals && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
     double T[16];
-    if ((rc = icp_core(ctx, ar, p, d_s, ns, d_sn, (double *)m->pts.p, m->n, m->has_normals ? (double *)m->nrms.p : nullptr, nullptr, T, stats, t_begin)))
-        return rc;                                                                     // test/GICP1.py:99-102, from identity
+    const IcpInput in = {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = (const double *)m->pts.p, .nt = m->n,
+                         .d_tn = m->has_normals ? (const double *)m->nrms.p : nullptr};
+    if ((rc = icp_core(ctx, ar, p, in, T, stats, t_begin))) return rc;                 // test/GICP1.py:99-102, from identity
     memcpy(T4x4, T, sizeof T);
     double *d_o, *d_on;
     if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ns, &d_o, &d_on))) return rc;    // :103 source.transform
@@ -5476,8 +5514,8 @@ int r3d_icp_dev(r3d_ctx *ctx, const r3d_icp_params *p, const double *d_src, int6
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
-    return icp_core(ctx, ar, p, const_cast<double *>(d_src), ns, const_cast<double *>(d_src_normals), const_cast<double *>(d_tgt), nt,
-                    const_cast<double *>(d_tgt_normals), init4x4, T4x4, stats, t_begin);
+    const IcpInput in = {.d_s = d_src, .ns = ns, .d_sn = d_src_normals, .d_t = d_tgt, .nt = nt, .d_tn = d_tgt_normals, .init4x4 = init4x4};
+    return icp_core(ctx, ar, p, in, T4x4, stats, t_begin);
 }
 
 // ---- coloured ICP (Open3D registration_colored_icp): the intensity gradients on their own, and the registration on host / device clouds
@@ -5542,7 +5580,7 @@ int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double 
     if ((rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc))) return rc;
     if ((rc = upload(ctx, ar, src_colors, ns * 3, &d_sc))) return rc;
     ci.d_sc = d_sc; ci.d_tc = d_tc;
-    return icp_core(ctx, ar, &ip, d_s, ns, nullptr, d_t, nt, d_tn, init4x4, T4x4, stats, t_begin, nullptr, 0, nullptr, &ci);
+    return icp_core(ctx, ar, &ip, {.d_s = d_s, .ns = ns, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = init4x4, .color = &ci}, T4x4, stats, t_begin);
 }
 
 int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *d_src, const double *d_src_colors, int64_t ns, const double *d_tgt,
@@ -5557,8 +5595,8 @@ int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const dou
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     ci.d_sc = d_src_colors; ci.d_tc = d_tgt_colors;
-    return icp_core(ctx, ar, &ip, const_cast<double *>(d_src), ns, nullptr, const_cast<double *>(d_tgt), nt, const_cast<double *>(d_tgt_normals),
-                    init4x4, T4x4, stats, t_begin, nullptr, 0, nullptr, &ci);
+    const IcpInput in = {.d_s = d_src, .ns = ns, .d_t = d_tgt, .nt = nt, .d_tn = d_tgt_normals, .init4x4 = init4x4, .color = &ci};
+    return icp_core(ctx, ar, &ip, in, T4x4, stats, t_begin);
 }
 
 // ---- FPFH features and feature-space nearest neighbours (Open3D compute_fpfh_feature / CorrespondencesFromFeatures' search)
@@ -5977,9 +6015,9 @@ extern "C" int r3d_debug_icp_correspondences(r3d_ctx *ctx, const double *src, in
     r3d_icp_params p = {};
     p.mode = MODE_P2P;
     p.max_correspondence_distance = max_correspondence_distance;
-    double T[16];
-    const IcpReadout ro = {corr_out, d2_out};
-    return icp_core(ctx, ar, &p, d_s, ns, nullptr, d_t, nt, nullptr, T4x4, T, nullptr, std::chrono::steady_clock::now(), nullptr, 0, &ro);
+    IcpWork w;
+    if ((rc = icp_setup(ctx, ar, &p, {.d_s = d_s, .ns = ns, .d_t = d_t, .nt = nt, .init4x4 = T4x4}, w))) return rc;
+    return icp_read_correspondences(ctx, ar, &p, w, d_t, corr_out, d2_out);
 }
 
 // diagnostic: what one evaluation of the registration loop accumulates -- icp_core's set-up in the given mode, one k_icp_eval at
@@ -5998,9 +6036,9 @@ extern "C" int r3d_debug_icp_sums(r3d_ctx *ctx, const r3d_icp_params *p, const d
     if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
     if (p->mode != MODE_P2P && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
     if (p->mode == MODE_GICP && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
-    double T[16];
-    const IcpReadout ro = {nullptr, nullptr, sums_out, origin_out};
-    return icp_core(ctx, ar, p, d_s, ns, d_sn, d_t, nt, d_tn, T4x4, T, nullptr, std::chrono::steady_clock::now(), nullptr, 0, &ro);
+    IcpWork w;
+    if ((rc = icp_setup(ctx, ar, p, {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = T4x4}, w))) return rc;
+    return icp_read_sums(ctx, ar, p, w, sums_out, origin_out);
 }
 
 extern "C" int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t n, int32_t op, int32_t *out) {

@@ -127,6 +127,31 @@ def test_one_nn_sources_cover_the_edges():
     assert (np.prod(ext) / 2 ** 26) ** (1 / 3) > 1000 * 1e-3
 
 
+def test_far_lattice_is_beyond_the_packed_search_and_its_reference_is_well_defined():
+    """the translated lattice of tests/test_neighbor_search_gpu.py: on the float64 side of the registration's search choice at
+    both distances, every coordinate exact, and the tied queries tied in the reference too"""
+    from tests import test_neighbor_search_gpu as ts
+    t = ts.far_lattice()
+    np.testing.assert_array_equal(t - ts.FAR_SHIFT, nr.cases()["lattice"])        # the translation rounded nothing
+    assert 1500 < len(t) < 2000
+    for cid, src, T, md, nothing, (corr, d2) in ts.far_nn_table():
+        # the search grid's cell never exceeds max_dist, so max|coordinate| / cell is at least this
+        assert np.abs(t).max() / md >= 1e9, cid
+        assert 3000 < len(src) < 6000
+        if T is not None:
+            continue
+        moved = src[nothing]
+        assert len(moved) == 2 * 144 and (corr[nothing] == -1).all()
+        np.testing.assert_array_equal(nr._pair_d2(t, moved).min(1), md * md)       # exactly AT the distance
+        D = nr._pair_d2(t, src[nothing.stop:])
+        ties = (D == D.min(1, keepdims=True)).sum(1)
+        assert len(D) == 11 ** 3 + 2 * 121 and (ties[:11 ** 3] == 8).all() and (ties[11 ** 3:] == 4).all()
+        h2 = nr.LATTICE_H ** 2
+        assert (D.min(1)[:11 ** 3] == 0.75 * h2).all() and (D.min(1)[11 ** 3:] == 6.75 * h2).all()
+        want = np.where(D.min(1) < md * md, (D == D.min(1, keepdims=True)).argmax(1), -1)
+        np.testing.assert_array_equal(corr[nothing.stop:], want)                   # the lowest index among the tied
+
+
 @pytest.mark.parametrize("name", nr.NORMAL_CLOUDS)
 def test_normal_neighbourhoods_are_sheets(name):
     """the well-separated-eigenvector filter of the normal comparison may drop at most 2 % of the points"""

@@ -2,6 +2,7 @@
 registration's 1-NN search (nn_block_* + nn_outer_shells, read out with r3d_debug_icp_correspondences) -- on clustered, tied and
 off-grid clouds (tests/neighbor_ref.py).  Neighbour lists, squared distances and correspondences are compared for EQUALITY with
 the reference; every search variant is compared with the reference itself, not with another variant."""
+import functools
 import os
 import subprocess
 import sys
@@ -103,6 +104,52 @@ def test_icp_correspondences_equal_brute_force(r3d, name):
         assert np.array_equal(corr, want_c), _describe(f"{cid} corr", corr, want_c)
         assert np.array_equal(d2, want_d), _describe(f"{cid} d2", d2, want_d)
         # the registration's own statistics of that evaluation
+        res = r3d.cloud_ops.registration(src, t, md, init=T, max_iteration=0)
+        count = int((want_c >= 0).sum())
+        assert res["correspondences"] == count and res["fitness"] == count / len(src), (cid, res, count)
+        if count:
+            rmse = np.sqrt(want_d[want_c >= 0].sum() / count)
+            assert abs(res["inlier_rmse"] - rmse) <= 1e-12 * rmse, (cid, res["inlier_rmse"], rmse)
+
+
+# the lattice so far from the origin that the registration's set-up keeps the all-float64 search by itself: with coordinates of
+# 2^30 against a cell of at most max_dist the packed candidates' cell-relative quantisation is no longer exact (the rule
+# Mq / cell >= 1e9 of the search choice).  2^-7 is a multiple of the ulp at 2^30 (2^-22), so every lattice coordinate, the
+# layers moved by exactly max_dist and the tied cell centres stay exactly representable.  Not one of nr.cases(): the kNN and
+# normal tables are not about this rule.
+FAR_SHIFT = np.array([2.0 ** 30, -2.0 ** 30, 2.0 ** 29])
+
+
+@functools.lru_cache(maxsize=None)
+def far_lattice():
+    t = np.ascontiguousarray(nr.cases()["lattice"] + FAR_SHIFT)      # cases() has shuffled the lattice (fixed seed)
+    t.setflags(write=False)
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def far_nn_table():
+    """nr.nn_table()'s rows for the translated lattice: [(case id, source, T or None, max_dist, slice that must find nothing,
+    (corr, d2) of nr.brute_nearest)].  The queries are nr.nn_queries' for the lattice, translated with it."""
+    T = nr.small_pose()
+    Ti = np.linalg.inv(T)
+    out = []
+    for md in nr.nn_max_dists("lattice"):
+        q, nothing = nr.nn_queries("lattice", md)
+        q = np.ascontiguousarray(q + FAR_SHIFT)
+        for cid, src, pose, none in ((f"far_lattice-{md:.3e}-identity", q, None, nothing),
+                                     (f"far_lattice-{md:.3e}-pose", np.ascontiguousarray(q @ Ti[:3, :3].T + Ti[:3, 3]), T, slice(0, 0))):
+            out.append((cid, src, pose, md, none, nr.brute_nearest(far_lattice(), src, pose, md)))
+    return out
+
+
+def test_icp_search_far_from_the_origin_equals_brute_force(r3d):
+    t = far_lattice()
+    for cid, src, T, md, nothing, (want_c, want_d) in far_nn_table():
+        corr, d2 = r3d.cloud_ops.debug_icp_correspondences(src, t, md, T)
+        assert np.array_equal(corr, want_c), _describe(f"{cid} corr", corr, want_c)
+        assert np.array_equal(d2, want_d), _describe(f"{cid} d2", d2, want_d)
+        assert (corr[nothing] == -1).all(), cid
         res = r3d.cloud_ops.registration(src, t, md, init=T, max_iteration=0)
         count = int((want_c >= 0).sum())
         assert res["correspondences"] == count and res["fitness"] == count / len(src), (cid, res, count)
