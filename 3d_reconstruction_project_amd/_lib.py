@@ -64,6 +64,11 @@ class IcpStats(ctypes.Structure):
                 ("loop_ms", ctypes.c_double)]
 
 
+class ResourceCounts(ctypes.Structure):
+    """r3d_resource_counts: what the library holds on the GPU right now, over the whole process."""
+    _fields_ = [(n, ctypes.c_int64) for n in ("device_allocs", "device_bytes", "pinned_allocs", "events", "streams")]
+
+
 _lib = None
 
 _vp = ctypes.c_void_p
@@ -97,6 +102,7 @@ _SIGS = {
     "r3d_sgbm_profile": ([_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32], ctypes.c_int),
     "r3d_sgbm_debug_fetch": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "r3d_sgbm_debug_hh_partial": ([_vp, ctypes.c_int32, _vp], ctypes.c_int),
+    "r3d_debug_resources": ([ctypes.POINTER(ResourceCounts)], ctypes.c_int),
 }
 
 
@@ -177,6 +183,15 @@ def register(sigs):
             fn = getattr(_lib, name)
             fn.argtypes = argt
             fn.restype = rest
+
+
+def live_resources():
+    """The library's live GPU resources over the whole process, as a dict (r3d_debug_resources; needs no context)."""
+    c = ResourceCounts()
+    rc = load().r3d_debug_resources(ctypes.byref(c))
+    if rc != R3D_OK:
+        raise R3DError(rc, "r3d_debug_resources failed")
+    return {n: int(getattr(c, n)) for n, _ in ResourceCounts._fields_}
 
 
 class R3DError(RuntimeError):

@@ -50,24 +50,6 @@ int r3d_fail(r3d_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
-int r3d_reserve(r3d_ctx *ctx, r3d_buf &b, size_t bytes) {
-    if (bytes <= b.cap) return R3D_OK;
-    if (b.p) {
-        (void)hipDeviceSynchronize();   // lanes run on their own streams
-        (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    size_t want = bytes + bytes / 8 + 4096;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return r3d_fail(ctx, R3D_E_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    }
-    b.cap = want;
-    return R3D_OK;
-}
-
 void r3d_prof_harvest(r3d_ctx *ctx, r3d_prof_set &ps) {
     ps.pending = false;
     if (ps.n == 0 || hipEventSynchronize(ps.ev[ps.n]) != hipSuccess) return;
@@ -106,7 +88,7 @@ int r3d_init(int device, r3d_ctx **out) {
     r3d_ctx *ctx = new (std::nothrow) r3d_ctx();
     if (!ctx) return r3d_fail(nullptr, R3D_E_OOM, "r3d_init: out of host memory");
     ctx->device = device;
-    if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking)) != hipSuccess) {
+    if ((e = hipSetDevice(device)) != hipSuccess || (e = ctx->own_stream.create(hipStreamNonBlocking)) != hipSuccess) {
         int rc = r3d_fail(nullptr, R3D_E_HIP, "r3d_init: %s", hipGetErrorString(e));
         delete ctx;
         return rc;
@@ -121,30 +103,17 @@ void r3d_destroy(r3d_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipDeviceSynchronize();
-    r3d_buf *bufs[] = {&ctx->img_l, &ctx->img_r, &ctx->out};
-    for (r3d_buf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (r3d_sgm_ws &ws : ctx->ws) {
-        r3d_buf *wb[] = {&ws.rec_l, &ws.rec_r, &ws.cost, &ws.cspec, &ws.hsum, &ws.ckpt, &ws.raw, &ws.mins, &ws.lrd, &ws.lrd2, &ws.flags, &ws.spk_l, &ws.spk_c};
-        for (r3d_buf *b : wb)
-            if (b->p) (void)hipFree(b->p);
-        if (ws.ev_created)
-            for (auto &ps : ws.prof)
-                for (int i = 0; i <= R3D_MAX_PROF; i++) (void)hipEventDestroy(ps.ev[i]);
-        if (ws.stream) (void)hipStreamDestroy(ws.stream);
-        if (ws.done) (void)hipEventDestroy(ws.done);
-    }
-    if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
-    if (ctx->icp_host) (void)hipHostFree(ctx->icp_host);
-    if (ctx->pin) (void)hipHostFree(ctx->pin);
-    for (r3d_buf &b : ctx->cloud_bufs)
-        if (b.p) (void)hipFree(b.p);
-    for (r3d_buf &b : ctx->pp_bufs)
-        if (b.p) (void)hipFree(b.p);
-    if (ctx->pp_minmax.p) (void)hipFree(ctx->pp_minmax.p);
-    if (ctx->pp_lut.p) (void)hipFree(ctx->pp_lut.p);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;   // every buffer, pinned block, event and stream is a member that frees itself (r3d_resources.h)
+}
+
+int r3d_debug_resources(r3d_resource_counts *out) {
+    if (!out) return R3D_E_BADARG;
+    out->device_allocs = r3d_live.device_allocs.load();
+    out->device_bytes = r3d_live.device_bytes.load();
+    out->pinned_allocs = r3d_live.pinned_allocs.load();
+    out->events = r3d_live.events.load();
+    out->streams = r3d_live.streams.load();
+    return R3D_OK;
 }
 
 const char *r3d_last_error(const r3d_ctx *ctx) { return ctx ? ctx->err.c_str() : g_init_err.c_str(); }
@@ -185,7 +154,7 @@ int r3d_dev_alloc(r3d_ctx *ctx, uint64_t bytes, void **out) {
     R3D_ROCTX_RANGE("r3d_dev_alloc");
     if (!ctx || !out) return R3D_E_BADARG;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
-    hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+    hipError_t e = r3d_hip_malloc(out, bytes ? bytes : 1, 0);
     if (e != hipSuccess) return r3d_fail(ctx, R3D_E_OOM, "hipMalloc(%llu): %s", (unsigned long long)bytes, hipGetErrorString(e));
     return R3D_OK;
 }
@@ -193,7 +162,7 @@ int r3d_dev_free(r3d_ctx *ctx, void *p) {
     R3D_ROCTX_RANGE("r3d_dev_free");
     if (!ctx) return R3D_E_BADARG;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    R3D_HIP(ctx, hipFree(p));
+    R3D_HIP(ctx, r3d_hip_free(p, 0));
     return R3D_OK;
 }
 int r3d_copy_h2d(r3d_ctx *ctx, void *d, const void *h, uint64_t bytes) {
@@ -213,13 +182,13 @@ int r3d_copy_d2h(r3d_ctx *ctx, void *h, const void *d, uint64_t bytes) {
 int r3d_event_create(r3d_ctx *ctx, void **out) {
     if (!ctx || !out) return R3D_E_BADARG;
     hipEvent_t e;
-    R3D_HIP(ctx, hipEventCreate(&e));
+    R3D_HIP(ctx, r3d_hip_event_create(&e));
     *out = (void *)e;
     return R3D_OK;
 }
 int r3d_event_destroy(r3d_ctx *ctx, void *e) {
     if (!ctx) return R3D_E_BADARG;
-    R3D_HIP(ctx, hipEventDestroy((hipEvent_t)e));
+    R3D_HIP(ctx, r3d_hip_event_destroy((hipEvent_t)e));
     return R3D_OK;
 }
 int r3d_event_record(r3d_ctx *ctx, void *e) {
@@ -296,11 +265,11 @@ int r3d_sgbm_compute_batch_cn_dev(r3d_ctx *ctx, const r3d_sgbm_params *p, int32_
     // maps in flight: R3D_SGM_LANES (default 3; measured A/B values 2 .. 6)
     static const int max_lanes = [] { const char *e = getenv("R3D_SGM_LANES"); const int v = e ? atoi(e) : R3D_SGM_LANES; return v < 1 ? 1 : (v > R3D_SGM_MAX_LANES ? R3D_SGM_MAX_LANES : v); }();
     const int lanes = n < max_lanes ? n : max_lanes;
-    if (!ctx->fork_ev) R3D_HIP(ctx, hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
+    if (!ctx->fork_ev) R3D_HIP(ctx, ctx->fork_ev.create(hipEventDisableTiming));
     for (int l = 0; l < lanes; l++) {
         r3d_sgm_ws &ws = ctx->ws[l];
-        if (!ws.stream) R3D_HIP(ctx, hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking));
-        if (!ws.done) R3D_HIP(ctx, hipEventCreateWithFlags(&ws.done, hipEventDisableTiming));
+        if (!ws.stream) R3D_HIP(ctx, ws.stream.create(hipStreamNonBlocking));
+        if (!ws.done) R3D_HIP(ctx, ws.done.create(hipEventDisableTiming));
     }
     // fork: every lane starts after whatever is already queued on the context stream
     R3D_HIP(ctx, hipEventRecord(ctx->fork_ev, ctx->stream));

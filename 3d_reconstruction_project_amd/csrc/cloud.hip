@@ -2244,10 +2244,10 @@ struct PinRead {
     void *host[8];
     explicit PinRead(r3d_ctx *c) : ctx(c) { d.n = 0; }
     int add(void *host_dst, const void *dev, size_t bytes) {   // bytes: a multiple of 4
-        if (!ctx->pin) {
-            hipError_t e = hipHostMalloc(&ctx->pin, R3D_PIN_BYTES, hipHostMallocMapped);
-            if (e != hipSuccess) { ctx->pin = nullptr; return r3d_fail(ctx, R3D_E_OOM, "hipHostMalloc(%d) failed: %s", R3D_PIN_BYTES, hipGetErrorString(e)); }
-            memset(ctx->pin, 0, 64);
+        if (!ctx->pin.p) {
+            hipError_t e = ctx->pin.alloc(R3D_PIN_BYTES, hipHostMallocMapped);
+            if (e != hipSuccess) return r3d_fail(ctx, R3D_E_OOM, "hipHostMalloc(%d) failed: %s", R3D_PIN_BYTES, hipGetErrorString(e));
+            memset(ctx->pin.p, 0, 64);
         }
         if (d.n >= 8 || (bytes & 3) || off + bytes > R3D_PIN_BYTES) return r3d_fail(ctx, R3D_E_HIP, "PinRead: too much for one read-back");
         d.src[d.n] = dev; d.off[d.n] = (unsigned)off; d.bytes[d.n] = (unsigned)bytes;
@@ -2257,7 +2257,7 @@ struct PinRead {
     }
     int wait() {
         char *dpin = nullptr;
-        R3D_HIP(ctx, hipHostGetDevicePointer((void **)&dpin, ctx->pin, 0));
+        R3D_HIP(ctx, hipHostGetDevicePointer((void **)&dpin, ctx->pin.p, 0));
         d.seq = ++ctx->pin_seq;
         k_publish<<<1, 256, 0, ctx->stream>>>(d, dpin);
         R3D_HIP(ctx, hipGetLastError());
@@ -2266,15 +2266,15 @@ struct PinRead {
         const auto t0 = std::chrono::steady_clock::now();
         bool done = false;
         for (unsigned spins = 0; !done; spins++) {
-            if (*(volatile unsigned *)ctx->pin == d.seq) { done = true; break; }
+            if (*(volatile unsigned *)ctx->pin.p == d.seq) { done = true; break; }
             if ((spins & 255) == 255 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 1e-3) break;
         }
         if (!done) {
             R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (*(volatile unsigned *)ctx->pin != d.seq) return r3d_fail(ctx, R3D_E_HIP, "PinRead: the published sequence number did not arrive");
+            if (*(volatile unsigned *)ctx->pin.p != d.seq) return r3d_fail(ctx, R3D_E_HIP, "PinRead: the published sequence number did not arrive");
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        for (int i = 0; i < d.n; i++) memcpy(host[i], (const char *)ctx->pin + d.off[i], d.bytes[i]);
+        for (int i = 0; i < d.n; i++) memcpy(host[i], (const char *)ctx->pin.p + d.off[i], d.bytes[i]);
         d.n = 0;
         off = 64;
         return R3D_OK;
@@ -4142,8 +4142,8 @@ static int icp_setup(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, const 
     w.d_st = (IcpState *)ar.get(sizeof(IcpState));
     if (ar.rc) return ar.rc;
     static_assert(sizeof(IcpState) <= ICP_SLOTS * sizeof(double), "the pinned landing buffer holds one IcpState");
-    if (!ctx->icp_host) R3D_HIP(ctx, hipHostMalloc((void **)&ctx->icp_host, ICP_SLOTS * sizeof(double), hipHostMallocMapped));
-    w.hst = (IcpState *)ctx->icp_host;   // pinned and mapped: k_icp_step publishes the state here, the host polls it
+    if (!ctx->icp_host.p) R3D_HIP(ctx, ctx->icp_host.alloc(ICP_SLOTS * sizeof(double), hipHostMallocMapped));
+    w.hst = (IcpState *)ctx->icp_host.p;   // pinned and mapped: k_icp_step publishes the state here, the host polls it
     w.d_mirror = nullptr;
     R3D_HIP(ctx, hipHostGetDevicePointer((void **)&w.d_mirror, w.hst, 0));
     memset(w.hst, 0, sizeof *w.hst);
@@ -5042,32 +5042,15 @@ struct r3d_model {
     int vt_rebuilds = 0, vt_updates = 0;   // statistics (r3d_model_voxel_table_stats)
     // bounding box of the rows [pend_lo, pend_hi) the last alignment appended: computed on the device when they were appended,
     // fetched with the NEXT call's first read-back (no round trip of its own); pend_host_ok: pend_box holds it already
-    double *d_pend = nullptr;
+    r3d_buf d_pend;
     int64_t pend_lo = 0, pend_hi = 0;
     bool pend_host_ok = false;
     double pend_box[6] = {0, 0, 0, 0, 0, 0};
 };
 namespace {
 // grows a model buffer to hold `rows` triplets, keeping the first `keep` rows
-int model_reserve(r3d_model *m, r3d_buf &b, int64_t rows, int64_t keep) {
-    r3d_ctx *ctx = m->ctx;
-    const size_t bytes = (size_t)rows * 24;
-    if (bytes <= b.cap) return R3D_OK;
-    const size_t want = bytes + bytes / 2 + 4096;
-    void *np = nullptr;
-    hipError_t e = hipMalloc(&np, want);
-    if (e != hipSuccess) return r3d_fail(ctx, R3D_E_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    if (b.p && keep > 0) {
-        e = hipMemcpyAsync(np, b.p, (size_t)keep * 24, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(np); return r3d_fail(ctx, R3D_E_HIP, "model grow copy failed: %s", hipGetErrorString(e)); }
-    }
-    if (b.p) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(b.p);
-    }
-    b.p = np;
-    b.cap = want;
-    return R3D_OK;
+int model_rows(r3d_model *m, r3d_buf &b, int64_t rows, int64_t keep) {
+    return b.reserve(m->ctx, m->ctx->stream, (size_t)rows * 24, R3D_GROW_MODEL, keep > 0 ? (size_t)keep * 24 : 0);
 }
 // appends n rows (device or host source) with the attribute rule of the legacy operator+= (an attribute survives only when
 // the model is empty or already carries it AND the appended cloud carries it)
@@ -5075,9 +5058,9 @@ int model_append(r3d_model *m, const double *xyz, const double *colors, const do
     r3d_ctx *ctx = m->ctx;
     const bool keep_c = (m->n == 0 || m->has_colors) && colors, keep_n = (m->n == 0 || m->has_normals) && normals;
     int rc;
-    if ((rc = model_reserve(m, m->pts, m->n + n, m->n))) return rc;
-    if (keep_c && (rc = model_reserve(m, m->cols, m->n + n, m->n))) return rc;
-    if (keep_n && (rc = model_reserve(m, m->nrms, m->n + n, m->n))) return rc;
+    if ((rc = model_rows(m, m->pts, m->n + n, m->n))) return rc;
+    if (keep_c && (rc = model_rows(m, m->cols, m->n + n, m->n))) return rc;
+    if (keep_n && (rc = model_rows(m, m->nrms, m->n + n, m->n))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync((double *)m->pts.p + m->n * 3, xyz, (size_t)n * 24, kind, ctx->stream));
     if (keep_c) R3D_HIP(ctx, hipMemcpyAsync((double *)m->cols.p + m->n * 3, colors, (size_t)n * 24, kind, ctx->stream));
     if (keep_n) R3D_HIP(ctx, hipMemcpyAsync((double *)m->nrms.p + m->n * 3, normals, (size_t)n * 24, kind, ctx->stream));
@@ -5103,9 +5086,6 @@ void r3d_model_destroy(r3d_model *m) {
     if (!m) return;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    for (r3d_buf *b : {&m->pts, &m->cols, &m->nrms, &m->vt_keys[0], &m->vt_keys[1], &m->vt_sums[0], &m->vt_sums[1], &m->vt_cnt[0], &m->vt_cnt[1]})
-        if (b->p) (void)hipFree(b->p);
-    if (m->d_pend) (void)hipFree(m->d_pend);
     delete m;
 }
 
@@ -5149,16 +5129,7 @@ int r3d_model_append(r3d_model *m, const double *xyz, const double *colors, cons
 }  // extern "C"
 namespace {
 // grow-only table buffer for `rows` voxels
-int vt_reserve(r3d_model *m, r3d_buf &b, int64_t rows, size_t elem) {
-    const size_t bytes = (size_t)rows * elem;
-    if (bytes <= b.cap) return R3D_OK;
-    const size_t want = bytes + bytes / 2 + 4096;
-    if (b.p) { (void)hipStreamSynchronize(m->ctx->stream); (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) { b.p = nullptr; return r3d_fail(m->ctx, R3D_E_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
-    b.cap = want;
-    return R3D_OK;
-}
+int vt_rows(r3d_model *m, r3d_buf &b, int64_t rows, size_t elem) { return b.reserve(m->ctx, m->ctx->stream, (size_t)rows * elem, R3D_GROW_VOXEL_TABLE); }
 // pointcloud_alignment.py:23 for the resident model: the legacy voxel grid of ALL model points, as means in lexicographic voxel
 // order in a fresh arena buffer.  Default: the incremental table above (full rebuild whenever the model's minimum corner moved, the
 // voxel size changed or the table does not exist); R3D_MODEL_IMPL=rebuild: the full sort of every model point, every frame.
@@ -5204,7 +5175,7 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
         }
         if ((rc = voxel_segments(ctx, ar, d_t, m->n, voxel, Vt, false, nullptr, nullptr, nullptr, bounds))) return rc;
         const int c = m->vt_cur;
-        if ((rc = vt_reserve(m, m->vt_keys[c], Vt.nseg, 8)) || (rc = vt_reserve(m, m->vt_sums[c], Vt.nseg, 24)) || (rc = vt_reserve(m, m->vt_cnt[c], Vt.nseg, 4))) return rc;
+        if ((rc = vt_rows(m, m->vt_keys[c], Vt.nseg, 8)) || (rc = vt_rows(m, m->vt_sums[c], Vt.nseg, 24)) || (rc = vt_rows(m, m->vt_cnt[c], Vt.nseg, 4))) return rc;
         k_vt_build<8><<<(unsigned)((Vt.nseg + 255) / 256), 256, 0, ctx->stream>>>(Vt.sorted, Vt.starts, Vt.nseg, m->n, bounds[0] - 0.5 * voxel,
                                                                                bounds[1] - 0.5 * voxel, bounds[2] - 0.5 * voxel, voxel,
                                                                                (unsigned long long *)m->vt_keys[c].p, (double *)m->vt_sums[c].p, (int *)m->vt_cnt[c].p);
@@ -5222,7 +5193,7 @@ int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_
         if ((rc = voxel_segments(ctx, ar, d_t + m->vt_pts * 3, ns, voxel, V, false, org, nmx))) return rc;
         const int c = m->vt_cur, o = c ^ 1;
         const int64_t cap = m->vt_n + V.nseg;
-        if ((rc = vt_reserve(m, m->vt_keys[o], cap, 8)) || (rc = vt_reserve(m, m->vt_sums[o], cap, 24)) || (rc = vt_reserve(m, m->vt_cnt[o], cap, 4))) return rc;
+        if ((rc = vt_rows(m, m->vt_keys[o], cap, 8)) || (rc = vt_rows(m, m->vt_sums[o], cap, 24)) || (rc = vt_rows(m, m->vt_cnt[o], cap, 4))) return rc;
         unsigned long long *segkey = (unsigned long long *)ar.get((size_t)V.nseg * 8);
         int64_t *ins = (int64_t *)ar.get((size_t)V.nseg * 8);
         double *nsum = (double *)ar.get((size_t)V.nseg * 24);
@@ -5309,11 +5280,8 @@ int model_align_core(r3d_model *m, DevArena &ar, const r3d_align_params *p, doub
     m->pend_host_ok = false;
     m->pend_lo = m->pend_hi = 0;
     if (p->voxel_size > 0 && ms > 0) {
-        if (!m->d_pend) {
-            hipError_t e = hipMalloc((void **)&m->d_pend, 64);
-            if (e != hipSuccess) { m->d_pend = nullptr; return R3D_OK; }       // no pending box: the next call computes it itself
-        }
-        if (cloud_bbox_enqueue_dn(ctx, ar, d_o, ms, nullptr, nullptr, nullptr, m->d_pend) == R3D_OK) { m->pend_lo = n_before; m->pend_hi = m->n; }
+        if (!m->d_pend.p && m->d_pend.alloc(64) != hipSuccess) return R3D_OK;   // no pending box: the next call computes it itself
+        if (cloud_bbox_enqueue_dn(ctx, ar, d_o, ms, nullptr, nullptr, nullptr, (double *)m->d_pend.p) == R3D_OK) { m->pend_lo = n_before; m->pend_hi = m->n; }
     }
     return R3D_OK;
 }
@@ -5406,7 +5374,7 @@ int r3d_model_align_append_depth(r3d_model *m, const r3d_align_params *p, const 
     int64_t n;
     double fbox[6];
     PinExtra pend;
-    if (m->d_pend && m->pend_hi > m->pend_lo && !m->pend_host_ok) { pend.host = m->pend_box; pend.dev = m->d_pend; pend.bytes = 48; }
+    if (m->d_pend.p && m->pend_hi > m->pend_lo && !m->pend_host_ok) { pend.host = m->pend_box; pend.dev = m->d_pend.p; pend.bytes = 48; }
     if ((rc = backproject_core(ctx, ar, depth, w, h, stride, cam, color, color_stride, false, &d_p, &d_c, nullptr, &n, fbox, &pend))) return rc;
     if (pend.host) m->pend_host_ok = true;
     if (frame_points) *frame_points = n;
@@ -5481,7 +5449,7 @@ int r3d_model_estimate_normals(r3d_model *m, double radius, int32_t max_nn) {
     double *d_n;
     // legacy EstimateNormals on a cloud that already has normals keeps their orientation (test/GICP1.py:148)
     if ((rc = normals_core(ctx, ar, (double *)m->pts.p, m->n, radius, max_nn, m->has_normals ? (double *)m->nrms.p : nullptr, &d_n))) return rc;
-    if ((rc = model_reserve(m, m->nrms, m->n, m->has_normals ? m->n : 0))) return rc;
+    if ((rc = model_rows(m, m->nrms, m->n, m->has_normals ? m->n : 0))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync(m->nrms.p, d_n, (size_t)m->n * 24, hipMemcpyDeviceToDevice, ctx->stream));
     m->has_normals = true;
     return R3D_OK;
@@ -5702,11 +5670,11 @@ int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_nor
     if (!ms3) return r3d_fail(ctx, R3D_E_BADARG, "debug_fpfh_stages: bad argument");
     if ((rc = fpfh_check(ctx, "debug_fpfh_stages", d_xyz, d_normals, d_fpfh, n, max_nn))) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
-    hipEvent_t ev[5] = {};
-    for (auto &e : ev) R3D_HIP(ctx, hipEventCreate(&e));
+    r3d_events<5> ev;
+    R3D_HIP(ctx, ev.create_all());
     {
         DevArena ar(ctx);
-        rc = fpfh_core(ctx, ar, d_xyz, d_normals, nullptr, n, radius, max_nn, d_fpfh, nullptr, ev);
+        rc = fpfh_core(ctx, ar, d_xyz, d_normals, nullptr, n, radius, max_nn, d_fpfh, nullptr, ev.e);
     }
     if (!rc) {
         DevArena ar(ctx);
@@ -5728,7 +5696,6 @@ int r3d_debug_fpfh_stages(r3d_ctx *ctx, const double *d_xyz, const double *d_nor
         (void)hipEventElapsedTime(&ms3[1], ev[0], ev[1]);
         (void)hipEventElapsedTime(&ms3[2], ev[1], ev[2]);
     }
-    for (auto &x : ev) (void)hipEventDestroy(x);
     if (rc) return rc;
     if (e != hipSuccess) return r3d_fail(ctx, R3D_E_HIP, "debug_fpfh_stages: %s", hipGetErrorString(e));
     return R3D_OK;

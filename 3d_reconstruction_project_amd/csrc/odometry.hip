@@ -456,9 +456,8 @@ int odo_iteration(r3d_ctx *ctx, const OdoWork &W, int l, int it, double *trace_r
 int odo_run(r3d_ctx *ctx, DevArena &ar, const r3d_odometry_params *p, const float *d_sI, const float *d_sD, const float *d_tI, const float *d_tD, int w,
             int h, int stride, OdoCam cam, const double *init4x4, double *T4x4, double *info6x6, r3d_odometry_stats *stats, double *trace_T) {
     hipStream_t st = ctx->stream;
-    hipEvent_t ev[3] = {};
-    for (auto &e : ev) R3D_HIP(ctx, hipEventCreate(&e));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
+    r3d_events<3> ev;
+    R3D_HIP(ctx, ev.create_all());
     R3D_HIP(ctx, hipEventRecord(ev[0], st));
     OdoWork W;
     int rc;

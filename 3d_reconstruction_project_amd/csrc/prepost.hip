@@ -15,20 +15,6 @@
 
 namespace {
 
-struct PPArena {  // bump allocator over ctx->pp_bufs (grow-only, reused across calls)
-    r3d_ctx *ctx;
-    size_t next = 0;
-    int rc = R3D_OK;
-    explicit PPArena(r3d_ctx *c) : ctx(c) {}
-    void *get(size_t bytes) {
-        if (rc) return nullptr;
-        if (next >= ctx->pp_bufs.size()) ctx->pp_bufs.emplace_back();
-        r3d_buf &b = ctx->pp_bufs[next++];
-        rc = r3d_reserve(ctx, b, bytes ? bytes : 16);
-        return rc ? nullptr : b.p;
-    }
-};
-
 // ------------------------------------------------------------------------------------------ rectification maps
 
 struct RectParams {
@@ -848,7 +834,7 @@ extern "C" int r3d_init_undistort_rectify_map(r3d_ctx *ctx, const double *camera
     P.v0 = camera3x3[5];
     P.fx = camera3x3[0];
     P.fy = camera3x3[4];
-    PPArena ar(ctx);
+    DevArena ar(ctx, ctx->pp_bufs);
     const size_t n = (size_t)w * h;
     int16_t *d1 = (int16_t *)ar.get(n * 4);
     uint16_t *d2 = (uint16_t *)ar.get(n * 2);
@@ -886,7 +872,7 @@ extern "C" int r3d_remap_u8(r3d_ctx *ctx, const uint8_t *src, int32_t sw, int32_
     if (check_ctx(ctx)) return R3D_E_BADARG;
     if (!src || !map1 || !map2 || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || cn < 1 || cn > 4 || sstride < sw * cn)
         return r3d_fail(ctx, R3D_E_BADARG, "remap: bad argument");
-    PPArena ar(ctx);
+    DevArena ar(ctx, ctx->pp_bufs);
     const size_t ns = (size_t)sstride * sh, nd = (size_t)dw * dh;
     uint8_t *ds = (uint8_t *)ar.get(ns), *dd = (uint8_t *)ar.get(nd * cn), *dg = (uint8_t *)ar.get(nd);
     int16_t *d1 = (int16_t *)ar.get(nd * 4);
@@ -917,7 +903,7 @@ extern "C" int r3d_bgr2gray(r3d_ctx *ctx, const uint8_t *bgr, int32_t w, int32_t
     R3D_ROCTX_RANGE("r3d_bgr2gray");
     if (check_ctx(ctx)) return R3D_E_BADARG;
     if (!bgr || !gray || w <= 0 || h <= 0 || (cn != 3 && cn != 4) || stride < w * cn) return r3d_fail(ctx, R3D_E_BADARG, "bgr2gray: bad argument");
-    PPArena ar(ctx);
+    DevArena ar(ctx, ctx->pp_bufs);
     const size_t ns = (size_t)stride * h, nd = (size_t)w * h;
     uint8_t *ds = (uint8_t *)ar.get(ns), *dg = (uint8_t *)ar.get(nd);
     if (ar.rc) return ar.rc;
@@ -949,7 +935,7 @@ extern "C" int r3d_normalize_minmax_s16(r3d_ctx *ctx, const int16_t *src, int64_
     R3D_ROCTX_RANGE("r3d_normalize_minmax_s16");
     if (check_ctx(ctx)) return R3D_E_BADARG;
     if (!src || !dst || n <= 0) return r3d_fail(ctx, R3D_E_BADARG, "normalize: bad argument");
-    PPArena ar(ctx);
+    DevArena ar(ctx, ctx->pp_bufs);
     int16_t *ds = (int16_t *)ar.get((size_t)n * 2), *dd = (int16_t *)ar.get((size_t)n * 2);
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemcpyAsync(ds, src, (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
@@ -960,7 +946,7 @@ extern "C" int r3d_normalize_minmax_s16(r3d_ctx *ctx, const int16_t *src, int64_
     return R3D_OK;
 }
 
-static int wls_run(r3d_ctx *ctx, PPArena &ar, const r3d_wls_params *p, const int16_t *d_dl, const int16_t *d_dr,
+static int wls_run(r3d_ctx *ctx, DevArena &ar, const r3d_wls_params *p, const int16_t *d_dl, const int16_t *d_dr,
                    const uint8_t *d_guide, int gcn, int gstride, int w, int h, int16_t *d_out, float *d_conf) {
     const int lo = std::max(0, p->min_disparity + p->num_disparities), ro = std::max(0, -p->min_disparity);
     const int lw = w - lo - ro, lx = lo, rx = w - (lo + lw);
@@ -1066,7 +1052,7 @@ extern "C" int r3d_wls_filter_dev(r3d_ctx *ctx, const r3d_wls_params *p, const i
     if (rc) return rc;
     if (!d_disp_left || !d_disp_right || !d_guide || !d_out || guide_stride < w * guide_cn)
         return r3d_fail(ctx, R3D_E_BADARG, "wls_filter: bad argument");
-    PPArena ar(ctx);
+    DevArena ar(ctx, ctx->pp_bufs);
     return wls_run(ctx, ar, p, d_disp_left, d_disp_right, d_guide, guide_cn, guide_stride, w, h, d_out, d_confidence);
 }
 
@@ -1078,7 +1064,7 @@ extern "C" int r3d_wls_filter(r3d_ctx *ctx, const r3d_wls_params *p, const int16
     int rc = wls_check(ctx, p, guide_cn, w, h);
     if (rc) return rc;
     if (!disp_left || !disp_right || !guide || !out || guide_stride < w * guide_cn) return r3d_fail(ctx, R3D_E_BADARG, "wls_filter: bad argument");
-    PPArena ar(ctx);
+    DevArena ar(ctx, ctx->pp_bufs);
     const size_t n = (size_t)w * h, ng = (size_t)guide_stride * h;
     int16_t *dl = (int16_t *)ar.get(n * 2), *dr = (int16_t *)ar.get(n * 2), *dout = (int16_t *)ar.get(n * 2);
     uint8_t *dg = (uint8_t *)ar.get(ng);

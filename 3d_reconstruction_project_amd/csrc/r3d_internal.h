@@ -9,11 +9,7 @@
 #include <vector>
 
 #include "../../include/r3d.h"
-
-struct r3d_buf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
+#include "r3d_resources.h"
 
 #define R3D_MAX_PROF 16
 #define R3D_PIN_BYTES 65536
@@ -21,7 +17,7 @@ struct r3d_buf {
 #define R3D_PROF_SETS 4
 
 struct r3d_prof_set {
-    hipEvent_t ev[R3D_MAX_PROF + 1] = {};
+    r3d_events<R3D_MAX_PROF + 1> ev;   // created at the first profiled call of the lane (r3d_prof_begin)
     const char *name[R3D_MAX_PROF] = {};
     int n = 0;
     bool pending = false;
@@ -35,8 +31,8 @@ struct r3d_prof_set {
 // bottlenecks (cost: VALU + writes, hscan: HBM, vscan: mixed) of consecutive maps overlap.
 struct r3d_sgm_ws {
     r3d_buf rec_l, rec_r, cost, cspec, hsum, ckpt, raw, mins, lrd, lrd2, flags, spk_l, spk_c;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
+    r3d_stream stream;
+    r3d_event done;
     r3d_prof_set prof[R3D_PROF_SETS];
     int prof_cur = 0;
     bool ev_created = false;
@@ -51,8 +47,8 @@ struct SgmGeom {
 
 struct r3d_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    r3d_stream own_stream;
+    hipStream_t stream = nullptr;   // own_stream, or the caller's (r3d_set_stream)
     std::string err;
     bool profiling = false;
     // set when a call gave up on work that is still queued on the stream (the registration loop's deadline): the arena and the
@@ -62,7 +58,7 @@ struct r3d_ctx {
     // grow-only workspace
     r3d_buf img_l, img_r, out;
     r3d_sgm_ws ws[R3D_SGM_MAX_LANES];
-    hipEvent_t fork_ev = nullptr;
+    r3d_event fork_ev;
     // geometry of the last sgbm call (for debug fetch)
     int last_w = 0, last_h = 0, last_w1 = 0, last_dp = 0;
     int last_mode = -1;        // r3d_sgbm_params.mode of that call
@@ -74,9 +70,9 @@ struct r3d_ctx {
     int n_acc = 0;
     // cloud workspace (cloud.hip)
     std::vector<r3d_buf> cloud_bufs;
-    double *icp_host = nullptr;    // pinned landing buffer of the per-iteration sums
+    r3d_pinned icp_host;           // pinned landing buffer of the per-iteration sums
     unsigned pin_seq = 0;          // sequence number of the latest PinRead
-    void *pin = nullptr;           // pinned landing buffer of the small device -> host reads between kernels (R3D_PIN_BYTES)
+    r3d_pinned pin;                // pinned landing buffer of the small device -> host reads between kernels (R3D_PIN_BYTES)
     // pre/post-processing workspace (prepost.hip)
     std::vector<r3d_buf> pp_bufs;
     r3d_buf pp_minmax, pp_lut;
@@ -84,8 +80,8 @@ struct r3d_ctx {
     int pp_lut_n = 0;
 };
 
-int r3d_fail(r3d_ctx *ctx, int code, const char *fmt, ...);
-int r3d_reserve(r3d_ctx *ctx, r3d_buf &b, size_t bytes);
+// grows a context workspace buffer (all of them are grow-only and settle during warm-up)
+static inline int r3d_reserve(r3d_ctx *ctx, r3d_buf &b, size_t bytes) { return b.reserve(ctx, ctx->stream, bytes, R3D_GROW_WORKSPACE); }
 
 #define R3D_HIP(ctx, call)                                                                          \
     do {                                                                                            \
@@ -95,19 +91,21 @@ int r3d_reserve(r3d_ctx *ctx, r3d_buf &b, size_t bytes);
                             __FILE__, __LINE__);                                                    \
     } while (0)
 
-struct DevArena {  // simple bump allocator over ctx->cloud_bufs (grow-only, reused across calls)
+struct DevArena {  // simple bump allocator over one of the context's buffer lists (grow-only, reused across calls)
     r3d_ctx *ctx;
+    std::vector<r3d_buf> &bufs;   // ctx->cloud_bufs, or ctx->pp_bufs for the pre/post stages
     size_t next = 0;
     int rc = R3D_OK;
-    explicit DevArena(r3d_ctx *c) : ctx(c) {}
+    explicit DevArena(r3d_ctx *c) : ctx(c), bufs(c->cloud_bufs) {}
+    DevArena(r3d_ctx *c, std::vector<r3d_buf> &v) : ctx(c), bufs(v) {}
     void *get(size_t bytes) {
         if (rc) return nullptr;
         if (ctx->poisoned) {
             rc = r3d_fail(ctx, R3D_E_HIP, "context poisoned by an earlier timed-out call (its kernels may still use the arena): destroy it");
             return nullptr;
         }
-        if (next >= ctx->cloud_bufs.size()) ctx->cloud_bufs.emplace_back();
-        r3d_buf &b = ctx->cloud_bufs[next++];
+        if (next >= bufs.size()) bufs.emplace_back();
+        r3d_buf &b = bufs[next++];
         rc = r3d_reserve(ctx, b, bytes ? bytes : 16);
         return rc ? nullptr : b.p;
     }
@@ -170,7 +168,7 @@ static inline void r3d_prof_begin(r3d_ctx *ctx, r3d_sgm_ws &ws) {
     if (!ctx->profiling) return;
     if (!ws.ev_created) {
         for (auto &ps : ws.prof)
-            for (int i = 0; i <= R3D_MAX_PROF; i++) (void)hipEventCreate(&ps.ev[i]);
+            for (int i = 0; i <= R3D_MAX_PROF; i++) (void)ps.ev.create(i);
         ws.ev_created = true;
     }
     ws.prof_cur = (ws.prof_cur + 1) % R3D_PROF_SETS;

@@ -1612,9 +1612,9 @@ int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int 
     const size_t row_words = row_bytes / 4, bytes = (size_t)rows * row_bytes;
     int rc;
     if ((rc = r3d_reserve(ctx, ctx->ws[0].cost, bytes)) || (rc = r3d_reserve(ctx, ctx->ws[0].hsum, bytes))) return rc;
-    hipEvent_t a, b;
-    R3D_HIP(ctx, hipEventCreate(&a));
-    R3D_HIP(ctx, hipEventCreate(&b));
+    r3d_event a, b;
+    R3D_HIP(ctx, a.create());
+    R3D_HIP(ctx, b.create());
     for (int i = 0; i < reps + 1; i++) {
         if (i == 1) R3D_HIP(ctx, hipEventRecord(a, ctx->stream));
         const int *in = (const int *)ctx->ws[0].cost.p;
@@ -1635,8 +1635,6 @@ int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int 
     R3D_HIP(ctx, hipEventSynchronize(b));
     R3D_HIP(ctx, hipEventElapsedTime(ms, a, b));
     *ms /= reps;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
     return R3D_OK;
 }
 

@@ -445,96 +445,64 @@ struct r3d_tsdf {
     r3d_tsdf_params prm = {};
     int cap = 0;                 // pool capacity in units
     int n_units = 0;
-    TsdfTable t = {};
-    float *tsdf = nullptr, *weight = nullptr;
-    double *c[3] = {};
-    unsigned long long *unit_keys = nullptr;
-    int *new_list = nullptr, *touched = nullptr, *order = nullptr;
-    TsdfCounters *d_cnt = nullptr, *h_cnt = nullptr;   // h_cnt: pinned
+    r3d_buf keys, slot, stamp;   // the hash table's arrays, tcap entries each (TsdfTable is the view kernels get)
+    int tcap = 0;
+    r3d_buf tsdf, weight, c[3];  // planes of cap units
+    r3d_buf unit_keys, order;    // cap entries
+    r3d_buf new_list, touched;   // tcap entries
+    r3d_buf d_cnt;
+    r3d_pinned h_cnt;
     int pass = 0;
     long long frames = 0;
     int last_touched = 0, growths = 0;
-    hipEvent_t ev[3] = {};
+    r3d_events<3> ev;
     bool timed = false;
+
+    TsdfTable table() const { return TsdfTable{(unsigned long long *)keys.p, (int *)slot.p, (int *)stamp.p, tcap}; }
 };
 
 namespace {
 
-template <class T> void tsdf_free(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-void tsdf_release(r3d_tsdf *v) {
-    tsdf_free(v->t.keys); tsdf_free(v->t.slot); tsdf_free(v->t.stamp);
-    tsdf_free(v->tsdf); tsdf_free(v->weight);
-    for (auto &p : v->c) tsdf_free(p);
-    tsdf_free(v->unit_keys); tsdf_free(v->new_list); tsdf_free(v->touched); tsdf_free(v->order); tsdf_free(v->d_cnt);
-    if (v->h_cnt) (void)hipHostFree(v->h_cnt);
-    v->h_cnt = nullptr;
-    for (auto &e : v->ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-}
-
-template <class T> int tsdf_alloc(r3d_ctx *ctx, T *&p, size_t count) {
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, count * sizeof(T));
-    if (e != hipSuccess) return r3d_fail(ctx, R3D_E_OOM, "tsdf: hipMalloc(%zu) failed: %s", count * sizeof(T), hipGetErrorString(e));
-    p = (T *)q;
-    return R3D_OK;
-}
-
-// a plane of `cap` units from one of `old_cap`: the first n_units blocks copied, the rest zero
-template <class T> int tsdf_grow_plane(r3d_tsdf *v, T *&p, size_t per_unit, int new_cap) {
-    r3d_ctx *ctx = v->ctx;
-    T *q = nullptr;
-    if (int rc = tsdf_alloc(ctx, q, (size_t)new_cap * per_unit)) return rc;
-    const size_t keep = (size_t)v->n_units * per_unit;
-    hipError_t e = hipSuccess;
-    if (p && keep) e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(q + keep, 0, ((size_t)new_cap * per_unit - keep) * sizeof(T), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(q);
-        return r3d_fail(ctx, R3D_E_HIP, "tsdf: growing a plane failed: %s", hipGetErrorString(e));
-    }
-    tsdf_free(p);
-    p = q;
-    return R3D_OK;
-}
-
 int tsdf_clear_table(r3d_tsdf *v) {
     r3d_ctx *ctx = v->ctx;
-    R3D_HIP(ctx, hipMemsetAsync(v->t.keys, 0xFF, (size_t)v->t.cap * 8, ctx->stream));
-    R3D_HIP(ctx, hipMemsetAsync(v->t.stamp, 0, (size_t)v->t.cap * 4, ctx->stream));
-    R3D_HIP(ctx, hipMemsetAsync(v->t.slot, 0xFF, (size_t)v->t.cap * 4, ctx->stream));
+    R3D_HIP(ctx, hipMemsetAsync(v->keys.p, 0xFF, (size_t)v->tcap * 8, ctx->stream));
+    R3D_HIP(ctx, hipMemsetAsync(v->stamp.p, 0, (size_t)v->tcap * 4, ctx->stream));
+    R3D_HIP(ctx, hipMemsetAsync(v->slot.p, 0xFF, (size_t)v->tcap * 4, ctx->stream));
     v->pass = 0;
-    if (v->n_units) k_tsdf_rebuild<<<(unsigned)((v->n_units + 255) / 256), 256, 0, ctx->stream>>>(v->t, v->unit_keys, v->n_units);
+    if (v->n_units)
+        k_tsdf_rebuild<<<(unsigned)((v->n_units + 255) / 256), 256, 0, ctx->stream>>>(v->table(), (const unsigned long long *)v->unit_keys.p, v->n_units);
     R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
 }
 
-// pool of new_cap units and a table of at least twice as many entries; the units kept, the table rebuilt from them
+// pool of new_cap units and a table of at least twice as many entries; the units kept, the table rebuilt from them.  Commits on
+// success: each plane is replaced only once its successor is allocated, copied and zeroed (a plane longer than the pool is
+// harmless), and the arrays that hold nothing worth keeping are built aside and moved in together with the capacities.  A failure
+// leaves the old capacity, the old arrays and a table the caller rebuilds with tsdf_clear_table.
 int tsdf_resize(r3d_tsdf *v, int new_cap) {
     r3d_ctx *ctx = v->ctx;
+    hipStream_t st = ctx->stream;
     int rc;
-    if ((rc = tsdf_grow_plane(v, v->tsdf, TSDF_UNIT, new_cap)) || (rc = tsdf_grow_plane(v, v->weight, TSDF_UNIT, new_cap))) return rc;
+    // a plane of new_cap units from one of v->cap: the first n_units blocks copied, the rest zero
+    auto grow_plane = [&](r3d_buf &b, size_t unit_bytes) {
+        return b.reserve(ctx, st, (size_t)new_cap * unit_bytes, R3D_GROW_TSDF, (size_t)v->n_units * unit_bytes, true);
+    };
+    if ((rc = grow_plane(v->tsdf, TSDF_UNIT * 4)) || (rc = grow_plane(v->weight, TSDF_UNIT * 4))) return rc;
     if (v->prm.color_type == R3D_TSDF_COLOR_RGB8)
         for (auto &p : v->c)
-            if ((rc = tsdf_grow_plane(v, p, TSDF_UNIT, new_cap))) return rc;
-    if ((rc = tsdf_grow_plane(v, v->unit_keys, 1, new_cap))) return rc;
-    tsdf_free(v->order);
-    if ((rc = tsdf_alloc(ctx, v->order, (size_t)new_cap))) return rc;
+            if ((rc = grow_plane(p, TSDF_UNIT * 8))) return rc;
+    if ((rc = grow_plane(v->unit_keys, 8))) return rc;
     int tcap = 16;
     while (tcap < 2 * new_cap) tcap *= 2;
-    tsdf_free(v->t.keys); tsdf_free(v->t.slot); tsdf_free(v->t.stamp); tsdf_free(v->new_list); tsdf_free(v->touched);
-    v->t.cap = tcap;
-    if ((rc = tsdf_alloc(ctx, v->t.keys, (size_t)tcap)) || (rc = tsdf_alloc(ctx, v->t.slot, (size_t)tcap)) ||
-        (rc = tsdf_alloc(ctx, v->t.stamp, (size_t)tcap)) || (rc = tsdf_alloc(ctx, v->new_list, (size_t)tcap)) ||
-        (rc = tsdf_alloc(ctx, v->touched, (size_t)tcap)))
+    r3d_buf order, keys, slot, stamp, new_list, touched;
+    if ((rc = order.reserve(ctx, st, (size_t)new_cap * 4, R3D_GROW_TSDF)) || (rc = keys.reserve(ctx, st, (size_t)tcap * 8, R3D_GROW_TSDF)) ||
+        (rc = slot.reserve(ctx, st, (size_t)tcap * 4, R3D_GROW_TSDF)) || (rc = stamp.reserve(ctx, st, (size_t)tcap * 4, R3D_GROW_TSDF)) ||
+        (rc = new_list.reserve(ctx, st, (size_t)tcap * 4, R3D_GROW_TSDF)) || (rc = touched.reserve(ctx, st, (size_t)tcap * 4, R3D_GROW_TSDF)))
         return rc;
+    v->order = std::move(order);
+    v->keys = std::move(keys); v->slot = std::move(slot); v->stamp = std::move(stamp);
+    v->new_list = std::move(new_list); v->touched = std::move(touched);
+    v->tcap = tcap;
     v->cap = new_cap;
     return tsdf_clear_table(v);
 }
@@ -587,14 +555,14 @@ int tsdf_integrate_dev(r3d_tsdf *v, const float *d_depth, int dstride, const uin
     TsdfCounters cnt;
     for (;;) {
         v->pass++;
-        R3D_HIP(ctx, hipMemsetAsync(v->d_cnt, 0, sizeof(TsdfCounters), st));
-        k_tsdf_touch<<<(unsigned)(((size_t)ni * nj + 255) / 256), 256, 0, st>>>(d_depth, dstride, s, nj, ni, cam, P, v->prm.sdf_trunc, ul, v->t, v->pass,
-                                                                                 v->new_list, v->touched, v->d_cnt);
+        R3D_HIP(ctx, hipMemsetAsync(v->d_cnt.p, 0, sizeof(TsdfCounters), st));
+        k_tsdf_touch<<<(unsigned)(((size_t)ni * nj + 255) / 256), 256, 0, st>>>(d_depth, dstride, s, nj, ni, cam, P, v->prm.sdf_trunc, ul, v->table(), v->pass,
+                                                                                 (int *)v->new_list.p, (int *)v->touched.p, (TsdfCounters *)v->d_cnt.p);
         R3D_HIP(ctx, hipGetLastError());
         // the one device -> host read of a frame: 16 bytes of counters (a frame that outgrows the pool repeats the pass and the read)
-        R3D_HIP(ctx, hipMemcpyAsync(v->h_cnt, v->d_cnt, sizeof(TsdfCounters), hipMemcpyDeviceToHost, st));
+        R3D_HIP(ctx, hipMemcpyAsync(v->h_cnt.p, v->d_cnt.p, sizeof(TsdfCounters), hipMemcpyDeviceToHost, st));
         R3D_HIP(ctx, hipStreamSynchronize(st));
-        cnt = *v->h_cnt;
+        cnt = *(const TsdfCounters *)v->h_cnt.p;
         if (cnt.out_of_range) {
             if (int rc = tsdf_clear_table(v)) return rc;
             return r3d_fail(ctx, R3D_E_UNSUPPORTED, "tsdf_integrate: a depth sample falls into a unit index outside +-2^20 (or is not finite)");
@@ -606,10 +574,16 @@ int tsdf_integrate_dev(r3d_tsdf *v, const float *d_depth, int dstride, const uin
             (void)tsdf_clear_table(v);
             return r3d_fail(ctx, R3D_E_OOM, "tsdf_integrate: more than 2^22 units");
         }
-        if (int rc = tsdf_resize(v, want)) return rc;
+        if (int rc = tsdf_resize(v, want)) {
+            // the touch pass has put keys without slots into the table: rebuild it from the units, keep the allocation's message
+            const std::string why = ctx->err;
+            (void)tsdf_clear_table(v);
+            ctx->err = why;
+            return rc;
+        }
         v->growths++;
     }
-    if (cnt.n_new) k_tsdf_assign<<<(unsigned)((cnt.n_new + 255) / 256), 256, 0, st>>>(v->t, v->new_list, cnt.n_new, v->n_units, v->unit_keys);
+    if (cnt.n_new) k_tsdf_assign<<<(unsigned)((cnt.n_new + 255) / 256), 256, 0, st>>>(v->table(), (const int *)v->new_list.p, cnt.n_new, v->n_units, (unsigned long long *)v->unit_keys.p);
     v->n_units += cnt.n_new;
     R3D_HIP(ctx, hipEventRecord(v->ev[1], st));
     if (cnt.n_touched) {
@@ -623,9 +597,9 @@ int tsdf_integrate_dev(r3d_tsdf *v, const float *d_depth, int dstride, const uin
         F.wlim = (float)((double)w - 0.0001); F.hlim = (float)((double)h - 0.0001);
         F.vld = v->prm.voxel_length; F.ul = ul;
         if (v->prm.color_type == R3D_TSDF_COLOR_RGB8)
-            k_tsdf_integrate<true><<<(unsigned)cnt.n_touched, 256, 0, st>>>(F, v->t, v->touched, v->tsdf, v->weight, v->c[0], v->c[1], v->c[2]);
+            k_tsdf_integrate<true><<<(unsigned)cnt.n_touched, 256, 0, st>>>(F, v->table(), (const int *)v->touched.p, (float *)v->tsdf.p, (float *)v->weight.p, (double *)v->c[0].p, (double *)v->c[1].p, (double *)v->c[2].p);
         else
-            k_tsdf_integrate<false><<<(unsigned)cnt.n_touched, 256, 0, st>>>(F, v->t, v->touched, v->tsdf, v->weight, nullptr, nullptr, nullptr);
+            k_tsdf_integrate<false><<<(unsigned)cnt.n_touched, 256, 0, st>>>(F, v->table(), (const int *)v->touched.p, (float *)v->tsdf.p, (float *)v->weight.p, nullptr, nullptr, nullptr);
         R3D_HIP(ctx, hipGetLastError());
     }
     R3D_HIP(ctx, hipEventRecord(v->ev[2], st));
@@ -637,14 +611,14 @@ int tsdf_integrate_dev(r3d_tsdf *v, const float *d_depth, int dstride, const uin
 
 TsdfVol tsdf_view(const r3d_tsdf *v) {
     TsdfVol V;
-    V.t = v->t; V.tsdf = v->tsdf; V.weight = v->weight;
-    for (int k = 0; k < 3; k++) V.c[k] = v->c[k];
+    V.t = v->table(); V.tsdf = (const float *)v->tsdf.p; V.weight = (const float *)v->weight.p;
+    for (int k = 0; k < 3; k++) V.c[k] = (const double *)v->c[k].p;
     V.vl = v->prm.voxel_length; V.ul = v->prm.voxel_length * TSDF_R;
     return V;
 }
 
 int tsdf_sort_units(r3d_tsdf *v) {
-    if (v->n_units) k_tsdf_rank<<<(unsigned)((v->n_units + 255) / 256), 256, 0, v->ctx->stream>>>(v->unit_keys, v->n_units, v->order);
+    if (v->n_units) k_tsdf_rank<<<(unsigned)((v->n_units + 255) / 256), 256, 0, v->ctx->stream>>>((const unsigned long long *)v->unit_keys.p, v->n_units, (int *)v->order.p);
     R3D_HIP(v->ctx, hipGetLastError());
     return R3D_OK;
 }
@@ -666,7 +640,7 @@ int tsdf_extract(r3d_tsdf *v, DevArena &ar, int64_t cap, double *d_xyz, double *
     int rc;
     if ((rc = tsdf_sort_units(v))) return rc;
     const TsdfVol V = tsdf_view(v);
-    k_tsdf_extract<false, false><<<(unsigned)n, 256, 0, st>>>(V, v->order, v->unit_keys, thread_off, unit_cnt, nullptr, nullptr, nullptr, nullptr);
+    k_tsdf_extract<false, false><<<(unsigned)n, 256, 0, st>>>(V, (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, thread_off, unit_cnt, nullptr, nullptr, nullptr, nullptr);
     k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, unit_off, d_total);
     R3D_HIP(ctx, hipGetLastError());
     long long total = 0;
@@ -682,9 +656,9 @@ int tsdf_extract(r3d_tsdf *v, DevArena &ar, int64_t cap, double *d_xyz, double *
         if (ar.rc) return ar.rc;
     }
     if (color)
-        k_tsdf_extract<true, true><<<(unsigned)n, 256, 0, st>>>(V, v->order, v->unit_keys, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, d_col);
+        k_tsdf_extract<true, true><<<(unsigned)n, 256, 0, st>>>(V, (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, d_col);
     else
-        k_tsdf_extract<true, false><<<(unsigned)n, 256, 0, st>>>(V, v->order, v->unit_keys, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, nullptr);
+        k_tsdf_extract<true, false><<<(unsigned)n, 256, 0, st>>>(V, (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, nullptr);
     R3D_HIP(ctx, hipGetLastError());
     if (host_out) {
         R3D_HIP(ctx, hipMemcpyAsync(xyz, d_xyz, (size_t)total * 24, hipMemcpyDeviceToHost, st));
@@ -717,14 +691,12 @@ int r3d_tsdf_create(r3d_ctx *ctx, const r3d_tsdf_params *p, r3d_tsdf **out) {
     r3d_tsdf *v = new r3d_tsdf;
     v->ctx = ctx;
     v->prm = *p;
-    int rc = tsdf_alloc(ctx, v->d_cnt, 1);
-    if (!rc && hipHostMalloc((void **)&v->h_cnt, sizeof(TsdfCounters), hipHostMallocDefault) != hipSuccess)
+    int rc = v->d_cnt.reserve(ctx, ctx->stream, sizeof(TsdfCounters), R3D_GROW_TSDF);
+    if (!rc && v->h_cnt.alloc(sizeof(TsdfCounters), hipHostMallocDefault) != hipSuccess)
         rc = r3d_fail(ctx, R3D_E_OOM, "tsdf_create: pinned allocation failed");
-    for (auto &e : v->ev)
-        if (!rc && hipEventCreate(&e) != hipSuccess) rc = r3d_fail(ctx, R3D_E_HIP, "tsdf_create: hipEventCreate failed");
+    if (!rc && v->ev.create_all() != hipSuccess) rc = r3d_fail(ctx, R3D_E_HIP, "tsdf_create: hipEventCreate failed");
     if (!rc) rc = tsdf_resize(v, p->initial_units ? p->initial_units : TSDF_DEFAULT_UNITS);
     if (rc) {
-        tsdf_release(v);
         delete v;
         return rc;
     }
@@ -739,7 +711,6 @@ int r3d_tsdf_destroy(r3d_ctx *ctx, r3d_tsdf *vol) {
     if (vol->ctx != ctx) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_destroy: the volume belongs to another context");
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    tsdf_release(vol);
     delete vol;
     return R3D_OK;
 }
@@ -751,10 +722,10 @@ int r3d_tsdf_reset(r3d_ctx *ctx, r3d_tsdf *vol) {
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const size_t used = (size_t)vol->n_units * TSDF_UNIT;
     if (used) {
-        R3D_HIP(ctx, hipMemsetAsync(vol->tsdf, 0, used * 4, ctx->stream));
-        R3D_HIP(ctx, hipMemsetAsync(vol->weight, 0, used * 4, ctx->stream));
+        R3D_HIP(ctx, hipMemsetAsync(vol->tsdf.p, 0, used * 4, ctx->stream));
+        R3D_HIP(ctx, hipMemsetAsync(vol->weight.p, 0, used * 4, ctx->stream));
         if (vol->prm.color_type == R3D_TSDF_COLOR_RGB8)
-            for (auto &p : vol->c) R3D_HIP(ctx, hipMemsetAsync(p, 0, used * 8, ctx->stream));
+            for (auto &p : vol->c) R3D_HIP(ctx, hipMemsetAsync(p.p, 0, used * 8, ctx->stream));
     }
     vol->n_units = 0;
     vol->frames = 0;
@@ -891,7 +862,7 @@ int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t
     double *d_c = color ? (double *)ar.get((size_t)n * TSDF_UNIT * 24) : nullptr;
     if (ar.rc) return ar.rc;
     if (int rc = tsdf_sort_units(vol)) return rc;
-    k_tsdf_gather<<<(unsigned)n, 256, 0, st>>>(tsdf_view(vol), color ? 1 : 0, vol->order, vol->unit_keys, d_idx, d_t, d_w, d_c);
+    k_tsdf_gather<<<(unsigned)n, 256, 0, st>>>(tsdf_view(vol), color ? 1 : 0, (const int *)vol->order.p, (const unsigned long long *)vol->unit_keys.p, d_idx, d_t, d_w, d_c);
     R3D_HIP(ctx, hipGetLastError());
     R3D_HIP(ctx, hipMemcpyAsync(idx3, d_idx, (size_t)n * 12, hipMemcpyDeviceToHost, st));
     R3D_HIP(ctx, hipMemcpyAsync(tsdf, d_t, (size_t)n * TSDF_UNIT * 4, hipMemcpyDeviceToHost, st));

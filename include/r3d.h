@@ -76,6 +76,14 @@ int r3d_event_destroy(r3d_ctx *ctx, void *event);
 int r3d_event_record(r3d_ctx *ctx, void *event);                        /* on the ctx stream */
 int r3d_event_elapsed_ms(r3d_ctx *ctx, void *start, void *stop, float *out_ms); /* synchronises `stop` */
 
+/* diagnostic: what this library holds on the GPU right now, summed over every context, model and volume of the process (a leak
+ * shows as a count that does not return to its earlier value once they are destroyed).  device_allocs counts r3d_dev_alloc
+ * handles too; device_bytes only the buffers the library owns itself.  Needs no context and no device. */
+typedef struct r3d_resource_counts {    /* 40 bytes */
+    int64_t device_allocs, device_bytes, pinned_allocs, events, streams;
+} r3d_resource_counts;
+int r3d_debug_resources(r3d_resource_counts *out);
+
 /* ---- stereo: semi-global block matching, 3-way ------------------------------------------------------------
  * replaces: cv2.StereoSGBM_create(**kwargs) + matcher.compute(gray_left, gray_right)
  *   Calib_depth/depth1.py:202-214,331  depth2.py:146-158,251  depth3.py:234-246,339

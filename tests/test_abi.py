@@ -26,6 +26,7 @@ def test_header_symbols_are_exported_and_bound(r3d):
 
 def test_struct_layouts_match_header(r3d):
     assert ctypes.sizeof(r3d._lib.SgbmParams) == 11 * 4
+    assert ctypes.sizeof(r3d._lib.ResourceCounts) == 40
 
 
 def test_no_cpu_fallback_without_device(r3d):
