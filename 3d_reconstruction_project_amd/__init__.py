@@ -13,7 +13,7 @@ from .cloud_ops import (compute_fpfh_feature, compute_rgbd_odometry, corresponde
 from .stereo_sgbm import (STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_SGBM_3WAY, StereoSGBM, StereoSGBM_create, createRightMatcher, depth,  # noqa: F401
                           filterSpeckles, reference_matcher)
 from .normal_estimation import NormalEstimation, estimate  # noqa: F401,E402
-from .pointcloud import PointCloud  # noqa: F401,E402
+from .pointcloud import PointCloud, TriangleMesh  # noqa: F401,E402
 from .pointcloud_alignment import GeneralizedICPAlignment, PointCloudAlignment, align, multi_scale_icp  # noqa: F401,E402
 from .pointcloud_processing import PointCloudProcessingWithCUDA  # noqa: F401,E402
 from .tsdf import ScalableTSDFVolume, TSDFVolumeColorType  # noqa: F401,E402

@@ -10,9 +10,12 @@
 // per touched unit, one thread per column).  Between touch and assign the host reads 16 bytes of counters: how many units are new
 // decides whether pool and table must grow first.  Which slot a unit gets depends on which thread won the race; nothing
 // observable does: extraction and the debug dump walk the units in key order.  No kernel waits for another workgroup.
+#include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "r3d_internal.h"
+#include "tsdf_mc_tables.h"
 
 namespace {
 
@@ -437,6 +440,199 @@ __global__ void __launch_bounds__(256) k_tsdf_gather(TsdfVol V, int color, const
     }
 }
 
+// ---- triangle mesh ----------------------------------------------------------------------------------------------------------------
+// Marching cubes over the cubes whose base voxel lies in an existing unit ("Triangle mesh").  A vertex is owned
+// by (lower voxel of its edge, axis), so it has one home: 3 ids per voxel, no hash map.  Four passes, each one workgroup per unit in
+// key order and one thread per (x, y) column, so thread order, z order, axis order is the contract's order:
+//   k_tsdf_mc_cubes     the cube byte of every base voxel (the cube index when the cube is active, else 0) into a plane;
+//   k_tsdf_mc_vertices  <false> counts the unit's vertices and triangles per thread, <true> writes the vertices and their ids;
+//   k_tsdf_mc_triangles writes the triangles from the ids.
+// A pass reads what the pass before wrote for the neighbour units (cube bytes of the -x/-y/-z side, ids of the +x/+y/+z side), so
+// they are separate launches; inside a launch no workgroup reads what another writes.  Both planes are indexed by pool slot.
+__device__ const int8_t d_mc_tri[256][16] = TSDF_MC_TRI_ROWS;
+__device__ const uint8_t d_mc_count[256] = TSDF_MC_COUNT_ROWS;
+
+constexpr unsigned long long tsdf_mc_edge_pack() {
+    unsigned long long p = 0;
+    for (int e = 0; e < 12; e++) p |= (unsigned long long)TSDF_MC_EDGE[e] << (5 * e);
+    return p;
+}
+constexpr unsigned long long TSDF_MC_EDGE_PACK = tsdf_mc_edge_pack();
+constexpr int TSDF_LAT = TSDF_R + 1, TSDF_LAT3 = TSDF_LAT * TSDF_LAT * TSDF_LAT;   // a unit and one layer of its neighbours
+
+// nb[(dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)] = the pool slot of unit (X + dx, Y + dy, Z + dz), -1 when absent or outside +-2^20
+__device__ __forceinline__ void tsdf_mc_neighbours(const TsdfTable &t, int X, int Y, int Z, int slot, int *nb) {
+    const int tid = (int)threadIdx.x;
+    if (tid < 27) nb[tid] = tid == 13 ? slot : tsdf_find(t, X + tid / 9 - 1, Y + (tid / 3) % 3 - 1, Z + tid % 3 - 1);
+    __syncthreads();
+}
+// number of the cube corner at offset (ox, oy, oz)
+__device__ __forceinline__ int tsdf_mc_corner(int ox, int oy, int oz) { return (oy ? 3 - ox : ox) + 4 * oz; }
+
+__global__ void __launch_bounds__(256) k_tsdf_mc_cubes(TsdfVol V, const int *__restrict__ order, const unsigned long long *__restrict__ unit_keys,
+                                                       uint8_t *__restrict__ cube) {
+    __shared__ int nb[27];
+    __shared__ uint8_t lat[TSDF_LAT3];   // corners 0..16 per axis: bit 0 = its unit exists and its weight is not 0, bit 1 = tsdf < 0
+    const int unit = blockIdx.x, tid = (int)threadIdx.x;
+    const int slot = order[unit];
+    int X, Y, Z;
+    tsdf_unpack(unit_keys[slot], X, Y, Z);
+    tsdf_mc_neighbours(V.t, X, Y, Z, slot, nb);
+    for (int e = tid; e < TSDF_LAT3; e += 256) {
+        const int cz = e % TSDF_LAT, cy = (e / TSDF_LAT) % TSDF_LAT, cx = e / (TSDF_LAT * TSDF_LAT);
+        const int s = nb[((cx >> 4) + 1) * 9 + ((cy >> 4) + 1) * 3 + (cz >> 4) + 1];
+        unsigned f = 0;
+        if (s >= 0) {
+            const size_t i = (size_t)s * TSDF_UNIT + (((cx & 15) * TSDF_R) + (cy & 15)) * TSDF_R + (cz & 15);
+            f = (V.weight[i] != 0.0f ? 1u : 0u) | (V.tsdf[i] < 0.0f ? 2u : 0u);
+        }
+        lat[e] = (uint8_t)f;
+    }
+    __syncthreads();
+    const int x = tid >> 4, y = tid & 15;
+    unsigned w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int z = 0; z < TSDF_R; z++) {
+        unsigned all = 1u, index = 0;
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const unsigned f = lat[((x + (((c + 1) >> 1) & 1)) * TSDF_LAT + y + ((c >> 1) & 1)) * TSDF_LAT + z + (c >> 2)];
+            all &= f;
+            index |= ((f >> 1) & 1u) << c;
+        }
+        w[z >> 2] |= (all ? index : 0u) << (8 * (z & 3));
+    }
+    reinterpret_cast<uint4 *>(cube + (size_t)slot * TSDF_UNIT)[tid] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// EMIT = false: thread_cnt[unit][thread] = the exclusive sums of (vertices | triangles << 16) over the unit's threads (a unit has at
+// most 12288 and 20480), unit_nv / unit_nt the unit's totals.  EMIT = true: the vertex rows at unit_off[unit] + the thread's
+// offset, and every voxel's three ids (-1: no vertex) into vid.
+template <bool EMIT, bool COLOR>
+__global__ void __launch_bounds__(256) k_tsdf_mc_vertices(TsdfVol V, const int *__restrict__ order, const unsigned long long *__restrict__ unit_keys,
+                                                          const uint8_t *__restrict__ cube, unsigned *__restrict__ thread_cnt, int *__restrict__ unit_nv,
+                                                          int *__restrict__ unit_nt, const long long *__restrict__ unit_off, int32_t *__restrict__ vid,
+                                                          double *__restrict__ xyz, double *__restrict__ col) {
+    __shared__ int nb[27];
+    __shared__ uint8_t cl[TSDF_LAT3];    // cube bytes of the base voxels -1..15 per axis, voxel v at v + 1
+    __shared__ unsigned scan[256];
+    const int unit = blockIdx.x, tid = (int)threadIdx.x;
+    const int slot = order[unit];
+    int X, Y, Z;
+    tsdf_unpack(unit_keys[slot], X, Y, Z);
+    tsdf_mc_neighbours(V.t, X, Y, Z, slot, nb);
+    for (int e = tid; e < TSDF_LAT3; e += 256) {
+        const int vz = e % TSDF_LAT - 1, vy = (e / TSDF_LAT) % TSDF_LAT - 1, vx = e / (TSDF_LAT * TSDF_LAT) - 1;
+        const int s = nb[((vx >> 4) + 1) * 9 + ((vy >> 4) + 1) * 3 + (vz >> 4) + 1];
+        cl[e] = s < 0 ? (uint8_t)0 : cube[(size_t)s * TSDF_UNIT + (((vx & 15) * TSDF_R) + (vy & 15)) * TSDF_R + (vz & 15)];
+    }
+    __syncthreads();
+    const int x = tid >> 4, y = tid & 15;
+    const long long own = (long long)slot * TSDF_UNIT + tid * TSDF_R;
+    long long up[3] = {-1, -1, -1};      // the column of the +1 voxel along x and y, the column above along z
+    long long out = 0;
+    if (EMIT) {
+        const int sx = x == TSDF_R - 1 ? nb[22] : slot, sy = y == TSDF_R - 1 ? nb[16] : slot, sz = nb[14];
+        if (sx >= 0) up[0] = (long long)sx * TSDF_UNIT + ((((x + 1) & 15) * TSDF_R) + y) * TSDF_R;
+        if (sy >= 0) up[1] = (long long)sy * TSDF_UNIT + ((x * TSDF_R) + ((y + 1) & 15)) * TSDF_R;
+        if (sz >= 0) up[2] = (long long)sz * TSDF_UNIT + tid * TSDF_R;
+        out = unit_off[unit] + (long long)(thread_cnt[(size_t)unit * 256 + tid] & 0xFFFFu);
+    }
+    int nv = 0, nt = 0;
+    for (int z = 0; z < TSDF_R; z++) {
+        const int h[3] = {x + 1, y + 1, z + 1};   // this voxel in cl
+        if (!EMIT) nt += d_mc_count[cl[(h[0] * TSDF_LAT + h[1]) * TSDF_LAT + h[2]]];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            // the edge from this voxel along a: a vertex iff one of the four cubes around it is active and has its ends on two sides
+            const int b = (a + 1) % 3, c = (a + 2) % 3;
+            bool exists = false;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                int d[3] = {0, 0, 0};     // this voxel's offset inside the cube with base voxel h - d
+                d[b] = q & 1;
+                d[c] = q >> 1;
+                const unsigned B = cl[((h[0] - d[0]) * TSDF_LAT + h[1] - d[1]) * TSDF_LAT + h[2] - d[2]];
+                const int lo = tsdf_mc_corner(d[0], d[1], d[2]);
+                d[a] = 1;
+                const int hi = tsdf_mc_corner(d[0], d[1], d[2]);
+                exists |= (((B >> lo) ^ (B >> hi)) & 1u) != 0;     // an inactive cube has B = 0
+            }
+            if (EMIT) {
+                int32_t id = -1;
+                if (exists) {
+                    id = (int32_t)(out + nv);
+                    const long long hi = a == 2 ? (z < TSDF_R - 1 ? own + z + 1 : up[2]) : (up[a] < 0 ? -1 : up[a] + z);
+                    const double f0 = fabs((double)V.tsdf[own + z]), f1 = hi < 0 ? 0.0 : fabs((double)V.tsdf[hi]);   // hi >= 0: an active cube has it
+                    const int g[3] = {X * TSDF_R + x, Y * TSDF_R + y, Z * TSDF_R + z};
+                    double p[3] = {0.5 * V.vl + V.vl * (double)g[0], 0.5 * V.vl + V.vl * (double)g[1], 0.5 * V.vl + V.vl * (double)g[2]};
+                    p[a] += (f0 * V.vl) / (f0 + f1);
+                    double *o = xyz + (out + nv) * 3;
+                    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+                    if (COLOR) {
+                        double *oc = col + (out + nv) * 3;
+                        for (int ch = 0; ch < 3; ch++) {
+                            const double c0 = V.c[ch][own + z], c1 = hi < 0 ? 0.0 : V.c[ch][hi];
+                            oc[ch] = ((f1 * c0 + f0 * c1) / (f0 + f1)) / 255.0;
+                        }
+                    }
+                }
+                vid[(own + z) * 3 + a] = id;
+            }
+            nv += exists;
+        }
+    }
+    if (EMIT) return;
+    const unsigned mine = (unsigned)nv | (unsigned)nt << 16;
+    scan[tid] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const unsigned v = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    thread_cnt[(size_t)unit * 256 + tid] = scan[tid] - mine;
+    if (tid == 255) {
+        unit_nv[unit] = (int)(scan[255] & 0xFFFFu);
+        unit_nt[unit] = (int)(scan[255] >> 16);
+    }
+}
+
+// triangles of the cubes with their base voxel in the unit: vertex ids of the edges (t0, t2, t1) of every table triple (Open3D's
+// swap: with "bit set = negative = inside" the faces look outward)
+__global__ void __launch_bounds__(256) k_tsdf_mc_triangles(TsdfTable t, const int *__restrict__ order, const unsigned long long *__restrict__ unit_keys,
+                                                           const uint8_t *__restrict__ cube, const int32_t *__restrict__ vid,
+                                                           const unsigned *__restrict__ thread_cnt, const long long *__restrict__ unit_off,
+                                                           int32_t *__restrict__ tri) {
+    __shared__ int nb[27];
+    const int unit = blockIdx.x, tid = (int)threadIdx.x;
+    const int slot = order[unit];
+    int X, Y, Z;
+    tsdf_unpack(unit_keys[slot], X, Y, Z);
+    tsdf_mc_neighbours(t, X, Y, Z, slot, nb);
+    const int x = tid >> 4, y = tid & 15;
+    const uint4 mine = reinterpret_cast<const uint4 *>(cube + (size_t)slot * TSDF_UNIT)[tid];
+    const unsigned w[4] = {mine.x, mine.y, mine.z, mine.w};
+    long long out = unit_off[unit] + (long long)(thread_cnt[(size_t)unit * 256 + tid] >> 16);
+    for (int z = 0; z < TSDF_R; z++) {
+        const unsigned B = (w[z >> 2] >> (8 * (z & 3))) & 0xFFu;
+        const int n = d_mc_count[B];
+        for (int k = 0; k < n; k++) {
+            int32_t id[3];
+            for (int j = 0; j < 3; j++) {
+                const unsigned code = (unsigned)(TSDF_MC_EDGE_PACK >> (5 * d_mc_tri[B][3 * k + j])) & 31u;
+                const int vx = x + (int)(code & 1u), vy = y + (int)((code >> 1) & 1u), vz = z + (int)((code >> 2) & 1u);
+                const int s = nb[((vx >> 4) + 1) * 9 + ((vy >> 4) + 1) * 3 + (vz >> 4) + 1];   // an active cube has all its corner units
+                id[j] = s < 0 ? -1 : vid[((size_t)s * TSDF_UNIT + (((vx & 15) * TSDF_R) + (vy & 15)) * TSDF_R + (vz & 15)) * 3 + (code >> 3)];
+            }
+            int32_t *o = tri + out * 3;
+            o[0] = id[0]; o[1] = id[2]; o[2] = id[1];
+            out++;
+        }
+    }
+}
+
 }  // namespace
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
@@ -669,6 +865,74 @@ int tsdf_extract(r3d_tsdf *v, DevArena &ar, int64_t cap, double *d_xyz, double *
     return R3D_OK;
 }
 
+// cube bytes, counts (always), then vertices, ids and triangles into device arrays when the capacities allow.  Returns after the
+// counts are known; with host_out after the rows are on the host.
+int tsdf_mesh(r3d_tsdf *v, DevArena &ar, int64_t cap_v, int64_t cap_t, double *d_vert, double *d_col, int32_t *d_tri, int64_t *out_nv, int64_t *out_nt,
+              bool host_out, double *vert, double *col, int32_t *tri) {
+    r3d_ctx *ctx = v->ctx;
+    hipStream_t st = ctx->stream;
+    const bool color = v->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    *out_nv = *out_nt = 0;
+    if (!v->n_units) return R3D_OK;
+    const int n = v->n_units;
+    uint8_t *cube = (uint8_t *)ar.get((size_t)n * TSDF_UNIT);
+    unsigned *thread_cnt = (unsigned *)ar.get((size_t)n * 256 * 4);
+    int *unit_cnt = (int *)ar.get((size_t)n * 2 * 4);              // vertices of every unit, then triangles of every unit
+    long long *unit_off = (long long *)ar.get((size_t)n * 2 * 8);
+    long long *d_total = (long long *)ar.get(16);
+    if (ar.rc) return ar.rc;
+    int rc;
+    if ((rc = tsdf_sort_units(v))) return rc;
+    const TsdfVol V = tsdf_view(v);
+    const int *order = (const int *)v->order.p;
+    const unsigned long long *keys = (const unsigned long long *)v->unit_keys.p;
+    k_tsdf_mc_cubes<<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube);
+    k_tsdf_mc_vertices<false, false><<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube, thread_cnt, unit_cnt, unit_cnt + n, nullptr, nullptr, nullptr, nullptr);
+    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, unit_off, d_total);
+    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt + n, n, unit_off + n, d_total + 1);
+    R3D_HIP(ctx, hipGetLastError());
+    long long total[2] = {0, 0};
+    R3D_HIP(ctx, hipMemcpyAsync(total, d_total, 16, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipStreamSynchronize(st));
+    *out_nv = total[0];
+    *out_nt = total[1];
+    if (total[0] > INT32_MAX || total[1] > INT32_MAX)
+        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "mesh_from_volume: %lld vertices and %lld triangles do not fit int32 indices", total[0], total[1]);
+    if ((cap_v == 0 && cap_t == 0) || (total[0] == 0 && total[1] == 0)) return R3D_OK;
+    if (cap_v < total[0] || cap_t < total[1])
+        return r3d_fail(ctx, R3D_E_BADARG, "mesh_from_volume: %lld vertices and %lld triangles do not fit capacities of %lld and %lld", total[0],
+                        total[1], (long long)cap_v, (long long)cap_t);
+    int32_t *vid = (int32_t *)ar.get((size_t)n * TSDF_UNIT * 12);
+    if (host_out) {
+        d_vert = (double *)ar.get((size_t)total[0] * 24);
+        d_col = color ? (double *)ar.get((size_t)total[0] * 24) : nullptr;
+        d_tri = (int32_t *)ar.get((size_t)total[1] * 12);
+    }
+    if (ar.rc) return ar.rc;
+    if (color)
+        k_tsdf_mc_vertices<true, true><<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube, thread_cnt, nullptr, nullptr, unit_off, vid, d_vert, d_col);
+    else
+        k_tsdf_mc_vertices<true, false><<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube, thread_cnt, nullptr, nullptr, unit_off, vid, d_vert, nullptr);
+    k_tsdf_mc_triangles<<<(unsigned)n, 256, 0, st>>>(V.t, order, keys, cube, vid, thread_cnt, unit_off + n, d_tri);
+    R3D_HIP(ctx, hipGetLastError());
+    if (host_out) {
+        if (total[0]) R3D_HIP(ctx, hipMemcpyAsync(vert, d_vert, (size_t)total[0] * 24, hipMemcpyDeviceToHost, st));
+        if (total[0] && color) R3D_HIP(ctx, hipMemcpyAsync(col, d_col, (size_t)total[0] * 24, hipMemcpyDeviceToHost, st));
+        if (total[1]) R3D_HIP(ctx, hipMemcpyAsync(tri, d_tri, (size_t)total[1] * 12, hipMemcpyDeviceToHost, st));
+        R3D_HIP(ctx, hipStreamSynchronize(st));
+    }
+    return R3D_OK;
+}
+
+int tsdf_mesh_args_ok(r3d_ctx *ctx, const r3d_tsdf *v, int64_t cap_v, int64_t cap_t, const void *vert, const void *col, const void *tri, const void *out_nv,
+                      const void *out_nt) {
+    if (int rc = tsdf_vol_ok(ctx, v, "mesh_from_volume")) return rc;
+    const bool color = v->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    if (!out_nv || !out_nt || cap_v < 0 || cap_t < 0 || (cap_v > 0 && (!vert || (color && !col))) || (cap_t > 0 && !tri))
+        return r3d_fail(ctx, R3D_E_BADARG, "mesh_from_volume: a missing array or a negative capacity");
+    return R3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -869,6 +1133,88 @@ int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t
     R3D_HIP(ctx, hipMemcpyAsync(weight, d_w, (size_t)n * TSDF_UNIT * 4, hipMemcpyDeviceToHost, st));
     if (color) R3D_HIP(ctx, hipMemcpyAsync(colour, d_c, (size_t)n * TSDF_UNIT * 24, hipMemcpyDeviceToHost, st));
     R3D_HIP(ctx, hipStreamSynchronize(st));
+    return R3D_OK;
+}
+
+int r3d_mesh_from_volume(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, int64_t cap_triangles, double *vertices, double *colors, int32_t *triangles,
+                         int64_t *out_nv, int64_t *out_nt) {
+    R3D_ROCTX_RANGE("r3d_mesh_from_volume");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_mesh_args_ok(ctx, vol, cap_vertices, cap_triangles, vertices, colors, triangles, out_nv, out_nt)) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    return tsdf_mesh(vol, ar, cap_vertices, cap_triangles, nullptr, nullptr, nullptr, out_nv, out_nt, true, vertices, colors, triangles);
+}
+
+int r3d_mesh_from_volume_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, int64_t cap_triangles, double *d_vertices, double *d_colors,
+                             int32_t *d_triangles, int64_t *out_nv, int64_t *out_nt) {
+    R3D_ROCTX_RANGE("r3d_mesh_from_volume_dev");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_mesh_args_ok(ctx, vol, cap_vertices, cap_triangles, d_vertices, d_colors, d_triangles, out_nv, out_nt)) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    if (int rc = tsdf_mesh(vol, ar, cap_vertices, cap_triangles, d_vertices, d_colors, d_triangles, out_nv, out_nt, false, nullptr, nullptr, nullptr)) return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the emitting kernels read arena buffers the next call may hand out again
+    return R3D_OK;
+}
+
+int r3d_debug_volume_load_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t n, const int32_t *idx3, const float *tsdf, const float *weight, const double *colour) {
+    R3D_ROCTX_RANGE("r3d_debug_volume_load_units");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = tsdf_vol_ok(ctx, vol, "debug_volume_load_units")) return rc;
+    const bool color = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    if (n < 0 || n > (1 << 22) || (n > 0 && (!idx3 || !tsdf || !weight || (color && !colour))))
+        return r3d_fail(ctx, R3D_E_BADARG, "debug_volume_load_units: a missing array, a negative count or more than 2^22 units");
+    std::vector<unsigned long long> keys((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t *u = idx3 + i * 3;
+        for (int k = 0; k < 3; k++)
+            if (u[k] < -TSDF_IDX_LIMIT || u[k] >= TSDF_IDX_LIMIT)
+                return r3d_fail(ctx, R3D_E_BADARG, "debug_volume_load_units: unit %lld has an index outside +-2^20", (long long)i);
+        keys[(size_t)i] = tsdf_pack(u[0], u[1], u[2]);
+    }
+    {
+        std::vector<unsigned long long> sorted(keys);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return r3d_fail(ctx, R3D_E_BADARG, "debug_volume_load_units: a unit index occurs twice");
+    }
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (n > vol->cap) {
+        if (int rc = tsdf_resize(vol, (int)n)) {   // nothing of the volume has changed yet; the table may have been cleared
+            const std::string why = ctx->err;
+            (void)tsdf_clear_table(vol);
+            ctx->err = why;
+            return rc;
+        }
+        vol->growths++;
+    }
+    const size_t used = (size_t)n * TSDF_UNIT, old_used = (size_t)vol->n_units * TSDF_UNIT;
+    if (n) {
+        R3D_HIP(ctx, hipMemcpyAsync(vol->unit_keys.p, keys.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+        R3D_HIP(ctx, hipMemcpyAsync(vol->tsdf.p, tsdf, used * 4, hipMemcpyHostToDevice, st));
+        R3D_HIP(ctx, hipMemcpyAsync(vol->weight.p, weight, used * 4, hipMemcpyHostToDevice, st));
+        if (color)
+            for (int ch = 0; ch < 3; ch++)   // host rows [unit][channel][4096] -> plane ch
+                R3D_HIP(ctx, hipMemcpy2DAsync(vol->c[ch].p, TSDF_UNIT * 8, colour + (size_t)ch * TSDF_UNIT, 3 * TSDF_UNIT * 8, TSDF_UNIT * 8, (size_t)n,
+                                              hipMemcpyHostToDevice, st));
+    }
+    if (old_used > used) {   // pool blocks past the units are zero, as k_tsdf_assign expects
+        R3D_HIP(ctx, hipMemsetAsync((float *)vol->tsdf.p + used, 0, (old_used - used) * 4, st));
+        R3D_HIP(ctx, hipMemsetAsync((float *)vol->weight.p + used, 0, (old_used - used) * 4, st));
+        if (color)
+            for (auto &p : vol->c) R3D_HIP(ctx, hipMemsetAsync((double *)p.p + used, 0, (old_used - used) * 8, st));
+    }
+    vol->n_units = (int)n;
+    if (int rc = tsdf_clear_table(vol)) return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(st));   // the host arrays are the caller's again
+    return R3D_OK;
+}
+
+int r3d_debug_mc_table(int8_t *tri256x16) {
+    if (!tri256x16) return R3D_E_BADARG;
+    memcpy(tri256x16, TSDF_MC_TRI, sizeof(TSDF_MC_TRI));
     return R3D_OK;
 }
 

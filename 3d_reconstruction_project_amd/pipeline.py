@@ -477,10 +477,11 @@ def poses_from_edges(edges):
     return poses
 
 
-def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, **volume_options):
+def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, mesh=False, **volume_options):
     """test/check84.py:41-44,295,307: every frame into a ScalableTSDFVolume with extrinsic = inv(pose), then
     extract_point_cloud().  frames: (colour, depth uint16) pairs or cloud_ops.RGBDImage, as odometry_edges takes them; camera:
-    cloud_ops.depth_camera(...); poses: camera-to-world 4x4 per frame (poses_from_edges).  -> PointCloud with normals[, colours]"""
+    cloud_ops.depth_camera(...); poses: camera-to-world 4x4 per frame (poses_from_edges).  -> PointCloud with normals[, colours];
+    mesh=True: extract_triangle_mesh() instead -> TriangleMesh"""
     if len(poses) != len(frames):
         raise ValueError(f"{len(frames)} frames but {len(poses)} poses")
     imgs = [f if isinstance(f, cloud_ops.RGBDImage) else cloud_ops.rgbd_image(f[0], f[1], camera.depth_scale, camera.depth_trunc) for f in frames]
@@ -488,4 +489,4 @@ def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=No
     with tsdf.ScalableTSDFVolume(voxel_length, sdf_trunc, kind, ctx=ctx, **volume_options) as volume:
         for img, pose in zip(imgs, poses):
             volume.integrate(img, camera, np.linalg.inv(np.asarray(pose, dtype=np.float64).reshape(4, 4)))
-        return volume.extract_point_cloud()
+        return volume.extract_triangle_mesh() if mesh else volume.extract_point_cloud()

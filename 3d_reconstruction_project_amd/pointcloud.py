@@ -76,6 +76,52 @@ class PointCloud:
         return self
 
 
+class TriangleMesh:
+    """Minimal stand-in for open3d.geometry.TriangleMesh, what ScalableTSDFVolume.extract_triangle_mesh returns: vertices float64
+    [n,3], vertex_colors float64 [n,3] or None, triangles int32 [m,3], vertex_normals float64 [n,3] or None (until
+    compute_vertex_normals).  io_formats.write_ply(path, mesh.vertices, colors=mesh.vertex_colors, faces=mesh.triangles) saves it."""
+
+    def __init__(self, vertices=None, triangles=None, vertex_colors=None, vertex_normals=None):
+        self.vertices = _arr(vertices)
+        self.triangles = np.zeros((0, 3), np.int32) if triangles is None else np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        self.vertex_colors = None if vertex_colors is None else _arr(vertex_colors)
+        self.vertex_normals = None if vertex_normals is None else _arr(vertex_normals)
+
+    def has_vertices(self):
+        return len(self.vertices) > 0
+
+    def has_triangles(self):
+        return len(self.vertices) > 0 and len(self.triangles) > 0
+
+    def has_vertex_colors(self):
+        return self.vertex_colors is not None and len(self.vertices) > 0 and len(self.vertex_colors) == len(self.vertices)
+
+    def has_vertex_normals(self):
+        return self.vertex_normals is not None and len(self.vertices) > 0 and len(self.vertex_normals) == len(self.vertices)
+
+    def compute_vertex_normals(self):
+        """Open3D's scheme [recalled]: every triangle adds its unnormalised cross product (v1 - v0) x (v2 - v0) to its three
+        vertices, in triangle order; the sums are normalised, a zero sum stays zero.  On the host in numpy: a helper."""
+        v, t = self.vertices, self.triangles
+        normals = np.zeros((len(v), 3))
+        if len(t):
+            face = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+            np.add.at(normals, t.reshape(-1), np.repeat(face, 3, axis=0))       # unbuffered: a vertex's sum runs in triangle order
+        length = np.sqrt((normals * normals).sum(1))
+        with np.errstate(all="ignore"):
+            self.vertex_normals = np.where(length[:, None] != 0, normals / length[:, None], normals)
+        return self
+
+    def transform(self, T):
+        from . import cloud_ops
+        T = np.asarray(T, dtype=np.float64)
+        if len(self.vertices):
+            self.vertices = cloud_ops.transform_points(self.vertices, T)
+        if self.has_vertex_normals():
+            self.vertex_normals = cloud_ops.transform_points(self.vertex_normals, T, rotate_only=True)
+        return self
+
+
 def as_arrays(pcd):
     """(points, colors|None, normals|None) float64 arrays from a PointCloud-like object or an (N,3) array."""
     if isinstance(pcd, np.ndarray):

@@ -6,7 +6,7 @@ import enum
 import numpy as np
 
 from . import _lib, cloud_ops
-from .pointcloud import PointCloud
+from .pointcloud import PointCloud, TriangleMesh
 
 _vp, _i32, _i64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -32,6 +32,7 @@ class TsdfInfo(ctypes.Structure):
 
 _integrate_f32_sig = ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _dbl, _dbl, _dbl, _vp], ctypes.c_int)
 _extract_sig = ([_vp, _vp, _i64, _vp, _vp, _vp, _i64p], ctypes.c_int)
+_mesh_sig = ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64p, _i64p], ctypes.c_int)
 _lib.register({
     "r3d_tsdf_create": ([_vp, ctypes.POINTER(TsdfParams), ctypes.POINTER(_vp)], ctypes.c_int),
     "r3d_tsdf_destroy": ([_vp, _vp], ctypes.c_int),
@@ -43,6 +44,10 @@ _lib.register({
     "r3d_tsdf_extract_point_cloud": _extract_sig,
     "r3d_tsdf_extract_point_cloud_dev": _extract_sig,
     "r3d_debug_tsdf_units": ([_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64p], ctypes.c_int),
+    "r3d_mesh_from_volume": _mesh_sig,
+    "r3d_mesh_from_volume_dev": _mesh_sig,
+    "r3d_debug_volume_load_units": ([_vp, _vp, _i64, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "r3d_debug_mc_table": ([_vp], ctypes.c_int),
 })
 
 
@@ -164,6 +169,47 @@ class ScalableTSDFVolume:
         self.ctx.call("r3d_tsdf_extract_point_cloud_dev", self._h, int(capacity), _vp(d_points), _vp(d_normals), _vp(d_colors), ctypes.byref(n))
         return n.value
 
+    # ---- triangle mesh
+    def mesh_counts(self):
+        """-> (vertices, triangles) of extract_triangle_mesh()"""
+        nv, nt = ctypes.c_int64(), ctypes.c_int64()
+        self.ctx.call("r3d_mesh_from_volume", self._h, 0, 0, None, None, None, ctypes.byref(nv), ctypes.byref(nt))
+        return nv.value, nt.value
+
+    def extract_triangle_mesh(self):
+        """volume.extract_triangle_mesh(): marching cubes on the device -> TriangleMesh (no vertex normals, as in Open3D: call
+        compute_vertex_normals()); vertices and triangles in this package's order ("Triangle mesh")"""
+        nv, nt = self.mesh_counts()
+        vert, tri = np.empty((nv, 3)), np.empty((nt, 3), np.int32)
+        col = np.empty((nv, 3)) if self.has_color else None
+        if nv:
+            gv, gt = ctypes.c_int64(), ctypes.c_int64()
+            self.ctx.call("r3d_mesh_from_volume", self._h, nv, nt, _ptr(vert), _ptr(col), _ptr(tri), ctypes.byref(gv), ctypes.byref(gt))
+            assert (gv.value, gt.value) == (nv, nt)
+        return TriangleMesh(vert, tri, col)
+
+    def extract_mesh_device(self, d_vertices, d_colors, d_triangles, cap_vertices, cap_triangles):
+        """r3d_mesh_from_volume_dev: device pointers to float64 [cap_vertices][3] (twice) and int32 [cap_triangles][3] arrays ->
+        the numbers of vertex and triangle rows written"""
+        nv, nt = ctypes.c_int64(), ctypes.c_int64()
+        self.ctx.call("r3d_mesh_from_volume_dev", self._h, int(cap_vertices), int(cap_triangles), _vp(d_vertices), _vp(d_colors), _vp(d_triangles),
+                      ctypes.byref(nv), ctypes.byref(nt))
+        return nv.value, nt.value
+
+    def load_units(self, idx, tsdf, weight, colour=None):
+        """the inverse of debug_units(), for the tests: the volume's content becomes these units (keys in any order)"""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1, 3)
+        n = len(idx)
+        tsdf = np.ascontiguousarray(tsdf, dtype=np.float32).reshape(n, UNIT_VOXELS)
+        weight = np.ascontiguousarray(weight, dtype=np.float32).reshape(n, UNIT_VOXELS)
+        if self.has_color:
+            if colour is None:
+                raise ValueError("an RGB8 volume needs the colour planes")
+            colour = np.ascontiguousarray(colour, dtype=np.float64).reshape(n, 3, UNIT_VOXELS)
+        else:
+            colour = None
+        self.ctx.call("r3d_debug_volume_load_units", self._h, n, _ptr(idx), _ptr(tsdf), _ptr(weight), _ptr(colour))
+
     def debug_units(self):
         """-> unit indices int32 [n,3] in (X, Y, Z) order, tsdf float32 [n,4096], weight float32 [n,4096], colour float64
         [n,3,4096] (None without colour); voxel (x, y, z) at x*256 + y*16 + z"""
@@ -176,3 +222,12 @@ class ScalableTSDFVolume:
             got = ctypes.c_int64()
             self.ctx.call("r3d_debug_tsdf_units", self._h, n, _ptr(idx), _ptr(t), _ptr(w), _ptr(c), ctypes.byref(got))
         return idx, t, w, c
+
+
+def mc_table():
+    """-> the marching-cubes triangle table the library was built with, int8 [256,16] (r3d_debug_mc_table; needs no device)"""
+    out = np.empty((256, 16), np.int8)
+    rc = _lib.load().r3d_debug_mc_table(_ptr(out))
+    if rc != _lib.R3D_OK:
+        raise _lib.R3DError(rc, "r3d_debug_mc_table failed")
+    return out

@@ -653,7 +653,8 @@ int r3d_debug_rgbd_iteration(r3d_ctx *ctx, const r3d_odometry_params *p, const f
  * UniformTSDFVolume.cpp]: Open3D is absent and the reference recorded no volume, so parity is UNPINNED; tests/tsdf_ref.py restates
  * the contract.  A sparse volume of 16^3-voxel units behind a device hash table; tsdf and weight float32, colour three float64 per
  * voxel.  The same bits on every run: which pool slot a unit gets is a race, everything a caller can see is ordered by unit index
- * (X, then Y, then Z).  extract_triangle_mesh, Gray32 and unit resolutions other than 16 are not built. */
+ * (X, then Y, then Z).  extract_triangle_mesh is r3d_mesh_from_volume below.  Gray32 and unit resolutions other than 16 are not
+ * built. */
 #define R3D_TSDF_COLOR_NONE 0
 #define R3D_TSDF_COLOR_RGB8 1
 typedef struct r3d_tsdf r3d_tsdf;
@@ -704,6 +705,26 @@ int r3d_tsdf_extract_point_cloud_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, d
  * volumes; else ignored) */
 int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t *idx3, float *tsdf, float *weight, double *colour,
                          int64_t *out_n);
+/* replaces: volume.extract_triangle_mesh() (Open3D ScalableTSDFVolume::ExtractTriangleMesh [recalled, 0.18]; parity UNPINNED like
+ * the cloud's).  Marching cubes on the device over every cube whose base voxel lies in an existing unit and whose eight corners
+ * all lie in existing units with weight != 0 (no 0.98 bound here); DESIGN.md section 4, "Triangle mesh", is the contract,
+ * tests/tsdf_mesh_ref.py restates it.  *out_nv / *out_nt = the numbers of vertices and triangles, always.  Both capacities 0: the
+ * counts alone.  A capacity below its count: R3D_E_BADARG and nothing is written.  Otherwise vertices and (RGB8 volumes; else
+ * ignored, may be NULL) colors receive *out_nv rows of 3 doubles, triangles *out_nt rows of 3 int32 vertex numbers, faces looking
+ * from inside (tsdf < 0) outward.  No vertex normals.  Order: a vertex belongs to the lower voxel of its edge: units by (X, Y, Z),
+ * voxels by flat index, axes x, y, z; triangles by base voxel in the same order, then in the table's order.  More than 2^31 - 1
+ * vertices or triangles: R3D_E_UNSUPPORTED.  The _dev form writes DEVICE arrays and returns when they are complete. */
+int r3d_mesh_from_volume(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, int64_t cap_triangles, double *vertices, double *colors,
+                         int32_t *triangles, int64_t *out_nv, int64_t *out_nt);
+int r3d_mesh_from_volume_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, int64_t cap_triangles, double *d_vertices,
+                             double *d_colors, int32_t *d_triangles, int64_t *out_nv, int64_t *out_nt);
+/* the inverse of r3d_debug_tsdf_units, for the tests: the volume's content becomes these n units (arrays laid out as that call
+ * returns them, keys in any order; colour is read by RGB8 volumes only).  A key that occurs twice or an index outside +-2^20:
+ * R3D_E_BADARG and the volume is unchanged.  The frame count stays; the pool grows to n units when it is smaller. */
+int r3d_debug_volume_load_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t n, const int32_t *idx3, const float *tsdf, const float *weight,
+                                const double *colour);
+/* the marching-cubes triangle table the library was built with, int8 [256][16]; host only: no context, no device */
+int r3d_debug_mc_table(int8_t *tri256x16);
 
 
 /* ---- per-frame stages either side of the matcher in Calib_depth/depth*.py --------------

@@ -1,6 +1,6 @@
 """Time of the TSDF volume (r3d_tsdf_integrate_f32_dev, r3d_tsdf_extract_point_cloud_dev) on a 16-frame sequence at 640x480.
 
-    python tools/gpu_bench_tsdf.py [--repeats 10] [--out profiles/tsdf.json] [--lib other/libr3d_hip.so]
+    python tools/gpu_bench_tsdf.py [--repeats 10] [--out profiles/tsdf.json] [--mesh-out profiles/tsdf_mesh.json] [--lib other/libr3d_hip.so]
 
 The frames are the synthetic height-field scene of tests/rgbd_scene.py along a smooth pose path (1.5 / -2 / 1 degrees and
 6 / -3 / 4 cm from the first to the last frame), colour = the intensity plane x 255 in three channels, planes resident on the
@@ -13,7 +13,13 @@ bytes_touched_state is the figure of merit the design names: units touched x 409
 24 colour), read and written, and share_of_peak is that over integrate_ms against 8 TB/s.  It is an upper bound of what the
 kernel moves: a column none of whose 16 voxels updates (outside the image, on a hole, far behind the surface) loads and stores
 nothing.  The numpy restatement's host time for one frame stands beside it, the restatement's case A once more (the largest
-normal difference of the GPU tests), and the two timed lines of the reference's own log as context: unknown hardware, no target."""
+normal difference of the GPU tests), and the two timed lines of the reference's own log as context: unknown hardware, no target.
+
+The mesh leg (r3d_mesh_from_volume_dev on the same volume, its own file) times two calls with events on the context stream: the
+counting call (both capacities 0: cube bytes, counts, unit offsets and the 16-byte read of the totals) and the whole call into
+device arrays; emit_ms is their difference (vertices with their ids, then triangles).  bytes_minimum is what the passes cannot
+avoid, the state once (units x 4096 x 8 B, or 32 B with colour) and the rows written; share_of_peak is that over the whole call
+against 8 TB/s.  The cloud extraction's time on the same volume stands beside it."""
 import argparse
 import hashlib
 import importlib
@@ -38,10 +44,45 @@ def _sha(path):
         return hashlib.sha256(f.read()).hexdigest()
 
 
+def mesh_leg(r3d, ctx, volume, repeats, ev, cloud):
+    """extract_triangle_mesh of the volume as the frames left it -> the report for profiles/tsdf_mesh.json"""
+    nv, nt = volume.mesh_counts()
+    units = len(volume)
+    d_out = [ctx.alloc(max(nv, 1) * 24), ctx.alloc(max(nv, 1) * 24), ctx.alloc(max(nt, 1) * 12)]
+    count_runs, whole_runs = [], []
+    for i in range(repeats + 2):
+        ctx.record(ev[0])
+        counts = volume.mesh_counts()
+        ctx.record(ev[1])
+        count_ms = ctx.elapsed_ms(ev[0], ev[1])
+        ctx.record(ev[0])
+        got = volume.extract_mesh_device(d_out[0], d_out[1], d_out[2], nv, nt)
+        ctx.record(ev[1])
+        assert counts == got == (nv, nt)
+        if i >= 2:
+            count_runs.append(count_ms)
+            whole_runs.append(ctx.elapsed_ms(ev[0], ev[1]))
+    for ptr in d_out:
+        ctx.free(ptr)
+    count_ms, whole_ms = statistics.median(count_runs), statistics.median(whole_runs)
+    moved = units * 4096 * BYTES_PER_VOXEL + nv * 48 + nt * 12
+    return dict(config=f"the volume of profiles/tsdf.json after its {FRAMES} frames ({units} units, RGB8); medians of {repeats} runs after two warm-up "
+                       "runs; events on the context stream around r3d_mesh_from_volume_dev",
+                vertices=nv, triangles=nt, units=units, count_ms=count_ms, whole_ms=whole_ms, emit_ms=whole_ms - count_ms,
+                count_ms_runs=[round(x, 4) for x in count_runs], whole_ms_runs=[round(x, 4) for x in whole_runs],
+                bytes_minimum=moved, share_of_peak=moved / (whole_ms * 1e-3) / PEAK_BYTES_PER_S,
+                cloud_extract_ms=cloud["extract_ms"], cloud_points=cloud["points"],
+                note="count_ms: the call with both capacities 0 (cube bytes, counts, offsets, the read of the totals); whole_ms: the call into device "
+                     "arrays, which repeats the counting; emit_ms: their difference.  bytes_minimum: the state once (units x 4096 x 32 B) plus the "
+                     "vertex, colour and triangle rows written; the passes also write and read the cube bytes (1 B per voxel) and the vertex ids "
+                     "(12 B per voxel)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tsdf.json"))
+    ap.add_argument("--mesh-out", default=os.path.join(ROOT, "profiles", "tsdf_mesh.json"))
     ap.add_argument("--lib", default=None, help="another build of libr3d_hip.so to time instead of lib/libr3d_hip.so")
     a = ap.parse_args()
     r3d = importlib.import_module("3d_reconstruction_project_amd")
@@ -108,6 +149,11 @@ def main():
                                 note="wall_ms: host time of one run, 16 x (integrate + r3d_tsdf_stats, which waits for the frame)"),
                   extract=dict(extract_ms=statistics.median(extract_runs), points=n, extract_ms_runs=[round(x, 4) for x in extract_runs],
                                note="count + unit offsets + emit into device arrays (r3d_tsdf_extract_point_cloud_dev), events on the context stream"))
+    mesh_report = mesh_leg(r3d, ctx, volume, a.repeats, ev, report["extract"])
+    mesh_report["library_sha256"], mesh_report["tsdf_hip_sha256"] = report["library_sha256"], report["tsdf_hip_sha256"]
+    with open(a.mesh_out, "w") as f:
+        json.dump(mesh_report, f, indent=1)
+    print(json.dumps(mesh_report))
     t0 = time.perf_counter()
     host = ref.Volume(VOXEL_LENGTH, SDF_TRUNC, True, 4)
     host.integrate(frames[0][0], frames[0][1], cam, extrinsics[0])
