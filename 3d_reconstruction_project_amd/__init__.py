@@ -4,7 +4,7 @@ The directory name starts with a digit (it mirrors the upstream project name), s
     import importlib; r3d = importlib.import_module("3d_reconstruction_project_amd")
 or through the `r3d` alias module at the repository root (`import r3d`).
 """
-from . import (_lib, cloud_ops, distributed, io_formats, pipeline, normal_estimation, orientation, pointcloud, pointcloud_alignment,  # noqa: F401
+from . import (_lib, cloud_ops, distributed, io_formats, mesh_ops, pipeline, normal_estimation, orientation, pointcloud, pointcloud_alignment,  # noqa: F401
                pointcloud_processing, stereo_prepost, stereo_sgbm, synth, tsdf)
 from ._lib import Context, R3DError, default_context  # noqa: F401
 from .cloud_ops import (compute_fpfh_feature, compute_rgbd_odometry, correspondences_from_features, registration_fgr_based_on_correspondence,  # noqa: F401
@@ -17,5 +17,6 @@ from .pointcloud import PointCloud, TriangleMesh  # noqa: F401,E402
 from .pointcloud_alignment import GeneralizedICPAlignment, PointCloudAlignment, align, multi_scale_icp  # noqa: F401,E402
 from .pointcloud_processing import PointCloudProcessingWithCUDA  # noqa: F401,E402
 from .tsdf import ScalableTSDFVolume, TSDFVolumeColorType  # noqa: F401,E402
+from .mesh_ops import FilterScope  # noqa: F401,E402
 from .stereo_prepost import (COLOR_BGR2GRAY, CV_16SC2, INTER_LINEAR, NORM_MINMAX, DisparityWLSFilter, createDisparityWLSFilter,  # noqa: F401,E402
                              cvtColor, initUndistortRectifyMap, normalize, remap)

@@ -3721,6 +3721,9 @@ __global__ void __launch_bounds__(FGR_OPT_BLOCK) k_fgr_optimize(const double *__
 
 }  // namespace
 
+// the int32 scan for the other translation units (trimesh.hip)
+int r3d_exclusive_scan_i32(r3d_ctx *ctx, DevArena &ar, const int *in, int *out, int64_t n) { return dev_exclusive_scan<int>(ctx, ar, in, out, n); }
+
 // ================================================================================================ C ABI
 // ---- device-pointer cores shared by the host-buffer entry points and the fused device-resident chain -------------
 

@@ -213,3 +213,6 @@ int r3d_sgm_hh_partial(r3d_ctx *ctx, int n_dirs);
 int r3d_selftest_run(r3d_ctx *ctx);
 int r3d_speckle_run(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, int16_t *d_img, int w, int h, int newVal, int maxSize, int maxDiff);
 int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int write, int delay, int reps, float *ms);
+
+// cloud.hip: exclusive scan of n ints on the ctx stream (in and out 16-byte aligned and distinct; tiles of 4096 elements)
+int r3d_exclusive_scan_i32(r3d_ctx *ctx, DevArena &ar, const int *in, int *out, int64_t n);

@@ -477,16 +477,33 @@ def poses_from_edges(edges):
     return poses
 
 
-def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, mesh=False, **volume_options):
+def mesh_postprocess(mesh, smooth_iterations=5, lambda_filter=0.5, ctx=None):
+    """The tail of mesh_reconstruction.py:22-37 after its Poisson call, restricted to what this package has, in the order of
+    SURVEY.md section 2: filter_smooth_laplacian(smooth_iterations), remove_degenerate_triangles, remove_unreferenced_vertices and
+    the non-finite scrub of check84.py:315-322, then compute_vertex_normals.  ASSUMED (the reference source is not in this
+    repository): lambda 0.5 and FilterScope.All, Open3D's defaults; the duplicate and non-manifold clean-ups the reference may
+    also call are not built and the marching-cubes mesh has none to remove.  The non-finite vertices go before
+    the unreferenced ones, so that a vertex left without triangles by the scrub goes too.  -> a new TriangleMesh"""
+    out = mesh.filter_smooth_laplacian(int(smooth_iterations), lambda_filter, ctx=ctx)
+    out.remove_degenerate_triangles(ctx=ctx).remove_non_finite_vertices(ctx=ctx).remove_unreferenced_vertices(ctx=ctx)
+    return out.compute_vertex_normals(device=True, ctx=ctx)
+
+
+def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, mesh=False, postprocess=False, **volume_options):
     """test/check84.py:41-44,295,307: every frame into a ScalableTSDFVolume with extrinsic = inv(pose), then
     extract_point_cloud().  frames: (colour, depth uint16) pairs or cloud_ops.RGBDImage, as odometry_edges takes them; camera:
     cloud_ops.depth_camera(...); poses: camera-to-world 4x4 per frame (poses_from_edges).  -> PointCloud with normals[, colours];
-    mesh=True: extract_triangle_mesh() instead -> TriangleMesh"""
+    mesh=True: extract_triangle_mesh() instead -> TriangleMesh; postprocess=True (with mesh=True): mesh_postprocess() of it"""
     if len(poses) != len(frames):
         raise ValueError(f"{len(frames)} frames but {len(poses)} poses")
+    if postprocess and not mesh:
+        raise ValueError("postprocess=True needs mesh=True")
     imgs = [f if isinstance(f, cloud_ops.RGBDImage) else cloud_ops.rgbd_image(f[0], f[1], camera.depth_scale, camera.depth_trunc) for f in frames]
     kind = tsdf.TSDFVolumeColorType.RGB8 if color else tsdf.TSDFVolumeColorType.NoColor
     with tsdf.ScalableTSDFVolume(voxel_length, sdf_trunc, kind, ctx=ctx, **volume_options) as volume:
         for img, pose in zip(imgs, poses):
             volume.integrate(img, camera, np.linalg.inv(np.asarray(pose, dtype=np.float64).reshape(4, 4)))
-        return volume.extract_triangle_mesh() if mesh else volume.extract_point_cloud()
+        if not mesh:
+            return volume.extract_point_cloud()
+        out = volume.extract_triangle_mesh()
+    return mesh_postprocess(out, ctx=ctx) if postprocess else out

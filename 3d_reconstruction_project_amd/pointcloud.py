@@ -79,13 +79,17 @@ class PointCloud:
 class TriangleMesh:
     """Minimal stand-in for open3d.geometry.TriangleMesh, what ScalableTSDFVolume.extract_triangle_mesh returns: vertices float64
     [n,3], vertex_colors float64 [n,3] or None, triangles int32 [m,3], vertex_normals float64 [n,3] or None (until
-    compute_vertex_normals).  io_formats.write_ply(path, mesh.vertices, colors=mesh.vertex_colors, faces=mesh.triangles) saves it."""
+    compute_vertex_normals).  io_formats.write_ply(path, mesh.vertices, colors=mesh.vertex_colors, faces=mesh.triangles) saves it.
+    The filters, compute_triangle_normals, compute_adjacency_list and the remove_* clean-ups run on the device (mesh_ops.py);
+    triangle_normals (float64 [m,3]) and adjacency_list (a list of ascending int32 arrays) are None until computed."""
 
     def __init__(self, vertices=None, triangles=None, vertex_colors=None, vertex_normals=None):
         self.vertices = _arr(vertices)
         self.triangles = np.zeros((0, 3), np.int32) if triangles is None else np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
         self.vertex_colors = None if vertex_colors is None else _arr(vertex_colors)
         self.vertex_normals = None if vertex_normals is None else _arr(vertex_normals)
+        self.triangle_normals = None
+        self.adjacency_list = None
 
     def has_vertices(self):
         return len(self.vertices) > 0
@@ -99,9 +103,14 @@ class TriangleMesh:
     def has_vertex_normals(self):
         return self.vertex_normals is not None and len(self.vertices) > 0 and len(self.vertex_normals) == len(self.vertices)
 
-    def compute_vertex_normals(self):
+    def compute_vertex_normals(self, device=False, ctx=None):
         """Open3D's scheme [recalled]: every triangle adds its unnormalised cross product (v1 - v0) x (v2 - v0) to its three
-        vertices, in triangle order; the sums are normalised, a zero sum stays zero.  On the host in numpy: a helper."""
+        vertices, in triangle order; the sums are normalised, a zero sum stays zero.  On the host in numpy: a helper.
+        device=True: the same sums in the same order on the device (mesh_ops.vertex_normals), bit for bit."""
+        if device:
+            from . import mesh_ops
+            self.vertex_normals = mesh_ops.vertex_normals(self.vertices, self.triangles, ctx=ctx)
+            return self
         v, t = self.vertices, self.triangles
         normals = np.zeros((len(v), 3))
         if len(t):
@@ -111,6 +120,90 @@ class TriangleMesh:
         with np.errstate(all="ignore"):
             self.vertex_normals = np.where(length[:, None] != 0, normals / length[:, None], normals)
         return self
+
+    def has_triangle_normals(self):
+        return self.triangle_normals is not None and len(self.triangles) > 0 and len(self.triangle_normals) == len(self.triangles)
+
+    def has_adjacency_list(self):
+        return self.adjacency_list is not None and len(self.vertices) > 0 and len(self.adjacency_list) == len(self.vertices)
+
+    def compute_triangle_normals(self, ctx=None):
+        """(v1 - v0) x (v2 - v0) per triangle, normalised; a zero vector stays zero"""
+        from . import mesh_ops
+        self.triangle_normals = mesh_ops.triangle_normals(self.vertices, self.triangles, ctx=ctx)
+        return self
+
+    def compute_adjacency_list(self, ctx=None):
+        """adjacency_list[v]: the vertices that share a triangle with v, ascending (Open3D keeps unordered sets)"""
+        from . import mesh_ops
+        off, nb = mesh_ops.adjacency(len(self.vertices), self.triangles, ctx=ctx)
+        self.adjacency_list = [nb[off[v]:off[v + 1]] for v in range(len(self.vertices))]
+        return self
+
+    # ---- smoothing filters: a new mesh, as in Open3D; triangles unchanged, unfiltered attributes copied
+    def _filtered(self, kind, number_of_iterations, lambda_filter, mu, filter_scope, ctx):
+        from . import mesh_ops
+        vert, nrm, col = mesh_ops.smooth(self.vertices, self.triangles, kind, number_of_iterations, lambda_filter, mu, filter_scope,
+                                         self.vertex_normals if self.has_vertex_normals() else None,
+                                         self.vertex_colors if self.has_vertex_colors() else None, ctx=ctx)
+        out = TriangleMesh(vert, self.triangles.copy(), col, nrm)
+        if self.triangle_normals is not None:
+            out.triangle_normals = self.triangle_normals.copy()
+        return out
+
+    def filter_smooth_simple(self, number_of_iterations=1, filter_scope=0, ctx=None):
+        """every vertex becomes the mean of itself and its neighbours, number_of_iterations times"""
+        from . import mesh_ops
+        return self._filtered(mesh_ops.SMOOTH_SIMPLE, number_of_iterations, 0.0, 0.0, filter_scope, ctx)
+
+    def filter_smooth_laplacian(self, number_of_iterations=1, lambda_filter=0.5, filter_scope=0, ctx=None):
+        """v += lambda (inverse-distance weighted mean of the neighbours - v), number_of_iterations times (mesh_reconstruction.py:22-37)"""
+        from . import mesh_ops
+        return self._filtered(mesh_ops.SMOOTH_LAPLACIAN, number_of_iterations, lambda_filter, 0.0, filter_scope, ctx)
+
+    def filter_smooth_taubin(self, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, filter_scope=0, ctx=None):
+        """a Laplacian step with lambda, then one with mu, number_of_iterations times: smooths without the shrinkage"""
+        from . import mesh_ops
+        return self._filtered(mesh_ops.SMOOTH_TAUBIN, number_of_iterations, lambda_filter, mu, filter_scope, ctx)
+
+    # ---- clean-ups: in place, survivors keep their order, colours and normals travel with their vertices
+    def _compact(self, flags=0, vertex_keep=None, triangle_keep=None, ctx=None):
+        from . import mesh_ops
+        vert, tri, nrm, col = mesh_ops.compact(self.vertices, self.triangles, flags, vertex_keep, triangle_keep,
+                                               self.vertex_normals if self.has_vertex_normals() else None,
+                                               self.vertex_colors if self.has_vertex_colors() else None, ctx=ctx)
+        if len(tri) != len(self.triangles):
+            self.triangle_normals = None            # recompute them: which triangles went is not reported
+        self.vertices, self.triangles = vert, tri
+        # an attribute array that did not match the vertices (has_* false) was not carried: it becomes empty, None stays None
+        self.vertex_normals = nrm if nrm is not None or self.vertex_normals is None else np.zeros((0, 3))
+        self.vertex_colors = col if col is not None or self.vertex_colors is None else np.zeros((0, 3))
+        self.adjacency_list = None
+        return self
+
+    def remove_degenerate_triangles(self, ctx=None):
+        """drops triangles with two equal indices"""
+        from . import mesh_ops
+        return self._compact(mesh_ops.DROP_DEGENERATE, ctx=ctx)
+
+    def remove_unreferenced_vertices(self, ctx=None):
+        from . import mesh_ops
+        return self._compact(mesh_ops.DROP_UNREFERENCED, ctx=ctx)
+
+    def remove_vertices_by_mask(self, vertex_mask, ctx=None):
+        """vertex_mask: truthy where a vertex is REMOVED (Open3D's sense); also drops every triangle that touches one"""
+        keep = ~(np.asarray(vertex_mask).reshape(-1) != 0)
+        return self._compact(0, vertex_keep=keep, ctx=ctx)
+
+    def remove_triangles_by_mask(self, triangle_mask, ctx=None):
+        """triangle_mask: truthy where a triangle is REMOVED"""
+        keep = ~(np.asarray(triangle_mask).reshape(-1) != 0)
+        return self._compact(0, triangle_keep=keep, ctx=ctx)
+
+    def remove_non_finite_vertices(self, ctx=None):
+        """the scrub of check84.py:315-322: remove_vertices_by_mask of the rows with a NaN or an infinity"""
+        from . import mesh_ops
+        return self._compact(mesh_ops.DROP_NON_FINITE, ctx=ctx)
 
     def transform(self, T):
         from . import cloud_ops

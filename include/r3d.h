@@ -792,6 +792,69 @@ int r3d_wls_filter_dev(r3d_ctx *ctx, const r3d_wls_params *p, const int16_t *d_d
 int r3d_normalize_minmax_s16(r3d_ctx *ctx, const int16_t *src, int64_t n, double alpha, double beta, int16_t *dst);
 int r3d_normalize_minmax_s16_dev(r3d_ctx *ctx, const int16_t *d_src, int64_t n, double alpha, double beta, int16_t *d_dst);
 
+/* ---- triangle-mesh operations (csrc/trimesh.hip; DESIGN.md section 4, "Triangle-mesh operations") -------------------------------
+ * replaces: mesh.filter_smooth_laplacian(5) and the clean-ups of mesh_reconstruction.py:22-37, the NaN scrub of check84.py:315-322.
+ * A mesh is nv rows of float64 xyz (optionally normals and colours of the same shape) and nt rows of three int32 vertex numbers.
+ * Every entry point refuses (R3D_E_BADARG) a missing required array, a negative count and a triangle index outside [0, nv); no
+ * such index is ever used as an address.  R3D_E_UNSUPPORTED: nv above 2^31 - 2 or 6 nt above 2^31 - 1 (offsets are int32).  nv = 0
+ * or nt = 0 is valid.  The _dev forms take DEVICE arrays, run on the ctx stream and return once their work is done; their output
+ * arrays must not overlap an input array or one another (a kernel would read rows that another thread has replaced): such a call
+ * is refused (R3D_E_BADARG) before anything runs.
+ *
+ * Incidence of vertex v: the corners 3 t + c with triangles[t][c] == v, ascending.  Adjacency: every triangle puts each of its
+ * vertices into the sets of the other two (a degenerate (a, a, b) puts a into its own set); a set is listed once, ascending.
+ * Both come as CSR: offsets[nv + 1], then the entries.  cap = 0 asks for the number of entries only (*out_n); otherwise offsets
+ * and the entries are written when cap >= *out_n and nothing is written when it is not (R3D_E_BADARG). */
+int r3d_trimesh_incidence(r3d_ctx *ctx, int64_t nv, int64_t nt, const int32_t *triangles, int64_t cap, int32_t *offsets, int32_t *corners,
+                          int64_t *out_n);
+int r3d_trimesh_adjacency(r3d_ctx *ctx, int64_t nv, int64_t nt, const int32_t *triangles, int64_t cap, int32_t *offsets, int32_t *neighbours,
+                          int64_t *out_n);
+
+#define R3D_SMOOTH_SIMPLE 0    /* out[v] = (prev[v] + sum of prev[nb]) / (deg + 1), added in adjacency order */
+#define R3D_SMOOTH_LAPLACIAN 1 /* w = 1 / (|prev[v] - prev[nb]| + 1e-12); out[v] = prev[v] + lambda (sum w prev[nb] / sum w - prev[v]) */
+#define R3D_SMOOTH_TAUBIN 2    /* per iteration a Laplacian step with lambda, then one with mu */
+#define R3D_SMOOTH_MAX_ITERATIONS (1 << 20) /* every step is a kernel launch: more iterations are R3D_E_UNSUPPORTED */
+#define R3D_SCOPE_ALL 0        /* Open3D's FilterScope: which of positions, normals and colours are filtered; the others are copied */
+#define R3D_SCOPE_COLOR 1
+#define R3D_SCOPE_NORMAL 2
+#define R3D_SCOPE_VERTEX 3
+/* filter_smooth_simple / _laplacian / _taubin: `iterations` steps from the previous step's arrays, float64, the weights always
+ * from the positions, normals not renormalised.  normals / colors may be NULL (then so may their outputs).  A vertex with an empty
+ * adjacency set keeps its values (Open3D divides 0 / 0 there).  iterations = 0 copies.  Also refused: iterations < 0, lambda or mu
+ * not finite, an unknown kind or scope.  R3D_E_UNSUPPORTED: iterations above R3D_SMOOTH_MAX_ITERATIONS. */
+int r3d_trimesh_smooth(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vertices, const double *normals, const double *colors,
+                       const int32_t *triangles, int32_t kind, int32_t iterations, double lambda, double mu, int32_t scope, double *out_vertices,
+                       double *out_normals, double *out_colors);
+int r3d_trimesh_smooth_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d_vertices, const double *d_normals, const double *d_colors,
+                           const int32_t *d_triangles, int32_t kind, int32_t iterations, double lambda, double mu, int32_t scope,
+                           double *d_out_vertices, double *d_out_normals, double *d_out_colors);
+
+#define R3D_NORMALS_RAW 1 /* leave the cross products (triangles) and their sums (vertices) unnormalised */
+/* compute_triangle_normals: (v1 - v0) x (v2 - v0), normalised; compute_vertex_normals: the unnormalised cross products added in
+ * ascending corner order, then normalised.  A zero vector stays zero.  Either output may be NULL.  Refused: unknown flags. */
+int r3d_trimesh_normals(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vertices, const int32_t *triangles, int32_t flags,
+                        double *triangle_normals, double *vertex_normals);
+int r3d_trimesh_normals_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d_vertices, const int32_t *d_triangles, int32_t flags,
+                            double *d_triangle_normals, double *d_vertex_normals);
+
+#define R3D_COMPACT_DROP_DEGENERATE 1   /* triangles with two equal indices */
+#define R3D_COMPACT_DROP_UNREFERENCED 2 /* vertices no surviving triangle uses */
+#define R3D_COMPACT_DROP_NON_FINITE 4   /* vertices with a NaN or an infinity in their position */
+/* The clean-ups.  vertex_keep / triangle_keep: one byte per row, 0 = remove, or NULL.  Triangles are decided first: a triangle
+ * goes when its mask says so, when DROP_DEGENERATE applies, or when it touches a vertex that its mask or DROP_NON_FINITE removes;
+ * "referenced" then means referenced by a surviving triangle.  Survivors keep their order, triangle indices are renumbered,
+ * normals and colours (NULL or given) travel with their vertices.  *out_nv and *out_nt are always set; cap_vertices = cap_triangles
+ * = 0 asks for them alone; otherwise rows are written when both capacities suffice and nothing is written when one does not
+ * (R3D_E_BADARG).  Refused: unknown flags. */
+int r3d_trimesh_compact(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vertices, const double *normals, const double *colors,
+                        const int32_t *triangles, const uint8_t *vertex_keep, const uint8_t *triangle_keep, int32_t flags, int64_t cap_vertices,
+                        int64_t cap_triangles, double *out_vertices, double *out_normals, double *out_colors, int32_t *out_triangles,
+                        int64_t *out_nv, int64_t *out_nt);
+int r3d_trimesh_compact_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d_vertices, const double *d_normals, const double *d_colors,
+                            const int32_t *d_triangles, const uint8_t *d_vertex_keep, const uint8_t *d_triangle_keep, int32_t flags,
+                            int64_t cap_vertices, int64_t cap_triangles, double *d_out_vertices, double *d_out_normals, double *d_out_colors,
+                            int32_t *d_out_triangles, int64_t *out_nv, int64_t *out_nt);
+
 #ifdef __cplusplus
 }
 #endif
