@@ -225,6 +225,7 @@ _lib.register({
     "r3d_model_voxel_table_stats": ([_vp, _i64p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "r3d_model_debug_voxel_table": ([_vp, ctypes.c_double, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _i64p, ctypes.POINTER(ctypes.c_int32)],
                                     ctypes.c_int),
+    "r3d_model_debug_fail_table_step": ([_vp, ctypes.c_int32], ctypes.c_int),
     "r3d_model_append": ([_vp, _vp, _vp, _vp, ctypes.c_int64], ctypes.c_int),
     "r3d_model_align_append": ([_vp, ctypes.POINTER(AlignParams), _vp, _vp, ctypes.c_int64, _vp, ctypes.POINTER(_lib.IcpStats), _i64p],
                                ctypes.c_int),
@@ -742,6 +743,11 @@ class ResidentModel:
             return dict(n=n, resident=res, keys=None, sums=None, counts=None, means=None, box=None)
         tab = (keys[:n].copy(), sums[:n].copy(), counts[:n].copy()) if res else (None, None, None)
         return dict(n=n, resident=res, keys=tab[0], sums=tab[1], counts=tab[2], means=means[:n].copy(), box=box)
+
+    def debug_fail_table_step(self, step):
+        """r3d_model_debug_fail_table_step (test hook): the next voxel-table call returns an error when it reaches point `step` (1: a
+        rebuild after its build kernel, 2: an update after the slice is added, 3: an update after its merge); one shot, 0 disarms."""
+        self._call("r3d_model_debug_fail_table_step", int(step))
 
     def clear(self):
         self._call("r3d_model_clear")

@@ -5030,25 +5030,65 @@ int r3d_icp(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns
 // r3d_model_download.  Every step runs the same kernels in the same order as the one-shot entry points on the same values
 // (the model is re-voxelised from its resident points, in their original order), so the results are identical to them.
 }  // extern "C"
+namespace {
+// the device arrays of a voxel table, one entry per voxel in key order; all null when there is no table
+struct VtView { const unsigned long long *keys = nullptr; const double *sums = nullptr; const int *cnt = nullptr; };
+// Incremental legacy voxel table of the model's points (k_vt_*), double-buffered for the merge.  The one invariant: `valid` implies
+// that the buffers at `cur` hold exactly the table of the model rows [0, rows) for voxel size `voxel` and minimum corner `min`: n
+// voxels, the rows' maximum corner in `max`.  table_rebuild and table_update keep it by dropping `valid` before they write into a
+// resident buffer and setting it again, with the fields that describe the table, after their last step that can fail: whatever
+// stops them in between, the next call finds no table and rebuilds.
+struct VoxelTable {
+    bool valid = false;
+    double voxel = 0, min[3] = {0, 0, 0}, max[3] = {0, 0, 0};
+    int64_t n = 0, rows = 0;
+    r3d_buf keys[2], sums[2], cnt[2];
+    int cur = 0;
+    int rebuilds = 0, updates = 0;   // successful ones (r3d_model_voxel_table_stats)
+    int fail_step = 0;               // r3d_model_debug_fail_table_step: armed for the next model_target_voxels only
+
+    struct Set { unsigned long long *keys; double *sums; int *cnt; };
+    Set set(int i) const { return {(unsigned long long *)keys[i].p, (double *)sums[i].p, (int *)cnt[i].p}; }
+    Set current() const { return set(cur); }
+    Set other() const { return set(cur ^ 1); }
+    VtView view() const { return valid ? VtView{current().keys, current().sums, current().cnt} : VtView(); }
+    // no table; the buffers and the statistics stay
+    void invalidate() { valid = false; n = rows = 0; }
+    // grow-only room for `voxels` entries in buffer set i; the policy frees before it allocates, so a failure leaves null buffers
+    int reserve(r3d_ctx *ctx, int i, int64_t voxels) {
+        int rc;
+        if ((rc = keys[i].reserve(ctx, ctx->stream, (size_t)voxels * 8, R3D_GROW_VOXEL_TABLE))) return rc;
+        if ((rc = sums[i].reserve(ctx, ctx->stream, (size_t)voxels * 24, R3D_GROW_VOXEL_TABLE))) return rc;
+        return cnt[i].reserve(ctx, ctx->stream, (size_t)voxels * 4, R3D_GROW_VOXEL_TABLE);
+    }
+};
+// Bounding box of the rows [lo, hi) the last alignment appended: computed on the device when they were appended, fetched with the
+// NEXT call's first read-back (no round trip of its own); host_ok: `box` holds it already
+struct PendingBox {
+    r3d_buf dev;
+    int64_t lo = 0, hi = 0;
+    bool host_ok = false;
+    double box[6] = {0, 0, 0, 0, 0, 0};
+
+    bool covers(int64_t a, int64_t b) const { return host_ok && lo == a && hi == b; }
+    void reset() { lo = hi = 0; host_ok = false; }
+    void set(int64_t a, int64_t b) { lo = a; hi = b; }   // the box of rows [a, b) has been enqueued into `dev`
+    // the read-back that brings an enqueued box to `box`; empty when there is none or the host has it (the caller sets host_ok
+    // once the read has come through)
+    PinExtra fetch() {
+        PinExtra e;
+        if (dev.p && hi > lo && !host_ok) { e.host = box; e.dev = dev.p; e.bytes = 48; }
+        return e;
+    }
+};
+}  // namespace
 struct r3d_model {
     r3d_ctx *ctx = nullptr;
     r3d_buf pts, cols, nrms;
     int64_t n = 0;
     bool has_colors = false, has_normals = false;
-    // incremental legacy voxel table of the model's points (k_vt_*): valid for voxel size vt_voxel while the model's minimum
-    // corner is vt_min; covers model rows [0, vt_pts); vt_n voxels in buffers [vt_cur] (double-buffered for the merge)
-    bool vt_valid = false;
-    double vt_voxel = 0, vt_min[3] = {0, 0, 0}, vt_max[3] = {0, 0, 0};
-    int64_t vt_n = 0, vt_pts = 0;
-    r3d_buf vt_keys[2], vt_sums[2], vt_cnt[2];
-    int vt_cur = 0;
-    int vt_rebuilds = 0, vt_updates = 0;   // statistics (r3d_model_voxel_table_stats)
-    // bounding box of the rows [pend_lo, pend_hi) the last alignment appended: computed on the device when they were appended,
-    // fetched with the NEXT call's first read-back (no round trip of its own); pend_host_ok: pend_box holds it already
-    r3d_buf d_pend;
-    int64_t pend_lo = 0, pend_hi = 0;
-    bool pend_host_ok = false;
-    double pend_box[6] = {0, 0, 0, 0, 0, 0};
+    VoxelTable table;
+    PendingBox pend;
 };
 namespace {
 // grows a model buffer to hold `rows` triplets, keeping the first `keep` rows
@@ -5096,10 +5136,8 @@ int r3d_model_clear(r3d_model *m) {
     if (!m) return R3D_E_BADARG;
     m->n = 0;
     m->has_colors = m->has_normals = false;
-    m->vt_valid = false;
-    m->vt_n = m->vt_pts = 0;
-    m->pend_lo = m->pend_hi = 0;
-    m->pend_host_ok = false;
+    m->table.invalidate();
+    m->pend.reset();
     return R3D_OK;
 }
 
@@ -5113,9 +5151,16 @@ int r3d_model_size(r3d_model *m, int64_t *n, int32_t *has_colors, int32_t *has_n
 
 int r3d_model_voxel_table_stats(r3d_model *m, int64_t *voxels, int32_t *rebuilds, int32_t *updates) {
     if (!m) return R3D_E_BADARG;
-    if (voxels) *voxels = m->vt_valid ? m->vt_n : 0;
-    if (rebuilds) *rebuilds = m->vt_rebuilds;
-    if (updates) *updates = m->vt_updates;
+    if (voxels) *voxels = m->table.n;   // 0 without a table (VoxelTable::invalidate)
+    if (rebuilds) *rebuilds = m->table.rebuilds;
+    if (updates) *updates = m->table.updates;
+    return R3D_OK;
+}
+
+int r3d_model_debug_fail_table_step(r3d_model *m, int32_t step) {
+    if (!m) return R3D_E_BADARG;
+    if (step < 0 || step > 3) return r3d_fail(m->ctx, R3D_E_BADARG, "model_debug_fail_table_step: step must be 0..3");
+    m->table.fail_step = step;
     return R3D_OK;
 }
 
@@ -5131,106 +5176,158 @@ int r3d_model_append(r3d_model *m, const double *xyz, const double *colors, cons
 
 }  // extern "C"
 namespace {
-// grow-only table buffer for `rows` voxels
-int vt_rows(r3d_model *m, r3d_buf &b, int64_t rows, size_t elem) { return b.reserve(m->ctx, m->ctx->stream, (size_t)rows * elem, R3D_GROW_VOXEL_TABLE); }
-// pointcloud_alignment.py:23 for the resident model: the legacy voxel grid of ALL model points, as means in lexicographic voxel
-// order in a fresh arena buffer.  Default: the incremental table above (full rebuild whenever the model's minimum corner moved, the
-// voxel size changed or the table does not exist); R3D_MODEL_IMPL=rebuild: the full sort of every model point, every frame.
-// table_out (r3d_model_debug_voxel_table): the resident table's device arrays behind the means, all null when there is none
-struct VtView { const unsigned long long *keys = nullptr; const double *sums = nullptr; const int *cnt = nullptr; };
-int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_out, int64_t *mt_out, double *box_out /* [6]: the model's box */,
-                        VtView *table_out = nullptr) {
-    r3d_ctx *ctx = m->ctx;
-    int rc;
-    double *d_t = (double *)m->pts.p;
-    if (table_out) *table_out = VtView();
+// The key space of the table: fewer than 2^21 voxels along every axis, counted from the grid's origin (the minimum corner less
+// half a voxel)
+bool vt_key_space_ok(const double *mn, const double *mx, double voxel) {
+    for (int a = 0; a < 3; a++) if (!((mx[a] - (mn[a] - 0.5 * voxel)) / voxel < 2097000.0)) return false;
+    return true;
+}
+// r3d_model_debug_fail_table_step: the error return that was asked for at point `step` of this call; nothing else happens there
+int table_injected(r3d_ctx *ctx, int armed, int step) {
+    return armed == step ? r3d_fail(ctx, R3D_E_HIP, "model voxel table: injected failure at step %d", step) : R3D_OK;
+}
+// What a call does about the table.  R3D_MODEL_IMPL=rebuild: no table, the full sort of every model point, every frame.
+enum TableStep { TABLE_FULL_PASS, TABLE_REBUILD, TABLE_UPDATE, TABLE_KEEP };
+// Decides and changes nothing.  Rebuild: there is no table for this voxel size, or the slice of rows the table does not cover yet
+// lies below the table's minimum corner (the grid origin moves: every key changes), or it reaches beyond the key space (the rebuild
+// then finds the same and ends in the plain full pass).  Update: nmx receives the maximum corner of the table's rows and the
+// slice.  The slice's box is the pending box when the slice is the block the last alignment appended, a pass over it otherwise.
+int table_decide(const r3d_model *m, DevArena &ar, double voxel, TableStep *step, double nmx[3]) {
     static const bool always_rebuild = [] { const char *e = getenv("R3D_MODEL_IMPL"); return e && !strcmp(e, "rebuild"); }();
-    if (always_rebuild) {
-        VoxelSegs Vt;
-        if ((rc = voxel_means(ctx, ar, d_t, m->n, voxel, Vt, d_tv_out, false, box_out))) return rc;
-        *mt_out = Vt.nseg;
+    r3d_ctx *ctx = m->ctx;
+    const VoxelTable &t = m->table;
+    *step = always_rebuild ? TABLE_FULL_PASS : TABLE_REBUILD;
+    if (always_rebuild || !t.valid || t.voxel != voxel || t.rows > m->n) return R3D_OK;
+    if (t.rows == m->n) { *step = TABLE_KEEP; return R3D_OK; }
+    int rc;
+    double smn[3], smx[3];
+    if (m->pend.covers(t.rows, m->n)) {
+        for (int a = 0; a < 3; a++) { smn[a] = m->pend.box[a]; smx[a] = m->pend.box[3 + a]; }
+        if ((rc = bbox_check(ctx, smn, smx))) return rc;
+    } else if ((rc = cloud_bbox(ctx, ar, (const double *)m->pts.p + t.rows * 3, m->n - t.rows, smn, smx))) return rc;
+    for (int a = 0; a < 3; a++) {
+        if (smn[a] < t.min[a]) return R3D_OK;
+        nmx[a] = std::max(t.max[a], smx[a]);
+    }
+    if (vt_key_space_ok(t.min, nmx, voxel)) *step = TABLE_UPDATE;
+    return R3D_OK;
+}
+// The plain full pass, as the one-shot entry points make it: no table is read or written.  known_bounds: the model's box when
+// the caller has it
+int model_full_pass(r3d_model *m, DevArena &ar, double voxel, const double *known_bounds, double **d_tv_out, int64_t *mt_out, double *box_out) {
+    VoxelSegs Vt;
+    if (known_bounds) for (int a = 0; a < 6; a++) box_out[a] = known_bounds[a];
+    if (int rc = voxel_means(m->ctx, ar, (const double *)m->pts.p, m->n, voxel, Vt, d_tv_out, false, known_bounds ? nullptr : box_out, known_bounds)) return rc;
+    *mt_out = Vt.nseg;
+    return R3D_OK;
+}
+// The table of all model rows, built from nothing into the buffers at `cur`.  bounds receives the model's box.  More than 2^21
+// voxels along an axis: success without a table (the caller makes the plain full pass).  An error return leaves no table either.
+int table_rebuild(r3d_model *m, DevArena &ar, double voxel, int fail, double bounds[6]) {
+    r3d_ctx *ctx = m->ctx;
+    VoxelTable &t = m->table;
+    const double *d_t = (const double *)m->pts.p;
+    int rc;
+    if ((rc = cloud_bbox(ctx, ar, d_t, m->n, bounds, bounds + 3))) return rc;   // (the pass voxel_segments would make itself)
+    if (!vt_key_space_ok(bounds, bounds + 3, voxel)) {
+        t.invalidate();
         return R3D_OK;
     }
-    bool rebuild = !m->vt_valid || m->vt_voxel != voxel || m->vt_pts > m->n;
-    const int64_t ns = m->n - m->vt_pts;
-    double smn[3], smx[3];
-    if (!rebuild && ns > 0) {
-        if (m->pend_host_ok && m->pend_lo == m->vt_pts && m->pend_hi == m->n) {   // the slice is the block the last alignment appended
-            for (int a = 0; a < 3; a++) { smn[a] = m->pend_box[a]; smx[a] = m->pend_box[3 + a]; }
-            if ((rc = bbox_check(ctx, smn, smx))) return rc;
-        } else if ((rc = cloud_bbox(ctx, ar, d_t + m->vt_pts * 3, ns, smn, smx))) return rc;
-        for (int a = 0; a < 3; a++) if (smn[a] < m->vt_min[a]) rebuild = true;   // the grid origin moves: every key changes
-    }
-    auto key_space_ok = [&](const double *mn, const double *mx) {
-        for (int a = 0; a < 3; a++) if (!((mx[a] - (mn[a] - 0.5 * voxel)) / voxel < 2097000.0)) return false;
-        return true;
-    };
-    if (rebuild) {
-        VoxelSegs Vt;
-        double bounds[6];
-        if ((rc = cloud_bbox(ctx, ar, d_t, m->n, bounds, bounds + 3))) return rc;   // (the pass voxel_segments would make itself)
-        for (int a = 0; a < 6; a++) box_out[a] = bounds[a];
-        if (!key_space_ok(bounds, bounds + 3)) {          // more than 2^21 voxels along an axis: no table, the plain full pass
-            if ((rc = voxel_means(ctx, ar, d_t, m->n, voxel, Vt, d_tv_out, false, nullptr, bounds))) return rc;
-            m->vt_valid = false;
-            *mt_out = Vt.nseg;
-            return R3D_OK;
-        }
-        if ((rc = voxel_segments(ctx, ar, d_t, m->n, voxel, Vt, false, nullptr, nullptr, nullptr, bounds))) return rc;
-        const int c = m->vt_cur;
-        if ((rc = vt_rows(m, m->vt_keys[c], Vt.nseg, 8)) || (rc = vt_rows(m, m->vt_sums[c], Vt.nseg, 24)) || (rc = vt_rows(m, m->vt_cnt[c], Vt.nseg, 4))) return rc;
-        k_vt_build<8><<<(unsigned)((Vt.nseg + 255) / 256), 256, 0, ctx->stream>>>(Vt.sorted, Vt.starts, Vt.nseg, m->n, bounds[0] - 0.5 * voxel,
-                                                                               bounds[1] - 0.5 * voxel, bounds[2] - 0.5 * voxel, voxel,
-                                                                               (unsigned long long *)m->vt_keys[c].p, (double *)m->vt_sums[c].p, (int *)m->vt_cnt[c].p);
-        R3D_HIP(ctx, hipGetLastError());
-        for (int a = 0; a < 3; a++) { m->vt_min[a] = bounds[a]; m->vt_max[a] = bounds[3 + a]; }
-        m->vt_n = Vt.nseg;
-        m->vt_voxel = voxel;
-        m->vt_valid = true;
-        m->vt_rebuilds++;
-    } else if (ns > 0) {
-        double nmx[3], org[3];
-        for (int a = 0; a < 3; a++) { nmx[a] = std::max(m->vt_max[a], smx[a]); org[a] = m->vt_min[a] - 0.5 * voxel; }
-        if (!key_space_ok(m->vt_min, nmx)) { m->vt_valid = false; return model_target_voxels(m, ar, voxel, d_tv_out, mt_out, box_out, table_out); }
-        VoxelSegs V;
-        if ((rc = voxel_segments(ctx, ar, d_t + m->vt_pts * 3, ns, voxel, V, false, org, nmx))) return rc;
-        const int c = m->vt_cur, o = c ^ 1;
-        const int64_t cap = m->vt_n + V.nseg;
-        if ((rc = vt_rows(m, m->vt_keys[o], cap, 8)) || (rc = vt_rows(m, m->vt_sums[o], cap, 24)) || (rc = vt_rows(m, m->vt_cnt[o], cap, 4))) return rc;
-        unsigned long long *segkey = (unsigned long long *)ar.get((size_t)V.nseg * 8);
-        int64_t *ins = (int64_t *)ar.get((size_t)V.nseg * 8);
-        double *nsum = (double *)ar.get((size_t)V.nseg * 24);
-        int *is_new = (int *)ar.get((size_t)V.nseg * 4), *rank = (int *)ar.get((size_t)V.nseg * 4), *ncnt = (int *)ar.get((size_t)V.nseg * 4);
-        if (ar.rc) return ar.rc;
-        const unsigned nbs = (unsigned)((V.nseg + 255) / 256);
-        k_vt_update<<<nbs, 256, 0, ctx->stream>>>(V.sorted, V.starts, V.nseg, ns, org[0], org[1], org[2], voxel, (const unsigned long long *)m->vt_keys[c].p,
-                                                  m->vt_n, (double *)m->vt_sums[c].p, (int *)m->vt_cnt[c].p, segkey, is_new, ins, nsum, ncnt);
-        if (int src = dev_exclusive_scan<int>(ctx, ar, is_new, rank, V.nseg)) return src;
-        CompactCount cc(rank, is_new, V.nseg);
-        PinRead rd(ctx);
-        if ((rc = cc.add_to(rd)) || (rc = rd.wait())) return rc;
-        const int total_new = (int)cc.count();
-        if (total_new > 0) {
-            k_vt_merge<<<(unsigned)((m->vt_n + V.nseg + 255) / 256), 256, 0, ctx->stream>>>(
-                (const unsigned long long *)m->vt_keys[c].p, (const double *)m->vt_sums[c].p, (const int *)m->vt_cnt[c].p, m->vt_n, segkey, is_new, rank, ins, nsum,
-                ncnt, V.nseg, total_new, (unsigned long long *)m->vt_keys[o].p, (double *)m->vt_sums[o].p, (int *)m->vt_cnt[o].p);
-            m->vt_cur = o;
-            m->vt_n += total_new;
-        }
-        R3D_HIP(ctx, hipGetLastError());
-        for (int a = 0; a < 3; a++) m->vt_max[a] = nmx[a];
-        m->vt_updates++;
-    }
-    m->vt_pts = m->n;
-    if (table_out) *table_out = VtView{(const unsigned long long *)m->vt_keys[m->vt_cur].p, (const double *)m->vt_sums[m->vt_cur].p, (const int *)m->vt_cnt[m->vt_cur].p};
-    double *d_tv = (double *)ar.get((size_t)m->vt_n * 24);
-    if (ar.rc) return ar.rc;
-    k_vt_means<<<(unsigned)((m->vt_n + 255) / 256), 256, 0, ctx->stream>>>((const double *)m->vt_sums[m->vt_cur].p, (const int *)m->vt_cnt[m->vt_cur].p, m->vt_n, d_tv);
+    VoxelSegs Vt;
+    if ((rc = voxel_segments(ctx, ar, d_t, m->n, voxel, Vt, false, nullptr, nullptr, nullptr, bounds))) return rc;
+    t.invalidate();   // the reserve may free the buffers at `cur` and the build overwrites them
+    if ((rc = t.reserve(ctx, t.cur, Vt.nseg))) return rc;
+    const VoxelTable::Set c = t.current();
+    k_vt_build<8><<<(unsigned)((Vt.nseg + 255) / 256), 256, 0, ctx->stream>>>(Vt.sorted, Vt.starts, Vt.nseg, m->n, bounds[0] - 0.5 * voxel,
+                                                                           bounds[1] - 0.5 * voxel, bounds[2] - 0.5 * voxel, voxel, c.keys, c.sums, c.cnt);
     R3D_HIP(ctx, hipGetLastError());
-    for (int a = 0; a < 3; a++) { box_out[a] = m->vt_min[a]; box_out[3 + a] = m->vt_max[a]; }
-    *d_tv_out = d_tv;
-    *mt_out = m->vt_n;
+    if ((rc = table_injected(ctx, fail, 1))) return rc;
+    for (int a = 0; a < 3; a++) { t.min[a] = bounds[a]; t.max[a] = bounds[3 + a]; }
+    t.voxel = voxel;
+    t.n = Vt.nseg;
+    t.rows = m->n;
+    t.valid = true;
+    t.rebuilds++;
     return R3D_OK;
+}
+// The rows the table does not cover yet, [rows, m->n), merged into it: their runs are added to the sums of the voxels that exist,
+// in place, and the voxels they open are merged into the other buffer set, which then becomes `cur`.  nmx: table_decide's.
+// Up to and including the reserve of the other buffers nothing resident is touched and an error return keeps the table.  From
+// k_vt_update on the sums at `cur` hold part of the slice, so the table is marked invalid before that launch and valid again only
+// after the last step that can fail.  The table is not made transactional by copying it first: an update that fails in between
+// costs one full rebuild on the next call.
+int table_update(r3d_model *m, DevArena &ar, double voxel, const double nmx[3], int fail) {
+    r3d_ctx *ctx = m->ctx;
+    VoxelTable &t = m->table;
+    int rc;
+    const int64_t ns = m->n - t.rows, tn = t.n;
+    double org[3];
+    for (int a = 0; a < 3; a++) org[a] = t.min[a] - 0.5 * voxel;
+    VoxelSegs V;
+    if ((rc = voxel_segments(ctx, ar, (const double *)m->pts.p + t.rows * 3, ns, voxel, V, false, org, nmx))) return rc;
+    if ((rc = t.reserve(ctx, t.cur ^ 1, tn + V.nseg))) return rc;
+    unsigned long long *segkey = (unsigned long long *)ar.get((size_t)V.nseg * 8);
+    int64_t *ins = (int64_t *)ar.get((size_t)V.nseg * 8);
+    double *nsum = (double *)ar.get((size_t)V.nseg * 24);
+    int *is_new = (int *)ar.get((size_t)V.nseg * 4), *rank = (int *)ar.get((size_t)V.nseg * 4), *ncnt = (int *)ar.get((size_t)V.nseg * 4);
+    if (ar.rc) return ar.rc;
+    const VoxelTable::Set c = t.current(), o = t.other();
+    const unsigned nbs = (unsigned)((V.nseg + 255) / 256);
+    t.invalidate();
+    k_vt_update<<<nbs, 256, 0, ctx->stream>>>(V.sorted, V.starts, V.nseg, ns, org[0], org[1], org[2], voxel, c.keys, tn, c.sums, c.cnt, segkey, is_new,
+                                              ins, nsum, ncnt);
+    if ((rc = table_injected(ctx, fail, 2))) return rc;
+    if (int src = dev_exclusive_scan<int>(ctx, ar, is_new, rank, V.nseg)) return src;
+    CompactCount cc(rank, is_new, V.nseg);
+    PinRead rd(ctx);
+    if ((rc = cc.add_to(rd)) || (rc = rd.wait())) return rc;
+    const int total_new = (int)cc.count();
+    if (total_new > 0) {
+        k_vt_merge<<<(unsigned)((tn + V.nseg + 255) / 256), 256, 0, ctx->stream>>>(c.keys, c.sums, c.cnt, tn, segkey, is_new, rank, ins, nsum, ncnt, V.nseg,
+                                                                                  total_new, o.keys, o.sums, o.cnt);
+        if ((rc = table_injected(ctx, fail, 3))) return rc;
+    }
+    R3D_HIP(ctx, hipGetLastError());
+    if (total_new > 0) t.cur ^= 1;   // the merged table is in the other buffers; without a new voxel the sums went on in place
+    t.n = tn + total_new;
+    for (int a = 0; a < 3; a++) t.max[a] = nmx[a];
+    t.rows = m->n;
+    t.valid = true;
+    t.updates++;
+    return R3D_OK;
+}
+// The means of the table's voxels in a fresh arena buffer, the model's box, and the table's arrays for the diagnostic read-out
+int table_emit(r3d_model *m, DevArena &ar, double **d_tv_out, int64_t *mt_out, double *box_out, VtView *table_out) {
+    r3d_ctx *ctx = m->ctx;
+    const VoxelTable &t = m->table;
+    if (table_out) *table_out = t.view();
+    double *d_tv = (double *)ar.get((size_t)t.n * 24);
+    if (ar.rc) return ar.rc;
+    k_vt_means<<<(unsigned)((t.n + 255) / 256), 256, 0, ctx->stream>>>(t.current().sums, t.current().cnt, t.n, d_tv);
+    R3D_HIP(ctx, hipGetLastError());
+    for (int a = 0; a < 3; a++) { box_out[a] = t.min[a]; box_out[3 + a] = t.max[a]; }
+    *d_tv_out = d_tv;
+    *mt_out = t.n;
+    return R3D_OK;
+}
+// pointcloud_alignment.py:23 for the resident model: the legacy voxel grid of ALL model points, as means in lexicographic voxel
+// order in a fresh arena buffer.  Default: the incremental table (full rebuild whenever the model's minimum corner moved, the
+// voxel size changed or the table does not exist); R3D_MODEL_IMPL=rebuild: the full sort of every model point, every frame.
+// table_out (r3d_model_debug_voxel_table): the resident table's device arrays behind the means, all null when there is none
+int model_target_voxels(r3d_model *m, DevArena &ar, double voxel, double **d_tv_out, int64_t *mt_out, double *box_out /* [6]: the model's box */,
+                        VtView *table_out = nullptr) {
+    const int fail = std::exchange(m->table.fail_step, 0);   // one shot: armed for this call only, whether or not it gets there
+    if (table_out) *table_out = VtView();
+    int rc;
+    TableStep step;
+    double nmx[3], bounds[6];
+    if ((rc = table_decide(m, ar, voxel, &step, nmx))) return rc;
+    if (step == TABLE_FULL_PASS) return model_full_pass(m, ar, voxel, nullptr, d_tv_out, mt_out, box_out);
+    if (step == TABLE_REBUILD) {
+        if ((rc = table_rebuild(m, ar, voxel, fail, bounds))) return rc;
+        if (!m->table.valid) return model_full_pass(m, ar, voxel, bounds, d_tv_out, mt_out, box_out);   // beyond the key space: no table
+    } else if (step == TABLE_UPDATE && (rc = table_update(m, ar, voxel, nmx, fail))) return rc;
+    return table_emit(m, ar, d_tv_out, mt_out, box_out, table_out);
 }
 int model_align_checks(r3d_model *m, const r3d_align_params *p, const char *who) {
     r3d_ctx *ctx = m->ctx;
@@ -5280,11 +5377,10 @@ int model_align_core(r3d_model *m, DevArena &ar, const r3d_align_params *p, doub
     if ((rc = model_append(m, d_o, d_c, d_on, ms, hipMemcpyDeviceToDevice))) return rc;   // main.py:49 combined += aligned
     if (appended) *appended = ms;
     // the appended block's bounding box, for the next frame's table update: enqueued now, fetched with that call's first read-back
-    m->pend_host_ok = false;
-    m->pend_lo = m->pend_hi = 0;
+    m->pend.reset();
     if (p->voxel_size > 0 && ms > 0) {
-        if (!m->d_pend.p && m->d_pend.alloc(64) != hipSuccess) return R3D_OK;   // no pending box: the next call computes it itself
-        if (cloud_bbox_enqueue_dn(ctx, ar, d_o, ms, nullptr, nullptr, nullptr, (double *)m->d_pend.p) == R3D_OK) { m->pend_lo = n_before; m->pend_hi = m->n; }
+        if (!m->pend.dev.p && m->pend.dev.alloc(64) != hipSuccess) return R3D_OK;   // no pending box: the next call computes it itself
+        if (cloud_bbox_enqueue_dn(ctx, ar, d_o, ms, nullptr, nullptr, nullptr, (double *)m->pend.dev.p) == R3D_OK) m->pend.set(n_before, m->n);
     }
     return R3D_OK;
 }
@@ -5376,10 +5472,9 @@ int r3d_model_align_append_depth(r3d_model *m, const r3d_align_params *p, const 
     double *d_p, *d_c;
     int64_t n;
     double fbox[6];
-    PinExtra pend;
-    if (m->d_pend.p && m->pend_hi > m->pend_lo && !m->pend_host_ok) { pend.host = m->pend_box; pend.dev = m->d_pend.p; pend.bytes = 48; }
+    PinExtra pend = m->pend.fetch();
     if ((rc = backproject_core(ctx, ar, depth, w, h, stride, cam, color, color_stride, false, &d_p, &d_c, nullptr, &n, fbox, &pend))) return rc;
-    if (pend.host) m->pend_host_ok = true;
+    if (pend.host) m->pend.host_ok = true;
     if (frame_points) *frame_points = n;
     if (appended) *appended = 0;
     if (n == 0) {   // no valid pixel: a failed capture, skipped like main.py:53-54 (identity, empty statistics, nothing appended)

@@ -969,6 +969,7 @@ static int wls_run(r3d_ctx *ctx, DevArena &ar, const r3d_wls_params *p, const in
     // weights_LUT[i] = -exp(-sqrt(i)/sigma): parameter table, fp64 on the host, rounded once to float
     const int nlut = gcn * 255 * 255 + 1;
     if (ctx->pp_lut_sigma != p->sigma_color || ctx->pp_lut_n != nlut) {
+        ctx->pp_lut_n = 0;   // r3d_reserve frees before it allocates: no key describes pp_lut until the upload below is through
         const int rc = r3d_reserve(ctx, ctx->pp_lut, (size_t)nlut * 4);
         if (rc) return rc;
         std::vector<float> hl((size_t)nlut);

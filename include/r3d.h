@@ -510,6 +510,14 @@ int r3d_model_voxel_table_stats(r3d_model *m, int64_t *voxels, int32_t *rebuilds
  * An empty model or voxel <= 0: R3D_E_BADARG. */
 int r3d_model_debug_voxel_table(r3d_model *m, double voxel, int64_t cap, uint64_t *keys, double *sums, int32_t *counts, double *means,
                                 double *box6, int64_t *n_out, int32_t *resident);
+/* test hook: makes the model's next voxel-table call (r3d_model_debug_voxel_table or an align call with voxel_size > 0) return
+ * R3D_E_HIP, "model voxel table: injected failure at step N", when it reaches point `step`, so that the state an error return
+ * leaves behind can be tested.  Only the return is injected: nothing is launched differently or freed.  1: in a rebuild, after the
+ * build kernel is enqueued; 2: in an update, after the slice is added to the resident sums; 3: in an update, after the merge of
+ * new voxels is enqueued (an update that opens no voxel never gets there).  One shot: that call disarms the hook when it starts,
+ * whether or not it reaches the point.  0 disarms; any other value: R3D_E_BADARG.  After such a return, as after any error from
+ * an align call, the model's rows are unchanged, there is no table and the next call rebuilds it. */
+int r3d_model_debug_fail_table_step(r3d_model *m, int32_t step);
 /* combined.points = frame.points ... (main.py:42-45) and `combined += cloud` for host clouds; colors / normals may be NULL */
 int r3d_model_append(r3d_model *m, const double *xyz, const double *colors, const double *normals, int64_t n);
 /* main.py:48-49: aligned = align_point_clouds(frame, combined, threshold, voxel_size, max_iter); combined += aligned.

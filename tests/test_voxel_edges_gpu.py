@@ -3,7 +3,8 @@
 Mean kernels (k_voxel_mean_sorted, k_voxel_mean_t, k_voxel_mean_big, double and float): voxels whose member counts sit on the
 8-member rounds, the 64-member chunks and VM_BIG = 192; waves of k_voxel_mean_t with every kind of big-voxel mask; more than 4 096
 big voxels (the grid-stride loop of _big).  Resident model table (k_vt_build / _update / _merge / _means, model_target_voxels):
-every branch driven on purpose and the table read out through r3d_model_debug_voxel_table after every step.
+every branch driven on purpose and the table read out through r3d_model_debug_voxel_table after every step; error returns injected
+through r3d_model_debug_fail_table_step, after which the next call has to rebuild the table of all rows.
 
 A voxel's mean is its members added in index order and the library is built with -ffp-contract=off, so every comparison with
 tests/voxel_ref.py is for equality."""
@@ -354,3 +355,124 @@ def test_table_after_align_append(model):
     assert len(rows) == n0 + res["appended"] + res2["appended"] + len(f) and (rows[n0:].min(0) >= rows[:n0].min(0)).all()
     assert_array_equal(rows[-len(f):], f)
     _check_table(model, rows, V, 1, 2)
+
+
+# ------------------------------------------------------------------------------------------------ error returns
+# r3d_model_debug_fail_table_step injects the error return only (no launch changes), at 1: a rebuild after k_vt_build, 2: an update
+# after k_vt_update has added the slice to the resident sums, 3: an update after k_vt_merge.  Whatever stops a call, the table is
+# marked valid only after its last fallible step, so the next call rebuilds from the model's rows.
+def _old_voxel_frames():
+    """the two frames of test_table_update_without_new_voxel: existing voxels only, so no k_vt_merge"""
+    rng = np.random.default_rng(11)
+    return [np.concatenate([_frame(rng.integers(1, 20, len(CELLS)), CELLS, 20 + step), _frame([5], [[0, 0, 0]], 30 + step, lo=0.6)])
+            for step in (1, 2)]
+
+
+def _mixed_frame():
+    """the first of those frames and the twelve new cells of the "above" placement: k_vt_merge runs"""
+    new = np.asarray(PLACEMENTS["above"][1]())
+    return np.concatenate([_old_voxel_frames()[0], _frame(np.random.default_rng(12).integers(1, 30, len(new)), new, 40)])
+
+
+FAIL_FRAMES = {"F_old": lambda: _old_voxel_frames()[0], "F_mix": _mixed_frame}
+
+
+@pytest.mark.parametrize("step,frame", [(2, "F_old"), (2, "F_mix"), (3, "F_mix")])
+def test_table_failed_update_forces_rebuild(r3d, model, step, frame):
+    """an update that returns an error after k_vt_update (the slice is in the resident sums already) or after k_vt_merge leaves no
+    table; the next call rebuilds it from all rows -- sums equal to the reference's, so the slice was not added twice -- and the
+    incremental path goes on from there"""
+    rows = _base()
+    model.append(rows)
+    _check_table(model, rows, V, 1, 0)
+    f = FAIL_FRAMES[frame]()
+    assert (f.min(0) >= rows.min(0)).all()                       # the minimum corner stays: an update, not a rebuild
+    model.append(f)
+    rows = np.concatenate([rows, f])
+    model.debug_fail_table_step(step)
+    with pytest.raises(r3d.R3DError, match="injected"):
+        model.debug_voxel_table(V)
+    assert model.voxel_table_stats() == (0, 1, 0)
+    _check_table(model, rows, V, 2, 0)
+    f2 = _old_voxel_frames()[1]
+    model.append(f2)
+    _check_table(model, np.concatenate([rows, f2]), V, 2, 1)
+
+
+def test_table_failed_rebuild_leaves_no_table(r3d, model):
+    """a rebuild for another voxel size that returns an error after k_vt_build has overwritten the buffers: no table, not the new
+    one under the old label; and the same for the first build of a model"""
+    model.append(_base())
+    n = _check_table(model, _base(), V, 1, 0)
+    assert model.voxel_table_stats() == (n, 1, 0)
+    model.debug_fail_table_step(1)
+    with pytest.raises(r3d.R3DError, match="injected"):
+        model.debug_voxel_table(0.02)
+    assert model.voxel_table_stats() == (0, 1, 0)
+    _check_table(model, _base(), V, 2, 0)
+    fresh = r3d.cloud_ops.ResidentModel()
+    try:
+        fresh.append(_base())
+        fresh.debug_fail_table_step(1)
+        with pytest.raises(r3d.R3DError, match="injected"):
+            fresh.debug_voxel_table(V)
+        assert fresh.voxel_table_stats() == (0, 0, 0)
+        _check_table(fresh, _base(), V, 1, 0)
+    finally:
+        fresh.close()
+
+
+def test_align_append_after_failed_update_equals_undisturbed(r3d):
+    """the public path: an align_append whose table update returns an error changes no row of the model, and the next one (which
+    rebuilds) gives bit for bit what a model that never saw the error gives (which updates)"""
+    a, b = r3d.cloud_ops.ResidentModel(), r3d.cloud_ops.ResidentModel()
+    try:
+        rows = np.concatenate([_base(), _mixed_frame()])
+        for m in (a, b):
+            m.append(_base())
+            _check_table(m, _base(), V, 1, 0)
+            m.append(_mixed_frame())
+        src = _base()[1::3]
+        a.debug_fail_table_step(2)
+        with pytest.raises(r3d.R3DError, match="injected"):
+            a.align_append(src, threshold=0.02, voxel_size=V, max_iteration=1)
+        assert len(a) == len(rows)
+        got = a.download()
+        assert_array_equal(got[0], rows)
+        assert got[1] is None and got[2] is None
+        ra, rb = (m.align_append(src, threshold=0.02, voxel_size=V, max_iteration=1) for m in (a, b))
+        assert_array_equal(ra["T"], rb["T"])
+        for k in ("fitness", "inlier_rmse", "iterations", "correspondences", "appended"):
+            assert ra[k] == rb[k], k
+        assert ra["appended"] > 0
+        da, db = a.download(), b.download()
+        assert_array_equal(da[0], db[0])
+        assert_array_equal(da[0][:len(rows)], rows)
+        for x, y in zip(da[1:], db[1:]):
+            assert (x is None and y is None) or np.array_equal(x, y)
+        n = len(vr.legacy_table(rows, V)[0])                      # the table covers the rows the frame was aligned to
+        assert a.voxel_table_stats() == (n, 2, 0) and b.voxel_table_stats() == (n, 1, 1)
+    finally:
+        a.close()
+        b.close()
+
+
+def test_fail_hook_arming(r3d, model):
+    """steps outside 0..3 are refused; the hook is cleared when the next table call starts, whether or not that call reaches the
+    step; step 0 disarms"""
+    for bad in (-1, 4):
+        with pytest.raises(r3d.R3DError):
+            model.debug_fail_table_step(bad)
+    rows = _base()
+    model.append(rows)
+    _check_table(model, rows, V, 1, 0)
+    f1, f2 = _old_voxel_frames()
+    new = np.asarray(PLACEMENTS["above"][1]())
+    for k, (arm, f) in enumerate((((3,), f1),                      # no merge in this update: step 3 is never reached
+                                  ((), _frame([3] * len(new), new, 41)),   # a merge: step 3 would fire here, were it still armed
+                                  ((2, 0), f2))):                # disarmed again before the call
+        for s in arm:
+            model.debug_fail_table_step(s)
+        model.append(f)
+        rows = np.concatenate([rows, f])
+        _check_table(model, rows, V, 1, k + 1)
