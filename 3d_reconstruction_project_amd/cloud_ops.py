@@ -112,6 +112,8 @@ _lib.register({
     "r3d_debug_icp_correspondences": ([_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp], ctypes.c_int),
     "r3d_debug_icp_sums": ([_vp, ctypes.POINTER(_lib.IcpParams), _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
                            ctypes.c_int),
+    "r3d_debug_icp_sums_colored": ([_vp, ctypes.POINTER(_lib.ColoredIcpParams), _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp,
+                                    _vp, _vp], ctypes.c_int),
 })
 
 
@@ -654,6 +656,21 @@ def registration_colored(source, source_colors, target, target_normals, target_c
     ctx.call("r3d_icp_colored", ctypes.byref(prm), _ptr(s), _ptr(sc), len(s), _ptr(t), _ptr(tn), _ptr(tc), len(t), _ptr(T0), _ptr(T),
              ctypes.byref(st))
     return _stats_dict(T, st)
+
+
+def debug_icp_sums_colored(source, source_colors, target, target_normals, target_colors, max_distance, T=None, lambda_geometric=0.968,
+                           gradient_radius=0.0, gradient_max_nn=0, ctx=None):
+    """r3d_debug_icp_sums_colored: (sums [29], records [nt,4]) of one evaluation of the coloured registration loop at pose T, as
+    the device reduces them for its step, and the target's (intensity, gradient) records as the set-up computed them, in the
+    caller's numbering.  gradient_radius 0: 2 * max_distance; gradient_max_nn 0: 30.  The slots' meaning: include/r3d.h."""
+    ctx = ctx or _lib.default_context()
+    s, sc, t, tn, tc = _c(source), _c(source_colors), _c(target), _c(target_normals), _c(target_colors)
+    T0 = None if T is None else np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+    prm = _colored_params(max_distance, lambda_geometric, 0, 0.0, 0.0, gradient_radius, gradient_max_nn)
+    sums, records = np.empty(29), np.empty((len(t), 4))
+    ctx.call("r3d_debug_icp_sums_colored", ctypes.byref(prm), _ptr(s), _ptr(sc), len(s), _ptr(t), _ptr(tn), _ptr(tc), len(t), _ptr(T0),
+             _ptr(sums), _ptr(records))
+    return sums, records
 
 
 def align_point_clouds(source, target, threshold=0.02, voxel_size=0.01, max_iteration=100, mode=P2P, normal_radius=None,

@@ -4050,6 +4050,7 @@ struct IcpWork {
     double *d_s, *d_sn, *d_tns;        // the source and its normals in Morton order, the target's normals in cell-sorted order
     int *sidx;                         // the permutation that sorted the source
     IcpColor colk;
+    const double *d_trec;              // MODE_COLORED: the target's records in the caller's numbering (colk.tgt_ig before k_gather4), else null
     double *d_part;
     IcpState *d_st, *hst, *d_mirror;   // hst is pinned and mapped: k_icp_step publishes the state there (d_mirror), the host polls it
     int nblocks, search;
@@ -4081,6 +4082,7 @@ static int icp_setup(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, const 
     // coloured mode: the target's intensities and gradients, once per call (a search grid of its own: the radius differs)
     double *d_trec = nullptr;
     if (color && (rc = color_gradients_core(ctx, ar, in.d_t, nt, in.d_tn, color->d_tc, color->radius, color->max_nn, &d_trec))) return rc;
+    w.d_trec = d_trec;
     double occ = 3.0;   // points per occupied cell the search grid aims at (R3D_ICP_OCC: A/B)
     if (const char *oe = getenv("R3D_ICP_OCC")) { const double v = atof(oe); if (v >= 0.5 && v <= 64) occ = v; }
     if ((rc = grid_build(ctx, ar, in.d_t, nt, p->max_correspondence_distance, occ, G, true, in.tgt_enclosing, in.tgt_spacing))) return rc;   // dense table: one load per row in the loop
@@ -6104,6 +6106,33 @@ extern "C" int r3d_debug_icp_sums(r3d_ctx *ctx, const r3d_icp_params *p, const d
     IcpWork w;
     if ((rc = icp_setup(ctx, ar, p, {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = T4x4}, w))) return rc;
     return icp_read_sums(ctx, ar, p, w, sums_out, origin_out);
+}
+
+// the same read-out for the coloured mode: r3d_icp_colored's checks and set-up, one evaluation, k_icp_step's reduction; and the
+// target's records as that set-up computed them
+extern "C" int r3d_debug_icp_sums_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *src, const double *src_colors, int64_t ns,
+                                          const double *tgt, const double *tgt_normals, const double *tgt_colors, int64_t nt, const double *T4x4,
+                                          double *sums_out, double *tgt_records_out) {
+    R3D_ROCTX_RANGE("r3d_debug_icp_sums_colored");
+    if (!ctx) return R3D_E_BADARG;
+    if (!sums_out) return r3d_fail(ctx, R3D_E_BADARG, "debug_icp_sums_colored: bad argument");
+    r3d_icp_params ip;
+    IcpColorInput ci;
+    int rc;
+    // (the check wants a non-null pose argument for the result of the registration calls; here the pose is an optional input)
+    if ((rc = colored_icp_check(ctx, "debug_icp_sums_colored", p, src, src_colors, ns, tgt, tgt_normals, tgt_colors, nt, sums_out, &ip, &ci))) return rc;
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    DevArena ar(ctx);
+    double *d_t, *d_tn, *d_tc, *d_s, *d_sc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
+    if ((rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
+    if ((rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc))) return rc;
+    if ((rc = upload(ctx, ar, src_colors, ns * 3, &d_sc))) return rc;
+    ci.d_sc = d_sc; ci.d_tc = d_tc;
+    IcpWork w;
+    if ((rc = icp_setup(ctx, ar, &ip, {.d_s = d_s, .ns = ns, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = T4x4, .color = &ci}, w))) return rc;
+    if (tgt_records_out) R3D_HIP(ctx, hipMemcpyAsync(tgt_records_out, w.d_trec, (size_t)nt * 32, hipMemcpyDeviceToHost, ctx->stream));
+    return icp_read_sums(ctx, ar, &ip, w, sums_out, nullptr);   // synchronises the stream
 }
 
 extern "C" int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t n, int32_t op, int32_t *out) {

@@ -341,6 +341,19 @@ int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double 
 int r3d_icp_colored_dev(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *d_src, const double *d_src_colors, int64_t ns,
                         const double *d_tgt, const double *d_tgt_normals, const double *d_tgt_colors, int64_t nt, const double *init4x4,
                         double *T4x4, r3d_icp_stats *stats);
+/* diagnostic: r3d_debug_icp_sums for the coloured mode.  Runs r3d_icp_colored's checks and set-up (the target's gradients, the source
+ * intensities) and ONE evaluation at pose T4x4 (NULL: identity) through the loop's own launch; sums_out[29] is the device's
+ * reduction, as for r3d_debug_icp_sums; no step is taken.  Refuses like r3d_icp_colored.
+ * Slots over the correspondences (p = T * src[i], t, n = its nearest target and that target's normal, (I_t, d) the target's
+ * record, I_s the source's intensity, sg = sqrt(lambda), sp = sqrt(1 - lambda)):  [0] count  [1] sum of squared distances
+ *   [2..22] the upper triangle of J_G^T J_G + J_I^T J_I, row by row   [23..28] J_G^T r_G + J_I^T r_I,  in absolute coordinates, with
+ *   e = (p - t).n    J_G = sg [p x n, n]   r_G = sg e
+ *   m = -(d - (d.n) n)   J_I = sp [p x m, m]   r_I = sp (I_s - (d.((p - e n) - t) + I_t)).
+ * tgt_records_out (may be NULL): [nt][4], the records that set-up computed for the target, (I_t, d_x, d_y, d_z) per point in the
+ * caller's numbering: r3d_color_gradients' output for (tgt, tgt_normals, tgt_colors, the resolved radius and max_nn). */
+int r3d_debug_icp_sums_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double *src, const double *src_colors, int64_t ns,
+                               const double *tgt, const double *tgt_normals, const double *tgt_colors, int64_t nt, const double *T4x4,
+                               double *sums_out, double *tgt_records_out);
 
 /* replaces: o3d.pipelines.registration.compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) (test/check_lama1.py:246-281,
  *           mini1.py, check8.py) and the nearest-neighbour search of CorrespondencesFromFeatures   [recalled, Open3D 0.18 Feature.cpp;

@@ -1,6 +1,6 @@
 """Plain restatement of ONE step of the registration loop of csrc/cloud.hip (k_icp_eval -> icp_accumulate<MODE> -> k_icp_step ->
-the point-to-point Umeyama step / solve6_to_matrix), for the modes 0 (point-to-point), 1 (point-to-plane) and 2 (GICP).  numpy,
-no GPU.  Every sum and every 3x3 inverse is formed in np.longdouble; what the final factorisations take (LAPACK's SVD, det and
+the point-to-point Umeyama step / solve6_to_matrix), for the modes 0 (point-to-point), 1 (point-to-plane), 2 (GICP) and
+3 (coloured: r3d_debug_icp_sums_colored's slots, from the formulas of include/r3d.h).  numpy, no GPU.  Every sum and every 3x3 inverse is formed in np.longdouble; what the final factorisations take (LAPACK's SVD, det and
 solve) is float64.
 
 Correspondences come from tests/neighbor_ref.py: brute force under (squared distance, index) with a strict `<` against the
@@ -10,13 +10,21 @@ Slot layout (include/r3d.h, r3d_debug_icp_sums): [0] count, [1] sum d2; point-to
 [8 + 3a + b] sum q_a u_b with q = p - o, u = t - o; the other modes [2..22] the upper triangle of J^T J row by row and [23..28] J^T r.
 Beside every slot stands the sum of the absolute values of its terms, a term being one elementary product of the data (the
 products a Jacobian entry or a residual is made of are expanded, each taken by absolute value): the rounding bound of a float64
-sum is stated against that figure."""
+sum is stated against that figure.
+
+Coloured mode: the target's records (intensity, gradient) and the source's intensities are INPUTS, like the normals; sg and sp are
+the float64 square roots the host passes to the kernel.  Its expanded terms: e = d.n has the three d_a n_a (d = p - t, a datum
+as in point-to-plane); m_a = -(g_a - (g.n) n_a) has g_a and the three g_b n_b n_a; the predicted intensity has, per axis,
+g_a p_a, the three g_a d_b n_b n_a and g_a t_a (the kernel forms (p_a - e n_a) - t_a in that order, so p and t enter by their own
+size, not by their difference), and I_t.  The longest chain of roundings behind one term of a slot: 8 in an entry of J_I
+(3 in g.n, its product with n_a, the subtraction, the product with p, the cross product's subtraction, the scale sp), 14 in r_I, so
+at most 8 + 14 + 1 = 23 in a product: the 64 of sum_bound covers the mode."""
 import numpy as np
 
 from tests import neighbor_ref as nr
 
 LD = np.longdouble
-P2P, P2PLANE, GICP = 0, 1, 2
+P2P, P2PLANE, GICP, COLORED = 0, 1, 2, 3
 NSLOTS = 29
 U53 = 2.0 ** -53
 TRIU = [(a, b) for a in range(6) for b in range(a, 6)]        # slot 2 + k  <->  JTJ[a][b]
@@ -68,11 +76,13 @@ def nearest(target, source, T, max_distance, threads=8):
 
 
 def evaluate(source, target, max_distance, mode, T=None, source_normals=None, target_normals=None, gicp_epsilon=0.0, origin=None,
-             pairs=None):
+             pairs=None, colors=None):
     """One evaluation at pose T.  Returns a dict: n (count), i / j (the pairs), d2, value [29] and abs [29] (longdouble), p / t
     (the paired points, float64), cond_M (largest cond(M) of GICP, else 1), and for point-to-point mean_p, mean_t and sigma (the
     centred covariance (1/n) sum (t - mt)(p - mp)^T in longdouble) with sigma64, the same in float64.
-    pairs: neighbor_ref.brute_nearest's result for these arguments, when the caller has it already (it depends on no mode)."""
+    pairs: neighbor_ref.brute_nearest's result for these arguments, when the caller has it already (it depends on no mode).
+    colors (mode 3): dict(src_intensity [ns], tgt_records [nt,4] (intensity, gradient), lambda_geometric).  The result then also
+    has geometric / photometric: the (value, abs) slot vectors of either row alone, scale included (their sum is value / abs)."""
     T = np.eye(4) if T is None else np.asarray(T, np.float64).reshape(4, 4)
     src = np.ascontiguousarray(source, np.float64).reshape(-1, 3)
     tgt = np.ascontiguousarray(target, np.float64).reshape(-1, 3)
@@ -113,6 +123,36 @@ def evaluate(source, target, max_distance, mode, T=None, source_normals=None, ta
         r, ra = (d * nn).sum(1), (np.abs(d) * na).sum(1)
         JTJ, JTJa = J.T @ J, Ja.T @ Ja
         JTr, JTra = J.T @ r, Ja.T @ ra
+    elif mode == COLORED:
+        lam = float(colors["lambda_geometric"])
+        sg, sp = LD(np.sqrt(lam)), LD(np.sqrt(1.0 - lam))
+        rec = np.asarray(colors["tgt_records"], np.float64).reshape(-1, 4)[j].astype(LD)
+        i_s, i_t, g = np.asarray(colors["src_intensity"], np.float64).reshape(-1)[i].astype(LD), rec[:, 0], rec[:, 1:]
+        nn = nt_.astype(LD)
+        pa, ta, na, ga, da = np.abs(p), np.abs(t), np.abs(nn), np.abs(g), np.abs(d)
+
+        def cross_abs(x, y):
+            return np.stack([x[:, 1] * y[:, 2] + x[:, 2] * y[:, 1], x[:, 2] * y[:, 0] + x[:, 0] * y[:, 2], x[:, 0] * y[:, 1] + x[:, 1] * y[:, 0]], 1)
+        e, ea = (d * nn).sum(1), (da * na).sum(1)
+        J_g, J_ga = sg * np.concatenate([np.cross(p, nn), nn], 1), sg * np.concatenate([cross_abs(pa, na), na], 1)
+        r_g, r_ga = sg * e, sg * ea
+        gn, gna = (g * nn).sum(1), (ga * na).sum(1)
+        m, ma = -(g - gn[:, None] * nn), ga + gna[:, None] * na
+        J_i, J_ia = sp * np.concatenate([np.cross(p, m), m], 1), sp * np.concatenate([cross_abs(pa, ma), ma], 1)
+        i0 = (g * ((p - e[:, None] * nn) - t)).sum(1) + i_t
+        i0a = (ga * (pa + ea[:, None] * na + ta)).sum(1) + np.abs(i_t)
+        r_i, r_ia = sp * (i_s - i0), sp * (np.abs(i_s) + i0a)
+        parts = []
+        for Jx, rx, Jxa, rxa in ((J_g, r_g, J_ga, r_ga), (J_i, r_i, J_ia, r_ia)):
+            pv, pab = np.zeros(NSLOTS, LD), np.zeros(NSLOTS, LD)
+            A, Aa = Jx.T @ Jx, Jxa.T @ Jxa
+            for k, (a, b) in enumerate(TRIU):
+                pv[2 + k], pab[2 + k] = A[a, b], Aa[a, b]
+            pv[23:29], pab[23:29] = Jx.T @ rx, Jxa.T @ rxa
+            parts.append((pv, pab, A, Aa))
+        out["geometric"], out["photometric"] = parts[0][:2], parts[1][:2]
+        JTJ, JTJa = parts[0][2] + parts[1][2], parts[0][3] + parts[1][3]
+        JTr, JTra = parts[0][0][23:29] + parts[1][0][23:29], parts[0][1][23:29] + parts[1][1][23:29]
     elif mode == GICP:
         eps = gicp_epsilon if gicp_epsilon > 0 else 1e-3
         a_ = effective_normals(nt_).astype(LD)

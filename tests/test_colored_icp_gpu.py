@@ -23,7 +23,10 @@ def _gradient_case(name):
     """(points, normals, colours, radius, max_nn) of one gradient case and its reference, computed once:
     float64 and long-double restatement on the SAME neighbour lists"""
     rng = np.random.default_rng(2)
-    if name == "table":          # 6000 points with radius 0.04: about 120 within the radius, so the max_nn = 30 cut is exercised
+    max_nn = 30
+    if name in EDGE_CASES:
+        pts, nrm, col, radius, max_nn = _edge_cloud(name)
+    elif name == "table":        # 6000 points with radius 0.04: about 120 within the radius, so the max_nn = 30 cut is exercised
         _, _, pts, nrm, col, _ = _scene(1e-3)
         radius = 0.04
     else:                        # the sparse cloud (300 points uniform in a 2 m cube, radius 0.2) and its first 3 / 5 points
@@ -34,15 +37,53 @@ def _gradient_case(name):
         col = rng.uniform(0, 1, (300, 3))
         pts, nrm, col = pts[:n], nrm[:n], col[:n]
         radius = 0.2 if name == "sparse" else 3.0       # 3 m: the few points all see each other
-    nb = co.hybrid_neighbors(pts, radius, 30)
-    i64, g64, cnt = cr.color_gradients(pts, nrm, col, radius, 30, np.float64, nb)
-    _, gld, _ = cr.color_gradients(pts, nrm, col, radius, 30, np.longdouble, nb)
+    nb = co.hybrid_neighbors(pts, radius, max_nn)
+    i64, g64, cnt = cr.color_gradients(pts, nrm, col, radius, max_nn, np.float64, nb)
+    _, gld, _ = cr.color_gradients(pts, nrm, col, radius, max_nn, np.longdouble, nb)
     scale = np.maximum(1.0, np.linalg.norm(gld.astype(np.float64), axis=1))[:, None]
     gap = float((np.abs(g64 - gld).astype(np.float64) / scale).max())
-    return pts, nrm, col, radius, i64, g64, cnt, scale, gap
+    return pts, nrm, col, radius, i64, g64, cnt, scale, gap, max_nn
 
 
-@pytest.mark.parametrize("name", ["table", "sparse", "n3", "n5"])
+LINEAR_NN, QUADRATIC_NN = (4, 5, 8, 9, 30), (5, 8)
+EDGE_CASES = (["line"] + [f"lattice_linear_nn{k}" for k in LINEAR_NN] + [f"lattice_quadratic_nn{k}" for k in QUADRATIC_NN]
+              + ["duplicates", "n63", "n64", "n65", "n129", "table+10", "table+100", "table+1000"])
+LINEAR_GRADIENT = (0.25, 0.5, 0.0)
+
+
+def _lattice():
+    gx, gy = np.meshgrid(np.arange(9) / 8.0, np.arange(9) / 8.0, indexing="ij")
+    return np.column_stack([gx.ravel(), gy.ravel(), np.zeros(81)])
+
+
+def _edge_cloud(name):
+    """(points, normals, colours, radius, max_nn) of the cases at the gradient kernel's edges"""
+    up = lambda n: np.tile([[0.0, 0.0, 1.0]], (n, 1))
+    grey = lambda inten: np.repeat(inten[:, None], 3, 1)         # (I + I) + I = 3 I and 3 I / 3 = I exactly for these dyadic I
+    if name == "line":           # rank 2 (the line's direction and the normal): the determinant is exactly zero
+        pts = np.column_stack([np.arange(8) / 8.0, np.zeros(8), np.zeros(8)])
+        return pts, up(8), np.random.default_rng(3).uniform(0, 1, (8, 3)), 1.0, 30
+    if name.startswith("lattice"):
+        pts = _lattice()         # spacing 1/8, radius 0.3: 4 neighbours at 1/8, 4 at sqrt(2)/8, 4 at 2/8, 8 at sqrt(5)/8: every cut is among ties
+        x, y = pts[:, 0], pts[:, 1]
+        inten = 0.25 * x + 0.5 * y + 0.125 if "linear" in name else x * x + 0.5 * x * y
+        return pts, up(81), grey(inten), 0.3, int(name.split("nn")[1])
+    if name == "duplicates":     # coincident pairs: a zero row of A, d2 = 0 ties between a point and its copy
+        rng = np.random.default_rng(4)
+        p, nrm = rng.uniform(0, 1, (150, 3)), rng.standard_normal((150, 3))
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        return np.concatenate([p, p]), np.concatenate([nrm, nrm]), rng.uniform(0, 1, (300, 3)), 0.3, 30
+    if name.startswith("table+"):
+        _, _, pts, nrm, col, _ = _scene(1e-3)
+        return pts + float(name[6:]) * np.array([1.0, -0.6, 0.8]), nrm, col, 0.04, 30
+    n = int(name[1:])            # n63 .. n129: either side of KNN_BLOCK = 64 and of two blocks, every point sees every other: lists of
+    rng = np.random.default_rng(n)                                 # min(n, 128), the longest the kernel keeps
+    pts, nrm = rng.uniform(0, 1, (n, 3)), rng.standard_normal((n, 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    return pts, nrm, rng.uniform(0, 1, (n, 3)), 3.0, 128
+
+
+@pytest.mark.parametrize("name", ["table", "sparse", "n3", "n5"] + EDGE_CASES)
 def test_gradients_match_the_restatement(r3d, name):
     """Tolerance: ten times the largest gap between the restatement evaluated in float64 and in long double (same neighbour
     lists), relative to max(1, |g|).  Measured on the CPU (x87 long double, 64-bit mantissa):
@@ -52,9 +93,17 @@ def test_gradients_match_the_restatement(r3d, name):
         n5      gap 2.6e-16  bound 2.6e-15
     (the cofactor inverse loses cond(A^T A)^2: oblique normals and few neighbours are the loosest).  The kernel sums and solves
     in the restatement's order: on the MI355X its gradients equalled the float64 restatement's bit for bit in all four cases
-    (error 0).  Zero gradients are exactly zero, on the same points."""
-    pts, nrm, col, radius, i64, g64, cnt, scale, gap = _gradient_case(name)
-    inten, grad = r3d.cloud_ops.color_gradients(pts, nrm, col, radius, 30)
+    (error 0).  Zero gradients are exactly zero, on the same points.
+    The cases at the kernel's edges (_edge_cloud), measured the same way:
+        line                      gap 0        every determinant exactly zero (QUIRK_SINGULAR): all eight gradients zero
+        lattice_linear_nn4..30    gap 5.6e-17 (nn5: 1.1e-16)  the restatement is within 1.2e-16 of (0.25, 0.5, 0) at every cut
+        lattice_quadratic_nn5 / 8 gap 2.6e-16 / 2.1e-16   the list is cut among tied distances: the (d2, index) order decides
+        duplicates                gap 3.0e-11  300 points, 150 coincident pairs, all solved on 6 to 30 neighbours
+        n63 / n64 / n65 / n129    gap 4.5e-13 / 2.7e-13 / 4.0e-13 / 9.9e-13   max_nn = 128, lists of min(n, 128)
+        table+10 / +100 / +1000   gap 8.2e-13 / 8.1e-13 / 7.8e-12   the table moved by c (1, -0.6, 0.8)
+    Left out on purpose: zero normals on the duplicated cloud, where the restatement's own gap is above 1 and judges nothing."""
+    pts, nrm, col, radius, i64, g64, cnt, scale, gap, max_nn = _gradient_case(name)
+    inten, grad = r3d.cloud_ops.color_gradients(pts, nrm, col, radius, max_nn)
     err = float((np.abs(grad - g64) / scale).max())
     print(f"{name}: float64 / long double gap {gap:.3e}, bound {10 * gap:.3e}, kernel against the float64 restatement {err:.3e}, "
           f"{int((cnt >= 4).sum())} of {len(pts)} solved")
@@ -64,8 +113,18 @@ def test_gradients_match_the_restatement(r3d, name):
     assert err <= 10 * gap
     if name == "sparse":
         assert 0 < (cnt >= 4).sum() < len(pts)
-    if name == "table":
+    if name.startswith("table"):
         assert (cnt == 30).all()
+    if name == "line":
+        assert (cnt == 8).all() and not g64.any() and not grad.any()
+    if name.startswith("lattice"):
+        assert (cnt == np.minimum(max_nn, _gradient_case("lattice_linear_nn30")[6])).all()      # 8 (corners) to 21 lie within the radius
+        if "linear" in name:     # the case's own condition: any cut of the tied neighbours determines the plane's gradient
+            assert np.abs(g64 - LINEAR_GRADIENT).max() <= 4 * 2.0 ** -53
+    if name == "duplicates":
+        assert np.array_equal(pts[:150], pts[150:]) and (cnt >= 4).sum() > 250
+    if name in ("n63", "n64", "n65", "n129"):
+        assert (cnt == min(len(pts), 128)).all()
 
 
 def _same_loop(got, want):
