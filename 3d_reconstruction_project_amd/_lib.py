@@ -102,6 +102,10 @@ _SIGS = {
     "r3d_sgbm_profile": ([_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32], ctypes.c_int),
     "r3d_sgbm_debug_fetch": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "r3d_sgbm_debug_hh_partial": ([_vp, ctypes.c_int32, _vp], ctypes.c_int),
+    # the selection stage on caller-supplied volumes: ctx, params, w, h, cost, cspec, hsum, cost_pad, hsum_pad, raw_out, mins_out, lrd_out
+    "r3d_sgbm_debug_select": ([_vp, ctypes.POINTER(SgbmParams), ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp], ctypes.c_int),
+    # raw_wta, mins, lrd of the last compute or debug_select call
+    "r3d_sgbm_debug_fetch_select": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "r3d_debug_resources": ([ctypes.POINTER(ResourceCounts)], ctypes.c_int),
 }
 

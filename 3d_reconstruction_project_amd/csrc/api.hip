@@ -365,4 +365,25 @@ int r3d_sgbm_debug_hh_partial(r3d_ctx *ctx, int32_t n_dirs, int16_t *S_out) {
     return R3D_OK;
 }
 
+int r3d_sgbm_debug_fetch_select(r3d_ctx *ctx, int16_t *raw_wta, int16_t *mins, int16_t *lrd) {
+    R3D_ROCTX_RANGE("r3d_sgbm_debug_fetch_select");
+    if (!ctx) return R3D_E_BADARG;
+    if (ctx->last_w == 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_fetch_select: no sgbm call yet");
+    if (ctx->last_w1 <= 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_fetch_select: the last call had an empty matching range (all-invalid map), no planes exist");
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t plane = (size_t)ctx->last_w * ctx->last_h * 2;
+    if (raw_wta) R3D_HIP(ctx, hipMemcpy(raw_wta, ctx->ws[0].raw.p, plane, hipMemcpyDeviceToHost));
+    if (mins) R3D_HIP(ctx, hipMemcpy(mins, ctx->ws[0].mins.p, plane, hipMemcpyDeviceToHost));
+    if (lrd) R3D_HIP(ctx, hipMemcpy(lrd, ctx->ws[0].lrd.p, plane, hipMemcpyDeviceToHost));
+    return R3D_OK;
+}
+
+int r3d_sgbm_debug_select(r3d_ctx *ctx, const r3d_sgbm_params *params, int32_t w, int32_t h, const int16_t *cost, const int16_t *cspec,
+                          const int16_t *hsum, int32_t cost_pad, int32_t hsum_pad, int16_t *raw_out, int16_t *mins_out, int16_t *lrd_out) {
+    R3D_ROCTX_RANGE("r3d_sgbm_debug_select");
+    if (!ctx) return R3D_E_BADARG;
+    if (int rc = r3d_sgm_debug_select(ctx, params, w, h, cost, cspec, hsum, cost_pad, hsum_pad)) return rc;
+    return r3d_sgbm_debug_fetch_select(ctx, raw_out, mins_out, lrd_out);
+}
+
 }  // extern "C"

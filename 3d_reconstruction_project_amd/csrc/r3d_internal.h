@@ -210,6 +210,8 @@ struct r3d_roctx_scope {
 int r3d_sgm_run(r3d_ctx *ctx, int lane, hipStream_t st, const r3d_sgbm_params *p, const uint8_t *d_left, const uint8_t *d_right,
                 int w, int h, int stride, int cn, int16_t *d_disp);
 int r3d_sgm_hh_partial(r3d_ctx *ctx, int n_dirs);
+int r3d_sgm_debug_select(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, const int16_t *cost, const int16_t *cspec,
+                         const int16_t *hsum, int cost_pad, int hsum_pad);
 int r3d_selftest_run(r3d_ctx *ctx);
 int r3d_speckle_run(r3d_ctx *ctx, r3d_sgm_ws &ws, hipStream_t st, int16_t *d_img, int w, int h, int newVal, int maxSize, int maxDiff);
 int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int write, int delay, int reps, float *ms);

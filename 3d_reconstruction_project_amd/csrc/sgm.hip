@@ -21,6 +21,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <initializer_list>
+#include <vector>
+
 #include "r3d_internal.h"
 
 namespace {
@@ -1604,6 +1608,78 @@ int r3d_sgm_hh_partial(r3d_ctx *ctx, int n_dirs) {
         launch_hh_path(ctx->stream, g, r, (const int *)ws.cost.p, (int *)ws.hsum.p, inv_a, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p, true);
         R3D_HIP(ctx, hipGetLastError());
     }
+    return R3D_OK;
+}
+
+// debug / stage parity (r3d_sgbm_debug_select): the selection stage alone on volumes the caller hands in.  Host code around the
+// product's launchers: the geometry of a compute call of this size (derive_geom, one channel; MODE_HH: one stripe, as sgm_run_hh),
+// the workspace of lane 0 reserved as sgm_run_impl does (the record images, which no kernel here reads, left out), the arrays
+// expanded to DP slots per column with the caller's padding values in slots D..DP-1, raw / mins / lrd filled with the invalid
+// marker, then launch_vscan2 (3WAY; one pass, no tiny-image second run, no assembly) or the last direction of launch_hh_path
+// (HH: r = 7, FOLD 2, ws.hsum as the running S), and k_lrcheck.  Synchronises; the caller copies the planes out.
+int r3d_sgm_debug_select(r3d_ctx *ctx, const r3d_sgbm_params *p, int w, int h, const int16_t *cost, const int16_t *cspec,
+                         const int16_t *hsum, int cost_pad, int hsum_pad) {
+    if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "context poisoned by an earlier timed-out call: destroy it");
+    SgmGeom g;
+    if (int rc = derive_geom(ctx, p, w, h, 1, g)) return rc;
+    if (!cost || !hsum) return r3d_fail(ctx, R3D_E_BADARG, "debug_select: cost or hsum is NULL");
+    if (g.W1 <= 0) return r3d_fail(ctx, R3D_E_BADARG, "debug_select: empty matching range (w1 = %d), no volumes exist", g.W1);
+    if (cost_pad < 0 || cost_pad > 16383 || hsum_pad < -32768 || hsum_pad > 32767)
+        return r3d_fail(ctx, R3D_E_BADARG, "debug_select: cost_pad %d outside 0..16383 or hsum_pad %d outside int16", cost_pad, hsum_pad);
+    const bool hh = p->mode == R3D_SGBM_MODE_HH;
+    if (hh) { g.stripe_sz = h; g.overlap = 0; }
+    const bool use_cspec = !hh && g.SH2 > 0;
+    const size_t D = g.D, DP = g.DP, cols = (size_t)h * g.W1, crows = use_cspec ? (size_t)3 * g.SH2 : 0;
+    for (size_t i = 0; i < cols * D; i++)
+        if (cost[i] < 0 || cost[i] > 16383)
+            return r3d_fail(ctx, R3D_E_BADARG, "debug_select: cost[%zu] = %d outside 0..16383 (the kernels' envelope)", i, (int)cost[i]);
+    if (use_cspec && cspec)
+        for (size_t i = 0; i < crows * g.W1 * D; i++)
+            if (cspec[i] < 0 || cspec[i] > 16383)
+                return r3d_fail(ctx, R3D_E_BADARG, "debug_select: cspec[%zu] = %d outside 0..16383 (the kernels' envelope)", i, (int)cspec[i]);
+    R3D_HIP(ctx, hipSetDevice(ctx->device));
+    r3d_sgm_ws &ws = ctx->ws[0];
+    hipStream_t st = ctx->stream;
+    const size_t npix = (size_t)w * h, rowBytes = (size_t)g.W1 * DP * 2, volBytes = rowBytes * h;
+    int rc;
+    if ((rc = r3d_reserve(ctx, ws.cost, volBytes)) || (rc = r3d_reserve(ctx, ws.cspec, rowBytes * 3 * (g.SH2 > 0 ? g.SH2 : 1))) ||
+        (rc = r3d_reserve(ctx, ws.raw, npix * 2)) || (rc = r3d_reserve(ctx, ws.mins, npix * 2)) || (rc = r3d_reserve(ctx, ws.lrd, npix * 2)) ||
+        (rc = r3d_reserve(ctx, ws.flags, 256)) || (rc = r3d_reserve(ctx, ws.hsum, volBytes)))
+        return rc;
+    ctx->last_w = w; ctx->last_h = h; ctx->last_w1 = g.W1; ctx->last_dp = g.DP;
+    ctx->last_mode = p->mode; ctx->last_geom = g;
+    // [columns][D] -> [columns][DP], slots D..DP-1 = pad
+    auto expand = [&](const int16_t *src, size_t ncols, int pad) {
+        std::vector<int16_t> v(ncols * DP, (int16_t)pad);
+        for (size_t c = 0; c < ncols; c++) memcpy(&v[c * DP], src + c * D, D * 2);
+        return v;
+    };
+    const std::vector<int16_t> c_h = expand(cost, cols, cost_pad), h_h = expand(hsum, cols, hsum_pad);
+    std::vector<int16_t> s_h;
+    if (use_cspec) {
+        if (cspec) s_h = expand(cspec, crows * g.W1, cost_pad);
+        else {   // what the cost kernel leaves when the box is not replicated: the volume's own rows from the stripe's first row on
+            s_h.resize(crows * g.W1 * DP);
+            for (int n = 1; n <= 3; n++) {
+                const int s0 = std::max(std::min(n * g.stripe_sz - g.overlap, h), 0);
+                for (int j = 0; j < g.SH2; j++)
+                    memcpy(&s_h[((size_t)(n - 1) * g.SH2 + j) * g.W1 * DP], &c_h[(size_t)std::min(s0 + j, h - 1) * g.W1 * DP], rowBytes);
+            }
+        }
+    }
+    R3D_HIP(ctx, hipMemcpyAsync(ws.cost.p, c_h.data(), volBytes, hipMemcpyHostToDevice, st));
+    R3D_HIP(ctx, hipMemcpyAsync(ws.hsum.p, h_h.data(), volBytes, hipMemcpyHostToDevice, st));
+    if (use_cspec) R3D_HIP(ctx, hipMemcpyAsync(ws.cspec.p, s_h.data(), s_h.size() * 2, hipMemcpyHostToDevice, st));
+    const unsigned nb = (unsigned)std::min<size_t>((npix + 255) / 256, 4096);
+    for (int16_t *plane : {(int16_t *)ws.raw.p, (int16_t *)ws.mins.p, (int16_t *)ws.lrd.p}) k_fill_s16<<<nb, 256, 0, st>>>(plane, npix, (int16_t)g.invalid);
+    R3D_HIP(ctx, hipGetLastError());
+    const float inv_a = 1.0f / (float)(100 - g.uniq);
+    if (hh) launch_hh_path(st, g, 7, (const int *)ws.cost.p, (int *)ws.hsum.p, inv_a, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p);
+    else launch_vscan2(st, g, inv_a, (const int *)ws.cost.p, (const int *)ws.cspec.p, (const int *)ws.hsum.p, (int16_t *)ws.raw.p, (int16_t *)ws.mins.p);
+    R3D_HIP(ctx, hipGetLastError());
+    k_lrcheck<<<h, 256, (size_t)w * 4, st>>>((const int16_t *)ws.raw.p, (const int16_t *)ws.mins.p, g, (int16_t *)ws.lrd.p);
+    R3D_HIP(ctx, hipGetLastError());
+    R3D_HIP(ctx, hipStreamSynchronize(st));   // also: the host vectors above outlive their copies
     return R3D_OK;
 }
 

@@ -176,6 +176,45 @@ class StereoSGBM:
         self.context.call("r3d_sgbm_debug_hh_partial", int(n), S.ctypes.data_as(ctypes.c_void_p))
         return S[:, :, :D]
 
+    def debug_select(self, cost, hsum, cspec=None, cost_pad=0, hsum_pad=32767, width=None):
+        """Selection-stage parity: runs the vertical path + winner-take-all (MODE_SGBM_3WAY) or the eighth direction fused with
+        the selection (MODE_HH), then the LR check, on the caller's volumes with this matcher's parameters.
+        cost, hsum: int16 [H, W1, D] (cost in 0..16383); cspec: optional int16 [3, blockSize // 2, W1, D], the block-cost rows
+        stripes 1..3 read for their first rows; cost_pad / hsum_pad fill the volume slots past D, which must not change any
+        result.  width: the image width (default: the one whose matching range has W1 columns).
+        Returns dict(raw_wta, mins, lrd) of int16 [H, width]."""
+        D, minD = self._p["numDisparities"], self._p["minDisparity"]
+        cost = np.ascontiguousarray(cost, dtype=np.int16)
+        hsum = np.ascontiguousarray(hsum, dtype=np.int16)
+        H, W1 = cost.shape[:2]
+        W = int(width) if width is not None else W1 + max(minD + D, 0) - min(minD, 0)
+        if cost.shape != (H, W1, D) or hsum.shape != cost.shape or (W + min(minD, 0)) - max(minD + D, 0) != W1:
+            raise ValueError(f"debug_select expects cost and hsum of shape [H, W1, {D}] with W1 the matching range of width {W}")
+        vp = ctypes.c_void_p
+        if cspec is not None:
+            cspec = np.ascontiguousarray(cspec, dtype=np.int16)
+            if cspec.shape != (3, self._p["blockSize"] // 2, W1, D):
+                raise ValueError(f"debug_select expects cspec of shape [3, blockSize // 2, W1, D], got {cspec.shape}")
+        out = {k: np.empty((H, W), np.int16) for k in ("raw_wta", "mins", "lrd")}
+        p = self.params_struct()
+        self.context.call("r3d_sgbm_debug_select", ctypes.byref(p), W, H, cost.ctypes.data_as(vp), _opt_ptr(cspec), hsum.ctypes.data_as(vp),
+                          int(cost_pad), int(hsum_pad), *[out[k].ctypes.data_as(vp) for k in ("raw_wta", "mins", "lrd")])
+        self._last_shape = (H, W)
+        return out
+
+    def debug_fetch_select(self):
+        """raw_wta (disparity x16 before the LR check), mins (min S) and lrd (after the LR check) of the last compute or
+        debug_select: dict of int16 [H, W].  raw_wta and mins are defined at the matching columns only."""
+        H, W = self._last_shape
+        out = {k: np.empty((H, W), np.int16) for k in ("raw_wta", "mins", "lrd")}
+        self.context.call("r3d_sgbm_debug_fetch_select", *[out[k].ctypes.data_as(ctypes.c_void_p) for k in ("raw_wta", "mins", "lrd")])
+        return out
+
+
+def _opt_ptr(a):
+    """ctypes pointer of an optional array (None -> NULL)."""
+    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
 
 def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, device=0):
     """cv2.filterSpeckles on an int16 image; returns the filtered copy."""

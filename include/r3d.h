@@ -170,6 +170,32 @@ int r3d_sgbm_debug_fetch(r3d_ctx *ctx, int16_t *cost, int16_t *hsum, int16_t *ra
  * n_dirs outside 1..8, S_out NULL. */
 int r3d_sgbm_debug_hh_partial(r3d_ctx *ctx, int32_t n_dirs, int16_t *S_out);
 
+/* debug / stage parity: the selection stage alone (vertical path, winner-take-all, uniqueness, sub-pixel, LR check) on volumes
+ * the CALLER hands in, HOST arrays, single-channel geometry of a w x h compute call with these params (w1, the four stripes and
+ * dp as there; MODE_HH: one stripe):
+ *   cost   int16 [h][w1][D]       block cost C, every entry in 0..16383 (the kernels' envelope)
+ *   hsum   int16 [h][w1][D]       MODE_SGBM_3WAY: L_left + L_right; MODE_HH: S after seven directions
+ *   cspec  int16 [3][SH2][w1][D]  the block-cost rows that stripes 1..3 read in place of `cost` for their first SH2 =
+ *                                 blockSize/2 rows (the cost kernel replicates the box at a stripe's top); NULL = copies of the
+ *                                 rows of `cost` at those positions; ignored at blockSize 1 and in MODE_HH
+ * The arrays are expanded to dp slots per column, slots D..dp-1 filled with cost_pad (0..16383) / hsum_pad (an int16): no
+ * result may depend on either.  raw, mins and lrd are filled with the invalid marker (minDisparity-1)*16, then the product's own
+ * launches run: MODE_SGBM_3WAY k_vscan2 once (for a tiny image this is the first of a compute call's two runs, without the row
+ * assembly), MODE_HH the eighth direction over `cost` with `hsum` as the running S, fused with the selection; then
+ * k_lrcheck.  Outputs, int16 [h][w], each may be NULL: raw_out = the winner-take-all disparity x16 before the LR check,
+ * mins_out = min_d S at every pixel of the matching columns, lrd_out = after the LR check (before the 3x3 median).
+ * Afterwards r3d_sgbm_debug_fetch returns the expanded volumes (MODE_HH hsum: the S handed in, the eighth direction stores none).
+ * R3D_E_BADARG: cost or hsum NULL, a cost or cost_pad outside 0..16383, hsum_pad outside int16, w1 <= 0; params as compute. */
+int r3d_sgbm_debug_select(r3d_ctx *ctx, const r3d_sgbm_params *params, int32_t w, int32_t h, const int16_t *cost, const int16_t *cspec,
+                          const int16_t *hsum, int32_t cost_pad, int32_t hsum_pad, int16_t *raw_out, int16_t *mins_out, int16_t *lrd_out);
+
+/* debug / stage parity: the three int16 [h][w] planes of the LAST r3d_sgbm_compute* (lane 0) or r3d_sgbm_debug_select call, to HOST
+ * buffers (NULL = skip): raw_wta = disparity x16 before the LR check, mins = min_d S (both written at columns [minX1, maxX1) only;
+ * the rest is whatever the buffer held, the invalid marker after r3d_sgbm_debug_select), lrd = after the LR check (what
+ * r3d_sgbm_debug_fetch returns as raw).  After a tiny-image MODE_SGBM_3WAY compute raw_wta and mins are those of its second,
+ * one-stripe run.  R3D_E_BADARG: no call yet, or the last call had an empty matching range. */
+int r3d_sgbm_debug_fetch_select(r3d_ctx *ctx, int16_t *raw_wta, int16_t *mins, int16_t *lrd);
+
 /* ---- point clouds (float64 xyz triplets, like the legacy open3d.geometry.PointCloud the reference passes) ----- */
 
 /* replaces: pcd.voxel_down_sample(voxel_size)   pointcloud_alignment.py:22-23, test/check84.py:180
