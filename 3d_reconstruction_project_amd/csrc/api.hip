@@ -316,7 +316,7 @@ int r3d_sgbm_compute_cn(r3d_ctx *ctx, const r3d_sgbm_params *p, const uint8_t *l
     R3D_HIP(ctx, hipMemcpyAsync(ctx->img_l.p, left, ib, hipMemcpyHostToDevice, ctx->stream));
     R3D_HIP(ctx, hipMemcpyAsync(ctx->img_r.p, right, ib, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = r3d_sgm_run(ctx, 0, ctx->stream, p, (const uint8_t *)ctx->img_l.p, (const uint8_t *)ctx->img_r.p, w, h, stride, cn, (int16_t *)ctx->out.p))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(disp, ctx->out.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, disp, (const int16_t *)ctx->out.p, (size_t)w * h))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -331,7 +331,7 @@ int r3d_filter_speckles(r3d_ctx *ctx, int16_t *img, int32_t w, int32_t h, int32_
     if ((rc = r3d_reserve(ctx, ctx->out, bytes))) return rc;
     R3D_HIP(ctx, hipMemcpyAsync(ctx->out.p, img, bytes, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = r3d_speckle_run(ctx, ctx->ws[0], ctx->stream, (int16_t *)ctx->out.p, w, h, new_val, max_speckle_size, max_diff))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(img, ctx->out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, img, (const int16_t *)ctx->out.p, (size_t)w * h))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }

@@ -3017,10 +3017,7 @@ __global__ void __launch_bounds__(1024) k_icp_step(const double *__restrict__ pa
 }
 
 int upload(r3d_ctx *ctx, DevArena &ar, const double *h, int64_t n3, double **d) {
-    *d = (double *)ar.get((size_t)n3 * 8);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(*d, h, (size_t)n3 * 8, hipMemcpyHostToDevice, ctx->stream));
-    return R3D_OK;
+    return r3d_upload(ctx, ar, h, (size_t)n3, (const double **)d);   // the cores take some of these arrays as non-const rows
 }
 // the (source, target) pair of a registration problem: ns / nt rows of `width` doubles (3: points, FPFH_DIM: features)
 int upload_pair(r3d_ctx *ctx, DevArena &ar, const double *src, int64_t ns, const double *tgt, int64_t nt, double **d_s, double **d_t, int width = 3) {
@@ -3031,10 +3028,7 @@ int upload_pair(r3d_ctx *ctx, DevArena &ar, const double *src, int64_t ns, const
 int upload_corres_problem(r3d_ctx *ctx, DevArena &ar, const double *src, int64_t ns, const double *tgt, int64_t nt, const int32_t *corres, int64_t M,
                           double **d_s, double **d_t, int **d_c) {
     if (int rc = upload_pair(ctx, ar, src, ns, tgt, nt, d_s, d_t)) return rc;
-    *d_c = (int *)ar.get((size_t)M * 8);
-    if (ar.rc) return ar.rc;
-    if (M > 0) R3D_HIP(ctx, hipMemcpyAsync(*d_c, corres, (size_t)M * 8, hipMemcpyHostToDevice, ctx->stream));
-    return R3D_OK;
+    return r3d_upload(ctx, ar, corres, (size_t)M * 2, (const int32_t **)d_c);
 }
 // source.transform(T) of a registered cloud into fresh arena buffers: the points moved, the normals (d_n may be null, *d_on then is) rotated
 int transform_cloud(r3d_ctx *ctx, DevArena &ar, const double T[16], const double *d_p, const double *d_n, int64_t n, double **d_o, double **d_on) {
@@ -3429,7 +3423,7 @@ int ransac_core(r3d_ctx *ctx, DevArena &ar, const r3d_ransac_params *p, const do
         } else {
             R3D_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)M, ctx->stream));
         }
-        if (mask_host) R3D_HIP(ctx, hipMemcpyAsync(mask_host, d_mask, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = r3d_download(ctx, mask_host, d_mask, (size_t)M))) return rc;
     }
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (stats) {
@@ -4182,7 +4176,7 @@ static int icp_read_sums(r3d_ctx *ctx, DevArena &ar, const r3d_icp_params *p, co
     icp_enqueue_eval(ctx, p, w, d_corr);
     k_icp_sums_readout<<<1, 1024, 0, ctx->stream>>>(w.d_part, w.nblocks, d_sums);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(sums, d_sums, ICP_SLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = r3d_download(ctx, sums, d_sums, ICP_SLOTS)) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (origin) { origin[0] = w.org.x; origin[1] = w.org.y; origin[2] = w.org.z; }
     return R3D_OK;
@@ -4198,8 +4192,8 @@ static int icp_read_correspondences(r3d_ctx *ctx, DevArena &ar, const r3d_icp_pa
     icp_enqueue_eval(ctx, p, w, d_corr);
     k_icp_corr_readout<<<(unsigned)((ns + 255) / 256), 256, 0, ctx->stream>>>(w.d_s, w.sidx, ns, w.d_st, d_t, d_corr, d_corr_out, d_d2_out);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(corr, d_corr_out, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (d2) R3D_HIP(ctx, hipMemcpyAsync(d2, d_d2_out, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+    int rc;
+    if ((rc = r3d_download(ctx, corr, d_corr_out, (size_t)ns)) || (rc = r3d_download(ctx, d2, d_d2_out, (size_t)ns))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -4455,8 +4449,7 @@ int fgr_optimise_stage(r3d_ctx *ctx, DevArena &ar, const r3d_fgr_params *p, cons
     memcpy(trans, h, 128);
     *final_par = h[16];
     if (trace_T) {
-        R3D_HIP(ctx, hipMemcpyAsync(trace_T, d_tr, (size_t)it * 128, hipMemcpyDeviceToHost, ctx->stream));
-        R3D_HIP(ctx, hipMemcpyAsync(trace_par, d_tr + (size_t)it * 16, (size_t)it * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = r3d_download(ctx, trace_T, d_tr, (size_t)it * 16)) || (rc = r3d_download(ctx, trace_par, d_tr + (size_t)it * 16, (size_t)it))) return rc;
         R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return R3D_OK;
@@ -4564,9 +4557,7 @@ static int voxel_downsample_impl(r3d_ctx *ctx, const double *xyz, const double *
     DevArena ar(ctx);
     double *d_p, *d_c = nullptr, *d_n = nullptr;
     int rc;
-    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
-    if (colors && (rc = upload(ctx, ar, colors, n * 3, &d_c))) return rc;
-    if (normals && (rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p)) || (rc = upload(ctx, ar, colors, n * 3, &d_c)) || (rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
     VoxelSegs V;
     double *d_out;
     const double *ins[3] = {d_p, d_c, d_n};
@@ -4574,7 +4565,7 @@ static int voxel_downsample_impl(r3d_ctx *ctx, const double *xyz, const double *
     for (int a = 0; a < 3; a++) {
         if (!ins[a]) continue;
         if ((rc = a == 0 ? voxel_means(ctx, ar, d_p, n, voxel, V, &d_out, tensor_grid) : voxel_attr_means(ctx, ar, V, ins[a], n, &d_out, tensor_grid))) return rc;
-        R3D_HIP(ctx, hipMemcpyAsync(outs[a], d_out, (size_t)V.nseg * 24, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = r3d_download(ctx, outs[a], d_out, (size_t)V.nseg * 3))) return rc;
         R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     *out_n = V.nseg;
@@ -4603,10 +4594,9 @@ int r3d_estimate_normals(r3d_ctx *ctx, const double *xyz, int64_t n, double radi
     DevArena ar(ctx);
     double *d_p, *d_prev = nullptr, *d_n;
     int rc;
-    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
-    if (prev_normals && (rc = upload(ctx, ar, prev_normals, n * 3, &d_prev))) return rc;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p)) || (rc = upload(ctx, ar, prev_normals, n * 3, &d_prev))) return rc;
     if ((rc = normals_core(ctx, ar, d_p, n, radius, max_nn, d_prev, &d_n))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, normals, d_n, (size_t)n * 3))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -4627,7 +4617,7 @@ int r3d_neighbor_score(r3d_ctx *ctx, const double *xyz, int64_t n, int32_t k, do
     double *d_s = (double *)ar.get((size_t)n * 8);
     if (ar.rc) return ar.rc;
     if ((rc = launch_knn(ctx, k_knn_score, G, n, kk, count_radius, d_s))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(score, d_s, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, score, d_s, (size_t)n))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -4640,18 +4630,16 @@ int r3d_reproject_disparity(r3d_ctx *ctx, const int16_t *disp, int32_t w, int32_
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     const size_t n = (size_t)w * h;
-    int16_t *d_d = (int16_t *)ar.get(n * 2);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(d_d, disp, n * 2, hipMemcpyHostToDevice, ctx->stream));
+    const int16_t *d_d;
     double *d_xyz;
     int *d_pix;
     int64_t m;
     int rc;
+    if ((rc = r3d_upload(ctx, ar, disp, n, &d_d))) return rc;
     if ((rc = reproject_core(ctx, ar, d_d, w, h, Q4x4, min_valid_x16, 0.0, out_pixel != nullptr, &d_xyz, &d_pix, &m))) return rc;
     *out_n = m;
     if (m == 0) return R3D_OK;
-    R3D_HIP(ctx, hipMemcpyAsync(out_xyz, d_xyz, (size_t)m * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_pixel) R3D_HIP(ctx, hipMemcpyAsync(out_pixel, d_pix, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, out_xyz, d_xyz, (size_t)m * 3)) || (rc = r3d_download(ctx, out_pixel, d_pix, (size_t)m))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -4780,8 +4768,7 @@ int r3d_align_point_clouds(r3d_ctx *ctx, const r3d_align_params *p, const double
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     double *d_s, *d_t, *d_c = nullptr;
-    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
-    if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t)) || (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
     int64_t ms = ns, mt = nt;
     double tbox[6];
     const double *tgt_box = nullptr;
@@ -4809,9 +4796,9 @@ int r3d_align_point_clouds(r3d_ctx *ctx, const r3d_align_params *p, const double
     memcpy(T4x4, T, sizeof T);
     double *d_o, *d_on;
     if ((rc = transform_cloud(ctx, ar, T, d_s, d_sn, ms, &d_o, &d_on))) return rc;  // :42 source.transform
-    R3D_HIP(ctx, hipMemcpyAsync(out_xyz, d_o, (size_t)ms * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (d_sn) R3D_HIP(ctx, hipMemcpyAsync(out_normals, d_on, (size_t)ms * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (d_c) R3D_HIP(ctx, hipMemcpyAsync(out_colors, d_c, (size_t)ms * 24, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, out_xyz, d_o, (size_t)ms * 3)) || (rc = r3d_download(ctx, out_normals, d_on, d_on ? (size_t)ms * 3 : 0)) ||
+        (rc = r3d_download(ctx, out_colors, d_c, d_c ? (size_t)ms * 3 : 0)))
+        return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out_n = ms;
     return R3D_OK;
@@ -4833,8 +4820,7 @@ int r3d_knn_graph(r3d_ctx *ctx, const double *xyz, int64_t n, int32_t k, double 
     double *d_d2 = d2 ? (double *)ar.get((size_t)n * k * 8) : nullptr;
     if (ar.rc) return ar.rc;
     if ((rc = launch_knn(ctx, k_knn_graph, G, n, k, radius, d_nb, d_d2))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(nbr, d_nb, (size_t)n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (d2) R3D_HIP(ctx, hipMemcpyAsync(d2, d_d2, (size_t)n * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, nbr, d_nb, (size_t)n * k)) || (rc = r3d_download(ctx, d2, d_d2, (size_t)n * k))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5003,7 +4989,7 @@ int r3d_transform_points(r3d_ctx *ctx, const double *xyz, int64_t n, const doubl
     if (ar.rc) return ar.rc;
     k_transform<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_p, n, to_rigid(T4x4), rotate_only, d_o);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(out, d_o, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, out, d_o, (size_t)n * 3))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5019,9 +5005,9 @@ int r3d_icp(r3d_ctx *ctx, const r3d_icp_params *p, const double *src, int64_t ns
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     double *d_t, *d_tn = nullptr, *d_s, *d_sn = nullptr;
-    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
-    if (src_normals && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
-    if (tgt_normals && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t)) || (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn)) ||
+        (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn)))
+        return rc;
     return icp_core(ctx, ar, p, {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = init4x4}, T4x4, stats, t_begin);
 }
 
@@ -5401,8 +5387,7 @@ int r3d_model_align_append(r3d_model *m, const r3d_align_params *p, const double
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     double *d_s, *d_c = nullptr;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s)) || (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
     return model_align_core(m, ar, p, d_s, d_c, ns, T4x4, stats, appended, t_begin);
 }
 
@@ -5427,12 +5412,10 @@ int r3d_model_debug_voxel_table(r3d_model *m, double voxel, int64_t cap, uint64_
     if (resident) *resident = vt.keys != nullptr;
     if (n <= cap) {
         if (box6) memcpy(box6, box, sizeof box);
-        if (means) R3D_HIP(ctx, hipMemcpyAsync(means, d_tv, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-        if (vt.keys) {
-            if (keys) R3D_HIP(ctx, hipMemcpyAsync(keys, vt.keys, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (sums) R3D_HIP(ctx, hipMemcpyAsync(sums, vt.sums, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-            if (counts) R3D_HIP(ctx, hipMemcpyAsync(counts, vt.cnt, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
+        if ((rc = r3d_download(ctx, means, d_tv, (size_t)n * 3))) return rc;
+        if (vt.keys && ((rc = r3d_download(ctx, keys, (const uint64_t *)vt.keys, (size_t)n)) || (rc = r3d_download(ctx, sums, vt.sums, (size_t)n * 3)) ||
+                        (rc = r3d_download(ctx, counts, vt.cnt, (size_t)n))))
+            return rc;
     }
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
@@ -5502,9 +5485,9 @@ int r3d_backproject_depth(r3d_ctx *ctx, const uint16_t *depth, int32_t w, int32_
     if ((rc = backproject_core(ctx, ar, depth, w, h, stride, cam, color, color_stride, out_pixel != nullptr, &d_p, &d_c, &d_pix, &n))) return rc;
     *out_n = n;
     if (n == 0) return R3D_OK;
-    R3D_HIP(ctx, hipMemcpyAsync(out_xyz, d_p, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (d_c) R3D_HIP(ctx, hipMemcpyAsync(out_colors, d_c, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_pixel) R3D_HIP(ctx, hipMemcpyAsync(out_pixel, d_pix, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, out_xyz, d_p, (size_t)n * 3)) || (rc = r3d_download(ctx, out_colors, d_c, d_c ? (size_t)n * 3 : 0)) ||
+        (rc = r3d_download(ctx, out_pixel, d_pix, (size_t)n)))
+        return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5523,9 +5506,8 @@ int r3d_model_register_append(r3d_model *m, const r3d_icp_params *p, const doubl
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     double *d_s, *d_c = nullptr, *d_sn = nullptr;
-    if ((rc = upload(ctx, ar, src, ns * 3, &d_s))) return rc;
-    if (src_colors && (rc = upload(ctx, ar, src_colors, ns * 3, &d_c))) return rc;
-    if (src_normals && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
+    if ((rc = upload(ctx, ar, src, ns * 3, &d_s)) || (rc = upload(ctx, ar, src_colors, ns * 3, &d_c)) || (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn)))
+        return rc;
     double T[16];
     const IcpInput in = {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = (const double *)m->pts.p, .nt = m->n,
                          .d_tn = m->has_normals ? (const double *)m->nrms.p : nullptr};
@@ -5562,9 +5544,10 @@ int r3d_model_download(r3d_model *m, double *xyz, double *colors, double *normal
     if (!xyz) return r3d_fail(ctx, R3D_E_BADARG, "model_download: bad argument");
     if (m->n == 0) return R3D_OK;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
-    R3D_HIP(ctx, hipMemcpyAsync(xyz, m->pts.p, (size_t)m->n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (colors && m->has_colors) R3D_HIP(ctx, hipMemcpyAsync(colors, m->cols.p, (size_t)m->n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (normals && m->has_normals) R3D_HIP(ctx, hipMemcpyAsync(normals, m->nrms.p, (size_t)m->n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t n3 = (size_t)m->n * 3;
+    if (int rc = r3d_download(ctx, xyz, (const double *)m->pts.p, n3)) return rc;
+    if (int rc = r3d_download(ctx, colors, (const double *)m->cols.p, m->has_colors ? n3 : 0)) return rc;
+    if (int rc = r3d_download(ctx, normals, (const double *)m->nrms.p, m->has_normals ? n3 : 0)) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5598,9 +5581,7 @@ int r3d_color_gradients(r3d_ctx *ctx, const double *xyz, const double *normals, 
     DevArena ar(ctx);
     double *d_p, *d_n, *d_c, *d_rec;
     int rc;
-    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
-    if ((rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
-    if ((rc = upload(ctx, ar, colors, n * 3, &d_c))) return rc;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p)) || (rc = upload(ctx, ar, normals, n * 3, &d_n)) || (rc = upload(ctx, ar, colors, n * 3, &d_c))) return rc;
     if ((rc = color_gradients_core(ctx, ar, d_p, n, d_n, d_c, radius, max_nn, &d_rec))) return rc;
     std::vector<double> rec((size_t)n * 4);
     R3D_HIP(ctx, hipMemcpyAsync(rec.data(), d_rec, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -5643,10 +5624,9 @@ int r3d_icp_colored(r3d_ctx *ctx, const r3d_colored_icp_params *p, const double 
     const auto t_begin = std::chrono::steady_clock::now();
     DevArena ar(ctx);
     double *d_t, *d_tn, *d_tc, *d_s, *d_sc;
-    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
-    if ((rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
-    if ((rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc))) return rc;
-    if ((rc = upload(ctx, ar, src_colors, ns * 3, &d_sc))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t)) || (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn)) ||
+        (rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc)) || (rc = upload(ctx, ar, src_colors, ns * 3, &d_sc)))
+        return rc;
     ci.d_sc = d_sc; ci.d_tc = d_tc;
     return icp_core(ctx, ar, &ip, {.d_s = d_s, .ns = ns, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = init4x4, .color = &ci}, T4x4, stats, t_begin);
 }
@@ -5692,13 +5672,11 @@ int r3d_compute_fpfh(r3d_ctx *ctx, const double *xyz, const double *normals, int
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_p, *d_n;
-    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
-    if ((rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p)) || (rc = upload(ctx, ar, normals, n * 3, &d_n))) return rc;
     double *d_f = (double *)ar.get((size_t)n * FPFH_DIM * 8), *d_s = spfh ? (double *)ar.get((size_t)n * FPFH_DIM * 8) : nullptr;
     if (ar.rc) return ar.rc;
     if ((rc = fpfh_core(ctx, ar, d_p, d_n, nullptr, n, radius, max_nn, d_f, d_s))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(fpfh, d_f, (size_t)n * FPFH_DIM * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (spfh) R3D_HIP(ctx, hipMemcpyAsync(spfh, d_s, (size_t)n * FPFH_DIM * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, fpfh, d_f, (size_t)n * FPFH_DIM)) || (rc = r3d_download(ctx, spfh, d_s, (size_t)n * FPFH_DIM))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5711,12 +5689,11 @@ int r3d_fpfh_from_spfh(r3d_ctx *ctx, const double *xyz, int64_t n, double radius
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_p, *d_s;
-    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p))) return rc;
-    if ((rc = upload(ctx, ar, spfh_in, n * FPFH_DIM, &d_s))) return rc;
+    if ((rc = upload(ctx, ar, xyz, n * 3, &d_p)) || (rc = upload(ctx, ar, spfh_in, n * FPFH_DIM, &d_s))) return rc;
     double *d_f = (double *)ar.get((size_t)n * FPFH_DIM * 8);
     if (ar.rc) return ar.rc;
     if ((rc = fpfh_core(ctx, ar, d_p, nullptr, d_s, n, radius, max_nn, d_f, nullptr))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(fpfh, d_f, (size_t)n * FPFH_DIM * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, fpfh, d_f, (size_t)n * FPFH_DIM))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5754,8 +5731,7 @@ int r3d_match_features(r3d_ctx *ctx, const double *src_feat, int64_t ns, const d
     double *d_d2 = d2_out ? (double *)ar.get((size_t)ns * 8) : nullptr;
     if (ar.rc) return ar.rc;
     if ((rc = match_core(ctx, ar, d_s, ns, d_t, nt, d_nn, d_d2))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(nn_out, d_nn, (size_t)ns * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (d2_out) R3D_HIP(ctx, hipMemcpyAsync(d2_out, d_d2, (size_t)ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, nn_out, d_nn, (size_t)ns)) || (rc = r3d_download(ctx, d2_out, d_d2, (size_t)ns))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -5855,9 +5831,9 @@ int r3d_debug_ransac_hypotheses(r3d_ctx *ctx, const r3d_ransac_params *p, const 
     std::vector<int> surv, cnt, fl(n);
     std::vector<double> err, Ts((size_t)n * 12);
     if (nsurv > 0 && (rc = ransac_read_results(ctx, W, nsurv, surv, cnt, err))) return rc;
-    if (samples) R3D_HIP(ctx, hipMemcpyAsync(samples, W.samples, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(fl.data(), W.flags, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(Ts.data(), W.T, (size_t)n * 96, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, samples, W.samples, (size_t)n * 4)) || (rc = r3d_download(ctx, fl.data(), W.flags, (size_t)n)) ||
+        (rc = r3d_download(ctx, Ts.data(), W.T, (size_t)n * 12)))
+        return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < n; i++) {
         if (flags) flags[i] = fl[i];
@@ -5935,8 +5911,7 @@ int r3d_fgr_feature_matching(r3d_ctx *ctx, const r3d_fgr_params *p, const double
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_s, *d_t, *d_sf, *d_tf;
-    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
-    if ((rc = upload_pair(ctx, ar, src_feat, ns, tgt_feat, nt, &d_sf, &d_tf, FPFH_DIM))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t)) || (rc = upload_pair(ctx, ar, src_feat, ns, tgt_feat, nt, &d_sf, &d_tf, FPFH_DIM))) return rc;
     return fgr_core(ctx, ar, p, d_s, ns, d_t, nt, nullptr, 0, d_sf, d_tf, T4x4, stats, t_begin);
 }
 
@@ -5963,8 +5938,7 @@ int r3d_debug_fgr_tuples(r3d_ctx *ctx, const r3d_fgr_params *p, const double *sr
     if (ar.rc) return ar.rc;
     k_fgr_tuples<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(rows, M, p->seed, t0, n, p->tuple_scale, d_samples, d_flags, nullptr);
     R3D_HIP(ctx, hipGetLastError());
-    if (samples) R3D_HIP(ctx, hipMemcpyAsync(samples, d_samples, (size_t)n * 12, hipMemcpyDeviceToHost, ctx->stream));
-    if (flags) R3D_HIP(ctx, hipMemcpyAsync(flags, d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, samples, d_samples, (size_t)n * 3)) || (rc = r3d_download(ctx, flags, d_flags, (size_t)n))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -6053,13 +6027,13 @@ extern "C" int r3d_debug_sort_by_cell(r3d_ctx *ctx, const double *xyz, int64_t n
     bool k32;
     int *idx;
     if ((rc = sort_by_cell(ctx, ar, d_p, n, org3, cell, dims, key_order, &keys, &k32, &idx, nullptr, impl))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(idx_out, idx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, idx_out, idx, (size_t)n))) return rc;
     std::vector<unsigned> k4;
     if (keys_out) {
         if (k32) {
             k4.resize((size_t)n);
             R3D_HIP(ctx, hipMemcpyAsync(k4.data(), keys, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        } else R3D_HIP(ctx, hipMemcpyAsync(keys_out, keys, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        } else if ((rc = r3d_download(ctx, keys_out, (const uint64_t *)keys, (size_t)n))) return rc;
     }
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (keys_out && k32)
@@ -6100,9 +6074,8 @@ extern "C" int r3d_debug_icp_sums(r3d_ctx *ctx, const r3d_icp_params *p, const d
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_t, *d_s, *d_tn = nullptr, *d_sn = nullptr;
-    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
-    if (p->mode != MODE_P2P && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
-    if (p->mode == MODE_GICP && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t)) || (p->mode != MODE_P2P && (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) ||
+        (p->mode == MODE_GICP && (rc = upload(ctx, ar, src_normals, ns * 3, &d_sn)))) return rc;
     IcpWork w;
     if ((rc = icp_setup(ctx, ar, p, {.d_s = d_s, .ns = ns, .d_sn = d_sn, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = T4x4}, w))) return rc;
     return icp_read_sums(ctx, ar, p, w, sums_out, origin_out);
@@ -6124,14 +6097,13 @@ extern "C" int r3d_debug_icp_sums_colored(r3d_ctx *ctx, const r3d_colored_icp_pa
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
     double *d_t, *d_tn, *d_tc, *d_s, *d_sc;
-    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t))) return rc;
-    if ((rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn))) return rc;
-    if ((rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc))) return rc;
-    if ((rc = upload(ctx, ar, src_colors, ns * 3, &d_sc))) return rc;
+    if ((rc = upload_pair(ctx, ar, src, ns, tgt, nt, &d_s, &d_t)) || (rc = upload(ctx, ar, tgt_normals, nt * 3, &d_tn)) ||
+        (rc = upload(ctx, ar, tgt_colors, nt * 3, &d_tc)) || (rc = upload(ctx, ar, src_colors, ns * 3, &d_sc)))
+        return rc;
     ci.d_sc = d_sc; ci.d_tc = d_tc;
     IcpWork w;
     if ((rc = icp_setup(ctx, ar, &ip, {.d_s = d_s, .ns = ns, .d_t = d_t, .nt = nt, .d_tn = d_tn, .init4x4 = T4x4, .color = &ci}, w))) return rc;
-    if (tgt_records_out) R3D_HIP(ctx, hipMemcpyAsync(tgt_records_out, w.d_trec, (size_t)nt * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, tgt_records_out, w.d_trec, (size_t)nt * 4))) return rc;
     return icp_read_sums(ctx, ar, &ip, w, sums_out, nullptr);   // synchronises the stream
 }
 
@@ -6141,12 +6113,12 @@ extern "C" int r3d_debug_exclusive_scan(r3d_ctx *ctx, const int32_t *in, int64_t
     if (!in || !out || n <= 0 || op < 0 || op > 1) return r3d_fail(ctx, R3D_E_BADARG, "debug_exclusive_scan: bad argument");
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    int *d_in = (int *)ar.get((size_t)n * 4), *d_out = (int *)ar.get((size_t)n * 4);
+    const int *d_in;
+    if (int rc = r3d_upload(ctx, ar, in, (size_t)n, &d_in)) return rc;
+    int *d_out = (int *)ar.get((size_t)n * 4);
     if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = op == 1 ? dev_exclusive_scan<int, true>(ctx, ar, d_in, d_out, n) : dev_exclusive_scan<int>(ctx, ar, d_in, d_out, n);
-    if (rc) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    int rc = op == 1 ? dev_exclusive_scan<int, true>(ctx, ar, d_in, d_out, n) : dev_exclusive_scan<int>(ctx, ar, d_in, d_out, n);
+    if (rc || (rc = r3d_download(ctx, out, d_out, (size_t)n))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }

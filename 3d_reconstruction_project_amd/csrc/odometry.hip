@@ -498,7 +498,7 @@ int odo_run(r3d_ctx *ctx, DevArena &ar, const r3d_odometry_params *p, const floa
     R3D_HIP(ctx, hipEventRecord(ev[2], st));
     OdoState hs;
     R3D_HIP(ctx, hipMemcpyAsync(&hs, W.st, sizeof(hs), hipMemcpyDeviceToHost, st));
-    if (d_trace) R3D_HIP(ctx, hipMemcpyAsync(trace_T, d_trace, (size_t)total * 128, hipMemcpyDeviceToHost, st));
+    if (d_trace && (rc = r3d_download(ctx, trace_T, d_trace, (size_t)total * 16))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(st));   // the one wait of the call
     const bool ok = !hs.failed;
     for (int i = 0; i < 16; i++) T4x4[i] = ok ? hs.T[i] : (double)(i % 5 == 0);
@@ -525,25 +525,15 @@ int odo_run(r3d_ctx *ctx, DevArena &ar, const r3d_odometry_params *p, const floa
     return R3D_OK;
 }
 
-// four host float planes -> contiguous device planes
-int odo_upload(r3d_ctx *ctx, DevArena &ar, const float *const host[4], int w, int h, int stride, float *dev[4]) {
-    for (int k = 0; k < 4; k++) {
-        dev[k] = (float *)ar.get((size_t)w * h * 4);
-        if (ar.rc) return ar.rc;
-        R3D_HIP(ctx, hipMemcpy2DAsync(dev[k], (size_t)w * 4, host[k], (size_t)stride * 4, (size_t)w * 4, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return R3D_OK;
-}
-
 int odo_convert(r3d_ctx *ctx, DevArena &ar, const uint16_t *depth, const uint8_t *color, int w, int h, int dstride, int cstride, int cn, int bgr,
                 const r3d_depth_camera *cam, float **d_I, float **d_D) {
-    uint16_t *dd = (uint16_t *)ar.get((size_t)w * h * 2);
-    uint8_t *dc = (uint8_t *)ar.get((size_t)w * h * cn);
+    uint16_t *dd;
+    uint8_t *dc;
+    int rc;
+    if ((rc = r3d_upload_plane(ctx, ar, depth, w, h, dstride, &dd)) || (rc = r3d_upload_plane(ctx, ar, color, w * cn, h, cstride, &dc))) return rc;
     *d_I = (float *)ar.get((size_t)w * h * 4);
     *d_D = (float *)ar.get((size_t)w * h * 4);
     if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpy2DAsync(dd, (size_t)w * 2, depth, (size_t)dstride * 2, (size_t)w * 2, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(ctx, hipMemcpy2DAsync(dc, (size_t)w * cn, color, (size_t)cstride, (size_t)w * cn, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
     k_odo_convert<<<odo_grid(w, h), 256, 0, ctx->stream>>>(dd, w, dc, w * cn, cn, bgr, (float)cam->depth_scale, (float)cam->depth_trunc, w, h, *d_I, *d_D);
     R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
@@ -588,7 +578,7 @@ int r3d_rgbd_odometry_f32(r3d_ctx *ctx, const r3d_odometry_params *p, const floa
     DevArena ar(ctx);
     const float *const host[4] = {src_intensity, src_depth, tgt_intensity, tgt_depth};
     float *dev[4];
-    if ((rc = odo_upload(ctx, ar, host, w, h, stride, dev))) return rc;
+    for (int k = 0; k < 4; k++) if ((rc = r3d_upload_plane(ctx, ar, host[k], w, h, stride, &dev[k]))) return rc;   // -> dense device planes
     return odo_run(ctx, ar, p, dev[0], dev[1], dev[2], dev[3], w, h, w, OdoCam{fx, fy, cx, cy}, init4x4, T4x4, info6x6, stats, trace_T);
 }
 
@@ -622,8 +612,7 @@ int r3d_debug_rgbd_convert(r3d_ctx *ctx, const uint16_t *depth, const uint8_t *c
     DevArena ar(ctx);
     float *dI, *dD;
     if ((rc = odo_convert(ctx, ar, depth, color, w, h, depth_stride, color_stride, color_channels, color_bgr, cam, &dI, &dD))) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(out_intensity, dI, (size_t)w * h * 4, hipMemcpyDeviceToHost, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(out_depth, dD, (size_t)w * h * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_download(ctx, out_intensity, dI, (size_t)w * h)) || (rc = r3d_download(ctx, out_depth, dD, (size_t)w * h))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -642,7 +631,7 @@ int r3d_debug_rgbd_prepare(r3d_ctx *ctx, const r3d_odometry_params *p, const flo
     DevArena ar(ctx);
     const float *const host[4] = {src_intensity, src_depth, tgt_intensity, tgt_depth};
     float *dev[4];
-    if ((rc = odo_upload(ctx, ar, host, w, h, stride, dev))) return rc;
+    for (int k = 0; k < 4; k++) if ((rc = r3d_upload_plane(ctx, ar, host[k], w, h, stride, &dev[k]))) return rc;   // -> dense device planes
     OdoWork W;
     if ((rc = odo_prepare(ctx, ar, p, dev[0], dev[1], dev[2], dev[3], w, h, w, OdoCam{fx, fy, cx, cy}, init4x4, W))) return rc;
     hipStream_t st = ctx->stream;
@@ -654,10 +643,10 @@ int r3d_debug_rgbd_prepare(r3d_ctx *ctx, const r3d_odometry_params *p, const flo
         const size_t n = (size_t)W.w[l] * W.h[l];
         const float *planes[4] = {W.src.I[l], W.src.D[l], W.tgt.I[l], W.tgt.D[l]};
         for (int k = 0; k < 4; k++)
-            if (outs[k]) R3D_HIP(ctx, hipMemcpyAsync(outs[k] + off, planes[k], n * 4, hipMemcpyDeviceToHost, st));
+            if (outs[k] && (rc = r3d_download(ctx, outs[k] + off, planes[k], n))) return rc;
         off += n;
     }
-    if (grad4) R3D_HIP(ctx, hipMemcpyAsync(grad4, W.grad[grad_level], (size_t)W.w[grad_level] * W.h[grad_level] * 16, hipMemcpyDeviceToHost, st));
+    if (grad4 && (rc = r3d_download(ctx, grad4, (const float *)W.grad[grad_level], (size_t)W.w[grad_level] * W.h[grad_level] * 4))) return rc;
     OdoState hs;
     R3D_HIP(ctx, hipMemcpyAsync(&hs, W.st, sizeof(hs), hipMemcpyDeviceToHost, st));
     R3D_HIP(ctx, hipStreamSynchronize(st));
@@ -681,7 +670,7 @@ int r3d_debug_rgbd_iteration(r3d_ctx *ctx, const r3d_odometry_params *p, const f
     DevArena ar(ctx);
     const float *const host[4] = {src_intensity, src_depth, tgt_intensity, tgt_depth};
     float *dev[4];
-    if ((rc = odo_upload(ctx, ar, host, w, h, stride, dev))) return rc;
+    for (int k = 0; k < 4; k++) if ((rc = r3d_upload_plane(ctx, ar, host[k], w, h, stride, &dev[k]))) return rc;   // -> dense device planes
     OdoWork W;
     if ((rc = odo_prepare(ctx, ar, p, dev[0], dev[1], dev[2], dev[3], w, h, w, OdoCam{fx, fy, cx, cy}, init4x4, W))) return rc;
     hipStream_t st = ctx->stream;

@@ -841,8 +841,8 @@ extern "C" int r3d_init_undistort_rectify_map(r3d_ctx *ctx, const double *camera
     if (ar.rc) return ar.rc;
     k_rectify_map<<<(h + 63) / 64, 64, 0, ctx->stream>>>(P, w, h, d1, d2);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(map1, d1, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(map2, d2, n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = r3d_download(ctx, map1, d1, n * 2)) return rc;
+    if (int rc = r3d_download(ctx, map2, d2, n)) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -874,17 +874,15 @@ extern "C" int r3d_remap_u8(r3d_ctx *ctx, const uint8_t *src, int32_t sw, int32_
         return r3d_fail(ctx, R3D_E_BADARG, "remap: bad argument");
     DevArena ar(ctx, ctx->pp_bufs);
     const size_t ns = (size_t)sstride * sh, nd = (size_t)dw * dh;
-    uint8_t *ds = (uint8_t *)ar.get(ns), *dd = (uint8_t *)ar.get(nd * cn), *dg = (uint8_t *)ar.get(nd);
-    int16_t *d1 = (int16_t *)ar.get(nd * 4);
-    uint16_t *d2 = (uint16_t *)ar.get(nd * 2);
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(ds, src, ns, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(d1, map1, nd * 4, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(d2, map2, nd * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = r3d_remap_u8_dev(ctx, ds, sw, sh, sstride, cn, d1, d2, dw, dh, border_value, dd, gray ? dg : nullptr);
-    if (rc) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(dst, dd, nd * cn, hipMemcpyDeviceToHost, ctx->stream));
-    if (gray) R3D_HIP(ctx, hipMemcpyAsync(gray, dg, nd, hipMemcpyDeviceToHost, ctx->stream));
+    const uint8_t *ds;
+    const int16_t *d1;
+    const uint16_t *d2;
+    int rc;
+    if ((rc = r3d_upload(ctx, ar, src, ns, &ds))) return rc;
+    uint8_t *dd = (uint8_t *)ar.get(nd * cn), *dg = (uint8_t *)ar.get(nd);
+    if ((rc = r3d_upload(ctx, ar, map1, nd * 2, &d1)) || (rc = r3d_upload(ctx, ar, map2, nd, &d2))) return rc;
+    if ((rc = r3d_remap_u8_dev(ctx, ds, sw, sh, sstride, cn, d1, d2, dw, dh, border_value, dd, gray ? dg : nullptr))) return rc;
+    if ((rc = r3d_download(ctx, dst, dd, nd * cn)) || (rc = r3d_download(ctx, gray, dg, nd))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -905,12 +903,12 @@ extern "C" int r3d_bgr2gray(r3d_ctx *ctx, const uint8_t *bgr, int32_t w, int32_t
     if (!bgr || !gray || w <= 0 || h <= 0 || (cn != 3 && cn != 4) || stride < w * cn) return r3d_fail(ctx, R3D_E_BADARG, "bgr2gray: bad argument");
     DevArena ar(ctx, ctx->pp_bufs);
     const size_t ns = (size_t)stride * h, nd = (size_t)w * h;
-    uint8_t *ds = (uint8_t *)ar.get(ns), *dg = (uint8_t *)ar.get(nd);
+    const uint8_t *ds;
+    int rc;
+    if ((rc = r3d_upload(ctx, ar, bgr, ns, &ds))) return rc;
+    uint8_t *dg = (uint8_t *)ar.get(nd);
     if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(ds, bgr, ns, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = r3d_bgr2gray_dev(ctx, ds, w, h, stride, cn, dg);
-    if (rc) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(gray, dg, nd, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_bgr2gray_dev(ctx, ds, w, h, stride, cn, dg)) || (rc = r3d_download(ctx, gray, dg, nd))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -936,12 +934,12 @@ extern "C" int r3d_normalize_minmax_s16(r3d_ctx *ctx, const int16_t *src, int64_
     if (check_ctx(ctx)) return R3D_E_BADARG;
     if (!src || !dst || n <= 0) return r3d_fail(ctx, R3D_E_BADARG, "normalize: bad argument");
     DevArena ar(ctx, ctx->pp_bufs);
-    int16_t *ds = (int16_t *)ar.get((size_t)n * 2), *dd = (int16_t *)ar.get((size_t)n * 2);
+    const int16_t *ds;
+    int rc;
+    if ((rc = r3d_upload(ctx, ar, src, (size_t)n, &ds))) return rc;
+    int16_t *dd = (int16_t *)ar.get((size_t)n * 2);
     if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(ds, src, (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = r3d_normalize_minmax_s16_dev(ctx, ds, n, alpha, beta, dd);
-    if (rc) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(dst, dd, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = r3d_normalize_minmax_s16_dev(ctx, ds, n, alpha, beta, dd)) || (rc = r3d_download(ctx, dst, dd, (size_t)n))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -1067,17 +1065,15 @@ extern "C" int r3d_wls_filter(r3d_ctx *ctx, const r3d_wls_params *p, const int16
     if (!disp_left || !disp_right || !guide || !out || guide_stride < w * guide_cn) return r3d_fail(ctx, R3D_E_BADARG, "wls_filter: bad argument");
     DevArena ar(ctx, ctx->pp_bufs);
     const size_t n = (size_t)w * h, ng = (size_t)guide_stride * h;
-    int16_t *dl = (int16_t *)ar.get(n * 2), *dr = (int16_t *)ar.get(n * 2), *dout = (int16_t *)ar.get(n * 2);
-    uint8_t *dg = (uint8_t *)ar.get(ng);
+    const int16_t *dl, *dr;
+    const uint8_t *dg;
+    if ((rc = r3d_upload(ctx, ar, disp_left, n, &dl)) || (rc = r3d_upload(ctx, ar, disp_right, n, &dr))) return rc;
+    int16_t *dout = (int16_t *)ar.get(n * 2);
+    if ((rc = r3d_upload(ctx, ar, guide, ng, &dg))) return rc;
     float *dc = confidence ? (float *)ar.get(n * 4) : nullptr;
     if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpyAsync(dl, disp_left, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(dr, disp_right, n * 2, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(ctx, hipMemcpyAsync(dg, guide, ng, hipMemcpyHostToDevice, ctx->stream));
-    rc = wls_run(ctx, ar, p, dl, dr, dg, guide_cn, guide_stride, w, h, dout, dc);
-    if (rc) return rc;
-    R3D_HIP(ctx, hipMemcpyAsync(out, dout, n * 2, hipMemcpyDeviceToHost, ctx->stream));
-    if (confidence) R3D_HIP(ctx, hipMemcpyAsync(confidence, dc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = wls_run(ctx, ar, p, dl, dr, dg, guide_cn, guide_stride, w, h, dout, dc))) return rc;
+    if ((rc = r3d_download(ctx, out, dout, n)) || (rc = r3d_download(ctx, confidence, dc, n))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }

@@ -111,6 +111,38 @@ struct DevArena {  // simple bump allocator over one of the context's buffer lis
     }
 };
 
+// ---- staging around the device core of a host-buffer entry point: copies on ctx->stream, enqueued only (the entry point synchronises).
+// host array -> fresh arena buffer; a null h gives a null *d and takes no arena slot, count == 0 takes a slot and copies nothing
+template <class T>
+int r3d_upload(r3d_ctx *ctx, DevArena &ar, const T *h, size_t count, const T **d) {
+    *d = nullptr;
+    if (!h) return R3D_OK;
+    T *p = (T *)ar.get(count * sizeof(T));
+    if (ar.rc) return ar.rc;
+    if (count) R3D_HIP(ctx, hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    *d = p;
+    return R3D_OK;
+}
+// strided host image (rows of row_elems elements, stride_elems apart, both in elements of T) -> dense plane in a fresh arena buffer
+template <class T>
+int r3d_upload_plane(r3d_ctx *ctx, DevArena &ar, const T *h, int row_elems, int rows, size_t stride_elems, T **d) {
+    const size_t row = (size_t)row_elems * sizeof(T);
+    *d = (T *)ar.get(row * rows);
+    if (ar.rc) return ar.rc;
+    R3D_HIP(ctx, hipMemcpy2DAsync(*d, row, h, stride_elems * sizeof(T), row, rows, hipMemcpyHostToDevice, ctx->stream));
+    return R3D_OK;
+}
+// device buffer -> host array; nothing for a null h (an output the caller did not ask for) or a zero count
+template <class T>
+int r3d_download(r3d_ctx *ctx, T *h, const T *d, size_t count) {
+    if (h && count) R3D_HIP(ctx, hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return R3D_OK;
+}
+// the refusal of a count / capacity protocol: `have` rows of `what` against the caller's capacity
+static inline int r3d_fits(r3d_ctx *ctx, const char *who, const char *what, int64_t have, int64_t cap) {
+    return have <= cap ? R3D_OK : r3d_fail(ctx, R3D_E_BADARG, "%s: %lld %s do not fit a capacity of %lld", who, (long long)have, what, (long long)cap);
+}
+
 // SolveJacobianSystemAndObtainExtrinsicMatrix: x = LDLT(JTJ) \ (-JTr); identity when |det| < det_tol (the registration loop's
 // 1e-6).  det_tol < 0 (FGR: Open3D's SolveLinearSystemPSD has no such rule): no determinant test; the identity only for a zero
 // pivot or a non-finite x.

@@ -309,22 +309,6 @@ int tm_distinct(r3d_ctx *ctx, const char *who, const TmSpan *out, int n_out, con
     return R3D_OK;
 }
 
-template <class T>
-int tm_upload(r3d_ctx *ctx, DevArena &ar, const T *h, size_t count, const T **d) {
-    *d = nullptr;
-    if (!h) return R3D_OK;
-    T *p = (T *)ar.get(count * sizeof(T));
-    if (ar.rc) return ar.rc;
-    if (count) R3D_HIP(ctx, hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    *d = p;
-    return R3D_OK;
-}
-template <class T>
-int tm_download(r3d_ctx *ctx, T *h, const T *d, size_t count) {
-    if (h && count) R3D_HIP(ctx, hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    return R3D_OK;
-}
-
 struct TmTopo {
     int *inc_off = nullptr, *inc = nullptr;   // [nv + 1], [3 nt]
     int *adj_off = nullptr, *adj = nullptr;   // [nv + 1], [<= 6 nt]
@@ -401,7 +385,7 @@ int tm_lists(r3d_ctx *ctx, const char *who, bool adjacency, int64_t nv, int64_t 
     }
     DevArena ar(ctx);
     const int32_t *d_tri;
-    if (int rc = tm_upload(ctx, ar, triangles, (size_t)nt * 3, &d_tri)) return rc;
+    if (int rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &d_tri)) return rc;
     TmTopo T;
     if (int rc = tm_topology(ctx, ar, who, (int)nv, nt, d_tri, adjacency ? TM_ADJACENCY : TM_INCIDENCE, T)) return rc;
     const int *d_off = adjacency ? T.adj_off : T.inc_off, *d_list = adjacency ? T.adj : T.inc;
@@ -410,9 +394,9 @@ int tm_lists(r3d_ctx *ctx, const char *who, bool adjacency, int64_t nv, int64_t 
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out_n = total;
     if (cap == 0) return R3D_OK;
-    if (cap < total) return r3d_fail(ctx, R3D_E_BADARG, "%s: %d entries do not fit a capacity of %lld", who, total, (long long)cap);
-    if (int rc = tm_download(ctx, offsets, d_off, (size_t)nv + 1)) return rc;
-    if (int rc = tm_download(ctx, list, d_list, (size_t)total)) return rc;
+    if (int rc = r3d_fits(ctx, who, "entries", total, cap)) return rc;
+    if (int rc = r3d_download(ctx, offsets, d_off, (size_t)nv + 1)) return rc;
+    if (int rc = r3d_download(ctx, list, d_list, (size_t)total)) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -627,16 +611,16 @@ int r3d_trimesh_smooth(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *verti
     const size_t n3 = (size_t)nv * 3;
     TmSmooth m = {nv, nt, nullptr, nullptr, nullptr, nullptr, kind, iterations, scope, lambda, mu, nullptr, nullptr, nullptr};
     int rc;
-    if ((rc = tm_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = tm_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = tm_upload(ctx, ar, colors, n3, &m.col)) ||
-        (rc = tm_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)))
+    if ((rc = r3d_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = r3d_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = r3d_upload(ctx, ar, colors, n3, &m.col)) ||
+        (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)))
         return rc;
     m.out_pos = (double *)ar.get(n3 * 8);
     m.out_nrm = normals ? (double *)ar.get(n3 * 8) : nullptr;
     m.out_col = colors ? (double *)ar.get(n3 * 8) : nullptr;
     if (ar.rc) return ar.rc;
     if ((rc = tm_smooth(ctx, ar, m))) return rc;
-    if ((rc = tm_download(ctx, out_vertices, m.out_pos, n3)) || (rc = tm_download(ctx, out_normals, m.out_nrm, normals ? n3 : 0)) ||
-        (rc = tm_download(ctx, out_colors, m.out_col, colors ? n3 : 0)))
+    if ((rc = r3d_download(ctx, out_vertices, m.out_pos, n3)) || (rc = r3d_download(ctx, out_normals, m.out_nrm, normals ? n3 : 0)) ||
+        (rc = r3d_download(ctx, out_colors, m.out_col, colors ? n3 : 0)))
         return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
@@ -674,12 +658,12 @@ int r3d_trimesh_normals(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vert
     const double *d_pos;
     const int32_t *d_tri;
     int rc;
-    if ((rc = tm_upload(ctx, ar, vertices, (size_t)nv * 3, &d_pos)) || (rc = tm_upload(ctx, ar, triangles, (size_t)nt * 3, &d_tri))) return rc;
+    if ((rc = r3d_upload(ctx, ar, vertices, (size_t)nv * 3, &d_pos)) || (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &d_tri))) return rc;
     double *d_tn = triangle_normals ? (double *)ar.get((size_t)nt * 24) : nullptr;
     double *d_vn = vertex_normals ? (double *)ar.get((size_t)nv * 24) : nullptr;
     if (ar.rc) return ar.rc;
     if ((rc = tm_normals(ctx, ar, nv, nt, d_pos, d_tri, flags, d_tn, d_vn))) return rc;
-    if ((rc = tm_download(ctx, triangle_normals, d_tn, (size_t)nt * 3)) || (rc = tm_download(ctx, vertex_normals, d_vn, (size_t)nv * 3))) return rc;
+    if ((rc = r3d_download(ctx, triangle_normals, d_tn, (size_t)nt * 3)) || (rc = r3d_download(ctx, vertex_normals, d_vn, (size_t)nv * 3))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -713,9 +697,9 @@ int r3d_trimesh_compact(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vert
     DevArena ar(ctx);
     const size_t n3 = (size_t)nv * 3;
     int rc;
-    if ((rc = tm_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = tm_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = tm_upload(ctx, ar, colors, n3, &m.col)) ||
-        (rc = tm_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)) || (rc = tm_upload(ctx, ar, vertex_keep, (size_t)nv, &m.vkeep)) ||
-        (rc = tm_upload(ctx, ar, triangle_keep, (size_t)nt, &m.tkeep)))
+    if ((rc = r3d_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = r3d_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = r3d_upload(ctx, ar, colors, n3, &m.col)) ||
+        (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)) || (rc = r3d_upload(ctx, ar, vertex_keep, (size_t)nv, &m.vkeep)) ||
+        (rc = r3d_upload(ctx, ar, triangle_keep, (size_t)nt, &m.tkeep)))
         return rc;
     // device outputs as large as the inputs: the counts are not known yet
     m.out_pos = (double *)ar.get(n3 * 8);
@@ -727,8 +711,8 @@ int r3d_trimesh_compact(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vert
     if ((rc = tm_compact(ctx, ar, m, out_nv, out_nt, &wrote))) return rc;
     if (!wrote) return R3D_OK;
     const size_t k3 = (size_t)*out_nv * 3;
-    if ((rc = tm_download(ctx, out_vertices, m.out_pos, k3)) || (rc = tm_download(ctx, out_normals, m.out_nrm, normals ? k3 : 0)) ||
-        (rc = tm_download(ctx, out_colors, m.out_col, colors ? k3 : 0)) || (rc = tm_download(ctx, out_triangles, m.out_tri, (size_t)*out_nt * 3)))
+    if ((rc = r3d_download(ctx, out_vertices, m.out_pos, k3)) || (rc = r3d_download(ctx, out_normals, m.out_nrm, normals ? k3 : 0)) ||
+        (rc = r3d_download(ctx, out_colors, m.out_col, colors ? k3 : 0)) || (rc = r3d_download(ctx, out_triangles, m.out_tri, (size_t)*out_nt * 3)))
         return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;

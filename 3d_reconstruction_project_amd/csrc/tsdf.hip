@@ -819,108 +819,100 @@ int tsdf_sort_units(r3d_tsdf *v) {
     return R3D_OK;
 }
 
-// count (always), then emit into device arrays when cap allows.  Returns after the count is known.
-int tsdf_extract(r3d_tsdf *v, DevArena &ar, int64_t cap, double *d_xyz, double *d_nrm, double *d_col, int64_t *out_n, bool host_out, double *xyz,
-                 double *nrm, double *col) {
+// extraction in two halves around the caller's capacity check: the count (always), then the rows into device arrays
+struct TsdfExtractWork {
+    int n = 0;   // units
+    int *thread_off = nullptr, *unit_cnt = nullptr;
+    long long *unit_off = nullptr, total = 0;
+};
+// allocates the scratch, counts, and returns after its one synchronisation with the total in W and *out_n (0 for an empty volume)
+int tsdf_extract_count(r3d_tsdf *v, DevArena &ar, TsdfExtractWork &W, int64_t *out_n) {
     r3d_ctx *ctx = v->ctx;
     hipStream_t st = ctx->stream;
-    const bool color = v->prm.color_type == R3D_TSDF_COLOR_RGB8;
     *out_n = 0;
     if (!v->n_units) return R3D_OK;
-    const int n = v->n_units;
-    int *thread_off = (int *)ar.get((size_t)n * 256 * 4);
-    int *unit_cnt = (int *)ar.get((size_t)n * 4);
-    long long *unit_off = (long long *)ar.get((size_t)n * 8);
+    const int n = W.n = v->n_units;
+    W.thread_off = (int *)ar.get((size_t)n * 256 * 4);
+    W.unit_cnt = (int *)ar.get((size_t)n * 4);
+    W.unit_off = (long long *)ar.get((size_t)n * 8);
     long long *d_total = (long long *)ar.get(8);
     if (ar.rc) return ar.rc;
-    int rc;
-    if ((rc = tsdf_sort_units(v))) return rc;
-    const TsdfVol V = tsdf_view(v);
-    k_tsdf_extract<false, false><<<(unsigned)n, 256, 0, st>>>(V, (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, thread_off, unit_cnt, nullptr, nullptr, nullptr, nullptr);
-    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, unit_off, d_total);
+    if (int rc = tsdf_sort_units(v)) return rc;
+    k_tsdf_extract<false, false><<<(unsigned)n, 256, 0, st>>>(tsdf_view(v), (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, W.thread_off, W.unit_cnt, nullptr, nullptr, nullptr, nullptr);
+    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(W.unit_cnt, n, W.unit_off, d_total);
     R3D_HIP(ctx, hipGetLastError());
-    long long total = 0;
-    R3D_HIP(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipMemcpyAsync(&W.total, d_total, 8, hipMemcpyDeviceToHost, st));
     R3D_HIP(ctx, hipStreamSynchronize(st));
-    *out_n = total;
-    if (cap == 0 || total == 0) return R3D_OK;
-    if (cap < total) return r3d_fail(ctx, R3D_E_BADARG, "tsdf_extract_point_cloud: %lld points do not fit a capacity of %lld", total, (long long)cap);
-    if (host_out) {
-        d_xyz = (double *)ar.get((size_t)total * 24);
-        d_nrm = (double *)ar.get((size_t)total * 24);
-        d_col = color ? (double *)ar.get((size_t)total * 24) : nullptr;
-        if (ar.rc) return ar.rc;
-    }
-    if (color)
-        k_tsdf_extract<true, true><<<(unsigned)n, 256, 0, st>>>(V, (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, d_col);
+    *out_n = W.total;
+    return R3D_OK;
+}
+// W.total > 0 rows into device arrays (d_col only for a coloured volume); enqueues only
+int tsdf_extract_emit(r3d_tsdf *v, const TsdfExtractWork &W, double *d_xyz, double *d_nrm, double *d_col) {
+    if (v->prm.color_type == R3D_TSDF_COLOR_RGB8)
+        k_tsdf_extract<true, true><<<(unsigned)W.n, 256, 0, v->ctx->stream>>>(tsdf_view(v), (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, W.thread_off, W.unit_cnt, W.unit_off, d_xyz, d_nrm, d_col);
     else
-        k_tsdf_extract<true, false><<<(unsigned)n, 256, 0, st>>>(V, (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, thread_off, unit_cnt, unit_off, d_xyz, d_nrm, nullptr);
-    R3D_HIP(ctx, hipGetLastError());
-    if (host_out) {
-        R3D_HIP(ctx, hipMemcpyAsync(xyz, d_xyz, (size_t)total * 24, hipMemcpyDeviceToHost, st));
-        R3D_HIP(ctx, hipMemcpyAsync(nrm, d_nrm, (size_t)total * 24, hipMemcpyDeviceToHost, st));
-        if (color) R3D_HIP(ctx, hipMemcpyAsync(col, d_col, (size_t)total * 24, hipMemcpyDeviceToHost, st));
-        R3D_HIP(ctx, hipStreamSynchronize(st));
-    }
+        k_tsdf_extract<true, false><<<(unsigned)W.n, 256, 0, v->ctx->stream>>>(tsdf_view(v), (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, W.thread_off, W.unit_cnt, W.unit_off, d_xyz, d_nrm, nullptr);
+    R3D_HIP(v->ctx, hipGetLastError());
     return R3D_OK;
 }
 
-// cube bytes, counts (always), then vertices, ids and triangles into device arrays when the capacities allow.  Returns after the
-// counts are known; with host_out after the rows are on the host.
-int tsdf_mesh(r3d_tsdf *v, DevArena &ar, int64_t cap_v, int64_t cap_t, double *d_vert, double *d_col, int32_t *d_tri, int64_t *out_nv, int64_t *out_nt,
-              bool host_out, double *vert, double *col, int32_t *tri) {
+// the mesh likewise: cube bytes and counts (always), then vertices, ids and triangles into device arrays
+struct TsdfMeshWork {
+    int n = 0;   // units
+    TsdfVol V;
+    const int *order = nullptr;               // v->order and v->unit_keys, typed
+    const unsigned long long *keys = nullptr;
+    uint8_t *cube = nullptr;
+    unsigned *thread_cnt = nullptr;
+    int32_t *vid = nullptr;   // the emitting half's vertex ids (tsdf_mesh_fits)
+    long long *unit_off = nullptr, total[2] = {0, 0};   // total: vertices, triangles
+};
+// as tsdf_extract_count, with the totals in W, *out_nv and *out_nt; refuses totals that int32 triangle indices cannot address
+int tsdf_mesh_count(r3d_tsdf *v, DevArena &ar, TsdfMeshWork &W, int64_t *out_nv, int64_t *out_nt) {
     r3d_ctx *ctx = v->ctx;
     hipStream_t st = ctx->stream;
-    const bool color = v->prm.color_type == R3D_TSDF_COLOR_RGB8;
     *out_nv = *out_nt = 0;
     if (!v->n_units) return R3D_OK;
-    const int n = v->n_units;
-    uint8_t *cube = (uint8_t *)ar.get((size_t)n * TSDF_UNIT);
-    unsigned *thread_cnt = (unsigned *)ar.get((size_t)n * 256 * 4);
+    const int n = W.n = v->n_units;
+    W.cube = (uint8_t *)ar.get((size_t)n * TSDF_UNIT);
+    W.thread_cnt = (unsigned *)ar.get((size_t)n * 256 * 4);
     int *unit_cnt = (int *)ar.get((size_t)n * 2 * 4);              // vertices of every unit, then triangles of every unit
-    long long *unit_off = (long long *)ar.get((size_t)n * 2 * 8);
+    W.unit_off = (long long *)ar.get((size_t)n * 2 * 8);
     long long *d_total = (long long *)ar.get(16);
     if (ar.rc) return ar.rc;
-    int rc;
-    if ((rc = tsdf_sort_units(v))) return rc;
-    const TsdfVol V = tsdf_view(v);
-    const int *order = (const int *)v->order.p;
-    const unsigned long long *keys = (const unsigned long long *)v->unit_keys.p;
-    k_tsdf_mc_cubes<<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube);
-    k_tsdf_mc_vertices<false, false><<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube, thread_cnt, unit_cnt, unit_cnt + n, nullptr, nullptr, nullptr, nullptr);
-    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, unit_off, d_total);
-    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt + n, n, unit_off + n, d_total + 1);
+    if (int rc = tsdf_sort_units(v)) return rc;
+    W.V = tsdf_view(v);
+    W.order = (const int *)v->order.p;
+    W.keys = (const unsigned long long *)v->unit_keys.p;
+    k_tsdf_mc_cubes<<<(unsigned)n, 256, 0, st>>>(W.V, W.order, W.keys, W.cube);
+    k_tsdf_mc_vertices<false, false><<<(unsigned)n, 256, 0, st>>>(W.V, W.order, W.keys, W.cube, W.thread_cnt, unit_cnt, unit_cnt + n, nullptr, nullptr, nullptr, nullptr);
+    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, W.unit_off, d_total);
+    k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt + n, n, W.unit_off + n, d_total + 1);
     R3D_HIP(ctx, hipGetLastError());
-    long long total[2] = {0, 0};
-    R3D_HIP(ctx, hipMemcpyAsync(total, d_total, 16, hipMemcpyDeviceToHost, st));
+    R3D_HIP(ctx, hipMemcpyAsync(W.total, d_total, 16, hipMemcpyDeviceToHost, st));
     R3D_HIP(ctx, hipStreamSynchronize(st));
-    *out_nv = total[0];
-    *out_nt = total[1];
-    if (total[0] > INT32_MAX || total[1] > INT32_MAX)
-        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "mesh_from_volume: %lld vertices and %lld triangles do not fit int32 indices", total[0], total[1]);
-    if ((cap_v == 0 && cap_t == 0) || (total[0] == 0 && total[1] == 0)) return R3D_OK;
-    if (cap_v < total[0] || cap_t < total[1])
-        return r3d_fail(ctx, R3D_E_BADARG, "mesh_from_volume: %lld vertices and %lld triangles do not fit capacities of %lld and %lld", total[0],
-                        total[1], (long long)cap_v, (long long)cap_t);
-    int32_t *vid = (int32_t *)ar.get((size_t)n * TSDF_UNIT * 12);
-    if (host_out) {
-        d_vert = (double *)ar.get((size_t)total[0] * 24);
-        d_col = color ? (double *)ar.get((size_t)total[0] * 24) : nullptr;
-        d_tri = (int32_t *)ar.get((size_t)total[1] * 12);
-    }
-    if (ar.rc) return ar.rc;
-    if (color)
-        k_tsdf_mc_vertices<true, true><<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube, thread_cnt, nullptr, nullptr, unit_off, vid, d_vert, d_col);
+    *out_nv = W.total[0]; *out_nt = W.total[1];
+    if (W.total[0] > INT32_MAX || W.total[1] > INT32_MAX)
+        return r3d_fail(ctx, R3D_E_UNSUPPORTED, "mesh_from_volume: %lld vertices and %lld triangles do not fit int32 indices", W.total[0], W.total[1]);
+    return R3D_OK;
+}
+// the capacity refusal of a non-empty mesh, then the emitting half's scratch: it comes ahead of any arena outputs of the caller
+int tsdf_mesh_fits(r3d_ctx *ctx, DevArena &ar, TsdfMeshWork &W, int64_t cap_v, int64_t cap_t) {
+    if (cap_v < W.total[0] || cap_t < W.total[1])
+        return r3d_fail(ctx, R3D_E_BADARG, "mesh_from_volume: %lld vertices and %lld triangles do not fit capacities of %lld and %lld", W.total[0],
+                        W.total[1], (long long)cap_v, (long long)cap_t);
+    W.vid = (int32_t *)ar.get((size_t)W.n * TSDF_UNIT * 12);
+    return ar.rc;
+}
+// the counted mesh into device arrays (d_col only for a coloured volume); enqueues only
+int tsdf_mesh_emit(r3d_tsdf *v, const TsdfMeshWork &W, double *d_vert, double *d_col, int32_t *d_tri) {
+    hipStream_t st = v->ctx->stream;
+    if (v->prm.color_type == R3D_TSDF_COLOR_RGB8)
+        k_tsdf_mc_vertices<true, true><<<(unsigned)W.n, 256, 0, st>>>(W.V, W.order, W.keys, W.cube, W.thread_cnt, nullptr, nullptr, W.unit_off, W.vid, d_vert, d_col);
     else
-        k_tsdf_mc_vertices<true, false><<<(unsigned)n, 256, 0, st>>>(V, order, keys, cube, thread_cnt, nullptr, nullptr, unit_off, vid, d_vert, nullptr);
-    k_tsdf_mc_triangles<<<(unsigned)n, 256, 0, st>>>(V.t, order, keys, cube, vid, thread_cnt, unit_off + n, d_tri);
-    R3D_HIP(ctx, hipGetLastError());
-    if (host_out) {
-        if (total[0]) R3D_HIP(ctx, hipMemcpyAsync(vert, d_vert, (size_t)total[0] * 24, hipMemcpyDeviceToHost, st));
-        if (total[0] && color) R3D_HIP(ctx, hipMemcpyAsync(col, d_col, (size_t)total[0] * 24, hipMemcpyDeviceToHost, st));
-        if (total[1]) R3D_HIP(ctx, hipMemcpyAsync(tri, d_tri, (size_t)total[1] * 12, hipMemcpyDeviceToHost, st));
-        R3D_HIP(ctx, hipStreamSynchronize(st));
-    }
+        k_tsdf_mc_vertices<true, false><<<(unsigned)W.n, 256, 0, st>>>(W.V, W.order, W.keys, W.cube, W.thread_cnt, nullptr, nullptr, W.unit_off, W.vid, d_vert, nullptr);
+    k_tsdf_mc_triangles<<<(unsigned)W.n, 256, 0, st>>>(W.V.t, W.order, W.keys, W.cube, W.vid, W.thread_cnt, W.unit_off + W.n, d_tri);
+    R3D_HIP(v->ctx, hipGetLastError());
     return R3D_OK;
 }
 
@@ -1021,11 +1013,9 @@ int r3d_tsdf_integrate_f32(r3d_ctx *ctx, r3d_tsdf *vol, const float *depth, cons
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const bool rgb = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
     DevArena ar(ctx);
-    float *dd = (float *)ar.get((size_t)w * h * 4);
-    uint8_t *dc = rgb ? (uint8_t *)ar.get((size_t)w * h * 3) : nullptr;
-    if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpy2DAsync(dd, (size_t)w * 4, depth, (size_t)depth_stride * 4, (size_t)w * 4, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
-    if (rgb) R3D_HIP(ctx, hipMemcpy2DAsync(dc, (size_t)w * 3, color, (size_t)color_stride, (size_t)w * 3, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    float *dd;
+    uint8_t *dc = nullptr;
+    if ((rc = r3d_upload_plane(ctx, ar, depth, w, h, depth_stride, &dd)) || (rgb && (rc = r3d_upload_plane(ctx, ar, color, w * 3, h, color_stride, &dc)))) return rc;
     if ((rc = tsdf_integrate_dev(vol, dd, w, dc, w * 3, w, h, TsdfCam{fx, fy, cx, cy}, extrinsic4x4))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
@@ -1045,12 +1035,12 @@ int r3d_tsdf_integrate(r3d_ctx *ctx, r3d_tsdf *vol, const uint16_t *depth, const
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     const bool rgb = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
     DevArena ar(ctx);
-    uint16_t *raw = (uint16_t *)ar.get((size_t)w * h * 2);
+    uint16_t *raw;
+    uint8_t *dc = nullptr;
+    if ((rc = r3d_upload_plane(ctx, ar, depth, w, h, depth_stride, &raw))) return rc;
     float *dd = (float *)ar.get((size_t)w * h * 4);
-    uint8_t *dc = rgb ? (uint8_t *)ar.get((size_t)w * h * 3) : nullptr;
     if (ar.rc) return ar.rc;
-    R3D_HIP(ctx, hipMemcpy2DAsync(raw, (size_t)w * 2, depth, (size_t)depth_stride * 2, (size_t)w * 2, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
-    if (rgb) R3D_HIP(ctx, hipMemcpy2DAsync(dc, (size_t)w * 3, color, (size_t)color_stride, (size_t)w * 3, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+    if (rgb && (rc = r3d_upload_plane(ctx, ar, color, w * 3, h, color_stride, &dc))) return rc;
     k_tsdf_depth_u16<<<(unsigned)(((size_t)w * h + 255) / 256), 256, 0, ctx->stream>>>(raw, w, h, (float)cam->depth_scale, (float)cam->depth_trunc, dd);
     R3D_HIP(ctx, hipGetLastError());
     if ((rc = tsdf_integrate_dev(vol, dd, w, dc, w * 3, w, h, TsdfCam{cam->fx, cam->fy, cam->ppx, cam->ppy}, extrinsic4x4))) return rc;
@@ -1089,7 +1079,19 @@ int r3d_tsdf_extract_point_cloud(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, doubl
         return r3d_fail(ctx, R3D_E_BADARG, "tsdf_extract_point_cloud: a missing array or a negative capacity");
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    return tsdf_extract(vol, ar, cap, nullptr, nullptr, nullptr, out_n, true, xyz, normals, colors);
+    TsdfExtractWork W;
+    int rc;
+    if ((rc = tsdf_extract_count(vol, ar, W, out_n))) return rc;
+    if (cap == 0 || W.total == 0) return R3D_OK;
+    if ((rc = r3d_fits(ctx, "tsdf_extract_point_cloud", "points", W.total, cap))) return rc;
+    const size_t n3 = (size_t)W.total * 3;
+    double *d_xyz = (double *)ar.get(n3 * 8), *d_nrm = (double *)ar.get(n3 * 8), *d_col = color ? (double *)ar.get(n3 * 8) : nullptr;
+    if (ar.rc) return ar.rc;
+    if ((rc = tsdf_extract_emit(vol, W, d_xyz, d_nrm, d_col)) || (rc = r3d_download(ctx, xyz, d_xyz, n3)) || (rc = r3d_download(ctx, normals, d_nrm, n3)) ||
+        (rc = r3d_download(ctx, colors, d_col, color ? n3 : 0)))
+        return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
 }
 
 int r3d_tsdf_extract_point_cloud_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, double *d_xyz, double *d_normals, double *d_colors, int64_t *out_n) {
@@ -1101,8 +1103,11 @@ int r3d_tsdf_extract_point_cloud_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap, d
         return r3d_fail(ctx, R3D_E_BADARG, "tsdf_extract_point_cloud: a missing array or a negative capacity");
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    int rc = tsdf_extract(vol, ar, cap, d_xyz, d_normals, d_colors, out_n, false, nullptr, nullptr, nullptr);
-    if (rc) return rc;
+    TsdfExtractWork W;
+    int rc;
+    if ((rc = tsdf_extract_count(vol, ar, W, out_n))) return rc;
+    if (cap > 0 && W.total > 0 && ((rc = r3d_fits(ctx, "tsdf_extract_point_cloud", "points", W.total, cap)) || (rc = tsdf_extract_emit(vol, W, d_xyz, d_normals, d_colors))))
+        return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the emit kernel reads arena buffers the next call may hand out again
     return R3D_OK;
 }
@@ -1117,7 +1122,7 @@ int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t
     const int n = vol->n_units;
     *out_n = n;
     if (cap_units == 0 || n == 0) return R3D_OK;
-    if (cap_units < n) return r3d_fail(ctx, R3D_E_BADARG, "debug_tsdf_units: %d units do not fit a capacity of %lld", n, (long long)cap_units);
+    if (int rc = r3d_fits(ctx, "debug_tsdf_units", "units", n, cap_units)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevArena ar(ctx);
@@ -1128,10 +1133,11 @@ int r3d_debug_tsdf_units(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_units, int32_t
     if (int rc = tsdf_sort_units(vol)) return rc;
     k_tsdf_gather<<<(unsigned)n, 256, 0, st>>>(tsdf_view(vol), color ? 1 : 0, (const int *)vol->order.p, (const unsigned long long *)vol->unit_keys.p, d_idx, d_t, d_w, d_c);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(idx3, d_idx, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(tsdf, d_t, (size_t)n * TSDF_UNIT * 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(weight, d_w, (size_t)n * TSDF_UNIT * 4, hipMemcpyDeviceToHost, st));
-    if (color) R3D_HIP(ctx, hipMemcpyAsync(colour, d_c, (size_t)n * TSDF_UNIT * 24, hipMemcpyDeviceToHost, st));
+    const size_t nvox = (size_t)n * TSDF_UNIT;
+    int rc;
+    if ((rc = r3d_download(ctx, idx3, d_idx, (size_t)n * 3)) || (rc = r3d_download(ctx, tsdf, d_t, nvox)) || (rc = r3d_download(ctx, weight, d_w, nvox)) ||
+        (rc = r3d_download(ctx, colour, d_c, color ? nvox * 3 : 0)))
+        return rc;
     R3D_HIP(ctx, hipStreamSynchronize(st));
     return R3D_OK;
 }
@@ -1143,7 +1149,21 @@ int r3d_mesh_from_volume(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, int6
     if (int rc = tsdf_mesh_args_ok(ctx, vol, cap_vertices, cap_triangles, vertices, colors, triangles, out_nv, out_nt)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    return tsdf_mesh(vol, ar, cap_vertices, cap_triangles, nullptr, nullptr, nullptr, out_nv, out_nt, true, vertices, colors, triangles);
+    TsdfMeshWork W;
+    int rc;
+    if ((rc = tsdf_mesh_count(vol, ar, W, out_nv, out_nt))) return rc;
+    if ((cap_vertices == 0 && cap_triangles == 0) || (W.total[0] == 0 && W.total[1] == 0)) return R3D_OK;
+    if ((rc = tsdf_mesh_fits(ctx, ar, W, cap_vertices, cap_triangles))) return rc;
+    const bool color = vol->prm.color_type == R3D_TSDF_COLOR_RGB8;
+    const size_t nv3 = (size_t)W.total[0] * 3, nt3 = (size_t)W.total[1] * 3;
+    double *d_vert = (double *)ar.get(nv3 * 8), *d_col = color ? (double *)ar.get(nv3 * 8) : nullptr;
+    int32_t *d_tri = (int32_t *)ar.get(nt3 * 4);
+    if (ar.rc) return ar.rc;
+    if ((rc = tsdf_mesh_emit(vol, W, d_vert, d_col, d_tri)) || (rc = r3d_download(ctx, vertices, d_vert, nv3)) ||
+        (rc = r3d_download(ctx, colors, d_col, color ? nv3 : 0)) || (rc = r3d_download(ctx, triangles, d_tri, nt3)))
+        return rc;
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
 }
 
 int r3d_mesh_from_volume_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, int64_t cap_triangles, double *d_vertices, double *d_colors,
@@ -1153,7 +1173,12 @@ int r3d_mesh_from_volume_dev(r3d_ctx *ctx, r3d_tsdf *vol, int64_t cap_vertices, 
     if (int rc = tsdf_mesh_args_ok(ctx, vol, cap_vertices, cap_triangles, d_vertices, d_colors, d_triangles, out_nv, out_nt)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    if (int rc = tsdf_mesh(vol, ar, cap_vertices, cap_triangles, d_vertices, d_colors, d_triangles, out_nv, out_nt, false, nullptr, nullptr, nullptr)) return rc;
+    TsdfMeshWork W;
+    int rc;
+    if ((rc = tsdf_mesh_count(vol, ar, W, out_nv, out_nt))) return rc;
+    if ((cap_vertices > 0 || cap_triangles > 0) && (W.total[0] > 0 || W.total[1] > 0) &&
+        ((rc = tsdf_mesh_fits(ctx, ar, W, cap_vertices, cap_triangles)) || (rc = tsdf_mesh_emit(vol, W, d_vertices, d_colors, d_triangles))))
+        return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the emitting kernels read arena buffers the next call may hand out again
     return R3D_OK;
 }

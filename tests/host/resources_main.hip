@@ -1,5 +1,5 @@
 // Stand-alone host check of csrc/r3d_resources.h on a machine WITHOUT a GPU, where every HIP create call fails cleanly: the
-// failure paths of the owning types, which cannot be provoked on a shared card.  Built with the host sanitizers and run by
+// failure paths of the owning types, the arena and the staging helpers, which cannot be provoked on a shared card.  Built with the host sanitizers and run by
 // tools/cpu_sanitize_resources.sh; not a pytest.  With a GPU present it does nothing.
 #include <stdarg.h>
 #include <stdio.h>
@@ -155,6 +155,41 @@ int main() {
     }
     CHECK(counts_zero());
     printf("an arena returns null and latches rc on a failed reserve and on a poisoned context\n");
+
+    // the staging helpers of the host-buffer entry points (r3d_internal.h)
+    {
+        r3d_ctx ctx;
+        DevArena ar(&ctx);
+        const double *d = (const double *)0x1;
+        CHECK(r3d_upload<double>(&ctx, ar, nullptr, 5, &d) == R3D_OK && d == nullptr && ar.next == 0 && ar.bufs.empty() && ctx.err.empty());
+        double host[4] = {1, 2, 3, 4};
+        CHECK(r3d_download<double>(&ctx, nullptr, (const double *)0x1000, 4) == R3D_OK);   // made-up device pointers: HIP must not see them
+        CHECK(r3d_download<double>(&ctx, host, (const double *)0x1000, 0) == R3D_OK);
+        CHECK(host[0] == 1 && host[3] == 4 && ctx.err.empty());
+        CHECK(r3d_fits(&ctx, "who", "rows", 3, 3) == R3D_OK && ctx.err.empty());
+        CHECK(r3d_fits(&ctx, "who", "rows", 4, 3) == R3D_E_BADARG && ctx.err == "who: 4 rows do not fit a capacity of 3");
+        CHECK(counts_zero());
+    }
+    printf("a null upload takes no slot, a null or empty download does not reach HIP, r3d_fits refuses with the shared message\n");
+    for (int plane = 0; plane < 2; plane++) {
+        const uint16_t img[2 * 8] = {};
+        const uint16_t *d = (const uint16_t *)0x1;
+        uint16_t *dp = (uint16_t *)0x1;
+        r3d_ctx ctx;
+        DevArena ar(&ctx);
+        const int rc = plane ? r3d_upload_plane(&ctx, ar, img, 5, 2, 8, &dp) : r3d_upload(&ctx, ar, img, 16, &d);
+        CHECK(rc == R3D_E_OOM && ar.rc == R3D_E_OOM && ar.next == 1 && (plane ? dp == nullptr : d == nullptr));
+        CHECK(ctx.err.find("hipMalloc(") == 0);
+        ctx.err = "latched";
+        CHECK((plane ? r3d_upload_plane(&ctx, ar, img, 5, 2, 8, &dp) : r3d_upload(&ctx, ar, img, 16, &d)) == R3D_E_OOM && ctx.err == "latched" && ar.next == 1);
+        r3d_ctx bad;
+        bad.poisoned = true;
+        DevArena ar2(&bad);
+        CHECK((plane ? r3d_upload_plane(&bad, ar2, img, 5, 2, 8, &dp) : r3d_upload(&bad, ar2, img, 16, &d)) == R3D_E_HIP);
+        CHECK(ar2.bufs.empty() && bad.err.find("context poisoned") == 0 && (plane ? dp == nullptr : d == nullptr));
+        CHECK(counts_zero());
+    }
+    printf("r3d_upload and r3d_upload_plane return the arena's latched failure and its refusal of a poisoned context\n");
 
     printf("resources_main: %d checks passed, all five counters zero throughout\n", g_checks);
     return 0;
