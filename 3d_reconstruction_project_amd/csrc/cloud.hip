@@ -3718,6 +3718,20 @@ __global__ void __launch_bounds__(FGR_OPT_BLOCK) k_fgr_optimize(const double *__
 // the int32 scan for the other translation units (trimesh.hip)
 int r3d_exclusive_scan_i32(r3d_ctx *ctx, DevArena &ar, const int *in, int *out, int64_t n) { return dev_exclusive_scan<int>(ctx, ar, in, out, n); }
 
+// the stable by-cell order for poisson.hip: voxel keys (key_order 1: floor((p - org) / cell) per axis with a true division, clamped
+// to the grid; key = (cx * dims[1] + cy) * dims[2] + cz), which must fit 32 bits
+int r3d_sort_by_voxel_u32(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, const double org[3], double cell, const int dims[3],
+                          const unsigned **keys_sorted, const int **idx_sorted) {
+    void *keys = nullptr;
+    int *idx = nullptr;
+    bool k32 = false;
+    if (int rc = sort_by_cell(ctx, ar, d_pts, n, org, cell, dims, 1, &keys, &k32, &idx)) return rc;
+    if (!k32) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sort_by_voxel_u32: a %d x %d x %d grid needs 64-bit keys", dims[0], dims[1], dims[2]);
+    *keys_sorted = (const unsigned *)keys;
+    *idx_sorted = idx;
+    return R3D_OK;
+}
+
 // ================================================================================================ C ABI
 // ---- device-pointer cores shared by the host-buffer entry points and the fused device-resident chain -------------
 

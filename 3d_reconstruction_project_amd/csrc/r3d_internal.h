@@ -250,3 +250,6 @@ int r3d_streambench_run(r3d_ctx *ctx, int mode, int rows, size_t row_bytes, int 
 
 // cloud.hip: exclusive scan of n ints on the ctx stream (in and out 16-byte aligned and distinct; tiles of 4096 elements)
 int r3d_exclusive_scan_i32(r3d_ctx *ctx, DevArena &ar, const int *in, int *out, int64_t n);
+// cloud.hip: point numbers in the stable order of their voxel key (cx * dims[1] + cy) * dims[2] + cz, c = clamp(floor((p - org) / cell))
+int r3d_sort_by_voxel_u32(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, const double org[3], double cell, const int dims[3],
+                          const unsigned **keys_sorted, const int **idx_sorted);

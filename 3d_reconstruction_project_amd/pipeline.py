@@ -489,6 +489,14 @@ def mesh_postprocess(mesh, smooth_iterations=5, lambda_filter=0.5, ctx=None):
     return out.compute_vertex_normals(device=True, ctx=ctx)
 
 
+def reconstruct_mesh(cloud, depth=6, smooth_iterations=5, ctx=None):
+    """mesh_reconstruction.py:22-37 from its first line: create_from_point_cloud_poisson(depth) of a cloud with normals (and
+    colours), then mesh_postprocess(smooth_iterations).  -> TriangleMesh"""
+    from . import poisson
+    mesh, _ = poisson.create_from_point_cloud_poisson(cloud, depth=depth, ctx=ctx)
+    return mesh_postprocess(mesh, smooth_iterations, ctx=ctx)
+
+
 def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, mesh=False, postprocess=False, **volume_options):
     """test/check84.py:41-44,295,307: every frame into a ScalableTSDFVolume with extrinsic = inv(pose), then
     extract_point_cloud().  frames: (colour, depth uint16) pairs or cloud_ops.RGBDImage, as odometry_edges takes them; camera:

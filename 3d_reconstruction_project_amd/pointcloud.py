@@ -91,6 +91,12 @@ class TriangleMesh:
         self.triangle_normals = None
         self.adjacency_list = None
 
+    @staticmethod
+    def create_from_point_cloud_poisson(pcd, depth=8, width=0, scale=1.1, linear_fit=False, n_threads=-1, **solver):
+        """-> (TriangleMesh, densities): poisson.create_from_point_cloud_poisson, on the device"""
+        from . import poisson
+        return poisson.create_from_point_cloud_poisson(pcd, depth, width, scale, linear_fit, n_threads, **solver)
+
     def has_vertices(self):
         return len(self.vertices) > 0
 

@@ -902,6 +902,48 @@ int r3d_trimesh_compact_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *
                             int64_t cap_vertices, int64_t cap_triangles, double *d_out_vertices, double *d_out_normals, double *d_out_colors,
                             int32_t *d_out_triangles, int64_t *out_nv, int64_t *out_nt);
 
+
+/* ---- Poisson surface reconstruction (mesh_reconstruction.py:22-37, visualizer.py:107-110) ---------------------------------------
+ * replaces: o3d.geometry.TriangleMesh.create_from_point_cloud_poisson(pcd, depth).  The screened Poisson formulation on a DENSE
+ * 2^depth grid: finite differences, a zero boundary value, densities in samples per cell; float64 throughout, every sum in a fixed
+ * order.  Parity with Open3D's octree solver is UNPINNED; DESIGN.md section 4, "Poisson reconstruction", is the contract and
+ * tests/poisson_ref.py restates it. */
+typedef struct r3d_poisson_params {
+    int32_t depth;           /* 2..8 (8): the grid has 2^depth cells and 2^depth + 1 nodes per axis; else R3D_E_UNSUPPORTED */
+    int32_t cycles;          /* 10: V-cycles from chi = 0 */
+    int32_t pre, post;       /* 2, 2: weighted-Jacobi sweeps before and after the coarse-grid step */
+    int32_t coarse_sweeps;   /* 40: sweeps on the coarsest level (at most 5 nodes per axis) */
+    int32_t reserved;
+    double scale;            /* 1.1: cube side / largest extent of the points */
+    double alpha;            /* 4.0: screening weight */
+    double omega;            /* 0.8: Jacobi weight */
+} r3d_poisson_params;
+/* xyz, normals [n][3] float64 (zero-length normals are accepted), colors [n][3] or NULL.  params NULL: the defaults above.
+ * *out_nv / *out_nt = the numbers of vertices and triangles, always.  Both capacities 0: the counts alone.  A capacity below its
+ * count: R3D_E_BADARG and nothing is written.  Otherwise vertices [*out_nv][3], densities [*out_nv] (samples per cell at the
+ * vertex), vertex_colors [*out_nv][3] (only with colors; else ignored, may be NULL) and triangles int32 [*out_nt][3], faces looking
+ * from chi < 0 outward (outward for outward normals).  A vertex belongs to the lower node of its edge: nodes by linear index
+ * (k G + j) G + i, then axis x, y, z; triangles by base node in the same order, then in the table's order.  Refused with
+ * R3D_E_BADARG and nothing written: n <= 0, a missing array, a non-finite coordinate or normal, points that all coincide, a
+ * parameter out of range.  The _dev form reads and writes DEVICE arrays and returns when they are complete. */
+int r3d_poisson_reconstruct(r3d_ctx *ctx, const double *xyz, const double *normals, const double *colors, int64_t n,
+                            const r3d_poisson_params *params, int64_t cap_vertices, int64_t cap_triangles, double *vertices, double *densities,
+                            double *vertex_colors, int32_t *triangles, int64_t *out_nv, int64_t *out_nt);
+int r3d_poisson_reconstruct_dev(r3d_ctx *ctx, const double *d_xyz, const double *d_normals, const double *d_colors, int64_t n,
+                                const r3d_poisson_params *params, int64_t cap_vertices, int64_t cap_triangles, double *d_vertices,
+                                double *d_densities, double *d_vertex_colors, int32_t *d_triangles, int64_t *out_nv, int64_t *out_nt);
+/* the fields, for the tests (G = 2^depth + 1 nodes per axis, node (i, j, k) at (k G + j) G + i; any output may be NULL):
+ * grid4 = {org x, org y, org z, h}; W0, D, b, chi [G^3]; C0 (needs colors), V [3][G^3] (one plane per channel / axis); dens [n];
+ * chi after k_cycles V-cycles, 0 <= k_cycles <= params->cycles */
+int r3d_debug_poisson_fields(r3d_ctx *ctx, const double *xyz, const double *normals, const double *colors, int64_t n,
+                             const r3d_poisson_params *params, int32_t k_cycles, double *grid4, double *W0, double *C0, double *dens, double *V,
+                             double *D, double *b, double *chi);
+/* the extraction alone, for the tests: marching cubes at iso 0 on a caller's chi, W0 [G^3] and C0 [3][G^3] (or NULL: no colours),
+ * with the outputs and the capacity protocol of r3d_poisson_reconstruct */
+int r3d_debug_poisson_extract(r3d_ctx *ctx, int32_t depth, const double *org3, double h, const double *chi, const double *W0, const double *C0,
+                              int64_t cap_vertices, int64_t cap_triangles, double *vertices, double *densities, double *vertex_colors,
+                              int32_t *triangles, int64_t *out_nv, int64_t *out_nt);
+
 #ifdef __cplusplus
 }
 #endif
