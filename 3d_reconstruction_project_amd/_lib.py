@@ -69,9 +69,27 @@ class ResourceCounts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("device_allocs", "device_bytes", "pinned_allocs", "events", "streams")]
 
 
+class PoseGraphParams(ctypes.Structure):
+    """r3d_posegraph_params: GlobalOptimizationOption and GlobalOptimizationConvergenceCriteria in one block"""
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "max_correspondence_distance", "edge_prune_threshold", "preference_loop_closure", "min_relative_increment",
+        "min_relative_residual_increment", "min_right_term", "min_residual")] + [(n, ctypes.c_int32) for n in (
+            "reference_node", "max_iteration", "max_iteration_lm", "trace_capacity")]
+
+
+class PoseGraphStats(ctypes.Structure):
+    """r3d_posegraph_stats"""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "outer_iterations", "trials", "rejected_trials", "failed_factorizations", "edges_pruned", "stop_first", "stop_second",
+        "reserved")] + [(n, ctypes.c_double) for n in (
+            "first_objective", "final_objective", "linearize_ms", "factor_ms", "substitute_ms", "rest_ms")]
+
+
 _lib = None
 
 _vp = ctypes.c_void_p
+_posegraph_optimize_sig = ([_vp, ctypes.POINTER(PoseGraphParams), ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                            ctypes.POINTER(PoseGraphStats), _vp], ctypes.c_int)
 _SIGS = {
     "r3d_init": ([ctypes.c_int, ctypes.POINTER(_vp)], ctypes.c_int),
     "r3d_destroy": ([_vp], None),
@@ -107,6 +125,14 @@ _SIGS = {
     # raw_wta, mins, lrd of the last compute or debug_select call
     "r3d_sgbm_debug_fetch_select": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "r3d_debug_resources": ([ctypes.POINTER(ResourceCounts)], ctypes.c_int),
+    # ctx, params, n_nodes, poses, n_edges, edge_nodes, edge_T, edge_info, edge_uncertain, edge_confidence, edge_kept, stats, trace
+    "r3d_posegraph_optimize": _posegraph_optimize_sig,
+    "r3d_posegraph_optimize_dev": _posegraph_optimize_sig,
+    # ctx, params, n_nodes, poses, n_edges, edge_nodes, edge_T, edge_info, edge_uncertain, edge_confidence, e, l, H, b, F
+    "r3d_debug_posegraph_linearize": ([_vp, ctypes.POINTER(PoseGraphParams), ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    # ctx, n, A, b, lambda, L, delta, failed_pivot
+    "r3d_debug_posegraph_solve": ([_vp, ctypes.c_int32, _vp, _vp, ctypes.c_double, _vp, _vp, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
 }
 
 

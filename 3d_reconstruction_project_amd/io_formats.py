@@ -99,3 +99,41 @@ def load_calibration(path):
     """Calib_depth/depth2.py:35-67 getStereoCameraParameters: the .npz keys, Q included."""
     d = np.load(path)
     return {k: d[k] for k in d.files}
+
+
+def write_pose_graph(path, pose_graph):
+    """o3d.io.write_pose_graph: Open3D's JSON form [recalled]: class_name / version_major / version_minor at every level, a node's
+    pose and an edge's transformation as 16 numbers and its information as 36, all COLUMN-major.  Python writes the shortest
+    decimal that reads back as the same float64, so the round trip is exact."""
+    import json
+
+    def col(m):
+        return [float(v) for v in np.asarray(m, dtype=np.float64).T.reshape(-1)]
+    doc = {"class_name": "PoseGraph", "version_major": 1, "version_minor": 0,
+           "nodes": [{"class_name": "PoseGraphNode", "version_major": 1, "version_minor": 0, "pose": col(n.pose)} for n in pose_graph.nodes],
+           "edges": [{"class_name": "PoseGraphEdge", "version_major": 1, "version_minor": 0, "source_node_id": int(e.source_node_id),
+                      "target_node_id": int(e.target_node_id), "transformation": col(e.transformation), "information": col(e.information),
+                      "uncertain": bool(e.uncertain), "confidence": float(e.confidence)} for e in pose_graph.edges]}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+
+
+def read_pose_graph(path):
+    """o3d.io.read_pose_graph -> posegraph.PoseGraph"""
+    import json
+
+    from . import posegraph
+    with open(path) as f:
+        doc = json.load(f)
+    if doc.get("class_name") != "PoseGraph":
+        raise ValueError(f"{path}: class_name is {doc.get('class_name')!r}, not 'PoseGraph'")
+
+    def mat(v, k):
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != (k * k,):
+            raise ValueError(f"{path}: {a.size} numbers where a {k}x{k} matrix is expected")
+        return a.reshape(k, k).T.copy()
+    nodes = [posegraph.PoseGraphNode(mat(n["pose"], 4)) for n in doc.get("nodes", [])]
+    edges = [posegraph.PoseGraphEdge(e["source_node_id"], e["target_node_id"], mat(e["transformation"], 4), mat(e["information"], 6),
+                                     e.get("uncertain", False), e.get("confidence", 1.0)) for e in doc.get("edges", [])]
+    return posegraph.PoseGraph(nodes, edges)

@@ -477,6 +477,47 @@ def poses_from_edges(edges):
     return poses
 
 
+def loop_closure_edges(frames, camera, every, ctx=None, **option):
+    """The loop-closure candidates of Open3D's make_fragments rule: RGB-D odometry from the identity between frames s < t with
+    s % every == 0, t % every == 0 and t - s > 1, source t -> target s (the direction of odometry_edges), uncertain=True.  A failed
+    pair is left out.  frames, camera, option: as odometry_edges.  -> [dict(source, target, T, info, uncertain)]"""
+    every = int(every)
+    if every < 1:
+        raise ValueError(f"every={every}: a positive key-frame distance is needed")
+    imgs = [f if isinstance(f, cloud_ops.RGBDImage) else cloud_ops.rgbd_image(f[0], f[1], camera.depth_scale, camera.depth_trunc) for f in frames]
+    edges = []
+    for s in range(0, len(imgs), every):
+        for t in range(s + every, len(imgs), every):
+            if t - s <= 1:
+                continue
+            ok, T, info = cloud_ops.compute_rgbd_odometry(imgs[t], imgs[s], camera, ctx=ctx, **option)
+            if ok:
+                edges.append(dict(source=t, target=s, T=T, info=info, uncertain=True))
+    return edges
+
+
+def pose_graph_from_edges(edges, poses=None):
+    """A posegraph.PoseGraph of edge dicts (odometry_edges, loop_closure_edges): the node poses are poses_from_edges(edges) when
+    the edges are a chain of consecutive frames, otherwise `poses` (camera-to-world 4x4 per frame), which must then be given."""
+    from . import posegraph
+    if poses is None:
+        poses = poses_from_edges(edges)
+    nodes = [posegraph.PoseGraphNode(p) for p in poses]
+    return posegraph.PoseGraph(nodes, [posegraph.PoseGraphEdge(e["source"], e["target"], e["T"], e["info"], e["uncertain"], e.get("confidence", 1.0))
+                                       for e in edges])
+
+
+def optimize_poses(edges, loop_closures=(), poses=None, criteria=None, option=None, ctx=None):
+    """test/check84.py:262-273: the poses of the frames after global_optimization of the graph of `edges` (a chain, odometry_edges)
+    and `loop_closures` (loop_closure_edges).  poses: the initial node poses; default poses_from_edges(edges).  option: default
+    GlobalOptimizationOption(reference_node=0), as the script's.  -> [4x4], which tsdf_fuse takes"""
+    from . import posegraph
+    graph = pose_graph_from_edges(list(edges) + list(loop_closures), poses if poses is not None else poses_from_edges(edges))
+    posegraph.global_optimization(graph, posegraph.GlobalOptimizationLevenbergMarquardt(), criteria,
+                                  option or posegraph.GlobalOptimizationOption(reference_node=0), ctx=ctx)
+    return [n.pose for n in graph.nodes]
+
+
 def mesh_postprocess(mesh, smooth_iterations=5, lambda_filter=0.5, ctx=None):
     """The tail of mesh_reconstruction.py:22-37 after its Poisson call, restricted to what this package has, in the order of
     SURVEY.md section 2: filter_smooth_laplacian(smooth_iterations), remove_degenerate_triangles, remove_unreferenced_vertices and

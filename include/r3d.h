@@ -944,6 +944,66 @@ int r3d_debug_poisson_extract(r3d_ctx *ctx, int32_t depth, const double *org3, d
                               int64_t cap_vertices, int64_t cap_triangles, double *vertices, double *densities, double *vertex_colors,
                               int32_t *triangles, int64_t *out_nv, int64_t *out_nt);
 
+/* ---- pose-graph optimisation (csrc/posegraph.hip; test/check84.py:262-273) ---------------------------------------------------------
+ * replaces: o3d.pipelines.registration.global_optimization(pose_graph, GlobalOptimizationLevenbergMarquardt(), criteria, option).
+ * float64 throughout, every sum in a fixed order.  Parity with Open3D is UNPINNED; DESIGN.md section 4, "Pose-graph optimisation", is
+ * the contract and tests/posegraph_ref.py restates it.  A node is a camera-to-world pose, 16 numbers row-major; an edge (s, t) carries
+ * T (source camera -> target camera coordinates, 16 numbers row-major), a 6x6 information matrix (36 numbers row-major; the lower
+ * triangle of what it contributes is used), an `uncertain` flag (loop closure) and a confidence (the line-process weight). */
+typedef struct r3d_posegraph_params {   /* 72 bytes */
+    double max_correspondence_distance;     /* 0.03: with the two below, GlobalOptimizationOption */
+    double edge_prune_threshold;            /* 0.25 */
+    double preference_loop_closure;         /* 1.0 */
+    double min_relative_increment;          /* 1e-6: with the three below and the iteration counts, GlobalOptimizationConvergenceCriteria */
+    double min_relative_residual_increment; /* 1e-6 */
+    double min_right_term;                  /* 1e-6 */
+    double min_residual;                    /* 1e-6 */
+    int32_t reference_node;                 /* -1: no node is held; 0..n_nodes-1: that node's step is zeroed in every trial */
+    int32_t max_iteration;                  /* 100 outer iterations per optimisation */
+    int32_t max_iteration_lm;               /* 20 trials per outer iteration */
+    int32_t trace_capacity;                 /* 0: rows the trace array can take */
+} r3d_posegraph_params;
+#define R3D_POSEGRAPH_STOP_RIGHT_TERM 1         /* max|b| < min_right_term */
+#define R3D_POSEGRAPH_STOP_INCREMENT 2          /* ||delta|| < min_relative_increment (||x|| + min_relative_increment) */
+#define R3D_POSEGRAPH_STOP_RESIDUAL_INCREMENT 3 /* F - F_new < min_relative_residual_increment F */
+#define R3D_POSEGRAPH_STOP_RESIDUAL 4           /* F_new < min_residual */
+#define R3D_POSEGRAPH_STOP_ITERATIONS 5         /* max_iteration outer iterations */
+#define R3D_POSEGRAPH_STOP_NO_EDGES 6           /* nothing to optimise */
+typedef struct r3d_posegraph_stats {    /* 80 bytes; the counts are over both optimisations (before and after the pruning) */
+    int32_t outer_iterations, trials, rejected_trials, failed_factorizations, edges_pruned;
+    int32_t stop_first, stop_second;        /* R3D_POSEGRAPH_STOP_* of the two optimisations */
+    int32_t reserved;
+    double first_objective, final_objective;
+    double linearize_ms, factor_ms, substitute_ms, rest_ms; /* device time by HIP events, summed over the trials */
+} r3d_posegraph_stats;
+/* global_optimization: optimise, drop the uncertain edges whose confidence is below edge_prune_threshold, optimise the rest.  poses
+ * [n_nodes][16] in/out; edge_nodes int32 [n_edges][2] (source, target); edge_uncertain, edge_kept: one byte per edge; edge_confidence
+ * [n_edges] in/out (an uncertain edge's initial weight; a certain edge's has to be finite, is not used and not changed); edge_kept out: 0 for a pruned
+ * edge.  params NULL: the defaults above.  stats may be NULL.  trace (may be NULL): params->trace_capacity rows of (lambda, F_new, rho,
+ * code), one per trial in order, code 1 accepted, 0 rejected, -1 the step was below the increment test (F_new = rho = 0), -2 the
+ * factorisation met a pivot <= 0 or not finite (counted as rejected; F_new = rho = 0); trials beyond the capacity are not recorded.
+ * Refused with R3D_E_BADARG before anything is written: n_nodes outside 1..1024, n_edges outside 0..2^20, a node id out of range,
+ * an edge with source == target, a pose, T, information matrix or confidence that is not finite, reference_node outside
+ * -1..n_nodes-1, a negative iteration count.  No edges: the poses are returned unchanged.  The _dev form takes every array but
+ * params and stats on the DEVICE (trace too) and returns when they are complete. */
+int r3d_posegraph_optimize(r3d_ctx *ctx, const r3d_posegraph_params *params, int64_t n_nodes, double *poses, int64_t n_edges,
+                           const int32_t *edge_nodes, const double *edge_T, const double *edge_info, const uint8_t *edge_uncertain,
+                           double *edge_confidence, uint8_t *edge_kept, r3d_posegraph_stats *stats, double *trace);
+int r3d_posegraph_optimize_dev(r3d_ctx *ctx, const r3d_posegraph_params *params, int64_t n_nodes, double *d_poses, int64_t n_edges,
+                               const int32_t *d_edge_nodes, const double *d_edge_T, const double *d_edge_info, const uint8_t *d_edge_uncertain,
+                               double *d_edge_confidence, uint8_t *d_edge_kept, r3d_posegraph_stats *stats, double *d_trace);
+/* the linearisation alone, for the tests (every edge kept, n_edges >= 1; any output may be NULL): e [n_edges][6], l [n_edges] (the
+ * weights), H [6 n_nodes][6 n_nodes] dense (the lower triangle is what is built; the upper one is its mirror image), b [6 n_nodes],
+ * F the objective */
+int r3d_debug_posegraph_linearize(r3d_ctx *ctx, const r3d_posegraph_params *params, int64_t n_nodes, const double *poses, int64_t n_edges,
+                                  const int32_t *edge_nodes, const double *edge_T, const double *edge_info, const uint8_t *edge_uncertain,
+                                  const double *edge_confidence, double *e, double *l, double *H, double *b, double *F);
+/* the solve alone, for the tests: (A + lambda I) delta = -b for a dense symmetric A of order n <= 6144 (its lower triangle is read).
+ * L [n][n] (may be NULL): the Cholesky factor, its strict upper triangle ZERO; delta [n] (may be NULL).  *failed_pivot = -1, or the
+ * index of the first pivot that was <= 0 or not finite: then L and delta are all zero (nothing that is not finite is written). */
+int r3d_debug_posegraph_solve(r3d_ctx *ctx, int32_t n, const double *A, const double *b, double lambda, double *L, double *delta,
+                              int32_t *failed_pivot);
+
 #ifdef __cplusplus
 }
 #endif
