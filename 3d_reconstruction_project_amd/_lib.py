@@ -37,7 +37,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libr3d_hip.so")
 
 R3D_OK = 0
 HIP_STREAM_LEGACY = 1       # hipStreamLegacy ((hipStream_t)1, hip_runtime_api.h): the null stream with legacy synchronisation
-ERR_NAMES = {-1: "R3D_E_BADARG", -2: "R3D_E_HIP", -3: "R3D_E_OOM", -4: "R3D_E_UNSUPPORTED", -5: "R3D_E_NODEVICE"}
+ERR_NAMES = {-1: "R3D_E_BADARG", -2: "R3D_E_HIP", -3: "R3D_E_OOM", -4: "R3D_E_UNSUPPORTED", -5: "R3D_E_NODEVICE", -6: "R3D_E_INTERNAL"}
 
 
 class SgbmParams(ctypes.Structure):
@@ -90,6 +90,13 @@ _lib = None
 _vp = ctypes.c_void_p
 _posegraph_optimize_sig = ([_vp, ctypes.POINTER(PoseGraphParams), ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
                             ctypes.POINTER(PoseGraphStats), _vp], ctypes.c_int)
+_i32, _i64 = ctypes.c_int32, ctypes.c_int64
+_i64p = ctypes.POINTER(ctypes.c_int64)
+# ctx, nv, nt, vertices, triangles, cap_clusters, triangle_clusters, cluster_n_triangles, cluster_area, out_n_clusters
+_meshtopo_components_sig = ([_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64p], ctypes.c_int)
+# ctx, nv, nt, vertices, normals, colors, triangles, flags, cap_vertices, cap_triangles, out_vertices, out_normals, out_colors, out_triangles,
+# vertex_map, triangle_origin, out_nv, out_nt
+_meshtopo_dedup_sig = ([_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64p, _i64p], ctypes.c_int)
 _SIGS = {
     "r3d_init": ([ctypes.c_int, ctypes.POINTER(_vp)], ctypes.c_int),
     "r3d_destroy": ([_vp], None),
@@ -133,6 +140,14 @@ _SIGS = {
                                        _vp, _vp, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     # ctx, n, A, b, lambda, L, delta, failed_pivot
     "r3d_debug_posegraph_solve": ([_vp, ctypes.c_int32, _vp, _vp, ctypes.c_double, _vp, _vp, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    # ctx, nv, nt, triangles, cap, edges, counts, stats, out_n
+    "r3d_meshtopo_edges": ([_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64p], ctypes.c_int),
+    "r3d_meshtopo_components": _meshtopo_components_sig,
+    "r3d_meshtopo_components_dev": _meshtopo_components_sig,
+    "r3d_meshtopo_dedup": _meshtopo_dedup_sig,
+    "r3d_meshtopo_dedup_dev": _meshtopo_dedup_sig,
+    # ctx, keys, values, n, bits, out_keys, out_values
+    "r3d_debug_sort_pairs_u64": ([_vp, _vp, _vp, _i64, _i32, _vp, _vp], ctypes.c_int),
 }
 
 

@@ -11,10 +11,10 @@ mkdir -p "$out" "$obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 COMMON=(--offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -Wno-unused-function "$@")
 pids=()
-for f in api sgm cloud prepost odometry tsdf trimesh poisson posegraph; do
+for f in api sgm cloud prepost odometry tsdf trimesh meshtopo poisson posegraph; do
     "$HIPCC" "${COMMON[@]}" -c "$here/$f.hip" -o "$obj/$f.o" &
     pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$obj"/api.o "$obj"/sgm.o "$obj"/cloud.o "$obj"/prepost.o "$obj"/odometry.o "$obj"/tsdf.o "$obj"/trimesh.o "$obj"/poisson.o "$obj"/posegraph.o -o "$out/libr3d_hip.so"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "$obj"/api.o "$obj"/sgm.o "$obj"/cloud.o "$obj"/prepost.o "$obj"/odometry.o "$obj"/tsdf.o "$obj"/trimesh.o "$obj"/meshtopo.o "$obj"/poisson.o "$obj"/posegraph.o -o "$out/libr3d_hip.so"
 echo "built $out/libr3d_hip.so"

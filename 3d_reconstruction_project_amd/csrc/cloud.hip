@@ -3732,6 +3732,42 @@ int r3d_sort_by_voxel_u32(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64
     return R3D_OK;
 }
 
+// the radix sort itself for meshtopo.hip: n (key, value) pairs in the stable order of the keys' low `bits` bits (at least one pass,
+// eight bits each), values = the index where d_vals is null.  The inputs are only read; the results are arena buffers.  Enqueued on
+// the ctx stream, no host round trip.  Positions are int32: n above 2^31 - 1 is refused.
+int r3d_sort_pairs_u64(r3d_ctx *ctx, DevArena &ar, const uint64_t *d_keys, const int *d_vals, int64_t n, int bits, const uint64_t **keys_sorted,
+                       const int **vals_sorted) {
+    *keys_sorted = nullptr;
+    *vals_sorted = nullptr;
+    if (n < 0 || bits < 0 || bits > 64) return r3d_fail(ctx, R3D_E_BADARG, "sort_pairs_u64: %lld pairs on %d bits", (long long)n, bits);
+    if (n > 0x7fffffff) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "sort_pairs_u64: %lld pairs do not fit int32 positions", (long long)n);
+    if (n == 0) return R3D_OK;
+    using KEY = unsigned long long;
+    KEY *k[2] = {(KEY *)ar.get((size_t)n * 8), (KEY *)ar.get((size_t)n * 8)};
+    int *v[2] = {(int *)ar.get((size_t)n * 4), (int *)ar.get((size_t)n * 4)};
+    const int ntiles = (int)((n + RX_TILE - 1) / RX_TILE);
+    int *hist = (int *)ar.get((size_t)256 * ntiles * 4), *offs = (int *)ar.get((size_t)256 * ntiles * 4);
+    int *part = (int *)ar.get((((size_t)256 * ntiles + SCAN_TILE - 1) / SCAN_TILE) * 4);   // one set of tile sums for every pass
+    if (ar.rc) return ar.rc;
+    const int passes = std::max(1, (bits + 7) / 8);
+    const KEY *kin = (const KEY *)d_keys;
+    const int *vin = d_vals;
+    for (int ps = 0; ps < passes; ps++) {
+        KEY *kout = k[ps & 1];
+        int *vout = v[ps & 1];
+        k_rx_hist<KEY><<<ntiles, 64, 0, ctx->stream>>>(kin, n, 8 * ps, hist, ntiles);
+        if (int rc = dev_exclusive_scan<int>(ctx, ar, hist, offs, (int64_t)256 * ntiles, nullptr, nullptr, part)) return rc;
+        if (vin) k_rx_scatter<KEY, false><<<ntiles, 64, 0, ctx->stream>>>(kin, vin, n, 8 * ps, offs, ntiles, kout, vout);
+        else k_rx_scatter<KEY, true><<<ntiles, 64, 0, ctx->stream>>>(kin, nullptr, n, 8 * ps, offs, ntiles, kout, vout);
+        R3D_HIP(ctx, hipGetLastError());
+        kin = kout;
+        vin = vout;
+    }
+    *keys_sorted = (const uint64_t *)kin;
+    *vals_sorted = vin;
+    return R3D_OK;
+}
+
 // ================================================================================================ C ABI
 // ---- device-pointer cores shared by the host-buffer entry points and the fused device-resident chain -------------
 

@@ -253,3 +253,8 @@ int r3d_exclusive_scan_i32(r3d_ctx *ctx, DevArena &ar, const int *in, int *out, 
 // cloud.hip: point numbers in the stable order of their voxel key (cx * dims[1] + cy) * dims[2] + cz, c = clamp(floor((p - org) / cell))
 int r3d_sort_by_voxel_u32(r3d_ctx *ctx, DevArena &ar, const double *d_pts, int64_t n, const double org[3], double cell, const int dims[3],
                           const unsigned **keys_sorted, const int **idx_sorted);
+// cloud.hip: the stable LSD radix sort (eight bits per pass) of n (uint64 key, int32 value) pairs whose keys are below 2^bits; values
+// default to the index (d_vals null).  Inputs are only read, results are arena buffers, all on the ctx stream without a host round
+// trip.  A key wider than 64 bits is sorted by chaining calls, least significant part first, the next part gathered through the values.
+int r3d_sort_pairs_u64(r3d_ctx *ctx, DevArena &ar, const uint64_t *d_keys, const int *d_vals, int64_t n, int bits, const uint64_t **keys_sorted,
+                       const int **vals_sorted);

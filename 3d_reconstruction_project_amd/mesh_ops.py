@@ -1,6 +1,7 @@
-"""Triangle-mesh operations on the device, arrays in and out ("Triangle-mesh operations"; C ABI:
-r3d_trimesh_*): incidence and adjacency lists, the smoothing filters, normals and the clean-ups.  TriangleMesh's methods call
-these; mesh_reconstruction.py:22-37 and check84.py:315-322 are what they replace."""
+"""Triangle-mesh operations on the device, arrays in and out ("Triangle-mesh operations" and "Mesh topology";
+C ABI: r3d_trimesh_*, r3d_meshtopo_*): incidence and adjacency lists, the smoothing filters, normals and the clean-ups; the edge
+table, connected components and the welds of duplicated vertices and triangles.  TriangleMesh's methods call these;
+mesh_reconstruction.py:22-37 and check84.py:315-322 are what they replace."""
 import ctypes
 import enum
 
@@ -14,6 +15,7 @@ _i64p = ctypes.POINTER(ctypes.c_int64)
 SMOOTH_SIMPLE, SMOOTH_LAPLACIAN, SMOOTH_TAUBIN = 0, 1, 2
 NORMALS_RAW = 1
 DROP_DEGENERATE, DROP_UNREFERENCED, DROP_NON_FINITE = 1, 2, 4
+DEDUP_VERTICES, DEDUP_TRIANGLES = 1, 2
 
 
 class FilterScope(enum.IntEnum):
@@ -180,3 +182,107 @@ def compact_device(d_vertices, d_triangles, n_vertices, n_triangles, flags, cap_
              _vp(d_vertex_keep), _vp(d_triangle_keep), int(flags), int(cap_vertices), int(cap_triangles), _vp(d_out_vertices), _vp(d_out_normals),
              _vp(d_out_colors), _vp(d_out_triangles), ctypes.byref(kv), ctypes.byref(kt))
     return kv.value, kt.value
+
+
+# ---- mesh topology (csrc/meshtopo.hip) ------------------------------------------------------------------------------------------------
+def sort_pairs_u64(keys, bits=64, values=None, ctx=None):
+    """r3d_debug_sort_pairs_u64: -> (keys, values) in the stable order of the keys' low `bits` bits; values default to the index"""
+    ctx = ctx or _lib.default_context()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    vals = None if values is None else np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+    if vals is not None and len(vals) != len(keys):
+        raise ValueError(f"{len(vals)} values for {len(keys)} keys")
+    ok, ov = np.empty_like(keys), np.empty(len(keys), np.int32)
+    ctx.call("r3d_debug_sort_pairs_u64", _ptr(keys), _ptr(vals), len(keys), int(bits), _ptr(ok), _ptr(ov))
+    return ok, ov
+
+
+def edges(n_vertices, triangles, ctx=None):
+    """-> edges int32 [n,2] (min, max) ascending, counts int32 [n] (sides on each), stats int64 [4] = (edges, boundary, non-manifold,
+    degenerate)"""
+    ctx = ctx or _lib.default_context()
+    tri = _tri(triangles)
+    nv, nt = int(n_vertices), len(tri)
+    n, stats = ctypes.c_int64(), np.zeros(4, np.int64)
+    ctx.call("r3d_meshtopo_edges", nv, nt, _ptr(tri), 0, None, None, _ptr(stats), ctypes.byref(n))
+    edg, cnt = np.empty((n.value, 2), np.int32), np.empty(n.value, np.int32)
+    if n.value:
+        got = ctypes.c_int64()
+        ctx.call("r3d_meshtopo_edges", nv, nt, _ptr(tri), n.value, _ptr(edg), _ptr(cnt), _ptr(stats), ctypes.byref(got))
+        assert got.value == n.value
+    return edg, cnt, stats
+
+
+def components(vertices, triangles, ctx=None):
+    """cluster_connected_triangles -> triangle_clusters int32 [nt] (components in ascending order of their lowest triangle),
+    cluster_n_triangles int64 [], cluster_area float64 []"""
+    ctx = ctx or _lib.default_context()
+    vert, tri = _rows(vertices), _tri(triangles)
+    nv, nt = len(vert), len(tri)
+    labels, n = np.empty(nt, np.int32), ctypes.c_int64()
+    ctx.call("r3d_meshtopo_components", nv, nt, _ptr(vert), _ptr(tri), 0, _ptr(labels), None, None, ctypes.byref(n))
+    cnt, area = np.empty(n.value, np.int64), np.empty(n.value, np.float64)
+    if n.value:
+        got = ctypes.c_int64()
+        ctx.call("r3d_meshtopo_components", nv, nt, _ptr(vert), _ptr(tri), n.value, _ptr(labels), _ptr(cnt), _ptr(area), ctypes.byref(got))
+        assert got.value == n.value
+    return labels, cnt, area
+
+
+def components_device(d_vertices, d_triangles, n_vertices, n_triangles, d_triangle_clusters, cap_clusters=0, d_cluster_n_triangles=None,
+                      d_cluster_area=None, ctx=None):
+    """r3d_meshtopo_components_dev: device pointers (int) -> the number of clusters; counts and areas are written when they fit"""
+    ctx = ctx or _lib.default_context()
+    n = ctypes.c_int64()
+    ctx.call("r3d_meshtopo_components_dev", int(n_vertices), int(n_triangles), _vp(d_vertices), _vp(d_triangles), int(cap_clusters),
+             _vp(d_triangle_clusters), _vp(d_cluster_n_triangles), _vp(d_cluster_area), ctypes.byref(n))
+    return n.value
+
+
+def dedup(vertices, triangles, flags=DEDUP_VERTICES | DEDUP_TRIANGLES, normals=None, colors=None, ctx=None):
+    """The welds.  flags: DEDUP_VERTICES | DEDUP_TRIANGLES (vertices first).  The first occurrence survives; survivors keep their
+    order.  -> (vertices, triangles, normals or None, colours or None, vertex_map int32 [nv], triangle_origin int32 [out nt])"""
+    ctx = ctx or _lib.default_context()
+    vert, tri = _rows(vertices), _tri(triangles)
+    nv, nt = len(vert), len(tri)
+    nrm, col = _rows(normals, nv, "normals"), _rows(colors, nv, "colors")
+    kv, kt = ctypes.c_int64(), ctypes.c_int64()
+    args = (nv, nt, _ptr(vert), _ptr(nrm), _ptr(col), _ptr(tri), int(flags))
+    ctx.call("r3d_meshtopo_dedup", *args, 0, 0, None, None, None, None, None, None, ctypes.byref(kv), ctypes.byref(kt))
+    ov, ot = np.empty((kv.value, 3)), np.empty((kt.value, 3), np.int32)
+    on = np.empty((kv.value, 3)) if nrm is not None else None
+    oc = np.empty((kv.value, 3)) if col is not None else None
+    vmap, origin = np.empty(nv, np.int32), np.empty(kt.value, np.int32)
+    if kv.value or kt.value:
+        gv, gt = ctypes.c_int64(), ctypes.c_int64()
+        ctx.call("r3d_meshtopo_dedup", *args, kv.value, kt.value, _ptr(ov), _ptr(on), _ptr(oc), _ptr(ot), _ptr(vmap), _ptr(origin), ctypes.byref(gv),
+                 ctypes.byref(gt))
+        assert (gv.value, gt.value) == (kv.value, kt.value)
+    return ov, ot, on, oc, vmap, origin
+
+
+def dedup_device(d_vertices, d_triangles, n_vertices, n_triangles, flags, cap_vertices, cap_triangles, d_out_vertices, d_out_triangles,
+                 d_normals=None, d_colors=None, d_out_normals=None, d_out_colors=None, d_vertex_map=None, d_triangle_origin=None, ctx=None):
+    """r3d_meshtopo_dedup_dev: device pointers (int) -> the numbers of vertex and triangle rows kept (written when both fit)"""
+    ctx = ctx or _lib.default_context()
+    kv, kt = ctypes.c_int64(), ctypes.c_int64()
+    ctx.call("r3d_meshtopo_dedup_dev", int(n_vertices), int(n_triangles), _vp(d_vertices), _vp(d_normals), _vp(d_colors), _vp(d_triangles), int(flags),
+             int(cap_vertices), int(cap_triangles), _vp(d_out_vertices), _vp(d_out_normals), _vp(d_out_colors), _vp(d_out_triangles), _vp(d_vertex_map),
+             _vp(d_triangle_origin), ctypes.byref(kv), ctypes.byref(kt))
+    return kv.value, kt.value
+
+
+def component_mask(labels, n_triangles, areas, min_triangles=0, min_area=0.0, keep_largest=False):
+    """The tutorial idiom on the arrays of components(), in numpy: -> bool [nt], True where a triangle is to be REMOVED.  A component
+    goes when it has fewer than min_triangles triangles or less than min_area area; keep_largest removes every component but the
+    one with the most triangles (ties: the lower label)."""
+    labels = np.asarray(labels).reshape(-1)
+    n_triangles, areas = np.asarray(n_triangles).reshape(-1), np.asarray(areas, dtype=np.float64).reshape(-1)
+    if len(n_triangles) != len(areas):
+        raise ValueError(f"{len(n_triangles)} triangle counts for {len(areas)} areas")
+    drop = (n_triangles < min_triangles) | (areas < min_area)
+    if keep_largest and len(n_triangles):
+        only = np.ones(len(n_triangles), bool)
+        only[int(np.argmax(n_triangles))] = False         # argmax returns the first of equals
+        drop |= only
+    return drop[labels] if len(labels) else np.zeros(0, bool)

@@ -518,15 +518,21 @@ def optimize_poses(edges, loop_closures=(), poses=None, criteria=None, option=No
     return [n.pose for n in graph.nodes]
 
 
-def mesh_postprocess(mesh, smooth_iterations=5, lambda_filter=0.5, ctx=None):
+def mesh_postprocess(mesh, smooth_iterations=5, lambda_filter=0.5, ctx=None, min_component_triangles=0, keep_largest_component=False, weld=False):
     """The tail of mesh_reconstruction.py:22-37 after its Poisson call, restricted to what this package has, in the order of
     SURVEY.md section 2: filter_smooth_laplacian(smooth_iterations), remove_degenerate_triangles, remove_unreferenced_vertices and
     the non-finite scrub of check84.py:315-322, then compute_vertex_normals.  ASSUMED (the reference source is not in this
-    repository): lambda 0.5 and FilterScope.All, Open3D's defaults; the duplicate and non-manifold clean-ups the reference may
-    also call are not built and the marching-cubes mesh has none to remove.  The non-finite vertices go before
-    the unreferenced ones, so that a vertex left without triangles by the scrub goes too.  -> a new TriangleMesh"""
+    repository): lambda 0.5 and FilterScope.All, Open3D's defaults.  The non-finite vertices go before the unreferenced ones, so
+    that a vertex left without triangles by the scrub goes too.  The topology clean-ups are off by default (the marching-cubes mesh
+    has no duplicates to remove, and today's output stays bit for bit); they run after the scrubs and before the normals:
+    weld=True: remove_duplicated_vertices and remove_duplicated_triangles; min_component_triangles / keep_largest_component:
+    remove_small_components.  remove_non_manifold_edges is not built.  -> a new TriangleMesh"""
     out = mesh.filter_smooth_laplacian(int(smooth_iterations), lambda_filter, ctx=ctx)
     out.remove_degenerate_triangles(ctx=ctx).remove_non_finite_vertices(ctx=ctx).remove_unreferenced_vertices(ctx=ctx)
+    if weld:
+        out.remove_duplicated_vertices(ctx=ctx).remove_duplicated_triangles(ctx=ctx)
+    if min_component_triangles > 0 or keep_largest_component:
+        out.remove_small_components(min_triangles=int(min_component_triangles), keep_largest=bool(keep_largest_component), ctx=ctx)
     return out.compute_vertex_normals(device=True, ctx=ctx)
 
 
@@ -538,11 +544,12 @@ def reconstruct_mesh(cloud, depth=6, smooth_iterations=5, ctx=None):
     return mesh_postprocess(mesh, smooth_iterations, ctx=ctx)
 
 
-def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, mesh=False, postprocess=False, **volume_options):
+def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=None, mesh=False, postprocess=False, postprocess_options=None, **volume_options):
     """test/check84.py:41-44,295,307: every frame into a ScalableTSDFVolume with extrinsic = inv(pose), then
     extract_point_cloud().  frames: (colour, depth uint16) pairs or cloud_ops.RGBDImage, as odometry_edges takes them; camera:
     cloud_ops.depth_camera(...); poses: camera-to-world 4x4 per frame (poses_from_edges).  -> PointCloud with normals[, colours];
-    mesh=True: extract_triangle_mesh() instead -> TriangleMesh; postprocess=True (with mesh=True): mesh_postprocess() of it"""
+    mesh=True: extract_triangle_mesh() instead -> TriangleMesh; postprocess=True (with mesh=True): mesh_postprocess() of it, with the
+    keywords of the dict postprocess_options (weld, min_component_triangles, ...)"""
     if len(poses) != len(frames):
         raise ValueError(f"{len(frames)} frames but {len(poses)} poses")
     if postprocess and not mesh:
@@ -555,4 +562,4 @@ def tsdf_fuse(frames, camera, poses, voxel_length, sdf_trunc, color=True, ctx=No
         if not mesh:
             return volume.extract_point_cloud()
         out = volume.extract_triangle_mesh()
-    return mesh_postprocess(out, ctx=ctx) if postprocess else out
+    return mesh_postprocess(out, ctx=ctx, **(postprocess_options or {})) if postprocess else out

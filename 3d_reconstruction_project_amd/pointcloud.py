@@ -80,8 +80,9 @@ class TriangleMesh:
     """Minimal stand-in for open3d.geometry.TriangleMesh, what ScalableTSDFVolume.extract_triangle_mesh returns: vertices float64
     [n,3], vertex_colors float64 [n,3] or None, triangles int32 [m,3], vertex_normals float64 [n,3] or None (until
     compute_vertex_normals).  io_formats.write_ply(path, mesh.vertices, colors=mesh.vertex_colors, faces=mesh.triangles) saves it.
-    The filters, compute_triangle_normals, compute_adjacency_list and the remove_* clean-ups run on the device (mesh_ops.py);
-    triangle_normals (float64 [m,3]) and adjacency_list (a list of ascending int32 arrays) are None until computed."""
+    The filters, compute_triangle_normals, compute_adjacency_list, the remove_* clean-ups, cluster_connected_triangles and the edge
+    queries run on the device (mesh_ops.py); triangle_normals (float64 [m,3]) and adjacency_list (a list of ascending int32 arrays)
+    are None until computed.  mesh_a + mesh_b concatenates, as Open3D's operator+."""
 
     def __init__(self, vertices=None, triangles=None, vertex_colors=None, vertex_normals=None):
         self.vertices = _arr(vertices)
@@ -210,6 +211,94 @@ class TriangleMesh:
         """the scrub of check84.py:315-322: remove_vertices_by_mask of the rows with a NaN or an infinity"""
         from . import mesh_ops
         return self._compact(mesh_ops.DROP_NON_FINITE, ctx=ctx)
+
+    # ---- topology (mesh_ops.py, csrc/meshtopo.hip): the edge table, connected components and the welds
+    def cluster_connected_triangles(self, ctx=None):
+        """-> triangle_clusters int32 [m], cluster_n_triangles int64 [], cluster_area float64 []: triangles that share an edge are
+        connected; the components are numbered in ascending order of their lowest triangle"""
+        from . import mesh_ops
+        return mesh_ops.components(self.vertices, self.triangles, ctx=ctx)
+
+    def remove_small_components(self, min_triangles=0, min_area=0.0, keep_largest=False, ctx=None):
+        """the tutorial idiom: cluster_connected_triangles, then the components with fewer than min_triangles triangles or less than
+        min_area area go (keep_largest: all but the one with the most triangles), with the vertices they leave unreferenced"""
+        from . import mesh_ops
+        labels, count, area = mesh_ops.components(self.vertices, self.triangles, ctx=ctx)
+        gone = mesh_ops.component_mask(labels, count, area, min_triangles, min_area, keep_largest)
+        if gone.any():
+            self.remove_triangles_by_mask(gone, ctx=ctx)
+        return self.remove_unreferenced_vertices(ctx=ctx)
+
+    def _dedup(self, flags, ctx):
+        from . import mesh_ops
+        vert, tri, nrm, col, _, origin = mesh_ops.dedup(self.vertices, self.triangles, flags,
+                                                        self.vertex_normals if self.has_vertex_normals() else None,
+                                                        self.vertex_colors if self.has_vertex_colors() else None, ctx=ctx)
+        if self.triangle_normals is not None:
+            self.triangle_normals = self.triangle_normals[origin] if len(self.triangle_normals) == len(self.triangles) else None
+        self.vertices, self.triangles = vert, tri
+        self.vertex_normals = nrm if nrm is not None or self.vertex_normals is None else np.zeros((0, 3))
+        self.vertex_colors = col if col is not None or self.vertex_colors is None else np.zeros((0, 3))
+        self.adjacency_list = None
+        return self
+
+    def remove_duplicated_vertices(self, ctx=None):
+        """vertices with equal x, y and z (as doubles: -0.0 == +0.0, a NaN equals nothing) become the first of them, which keeps its
+        own normal and colour; triangles are renumbered, none is dropped"""
+        from . import mesh_ops
+        return self._dedup(mesh_ops.DEDUP_VERTICES, ctx)
+
+    def remove_duplicated_triangles(self, ctx=None):
+        """triangles equal up to rotation become the first of them ((a,c,b) is another triangle than (a,b,c)); triangle_normals follow"""
+        from . import mesh_ops
+        return self._dedup(mesh_ops.DEDUP_TRIANGLES, ctx)
+
+    def _edge_table(self, ctx):
+        from . import mesh_ops
+        return mesh_ops.edges(len(self.vertices), self.triangles, ctx=ctx)
+
+    def get_non_manifold_edges(self, allow_boundary_edges=True, ctx=None):
+        """-> int32 [k,2] (min, max) ascending: the edges with more than two sides on them; allow_boundary_edges=False adds the
+        edges with one (every edge whose count is not 2).  Open3D's order is its hash map's."""
+        edg, cnt, _ = self._edge_table(ctx)
+        return edg[cnt > 2 if allow_boundary_edges else cnt != 2]
+
+    def is_edge_manifold(self, allow_boundary_edges=True, ctx=None):
+        _, _, stats = self._edge_table(ctx)
+        return bool(stats[2] == 0 and (allow_boundary_edges or stats[1] == 0))
+
+    def euler_poincare_characteristic(self, ctx=None):
+        """V + F - E with every vertex counted, referenced or not, as Open3D does"""
+        _, _, stats = self._edge_table(ctx)
+        return int(len(self.vertices) + len(self.triangles) - stats[0])
+
+    def __iadd__(self, other):
+        """Open3D's operator+=: the other mesh's vertices and triangles behind this one's, its indices offset; colours, vertex
+        normals and triangle normals stay only when both meshes have them (an empty mesh has everything)"""
+        if not len(other.vertices):
+            return self
+        nv = len(self.vertices)
+
+        def both(mine, theirs, have, n_mine):
+            return np.concatenate([mine, theirs]) if theirs is not None and (n_mine == 0 or have) else None
+        colors = both(self.vertex_colors if nv else np.zeros((0, 3)), other.vertex_colors if other.has_vertex_colors() else None, self.has_vertex_colors(), nv)
+        normals = both(self.vertex_normals if nv else np.zeros((0, 3)), other.vertex_normals if other.has_vertex_normals() else None,
+                       self.has_vertex_normals(), nv)
+        nt = len(self.triangles)
+        tnormals = both(self.triangle_normals if nt else np.zeros((0, 3)), other.triangle_normals if other.has_triangle_normals() else None,
+                        self.has_triangle_normals(), nt)
+        self.vertices = np.concatenate([self.vertices, other.vertices])
+        self.triangles = np.ascontiguousarray(np.concatenate([self.triangles, other.triangles + np.int32(nv)]), dtype=np.int32)
+        self.vertex_colors, self.vertex_normals, self.triangle_normals = colors, normals, tnormals
+        self.adjacency_list = None
+        return self
+
+    def __add__(self, other):
+        out = TriangleMesh(self.vertices.copy(), self.triangles.copy(), None if self.vertex_colors is None else self.vertex_colors.copy(),
+                           None if self.vertex_normals is None else self.vertex_normals.copy())
+        out.triangle_normals = None if self.triangle_normals is None else self.triangle_normals.copy()
+        out += other
+        return out
 
     def transform(self, T):
         from . import cloud_ops

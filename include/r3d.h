@@ -28,6 +28,7 @@ extern "C" {
 #define R3D_E_OOM (-3)         /* device or host allocation failed */
 #define R3D_E_UNSUPPORTED (-4) /* valid for the reference, outside this library's exact-arithmetic envelope */
 #define R3D_E_NODEVICE (-5)    /* no gfx950 device visible */
+#define R3D_E_INTERNAL (-6)    /* a capped device loop ran over its cap: a defect of the library, reported in place of a hang */
 
 typedef struct r3d_ctx r3d_ctx;
 
@@ -902,6 +903,49 @@ int r3d_trimesh_compact_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *
                             int64_t cap_vertices, int64_t cap_triangles, double *d_out_vertices, double *d_out_normals, double *d_out_colors,
                             int32_t *d_out_triangles, int64_t *out_nv, int64_t *out_nt);
 
+
+/* ---- mesh topology (csrc/meshtopo.hip; DESIGN.md section 4, "Mesh topology") -----------------------------------------------------------
+ * The edge table, connected components and duplicate clean-ups of Open3D's TriangleMesh (get_non_manifold_edges,
+ * cluster_connected_triangles, remove_duplicated_vertices, remove_duplicated_triangles).  Parity with Open3D is UNPINNED;
+ * tests/meshtopo_ref.py restates the contract.  Sizes, the refusal of an index outside [0, nv), empty meshes and the _dev rules are
+ * those of the triangle-mesh operations above.  R3D_E_INTERNAL: a union-find walk passed its cap (never expected; reported, not hung).
+ *
+ * Edge table: triangle (a, b, c) has the sides (a,b), (b,c), (c,a); a side's edge is (min, max); a degenerate (a, a, b) has a side
+ * (a, a) and two on (a, b).  The distinct edges come ascending by (min, max) with their numbers of sides.  cap = 0 asks for the
+ * number of edges only (*out_n); otherwise edges int32 [n][2] and counts int32 [n] are written when cap >= *out_n and nothing is
+ * written when it is not (R3D_E_BADARG).  stats (optional, always set) = {edges, boundary (count 1), non-manifold (count > 2),
+ * degenerate (min == max)}. */
+int r3d_meshtopo_edges(r3d_ctx *ctx, int64_t nv, int64_t nt, const int32_t *triangles, int64_t cap, int32_t *edges, int32_t *counts, int64_t *stats,
+                       int64_t *out_n);
+/* Connected components: two triangles are adjacent when they have a side on the same edge (all triangles on a non-manifold edge
+ * are mutually adjacent; a shared vertex alone does not join).  triangle_clusters int32 [nt] numbers the components in ascending
+ * order of their lowest triangle; *out_n_clusters is always set.  cap_clusters = 0: labels alone (vertices may be NULL).  Otherwise,
+ * when cap_clusters >= *out_n_clusters, cluster_n_triangles int64 [] and cluster_area double [] as well; when it is not, R3D_E_BADARG
+ * and nothing is written.  cluster_area[c]: the terms 0.5 * sqrt((n0 n0 + n1 n1) + n2 n2), n = (p1 - p0) x (p2 - p0), float64 without
+ * fused multiply-add, of the component's triangles in ascending index, added in consecutive chunks of 256 from the front of each,
+ * then the chunk sums from the front. */
+int r3d_meshtopo_components(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vertices, const int32_t *triangles, int64_t cap_clusters,
+                            int32_t *triangle_clusters, int64_t *cluster_n_triangles, double *cluster_area, int64_t *out_n_clusters);
+int r3d_meshtopo_components_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d_vertices, const int32_t *d_triangles, int64_t cap_clusters,
+                                int32_t *d_triangle_clusters, int64_t *d_cluster_n_triangles, double *d_cluster_area, int64_t *out_n_clusters);
+
+#define R3D_DEDUP_VERTICES 1  /* vertices whose x, y and z compare equal as doubles (-0.0 == +0.0; a row with a NaN equals nothing) */
+#define R3D_DEDUP_TRIANGLES 2 /* triangles equal up to rotation ((a,b,c) = (b,c,a) = (c,a,b); (a,c,b) is another) */
+/* The welds.  The first occurrence survives, a vertex with its own normal and colour, a triangle in its own rotation; survivors
+ * keep their order.  DEDUP_VERTICES renumbers the triangles and drops none; DEDUP_TRIANGLES leaves the vertices alone; with both,
+ * vertices go first.  Arrays, capacities and refusals as r3d_trimesh_compact.  Optional outputs (written with the rows):
+ * vertex_map int32 [nv], the new number of every input vertex, and triangle_origin int32 [*out_nt], the input triangle each
+ * surviving triangle was.  Refused: unknown flags. */
+int r3d_meshtopo_dedup(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vertices, const double *normals, const double *colors, const int32_t *triangles,
+                       int32_t flags, int64_t cap_vertices, int64_t cap_triangles, double *out_vertices, double *out_normals, double *out_colors,
+                       int32_t *out_triangles, int32_t *vertex_map, int32_t *triangle_origin, int64_t *out_nv, int64_t *out_nt);
+int r3d_meshtopo_dedup_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d_vertices, const double *d_normals, const double *d_colors,
+                           const int32_t *d_triangles, int32_t flags, int64_t cap_vertices, int64_t cap_triangles, double *d_out_vertices,
+                           double *d_out_normals, double *d_out_colors, int32_t *d_out_triangles, int32_t *d_vertex_map, int32_t *d_triangle_origin,
+                           int64_t *out_nv, int64_t *out_nt);
+/* the sort under all of the above, for the tests: n host (key, value) pairs in the stable order of the keys, which must be below 2^bits (bits 0..64;
+ * eight per pass, at least one pass); values NULL: the index */
+int r3d_debug_sort_pairs_u64(r3d_ctx *ctx, const uint64_t *keys, const int32_t *values, int64_t n, int32_t bits, uint64_t *out_keys, int32_t *out_values);
 
 /* ---- Poisson surface reconstruction (mesh_reconstruction.py:22-37, visualizer.py:107-110) ---------------------------------------
  * replaces: o3d.geometry.TriangleMesh.create_from_point_cloud_poisson(pcd, depth).  The screened Poisson formulation on a DENSE
