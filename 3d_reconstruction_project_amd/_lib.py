@@ -239,6 +239,11 @@ def live_resources():
     return {n: int(getattr(c, n)) for n, _ in ResourceCounts._fields_}
 
 
+def ptr(a):
+    """a numpy array's data as the void pointer the entry points take; None stays None (an absent array)"""
+    return None if a is None else a.ctypes.data_as(_vp)
+
+
 class R3DError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -274,6 +279,22 @@ class Context:
 
     def call(self, name, *args):
         self.check(getattr(self._lib, name)(self._h, *args))
+
+    def count_then_fill(self, name, head, n_outputs, alloc, n_counts=1):
+        """The count / capacity protocol of an entry point whose arguments end (capacities..., outputs..., counts...): one call with
+        capacities 0 and null outputs for the counts; alloc(*counts) -> the n_outputs host arrays in the entry point's order (None:
+        an output it does not have); then, unless every count is 0, the call again with the counts as capacities, which must
+        report the same counts.  -> (counts, arrays)"""
+        def run(caps, outs):
+            got = [ctypes.c_int64() for _ in caps]
+            self.call(name, *head, *caps, *outs, *map(ctypes.byref, got))
+            return tuple(g.value for g in got)
+        counts = run((0,) * n_counts, (None,) * n_outputs)
+        arrays = tuple(alloc(*counts))
+        assert len(arrays) == n_outputs
+        if any(counts):
+            assert run(counts, [ptr(a) for a in arrays]) == counts
+        return counts, arrays
 
     # --- memory / timing plumbing
     def alloc(self, nbytes):

@@ -251,8 +251,7 @@ def _c(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+_ptr = _lib.ptr
 
 
 def voxel_down_sample(points, voxel, colors=None, normals=None, ctx=None, tensor=False):

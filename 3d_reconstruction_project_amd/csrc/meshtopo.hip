@@ -8,7 +8,7 @@
 // roots and count; the hooks always put the larger root under the smaller, so every component's root is its lowest triangle
 // whatever the arrival order, and no arrival order reaches a result.  No kernel waits for another workgroup: every walk is capped
 // and a trip over the cap raises an error word (R3D_E_INTERNAL).
-#include "r3d_internal.h"
+#include "r3d_mesh.h"
 
 #include <climits>
 
@@ -311,37 +311,10 @@ __global__ void __launch_bounds__(256) k_mt_vertex_map(const int *__restrict__ f
 }
 
 // ====================================================================================================================== host side
-inline unsigned mt_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 inline int mt_bit_length(int64_t x) {
     int b = 0;
     while (x > 0) { b++; x >>= 1; }
     return b;
-}
-
-// the size limits of the triangle-mesh entry points (trimesh.hip: tm_sizes_ok), the poisoned-context refusal included
-int mt_sizes_ok(r3d_ctx *ctx, const char *who, int64_t nv, int64_t nt) {
-    if (nv < 0 || nt < 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: a negative count", who);
-    if (nv > INT32_MAX - 1) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: %lld vertices do not fit int32 indices", who, (long long)nv);
-    if (nt > (int64_t)INT32_MAX / 6) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: 6 x %lld triangles do not fit int32 offsets", who, (long long)nt);
-    if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "%s: context poisoned by an earlier timed-out call: destroy it", who);
-    return R3D_OK;
-}
-
-// the _dev forms refuse outputs that overlap an input or one another (trimesh.hip: tm_distinct)
-struct MtSpan { const void *p; size_t bytes; };
-int mt_distinct(r3d_ctx *ctx, const char *who, const MtSpan *out, int n_out, const MtSpan *in, int n_in) {
-    auto overlap = [](const MtSpan &a, const MtSpan &b) {
-        if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-        return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-    };
-    for (int i = 0; i < n_out; i++) {
-        for (int j = 0; j < n_in; j++)
-            if (overlap(out[i], in[j])) return r3d_fail(ctx, R3D_E_BADARG, "%s: an output array overlaps an input array", who);
-        for (int j = 0; j < i; j++)
-            if (overlap(out[i], out[j])) return r3d_fail(ctx, R3D_E_BADARG, "%s: two output arrays overlap", who);
-    }
-    return R3D_OK;
 }
 
 // the sides of nt > 0 triangles sorted by edge, with run heads and their scan; nothing read back yet
@@ -362,23 +335,14 @@ int mt_sorted_sides(r3d_ctx *ctx, DevArena &ar, int nv, int64_t nt, const int32_
     S.hdr = (MtHdr *)ar.get(sizeof(MtHdr));
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemsetAsync(S.hdr, 0, sizeof(MtHdr), st));
-    k_mt_sides<<<mt_blocks(n3), 256, 0, st>>>(d_tri, n3, nv, S.b, key, S.hdr);
+    k_mt_sides<<<r3d_blocks(n3), 256, 0, st>>>(d_tri, n3, nv, S.b, key, S.hdr);
     R3D_HIP(ctx, hipGetLastError());
     const uint64_t *ks;
     if (int rc = r3d_sort_pairs_u64(ctx, ar, (const uint64_t *)key, nullptr, n3, 2 * S.b, &ks, &S.side)) return rc;
     S.key = (const u64 *)ks;
-    k_mt_heads<<<mt_blocks(n3 + 1), 256, 0, st>>>(S.key, n3, S.head);
+    k_mt_heads<<<r3d_blocks(n3 + 1), 256, 0, st>>>(S.key, n3, S.head);
     R3D_HIP(ctx, hipGetLastError());
     return r3d_exclusive_scan_i32(ctx, ar, S.head, S.ex, n3 + 1);
-}
-
-// the header and one more int in one wait
-int mt_read(r3d_ctx *ctx, const MtHdr *d_hdr, MtHdr *h, const int *d_a, int *a, const int *d_b = nullptr, int *b = nullptr) {
-    R3D_HIP(ctx, hipMemcpyAsync(h, d_hdr, sizeof(MtHdr), hipMemcpyDeviceToHost, ctx->stream));
-    if (d_a) R3D_HIP(ctx, hipMemcpyAsync(a, d_a, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (d_b) R3D_HIP(ctx, hipMemcpyAsync(b, d_b, 4, hipMemcpyDeviceToHost, ctx->stream));
-    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return R3D_OK;
 }
 
 // ---- components: device arrays in and out.  d_labels [nt]; d_count / d_area [cap] are written when 0 < cap and the clusters fit.
@@ -387,7 +351,7 @@ int mt_components(r3d_ctx *ctx, DevArena &ar, const char *who, int64_t nv64, int
     hipStream_t st = ctx->stream;
     *out_ncl = 0;
     if (nt64 == 0) return R3D_OK;
-    if (nv64 == 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, 0)", who);
+    if (int rc = r3d_mesh_empty_ok(ctx, who, nv64, nt64)) return rc;
     const int nv = (int)nv64, nt = (int)nt64;
     const int64_t n3 = 3 * nt64;
     MtSides S;
@@ -398,17 +362,17 @@ int mt_components(r3d_ctx *ctx, DevArena &ar, const char *who, int64_t nv64, int
     u64 *lkey = (u64 *)ar.get((size_t)nt * 8);
     if (ar.rc) return ar.rc;
     MtHdr h = {};
-    if (int rc = mt_read(ctx, S.hdr, &h, nullptr, nullptr)) return rc;
+    if (int rc = r3d_read_back(ctx, {{&h, S.hdr, sizeof(MtHdr)}})) return rc;
     if (h.bad_index) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, %d)", who, nv);
-    k_mt_iota<<<mt_blocks(nt), 256, 0, st>>>(parent, nt);
-    k_mt_link<<<mt_blocks(n3), 256, 0, st>>>(S.side, S.head, n3, nt, parent, S.hdr);
-    k_mt_flatten<<<mt_blocks(nt + 1), 256, 0, st>>>(parent, nt, root, is_root, S.hdr);
+    k_mt_iota<<<r3d_blocks(nt), 256, 0, st>>>(parent, nt);
+    k_mt_link<<<r3d_blocks(n3), 256, 0, st>>>(S.side, S.head, n3, nt, parent, S.hdr);
+    k_mt_flatten<<<r3d_blocks(nt + 1), 256, 0, st>>>(parent, nt, root, is_root, S.hdr);
     R3D_HIP(ctx, hipGetLastError());
     if (int rc = r3d_exclusive_scan_i32(ctx, ar, is_root, number, (int64_t)nt + 1)) return rc;
-    k_mt_labels<<<mt_blocks(nt), 256, 0, st>>>(root, number, nt, label, lkey);
+    k_mt_labels<<<r3d_blocks(nt), 256, 0, st>>>(root, number, nt, label, lkey);
     R3D_HIP(ctx, hipGetLastError());
     int ncl = 0;
-    if (int rc = mt_read(ctx, S.hdr, &h, number + nt, &ncl)) return rc;
+    if (int rc = r3d_read_back(ctx, {{&h, S.hdr, sizeof(MtHdr)}, {&ncl, number + nt, 4}})) return rc;
     if (h.walk_cap) return r3d_fail(ctx, R3D_E_INTERNAL, "%s: a union-find walk passed its cap of %d steps", who, nt);
     *out_ncl = ncl;
     if (cap > 0) {
@@ -416,13 +380,13 @@ int mt_components(r3d_ctx *ctx, DevArena &ar, const char *who, int64_t nv64, int
         double *area = (double *)ar.get((size_t)nt * 8), *part = (double *)ar.get((size_t)nt * 8);
         int *start = (int *)ar.get((size_t)ncl * 4), *long_list = (int *)ar.get((size_t)(nt / MT_CHUNK + 1) * 4);
         if (ar.rc) return ar.rc;
-        k_mt_area<<<mt_blocks(nt), 256, 0, st>>>(d_pos, d_tri, nt, area);
+        k_mt_area<<<r3d_blocks(nt), 256, 0, st>>>(d_pos, d_tri, nt, area);
         R3D_HIP(ctx, hipGetLastError());
         const uint64_t *ks;
         const int *order;
         if (int rc = r3d_sort_pairs_u64(ctx, ar, (const uint64_t *)lkey, nullptr, nt, mt_bit_length((int64_t)ncl - 1), &ks, &order)) return rc;
-        k_mt_cluster_starts<<<mt_blocks(nt), 256, 0, st>>>((const u64 *)ks, nt, start);
-        k_mt_cluster_short<<<mt_blocks(ncl), 256, 0, st>>>(start, order, area, ncl, nt, d_count, d_area, long_list, S.hdr);
+        k_mt_cluster_starts<<<r3d_blocks(nt), 256, 0, st>>>((const u64 *)ks, nt, start);
+        k_mt_cluster_short<<<r3d_blocks(ncl), 256, 0, st>>>(start, order, area, ncl, nt, d_count, d_area, long_list, S.hdr);
         k_mt_cluster_long<<<(unsigned)(nt / MT_CHUNK + 1), 256, 0, st>>>(start, order, area, ncl, nt, long_list, S.hdr, part, d_area);
         R3D_HIP(ctx, hipGetLastError());
     }
@@ -432,7 +396,7 @@ int mt_components(r3d_ctx *ctx, DevArena &ar, const char *who, int64_t nv64, int
 
 int mt_components_args_ok(r3d_ctx *ctx, const char *who, int64_t nv, int64_t nt, const void *vertices, const void *triangles, int64_t cap, const void *labels,
                           const void *counts, const void *areas, const void *out_n) {
-    if (int rc = mt_sizes_ok(ctx, who, nv, nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, who, nv, nt)) return rc;
     if (!out_n || cap < 0 || (nt > 0 && (!triangles || !labels)) || (cap > 0 && (!counts || !areas || (nv > 0 && !vertices))))
         return r3d_fail(ctx, R3D_E_BADARG, "%s: a missing array or a negative capacity", who);
     return R3D_OK;
@@ -447,28 +411,27 @@ int mt_group(r3d_ctx *ctx, DevArena &ar, int n, const int *perm, int *head, int 
     *map = (int *)ar.get((size_t)(n + 1) * 4);
     if (ar.rc) return ar.rc;
     if (int rc = r3d_exclusive_scan_i32(ctx, ar, head, ex, (int64_t)n + 1)) return rc;
-    k_mt_run_first<<<mt_blocks(n), 256, 0, ctx->stream>>>(perm, head, ex, n, run_first);
-    k_mt_first<<<mt_blocks(n + 1), 256, 0, ctx->stream>>>(perm, head, ex, run_first, n, *first, *keep);
+    k_mt_run_first<<<r3d_blocks(n), 256, 0, ctx->stream>>>(perm, head, ex, n, run_first);
+    k_mt_first<<<r3d_blocks(n + 1), 256, 0, ctx->stream>>>(perm, head, ex, run_first, n, *first, *keep);
     R3D_HIP(ctx, hipGetLastError());
     return r3d_exclusive_scan_i32(ctx, ar, *keep, *map, (int64_t)n + 1);
 }
 
 struct MtDedup {
     int64_t nv, nt;
-    const double *pos, *nrm, *col;
-    const int32_t *tri;
+    r3d_mesh_in in;
     int flags;
     int64_t cap_v, cap_t;
-    double *out_pos, *out_nrm, *out_col;
-    int32_t *out_tri, *vertex_map, *triangle_origin;
+    r3d_mesh_out out;
+    int32_t *vertex_map, *triangle_origin;
 };
 constexpr int MT_DEDUP_FLAGS = R3D_DEDUP_VERTICES | R3D_DEDUP_TRIANGLES;
 
 int mt_dedup_args_ok(r3d_ctx *ctx, const char *who, const MtDedup &m, const void *out_nv, const void *out_nt) {
-    if (int rc = mt_sizes_ok(ctx, who, m.nv, m.nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, who, m.nv, m.nt)) return rc;
     if (m.flags & ~MT_DEDUP_FLAGS) return r3d_fail(ctx, R3D_E_BADARG, "%s: unknown flags %d", who, m.flags);
-    if (!out_nv || !out_nt || m.cap_v < 0 || m.cap_t < 0 || (m.nv > 0 && !m.pos) || (m.nt > 0 && !m.tri) ||
-        (m.cap_v > 0 && (!m.out_pos || (m.nrm && !m.out_nrm) || (m.col && !m.out_col))) || (m.cap_t > 0 && !m.out_tri))
+    if (!out_nv || !out_nt || m.cap_v < 0 || m.cap_t < 0 || (m.nv > 0 && !m.in.pos) || (m.nt > 0 && !m.in.tri) ||
+        (m.cap_v > 0 && (!m.out.pos || (m.in.nrm && !m.out.nrm) || (m.in.col && !m.out.col))) || (m.cap_t > 0 && !m.out.tri))
         return r3d_fail(ctx, R3D_E_BADARG, "%s: a missing array or a negative capacity", who);
     return R3D_OK;
 }
@@ -478,10 +441,8 @@ int mt_dedup(r3d_ctx *ctx, DevArena &ar, const char *who, const MtDedup &m, int6
     hipStream_t st = ctx->stream;
     *out_nv = *out_nt = 0;
     *wrote = false;
-    if (m.nv == 0) {
-        if (m.nt) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, 0)", who);
-        return R3D_OK;
-    }
+    if (int rc = r3d_mesh_empty_ok(ctx, who, m.nv, m.nt)) return rc;
+    if (m.nv == 0) return R3D_OK;
     const int nv = (int)m.nv, nt = (int)m.nt;
     const int64_t n3 = 3 * m.nt;
     const int b = mt_bit_length((int64_t)nv - 1);
@@ -496,18 +457,18 @@ int mt_dedup(r3d_ctx *ctx, DevArena &ar, const char *who, const MtDedup &m, int6
         if (ar.rc) return ar.rc;
         const int *perm = nullptr;
         for (int axis = 2; axis >= 0; axis--) {
-            k_mt_vertex_keys<<<mt_blocks(nv), 256, 0, st>>>(m.pos, perm, nv, axis, key);
+            k_mt_vertex_keys<<<r3d_blocks(nv), 256, 0, st>>>(m.in.pos, perm, nv, axis, key);
             R3D_HIP(ctx, hipGetLastError());
             const uint64_t *ks;
             if (int rc = r3d_sort_pairs_u64(ctx, ar, (const uint64_t *)key, perm, nv, 64, &ks, &perm)) return rc;
         }
-        k_mt_vertex_heads<<<mt_blocks(nv + 1), 256, 0, st>>>(m.pos, perm, nv, head);
+        k_mt_vertex_heads<<<r3d_blocks(nv + 1), 256, 0, st>>>(m.in.pos, perm, nv, head);
         R3D_HIP(ctx, hipGetLastError());
         if (int rc = mt_group(ctx, ar, nv, perm, head, &vfirst, &vkeep, &vmap)) return rc;
     }
     int32_t *tri2 = (int32_t *)ar.get((size_t)n3 * 4);
     if (ar.rc) return ar.rc;
-    if (nt) k_mt_remap<<<mt_blocks(n3), 256, 0, st>>>(m.tri, n3, nv, vfirst, vmap, tri2, hdr);
+    if (nt) k_mt_remap<<<r3d_blocks(n3), 256, 0, st>>>(m.in.tri, n3, nv, vfirst, vmap, tri2, hdr);
     R3D_HIP(ctx, hipGetLastError());
     int *tfirst = nullptr, *tkeep = nullptr, *tmap = nullptr;
     if ((m.flags & R3D_DEDUP_TRIANGLES) && nt) {
@@ -517,31 +478,29 @@ int mt_dedup(r3d_ctx *ctx, DevArena &ar, const char *who, const MtDedup &m, int6
         if (ar.rc) return ar.rc;
         const uint64_t *ks;
         const int *perm = nullptr;
-        k_mt_triangle_keys<<<mt_blocks(nt), 256, 0, st>>>(tri2, nullptr, nt, b, 1, key);
+        k_mt_triangle_keys<<<r3d_blocks(nt), 256, 0, st>>>(tri2, nullptr, nt, b, 1, key);
         R3D_HIP(ctx, hipGetLastError());
         if (int rc = r3d_sort_pairs_u64(ctx, ar, (const uint64_t *)key, nullptr, nt, b, &ks, &perm)) return rc;
-        k_mt_triangle_keys<<<mt_blocks(nt), 256, 0, st>>>(tri2, perm, nt, b, 0, key);
+        k_mt_triangle_keys<<<r3d_blocks(nt), 256, 0, st>>>(tri2, perm, nt, b, 0, key);
         R3D_HIP(ctx, hipGetLastError());
         if (int rc = r3d_sort_pairs_u64(ctx, ar, (const uint64_t *)key, perm, nt, 2 * b, &ks, &perm)) return rc;
-        k_mt_triangle_heads<<<mt_blocks(nt + 1), 256, 0, st>>>(tri2, perm, nt, head);
+        k_mt_triangle_heads<<<r3d_blocks(nt + 1), 256, 0, st>>>(tri2, perm, nt, head);
         R3D_HIP(ctx, hipGetLastError());
         if (int rc = mt_group(ctx, ar, nt, perm, head, &tfirst, &tkeep, &tmap)) return rc;
     }
     MtHdr h = {};
     int kept_v = nv, kept_t = nt;
-    if (int rc = mt_read(ctx, hdr, &h, vmap ? vmap + nv : nullptr, &kept_v, tmap ? tmap + nt : nullptr, &kept_t)) return rc;
+    if (int rc = r3d_read_back(ctx, {{&h, hdr, sizeof(MtHdr)}, {&kept_v, vmap ? vmap + nv : nullptr, 4}, {&kept_t, tmap ? tmap + nt : nullptr, 4}})) return rc;
     if (h.bad_index) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, %d)", who, nv);
     *out_nv = kept_v;
     *out_nt = kept_t;
     if (m.cap_v == 0 && m.cap_t == 0) return R3D_OK;
-    if (m.cap_v < kept_v || m.cap_t < kept_t)
-        return r3d_fail(ctx, R3D_E_BADARG, "%s: %d vertices and %d triangles do not fit capacities of %lld and %lld", who, kept_v, kept_t,
-                        (long long)m.cap_v, (long long)m.cap_t);
-    k_mt_scatter_rows<<<mt_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.pos, m.out_pos);
-    if (m.nrm) k_mt_scatter_rows<<<mt_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.nrm, m.out_nrm);
-    if (m.col) k_mt_scatter_rows<<<mt_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.col, m.out_col);
-    if (m.vertex_map) k_mt_vertex_map<<<mt_blocks(nv), 256, 0, st>>>(vfirst, vmap, nv, m.vertex_map);
-    if (nt) k_mt_scatter_triangles<<<mt_blocks(nt), 256, 0, st>>>(tkeep, tmap, tri2, nt, m.out_tri, m.triangle_origin);
+    if (int rc = r3d_fits2(ctx, who, "vertices", kept_v, "triangles", kept_t, m.cap_v, m.cap_t)) return rc;
+    k_mt_scatter_rows<<<r3d_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.in.pos, m.out.pos);
+    if (m.in.nrm) k_mt_scatter_rows<<<r3d_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.in.nrm, m.out.nrm);
+    if (m.in.col) k_mt_scatter_rows<<<r3d_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.in.col, m.out.col);
+    if (m.vertex_map) k_mt_vertex_map<<<r3d_blocks(nv), 256, 0, st>>>(vfirst, vmap, nv, m.vertex_map);
+    if (nt) k_mt_scatter_triangles<<<r3d_blocks(nt), 256, 0, st>>>(tkeep, tmap, tri2, nt, m.out.tri, m.triangle_origin);
     R3D_HIP(ctx, hipGetLastError());
     *wrote = true;
     return R3D_OK;
@@ -556,14 +515,14 @@ int r3d_meshtopo_edges(r3d_ctx *ctx, int64_t nv, int64_t nt, const int32_t *tria
     R3D_ROCTX_RANGE("r3d_meshtopo_edges");
     if (!ctx) return R3D_E_BADARG;
     const char *who = "meshtopo_edges";
-    if (int rc = mt_sizes_ok(ctx, who, nv, nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, who, nv, nt)) return rc;
     if (!out_n || cap < 0 || (nt > 0 && !triangles) || (cap > 0 && (!edges || !counts)))
         return r3d_fail(ctx, R3D_E_BADARG, "%s: a missing array or a negative capacity", who);
     *out_n = 0;
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     if (nt == 0) return R3D_OK;
-    if (nv == 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, 0)", who);
+    if (int rc = r3d_mesh_empty_ok(ctx, who, nv, nt)) return rc;
     DevArena ar(ctx);
     hipStream_t st = ctx->stream;
     const int64_t n3 = 3 * nt;
@@ -577,15 +536,14 @@ int r3d_meshtopo_edges(r3d_ctx *ctx, int64_t nv, int64_t nt, const int32_t *tria
     if (ar.rc) return ar.rc;
     MtHdr h = {};
     int ne = 0;
-    if (int rc = mt_read(ctx, S.hdr, &h, S.ex + n3, &ne)) return rc;
+    if (int rc = r3d_read_back(ctx, {{&h, S.hdr, sizeof(MtHdr)}, {&ne, S.ex + n3, 4}})) return rc;
     if (h.bad_index) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, %d)", who, (int)nv);
     R3D_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(MtStats), st));
-    k_mt_edge_rows<<<mt_blocks(n3), 256, 0, st>>>(S.key, S.head, S.ex, n3, S.b, start, d_edges);
-    k_mt_edge_counts<<<mt_blocks(ne), 256, 0, st>>>(start, S.ex, n3, d_edges, d_counts, d_stats);
+    k_mt_edge_rows<<<r3d_blocks(n3), 256, 0, st>>>(S.key, S.head, S.ex, n3, S.b, start, d_edges);
+    k_mt_edge_counts<<<r3d_blocks(ne), 256, 0, st>>>(start, S.ex, n3, d_edges, d_counts, d_stats);
     R3D_HIP(ctx, hipGetLastError());
     MtStats hs = {};
-    R3D_HIP(ctx, hipMemcpyAsync(&hs, d_stats, sizeof(MtStats), hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = r3d_read_back(ctx, {{&hs, d_stats, sizeof(MtStats)}})) return rc;
     *out_n = ne;
     if (stats) { stats[0] = hs.n_edges; stats[1] = hs.boundary; stats[2] = hs.non_manifold; stats[3] = hs.degenerate; }
     if (cap == 0) return R3D_OK;
@@ -605,16 +563,14 @@ int r3d_meshtopo_components(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *
         return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    const double *d_pos;
-    const int32_t *d_tri;
+    r3d_mesh_in d;   // the areas alone read the vertices
     int rc;
-    if ((rc = r3d_upload(ctx, ar, cap_clusters > 0 ? vertices : nullptr, (size_t)nv * 3, &d_pos)) || (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &d_tri)))
-        return rc;
+    if ((rc = r3d_mesh_upload(ctx, ar, {cap_clusters > 0 ? vertices : nullptr, nullptr, nullptr, triangles}, nv, nt, &d))) return rc;
     int32_t *d_labels = (int32_t *)ar.get((size_t)nt * 4);
     int64_t *d_count = cap_clusters > 0 ? (int64_t *)ar.get((size_t)cap_clusters * 8) : nullptr;
     double *d_area = cap_clusters > 0 ? (double *)ar.get((size_t)cap_clusters * 8) : nullptr;
     if (ar.rc) return ar.rc;
-    if ((rc = mt_components(ctx, ar, who, nv, nt, d_pos, d_tri, cap_clusters, d_labels, d_count, d_area, out_n_clusters))) return rc;
+    if ((rc = mt_components(ctx, ar, who, nv, nt, d.pos, d.tri, cap_clusters, d_labels, d_count, d_area, out_n_clusters))) return rc;
     const size_t ncl = cap_clusters > 0 ? (size_t)*out_n_clusters : 0;
     if ((rc = r3d_download(ctx, triangle_clusters, (const int32_t *)d_labels, (size_t)nt)) ||
         (rc = r3d_download(ctx, cluster_n_triangles, (const int64_t *)d_count, ncl)) || (rc = r3d_download(ctx, cluster_area, (const double *)d_area, ncl)))
@@ -632,9 +588,9 @@ int r3d_meshtopo_components_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const doub
                                        out_n_clusters))
         return rc;
     {
-        const MtSpan out[] = {{d_triangle_clusters, (size_t)nt * 4}, {d_cluster_n_triangles, (size_t)cap_clusters * 8}, {d_cluster_area, (size_t)cap_clusters * 8}};
-        const MtSpan in[] = {{d_vertices, (size_t)nv * 24}, {d_triangles, (size_t)nt * 12}};
-        if (int rc = mt_distinct(ctx, who, out, 3, in, 2)) return rc;
+        const r3d_span out[] = {{d_triangle_clusters, (size_t)nt * 4}, {d_cluster_n_triangles, (size_t)cap_clusters * 8}, {d_cluster_area, (size_t)cap_clusters * 8}};
+        const r3d_span in[] = {{d_vertices, (size_t)nv * 24}, {d_triangles, (size_t)nt * 12}};
+        if (int rc = r3d_distinct(ctx, who, out, 3, in, 2)) return rc;
     }
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
@@ -651,32 +607,22 @@ int r3d_meshtopo_dedup(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *verti
     R3D_ROCTX_RANGE("r3d_meshtopo_dedup");
     if (!ctx) return R3D_E_BADARG;
     const char *who = "meshtopo_dedup";
-    MtDedup m = {nv, nt, vertices, normals, colors, triangles, flags, cap_vertices, cap_triangles, out_vertices, out_normals, out_colors, out_triangles,
-                 vertex_map, triangle_origin};
+    const r3d_mesh_in h_in = {vertices, normals, colors, triangles};
+    const r3d_mesh_out h_out = {out_vertices, out_normals, out_colors, out_triangles};
+    MtDedup m = {nv, nt, h_in, flags, cap_vertices, cap_triangles, h_out, vertex_map, triangle_origin};
     if (int rc = mt_dedup_args_ok(ctx, who, m, out_nv, out_nt)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    const size_t n3 = (size_t)nv * 3;
     int rc;
-    if ((rc = r3d_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = r3d_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = r3d_upload(ctx, ar, colors, n3, &m.col)) ||
-        (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)))
-        return rc;
-    // device outputs as large as the inputs: the counts are not known yet
-    m.out_pos = (double *)ar.get(n3 * 8);
-    m.out_nrm = normals ? (double *)ar.get(n3 * 8) : nullptr;
-    m.out_col = colors ? (double *)ar.get(n3 * 8) : nullptr;
-    m.out_tri = (int32_t *)ar.get((size_t)nt * 12);
+    if ((rc = r3d_mesh_upload(ctx, ar, h_in, nv, nt, &m.in))) return rc;
+    r3d_mesh_outputs(ar, m.in, nv, nt, true, &m.out);
     m.vertex_map = vertex_map ? (int32_t *)ar.get((size_t)nv * 4) : nullptr;
     m.triangle_origin = triangle_origin ? (int32_t *)ar.get((size_t)nt * 4) : nullptr;
     if (ar.rc) return ar.rc;
     bool wrote = false;
     if ((rc = mt_dedup(ctx, ar, who, m, out_nv, out_nt, &wrote))) return rc;
     if (!wrote) return R3D_OK;
-    const size_t k3 = (size_t)*out_nv * 3;
-    if ((rc = r3d_download(ctx, out_vertices, (const double *)m.out_pos, k3)) || (rc = r3d_download(ctx, out_normals, (const double *)m.out_nrm, normals ? k3 : 0)) ||
-        (rc = r3d_download(ctx, out_colors, (const double *)m.out_col, colors ? k3 : 0)) ||
-        (rc = r3d_download(ctx, out_triangles, (const int32_t *)m.out_tri, (size_t)*out_nt * 3)) ||
-        (rc = r3d_download(ctx, vertex_map, (const int32_t *)m.vertex_map, (size_t)nv)) ||
+    if ((rc = r3d_mesh_download(ctx, h_out, m.out, *out_nv, *out_nt)) || (rc = r3d_download(ctx, vertex_map, (const int32_t *)m.vertex_map, (size_t)nv)) ||
         (rc = r3d_download(ctx, triangle_origin, (const int32_t *)m.triangle_origin, (size_t)*out_nt)))
         return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -690,15 +636,15 @@ int r3d_meshtopo_dedup_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d
     R3D_ROCTX_RANGE("r3d_meshtopo_dedup_dev");
     if (!ctx) return R3D_E_BADARG;
     const char *who = "meshtopo_dedup_dev";
-    const MtDedup m = {nv, nt, d_vertices, d_normals, d_colors, d_triangles, flags, cap_vertices, cap_triangles, d_out_vertices, d_out_normals, d_out_colors,
-                       d_out_triangles, d_vertex_map, d_triangle_origin};
+    const MtDedup m = {nv, nt, {d_vertices, d_normals, d_colors, d_triangles}, flags, cap_vertices, cap_triangles,
+                       {d_out_vertices, d_out_normals, d_out_colors, d_out_triangles}, d_vertex_map, d_triangle_origin};
     if (int rc = mt_dedup_args_ok(ctx, who, m, out_nv, out_nt)) return rc;
     {
         const size_t rows = (size_t)nv * 24, orows = (size_t)cap_vertices * 24;
-        const MtSpan out[] = {{d_out_vertices, orows}, {d_out_normals, d_normals ? orows : 0}, {d_out_colors, d_colors ? orows : 0},
-                              {d_out_triangles, (size_t)cap_triangles * 12}, {d_vertex_map, (size_t)nv * 4}, {d_triangle_origin, (size_t)cap_triangles * 4}};
-        const MtSpan in[] = {{d_vertices, rows}, {d_normals, rows}, {d_colors, rows}, {d_triangles, (size_t)nt * 12}};
-        if (int rc = mt_distinct(ctx, who, out, 6, in, 4)) return rc;
+        const r3d_span out[] = {{d_out_vertices, orows}, {d_out_normals, d_normals ? orows : 0}, {d_out_colors, d_colors ? orows : 0},
+                                {d_out_triangles, (size_t)cap_triangles * 12}, {d_vertex_map, (size_t)nv * 4}, {d_triangle_origin, (size_t)cap_triangles * 4}};
+        const r3d_span in[] = {{d_vertices, rows}, {d_normals, rows}, {d_colors, rows}, {d_triangles, (size_t)nt * 12}};
+        if (int rc = r3d_distinct(ctx, who, out, 6, in, 4)) return rc;
     }
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);

@@ -349,8 +349,6 @@ __global__ void __launch_bounds__(256) k_po_mc_triangles(int G, const uint8_t *_
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 constexpr r3d_poisson_params PO_DEFAULTS = {8, 10, 2, 2, 40, 0, 1.1, 4.0, 0.8};
 
-inline unsigned po_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-
 int po_params_ok(r3d_ctx *ctx, const r3d_poisson_params &p) {
     if (p.cycles < 0 || p.pre < 0 || p.post < 0 || p.coarse_sweeps < 0 || !(p.scale > 0.0) || !std::isfinite(p.scale) || !(p.alpha >= 0.0) ||
         !std::isfinite(p.alpha) || !(p.omega > 0.0) || !std::isfinite(p.omega))
@@ -388,10 +386,10 @@ int po_vcycle(r3d_ctx *ctx, std::vector<PoLevel> &lv, size_t l, const r3d_poisso
     int rc;
     if ((rc = po_sweeps(ctx, L, p.pre, p.omega))) return rc;
     const size_t nc = (size_t)(C.G - 2) * (C.G - 2) * (C.G - 2), nf = (size_t)(L.G - 2) * (L.G - 2) * (L.G - 2);
-    k_po_restrict<true><<<po_blocks(nc), 256, 0, ctx->stream>>>(L.G, C.G, L.rhs, L.x, L.diag, C.rhs);
+    k_po_restrict<true><<<r3d_blocks(nc), 256, 0, ctx->stream>>>(L.G, C.G, L.rhs, L.x, L.diag, C.rhs);
     R3D_HIP(ctx, hipMemsetAsync(C.x, 0, (size_t)C.G * C.G * C.G * 8, ctx->stream));
     if ((rc = po_vcycle(ctx, lv, l + 1, p))) return rc;
-    k_po_prolong_add<<<po_blocks(nf), 256, 0, ctx->stream>>>(L.G, C.G, C.x, L.x);
+    k_po_prolong_add<<<r3d_blocks(nf), 256, 0, ctx->stream>>>(L.G, C.G, C.x, L.x);
     R3D_HIP(ctx, hipGetLastError());
     return po_sweeps(ctx, L, p.post, p.omega);
 }
@@ -452,19 +450,19 @@ int po_solve(r3d_ctx *ctx, DevArena &ar, const double *d_xyz, const double *d_nr
     }
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemsetAsync(first, 0xFF, R3 * 4, st));
-    k_po_cell_first<<<po_blocks((size_t)n), 256, 0, st>>>(keys, n, first);
-    k_po_fractions<<<po_blocks((size_t)n), 256, 0, st>>>(g, d_xyz, keys, idx, n, frac);
+    k_po_cell_first<<<r3d_blocks((size_t)n), 256, 0, st>>>(keys, n, first);
+    k_po_fractions<<<r3d_blocks((size_t)n), 256, 0, st>>>(g, d_xyz, keys, idx, n, frac);
 
     // splats
     r3d_prof_mark(ctx, ctx->ws[0], st, "poisson_splats");
-    k_po_gather<1><<<po_blocks(G3), 256, 0, st>>>(g, n, first, keys, idx, frac, d_col, nullptr, F.W0, F.C0);
-    k_po_density<<<po_blocks((size_t)n), 256, 0, st>>>(g, n, keys, idx, frac, F.W0, F.dens, wt_s);
-    k_po_gather<2><<<po_blocks(G3), 256, 0, st>>>(g, n, first, keys, idx, frac, d_nrm, wt_s, F.D, F.V);
+    k_po_gather<1><<<r3d_blocks(G3), 256, 0, st>>>(g, n, first, keys, idx, frac, d_col, nullptr, F.W0, F.C0);
+    k_po_density<<<r3d_blocks((size_t)n), 256, 0, st>>>(g, n, keys, idx, frac, F.W0, F.dens, wt_s);
+    k_po_gather<2><<<r3d_blocks(G3), 256, 0, st>>>(g, n, first, keys, idx, frac, d_nrm, wt_s, F.D, F.V);
 
     // solve: right-hand side, the coarse diagonals, then the cycles.  Both buffers of every level start at zero and a sweep writes
     // interior nodes only, so the faces stay zero.
     r3d_prof_mark(ctx, ctx->ws[0], st, "poisson_solve");
-    k_po_divergence<<<po_blocks(G3), 256, 0, st>>>(G, F.V, F.D, p.alpha, F.b, F.diag);
+    k_po_divergence<<<r3d_blocks(G3), 256, 0, st>>>(G, F.V, F.D, p.alpha, F.b, F.diag);
     R3D_HIP(ctx, hipGetLastError());
     for (size_t l = 0; l < lv.size(); l++) {
         const size_t bytes = (size_t)lv[l].G * lv[l].G * lv[l].G * 8;
@@ -474,7 +472,7 @@ int po_solve(r3d_ctx *ctx, DevArena &ar, const double *d_xyz, const double *d_nr
             const size_t nc = (size_t)(lv[l].G - 2) * (lv[l].G - 2) * (lv[l].G - 2);
             R3D_HIP(ctx, hipMemsetAsync(lv[l].diag, 0, bytes, st));
             R3D_HIP(ctx, hipMemsetAsync(lv[l].rhs, 0, bytes, st));
-            k_po_restrict<false><<<po_blocks(nc), 256, 0, st>>>(lv[l - 1].G, lv[l].G, lv[l - 1].diag, nullptr, nullptr, lv[l].diag);
+            k_po_restrict<false><<<r3d_blocks(nc), 256, 0, st>>>(lv[l - 1].G, lv[l].G, lv[l - 1].diag, nullptr, nullptr, lv[l].diag);
         }
     }
     R3D_HIP(ctx, hipGetLastError());
@@ -503,17 +501,14 @@ int po_mesh_count(r3d_ctx *ctx, DevArena &ar, PoMeshWork &W, int64_t *out_nv, in
     W.offv = (int *)ar.get(G3 * 4);
     W.offt = (int *)ar.get(G3 * 4);
     if (ar.rc) return ar.rc;
-    k_po_mc_cubes<<<po_blocks(G3), 256, 0, st>>>(G, W.chi, W.cube);
-    k_po_mc_count<<<po_blocks(G3), 256, 0, st>>>(G, W.chi, W.cube, W.emask, cntv, cntt);
+    k_po_mc_cubes<<<r3d_blocks(G3), 256, 0, st>>>(G, W.chi, W.cube);
+    k_po_mc_count<<<r3d_blocks(G3), 256, 0, st>>>(G, W.chi, W.cube, W.emask, cntv, cntt);
     R3D_HIP(ctx, hipGetLastError());
     int rc;
     if ((rc = r3d_exclusive_scan_i32(ctx, ar, cntv, W.offv, (int64_t)G3)) || (rc = r3d_exclusive_scan_i32(ctx, ar, cntt, W.offt, (int64_t)G3))) return rc;
     int last[4];
-    R3D_HIP(ctx, hipMemcpyAsync(&last[0], W.offv + G3 - 1, 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(&last[1], cntv + G3 - 1, 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(&last[2], W.offt + G3 - 1, 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(&last[3], cntt + G3 - 1, 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = r3d_read_back(ctx, {{&last[0], W.offv + G3 - 1, 4}, {&last[1], cntv + G3 - 1, 4}, {&last[2], W.offt + G3 - 1, 4}, {&last[3], cntt + G3 - 1, 4}})))
+        return rc;
     *out_nv = W.total[0] = (long long)last[0] + last[1];
     *out_nt = W.total[1] = (long long)last[2] + last[3];
     return R3D_OK;
@@ -521,8 +516,8 @@ int po_mesh_count(r3d_ctx *ctx, DevArena &ar, PoMeshWork &W, int64_t *out_nv, in
 int po_mesh_emit(r3d_ctx *ctx, const PoMeshWork &W, double *d_vert, double *d_dens, double *d_col, int32_t *d_tri) {
     const int G = W.g.G;
     const size_t G3 = (size_t)G * G * G;
-    k_po_mc_vertices<<<po_blocks(G3), 256, 0, ctx->stream>>>(W.g, W.chi, W.W0, W.C0, W.emask, W.offv, d_vert, d_dens, W.C0 ? d_col : nullptr);
-    k_po_mc_triangles<<<po_blocks(G3), 256, 0, ctx->stream>>>(G, W.cube, W.emask, W.offv, W.offt, d_tri);
+    k_po_mc_vertices<<<r3d_blocks(G3), 256, 0, ctx->stream>>>(W.g, W.chi, W.W0, W.C0, W.emask, W.offv, d_vert, d_dens, W.C0 ? d_col : nullptr);
+    k_po_mc_triangles<<<r3d_blocks(G3), 256, 0, ctx->stream>>>(G, W.cube, W.emask, W.offv, W.offt, d_tri);
     R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
 }

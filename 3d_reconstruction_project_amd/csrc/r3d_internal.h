@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <atomic>
 #include <cmath>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -141,6 +142,43 @@ int r3d_download(r3d_ctx *ctx, T *h, const T *d, size_t count) {
 // the refusal of a count / capacity protocol: `have` rows of `what` against the caller's capacity
 static inline int r3d_fits(r3d_ctx *ctx, const char *who, const char *what, int64_t have, int64_t cap) {
     return have <= cap ? R3D_OK : r3d_fail(ctx, R3D_E_BADARG, "%s: %lld %s do not fit a capacity of %lld", who, (long long)have, what, (long long)cap);
+}
+// the same for two quantities that are written together or not at all: one message with both counts when either does not fit
+static inline int r3d_fits2(r3d_ctx *ctx, const char *who, const char *what_a, int64_t have_a, const char *what_b, int64_t have_b, int64_t cap_a,
+                            int64_t cap_b) {
+    if (have_a <= cap_a && have_b <= cap_b) return R3D_OK;
+    return r3d_fail(ctx, R3D_E_BADARG, "%s: %lld %s and %lld %s do not fit capacities of %lld and %lld", who, (long long)have_a, what_a, (long long)have_b,
+                    what_b, (long long)cap_a, (long long)cap_b);
+}
+// small device -> host reads between kernels: the copies in list order on ctx->stream (a null dev: an entry that is not read), then the
+// call's one wait.  A HIP failure here reports this header's line, not the caller's: the entry point's roctx range names the call.
+struct r3d_read { void *host; const void *dev; size_t bytes; };
+static inline int r3d_read_back(r3d_ctx *ctx, std::initializer_list<r3d_read> reads) {
+    for (const r3d_read &r : reads)
+        if (r.dev) R3D_HIP(ctx, hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return R3D_OK;
+}
+
+// 256-thread blocks for n items
+static inline unsigned r3d_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// the _dev forms refuse outputs that overlap an input or one another: a kernel would read rows another thread has already replaced.
+// A null or empty span overlaps nothing; an output is tested against the inputs first, then against the outputs before it.
+struct r3d_span { const void *p; size_t bytes; };
+static inline int r3d_distinct(r3d_ctx *ctx, const char *who, const r3d_span *out, int n_out, const r3d_span *in, int n_in) {
+    auto overlap = [](const r3d_span &a, const r3d_span &b) {
+        if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+        return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+    };
+    for (int i = 0; i < n_out; i++) {
+        for (int j = 0; j < n_in; j++)
+            if (overlap(out[i], in[j])) return r3d_fail(ctx, R3D_E_BADARG, "%s: an output array overlaps an input array", who);
+        for (int j = 0; j < i; j++)
+            if (overlap(out[i], out[j])) return r3d_fail(ctx, R3D_E_BADARG, "%s: two output arrays overlap", who);
+    }
+    return R3D_OK;
 }
 
 // SolveJacobianSystemAndObtainExtrinsicMatrix: x = LDLT(JTJ) \ (-JTr); identity when |det| < det_tol (the registration loop's

@@ -5,7 +5,7 @@
 // Order is what makes the floating-point results unique: a vertex's incidence list holds its corners 3 t + c ascending, its
 // adjacency list its neighbours ascending without repeats, and every sum walks one of the two from the front.  Atomics only count
 // and hand out slots; every segment they fill is sorted afterwards, so their arrival order never reaches a result.
-#include "r3d_internal.h"
+#include "r3d_mesh.h"
 
 #include <climits>
 
@@ -282,40 +282,13 @@ __global__ void __launch_bounds__(256) k_tm_scatter_triangles(const int *__restr
 }
 
 // ====================================================================================================================== host side
-inline unsigned tm_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-int tm_sizes_ok(r3d_ctx *ctx, const char *who, int64_t nv, int64_t nt) {
-    if (nv < 0 || nt < 0) return r3d_fail(ctx, R3D_E_BADARG, "%s: a negative count", who);
-    if (nv > INT32_MAX - 1) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: %lld vertices do not fit int32 indices", who, (long long)nv);
-    if (nt > (int64_t)INT32_MAX / 6) return r3d_fail(ctx, R3D_E_UNSUPPORTED, "%s: 6 x %lld triangles do not fit int32 offsets", who, (long long)nt);
-    if (ctx->poisoned) return r3d_fail(ctx, R3D_E_HIP, "%s: context poisoned by an earlier timed-out call: destroy it", who);
-    return R3D_OK;
-}
-
-// the _dev forms refuse outputs that overlap an input or one another: a kernel would read rows another thread has already replaced
-struct TmSpan { const void *p; size_t bytes; };
-int tm_distinct(r3d_ctx *ctx, const char *who, const TmSpan *out, int n_out, const TmSpan *in, int n_in) {
-    auto overlap = [](const TmSpan &a, const TmSpan &b) {
-        if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-        return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-    };
-    for (int i = 0; i < n_out; i++) {
-        for (int j = 0; j < n_in; j++)
-            if (overlap(out[i], in[j])) return r3d_fail(ctx, R3D_E_BADARG, "%s: an output array overlaps an input array", who);
-        for (int j = 0; j < i; j++)
-            if (overlap(out[i], out[j])) return r3d_fail(ctx, R3D_E_BADARG, "%s: two output arrays overlap", who);
-    }
-    return R3D_OK;
-}
-
 struct TmTopo {
     int *inc_off = nullptr, *inc = nullptr;   // [nv + 1], [3 nt]
     int *adj_off = nullptr, *adj = nullptr;   // [nv + 1], [<= 6 nt]
 };
 
 int tm_sort_segments(r3d_ctx *ctx, const int *off, int nv, const int *long_list, int n_long, int mul, int *data) {
-    k_tm_sort_short<<<tm_blocks(nv), 256, 0, ctx->stream>>>(off, nv, mul, data);
+    k_tm_sort_short<<<r3d_blocks(nv), 256, 0, ctx->stream>>>(off, nv, mul, data);
     if (n_long) k_tm_sort_long<<<(unsigned)n_long, 256, 0, ctx->stream>>>(off, long_list, mul, data);
     R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
@@ -338,17 +311,16 @@ int tm_topology(r3d_ctx *ctx, DevArena &ar, const char *who, int nv, int64_t nt,
     if (ar.rc) return ar.rc;
     R3D_HIP(ctx, hipMemsetAsync(count, 0, (size_t)(nv + 1) * 4 * 2, st));
     R3D_HIP(ctx, hipMemsetAsync(hdr, 0, sizeof(TmHdr), st));
-    if (nt) k_tm_count<<<tm_blocks(n3), 256, 0, st>>>(d_tri, n3, nv, count, hdr);
-    k_tm_classify<<<tm_blocks(nv), 256, 0, st>>>(count, nv, long_list, hdr);
+    if (nt) k_tm_count<<<r3d_blocks(n3), 256, 0, st>>>(d_tri, n3, nv, count, hdr);
+    k_tm_classify<<<r3d_blocks(nv), 256, 0, st>>>(count, nv, long_list, hdr);
     R3D_HIP(ctx, hipGetLastError());
     if (int rc = r3d_exclusive_scan_i32(ctx, ar, count, T.inc_off, (int64_t)nv + 1)) return rc;
     TmHdr h = {};
-    R3D_HIP(ctx, hipMemcpyAsync(&h, hdr, sizeof(TmHdr), hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = r3d_read_back(ctx, {{&h, hdr, sizeof(TmHdr)}})) return rc;
     if (h.bad_index) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, %d)", who, nv);
     if (level == TM_CHECK) return R3D_OK;
     if (nt) {
-        k_tm_fill<<<tm_blocks(n3), 256, 0, st>>>(d_tri, n3, T.inc_off, cursor, T.inc);
+        k_tm_fill<<<r3d_blocks(n3), 256, 0, st>>>(d_tri, n3, T.inc_off, cursor, T.inc);
         if (int rc = tm_sort_segments(ctx, T.inc_off, nv, long_list, h.n_long, 1, T.inc)) return rc;
     }
     if (level == TM_INCIDENCE) return R3D_OK;
@@ -358,14 +330,14 @@ int tm_topology(r3d_ctx *ctx, DevArena &ar, const char *who, int nv, int64_t nt,
     T.adj = (int *)ar.get((size_t)n3 * 2 * 4);
     if (ar.rc) return ar.rc;
     if (nt) {
-        k_tm_candidates<<<tm_blocks(n3), 256, 0, st>>>(d_tri, T.inc, n3, cand);
+        k_tm_candidates<<<r3d_blocks(n3), 256, 0, st>>>(d_tri, T.inc, n3, cand);
         if (int rc = tm_sort_segments(ctx, T.inc_off, nv, long_list, h.n_long, 2, cand)) return rc;
     }
     R3D_HIP(ctx, hipMemsetAsync(adj_cnt + nv, 0, 4, st));
-    k_tm_unique<false><<<tm_blocks(nv), 256, 0, st>>>(T.inc_off, cand, nv, adj_cnt, nullptr, nullptr);
+    k_tm_unique<false><<<r3d_blocks(nv), 256, 0, st>>>(T.inc_off, cand, nv, adj_cnt, nullptr, nullptr);
     R3D_HIP(ctx, hipGetLastError());
     if (int rc = r3d_exclusive_scan_i32(ctx, ar, adj_cnt, T.adj_off, (int64_t)nv + 1)) return rc;
-    k_tm_unique<true><<<tm_blocks(nv), 256, 0, st>>>(T.inc_off, cand, nv, nullptr, T.adj_off, T.adj);
+    k_tm_unique<true><<<r3d_blocks(nv), 256, 0, st>>>(T.inc_off, cand, nv, nullptr, T.adj_off, T.adj);
     R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
 }
@@ -373,13 +345,13 @@ int tm_topology(r3d_ctx *ctx, DevArena &ar, const char *who, int nv, int64_t nt,
 // the lists on the host: the count always, offsets and entries when cap allows
 int tm_lists(r3d_ctx *ctx, const char *who, bool adjacency, int64_t nv, int64_t nt, const int32_t *triangles, int64_t cap, int32_t *offsets, int32_t *list,
              int64_t *out_n) {
-    if (int rc = tm_sizes_ok(ctx, who, nv, nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, who, nv, nt)) return rc;
     if (!out_n || cap < 0 || (nt > 0 && !triangles) || (cap > 0 && (!offsets || !list)))
         return r3d_fail(ctx, R3D_E_BADARG, "%s: a missing array or a negative capacity", who);
     *out_n = 0;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = r3d_mesh_empty_ok(ctx, who, nv, nt)) return rc;
     if (nv == 0) {
-        if (nt) return r3d_fail(ctx, R3D_E_BADARG, "%s: a triangle index outside [0, 0)", who);
         if (cap > 0) offsets[0] = 0;
         return R3D_OK;
     }
@@ -390,8 +362,7 @@ int tm_lists(r3d_ctx *ctx, const char *who, bool adjacency, int64_t nv, int64_t 
     if (int rc = tm_topology(ctx, ar, who, (int)nv, nt, d_tri, adjacency ? TM_ADJACENCY : TM_INCIDENCE, T)) return rc;
     const int *d_off = adjacency ? T.adj_off : T.inc_off, *d_list = adjacency ? T.adj : T.inc;
     int total = 0;
-    R3D_HIP(ctx, hipMemcpyAsync(&total, d_off + nv, 4, hipMemcpyDeviceToHost, ctx->stream));
-    R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = r3d_read_back(ctx, {{&total, d_off + nv, 4}})) return rc;
     *out_n = total;
     if (cap == 0) return R3D_OK;
     if (int rc = r3d_fits(ctx, who, "entries", total, cap)) return rc;
@@ -404,16 +375,15 @@ int tm_lists(r3d_ctx *ctx, const char *who, bool adjacency, int64_t nv, int64_t 
 // ---- smoothing ----------------------------------------------------------------------------------------------------------------------
 struct TmSmooth {
     int64_t nv, nt;
-    const double *pos, *nrm, *col;   // device; nrm / col may be null
-    const int32_t *tri;
+    r3d_mesh_in in;     // device; nrm / col may be null
     int kind, iterations, scope;
     double lambda, mu;
-    double *out_pos, *out_nrm, *out_col;
+    r3d_mesh_out out;   // no triangles
 };
 
 int tm_smooth_args_ok(r3d_ctx *ctx, int64_t nv, int64_t nt, const void *vertices, const void *normals, const void *colors, const void *triangles, int kind,
                       int iterations, double lambda, double mu, int scope, const void *out_vertices, const void *out_normals, const void *out_colors) {
-    if (int rc = tm_sizes_ok(ctx, "trimesh_smooth", nv, nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, "trimesh_smooth", nv, nt)) return rc;
     if (iterations < 0) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_smooth: %d iterations", iterations);
     if (iterations > R3D_SMOOTH_MAX_ITERATIONS)   // every step is a launch
         return r3d_fail(ctx, R3D_E_UNSUPPORTED, "trimesh_smooth: %d iterations, more than %d", iterations, R3D_SMOOTH_MAX_ITERATIONS);
@@ -431,37 +401,35 @@ template <bool LAPLACE, int NA>
 void tm_launch_smooth(hipStream_t st, const TmTopo &T, int nv, double lambda, const double *pos, const double *const src[3], double *const dst[3]) {
     TmAttrs<NA> A;
     for (int a = 0; a < NA; a++) { A.src[a] = src[a]; A.dst[a] = dst[a]; }
-    k_tm_smooth<LAPLACE, NA><<<tm_blocks(nv), 256, 0, st>>>(T.adj_off, T.adj, nv, lambda, pos, A);
+    k_tm_smooth<LAPLACE, NA><<<r3d_blocks(nv), 256, 0, st>>>(T.adj_off, T.adj, nv, lambda, pos, A);
 }
 
 // device arrays in and out.  Step k of S writes the caller's output arrays when S - k is even and arena copies otherwise, so the
 // last step lands in the outputs; the first step reads the inputs.
 int tm_smooth(r3d_ctx *ctx, DevArena &ar, const TmSmooth &m) {
     hipStream_t st = ctx->stream;
-    if (m.nv == 0) {
-        if (m.nt) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_smooth: a triangle index outside [0, 0)");
-        return R3D_OK;
-    }
+    if (int rc = r3d_mesh_empty_ok(ctx, "trimesh_smooth", m.nv, m.nt)) return rc;
+    if (m.nv == 0) return R3D_OK;
     const int nv = (int)m.nv;
     const size_t bytes = (size_t)nv * 24;
     TmTopo T;
-    if (int rc = tm_topology(ctx, ar, "trimesh_smooth", nv, m.nt, m.tri, TM_ADJACENCY, T)) return rc;
+    if (int rc = tm_topology(ctx, ar, "trimesh_smooth", nv, m.nt, m.in.tri, TM_ADJACENCY, T)) return rc;
     // the filtered attributes, positions first
     const bool f_pos = m.scope == R3D_SCOPE_ALL || m.scope == R3D_SCOPE_VERTEX;
-    const bool f_nrm = m.nrm && (m.scope == R3D_SCOPE_ALL || m.scope == R3D_SCOPE_NORMAL);
-    const bool f_col = m.col && (m.scope == R3D_SCOPE_ALL || m.scope == R3D_SCOPE_COLOR);
+    const bool f_nrm = m.in.nrm && (m.scope == R3D_SCOPE_ALL || m.scope == R3D_SCOPE_NORMAL);
+    const bool f_col = m.in.col && (m.scope == R3D_SCOPE_ALL || m.scope == R3D_SCOPE_COLOR);
     const double *in[3] = {};
     double *out[3] = {}, *tmp[3] = {};
     int na = 0;
-    if (f_pos) { in[na] = m.pos; out[na++] = m.out_pos; }
-    if (f_nrm) { in[na] = m.nrm; out[na++] = m.out_nrm; }
-    if (f_col) { in[na] = m.col; out[na++] = m.out_col; }
+    if (f_pos) { in[na] = m.in.pos; out[na++] = m.out.pos; }
+    if (f_nrm) { in[na] = m.in.nrm; out[na++] = m.out.nrm; }
+    if (f_col) { in[na] = m.in.col; out[na++] = m.out.col; }
     const int steps = m.kind == R3D_SMOOTH_TAUBIN ? 2 * m.iterations : m.iterations;   // at most 2 R3D_SMOOTH_MAX_ITERATIONS
     const bool filtering = steps > 0 && na > 0;
     // what is not filtered is copied
-    if (!(filtering && f_pos)) R3D_HIP(ctx, hipMemcpyAsync(m.out_pos, m.pos, bytes, hipMemcpyDeviceToDevice, st));
-    if (m.nrm && !(filtering && f_nrm)) R3D_HIP(ctx, hipMemcpyAsync(m.out_nrm, m.nrm, bytes, hipMemcpyDeviceToDevice, st));
-    if (m.col && !(filtering && f_col)) R3D_HIP(ctx, hipMemcpyAsync(m.out_col, m.col, bytes, hipMemcpyDeviceToDevice, st));
+    if (!(filtering && f_pos)) R3D_HIP(ctx, hipMemcpyAsync(m.out.pos, m.in.pos, bytes, hipMemcpyDeviceToDevice, st));
+    if (m.in.nrm && !(filtering && f_nrm)) R3D_HIP(ctx, hipMemcpyAsync(m.out.nrm, m.in.nrm, bytes, hipMemcpyDeviceToDevice, st));
+    if (m.in.col && !(filtering && f_col)) R3D_HIP(ctx, hipMemcpyAsync(m.out.col, m.in.col, bytes, hipMemcpyDeviceToDevice, st));
     if (!filtering) return R3D_OK;
     if (steps > 1) {
         for (int a = 0; a < na; a++) tmp[a] = (double *)ar.get(bytes);
@@ -470,7 +438,7 @@ int tm_smooth(r3d_ctx *ctx, DevArena &ar, const TmSmooth &m) {
     const double *src[3] = {in[0], in[1], in[2]};
     for (int k = 1; k <= steps; k++) {
         double *const *dst = (steps - k) % 2 == 0 ? out : tmp;
-        const double *pos = f_pos ? src[0] : m.pos;   // the positions this step starts from
+        const double *pos = f_pos ? src[0] : m.in.pos;   // the positions this step starts from
         const double lam = m.kind == R3D_SMOOTH_TAUBIN && k % 2 == 0 ? m.mu : m.lambda;
         if (m.kind == R3D_SMOOTH_SIMPLE) {
             if (na == 1) tm_launch_smooth<false, 1>(st, T, nv, lam, pos, src, dst);
@@ -489,7 +457,7 @@ int tm_smooth(r3d_ctx *ctx, DevArena &ar, const TmSmooth &m) {
 
 // ---- normals ------------------------------------------------------------------------------------------------------------------------
 int tm_normals_args_ok(r3d_ctx *ctx, int64_t nv, int64_t nt, const void *vertices, const void *triangles, int flags) {
-    if (int rc = tm_sizes_ok(ctx, "trimesh_normals", nv, nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, "trimesh_normals", nv, nt)) return rc;
     if (flags & ~R3D_NORMALS_RAW) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_normals: unknown flags %d", flags);
     if ((nv > 0 && !vertices) || (nt > 0 && !triangles)) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_normals: a missing array");
     return R3D_OK;
@@ -497,15 +465,13 @@ int tm_normals_args_ok(r3d_ctx *ctx, int64_t nv, int64_t nt, const void *vertice
 
 int tm_normals(r3d_ctx *ctx, DevArena &ar, int64_t nv, int64_t nt, const double *d_pos, const int32_t *d_tri, int flags, double *d_tn, double *d_vn) {
     hipStream_t st = ctx->stream;
-    if (nv == 0) {
-        if (nt) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_normals: a triangle index outside [0, 0)");
-        return R3D_OK;
-    }
+    if (int rc = r3d_mesh_empty_ok(ctx, "trimesh_normals", nv, nt)) return rc;
+    if (nv == 0) return R3D_OK;
     TmTopo T;   // triangle normals alone need the index check, not the lists
     if (int rc = tm_topology(ctx, ar, "trimesh_normals", (int)nv, nt, d_tri, d_vn ? TM_INCIDENCE : TM_CHECK, T)) return rc;
     const int raw = flags & R3D_NORMALS_RAW;
-    if (d_tn && nt) k_tm_triangle_normals<<<tm_blocks(nt), 256, 0, st>>>(d_pos, d_tri, nt, raw, d_tn);
-    if (d_vn) k_tm_vertex_normals<<<tm_blocks(nv), 256, 0, st>>>(d_pos, d_tri, T.inc_off, T.inc, (int)nv, raw, d_vn);
+    if (d_tn && nt) k_tm_triangle_normals<<<r3d_blocks(nt), 256, 0, st>>>(d_pos, d_tri, nt, raw, d_tn);
+    if (d_vn) k_tm_vertex_normals<<<r3d_blocks(nv), 256, 0, st>>>(d_pos, d_tri, T.inc_off, T.inc, (int)nv, raw, d_vn);
     R3D_HIP(ctx, hipGetLastError());
     return R3D_OK;
 }
@@ -513,21 +479,19 @@ int tm_normals(r3d_ctx *ctx, DevArena &ar, int64_t nv, int64_t nt, const double 
 // ---- compaction ---------------------------------------------------------------------------------------------------------------------
 struct TmCompact {
     int64_t nv, nt;
-    const double *pos, *nrm, *col;
-    const int32_t *tri;
+    r3d_mesh_in in;
     const uint8_t *vkeep, *tkeep;
     int flags;
     int64_t cap_v, cap_t;
-    double *out_pos, *out_nrm, *out_col;
-    int32_t *out_tri;
+    r3d_mesh_out out;
 };
 constexpr int TM_COMPACT_FLAGS = R3D_COMPACT_DROP_DEGENERATE | R3D_COMPACT_DROP_UNREFERENCED | R3D_COMPACT_DROP_NON_FINITE;
 
 int tm_compact_args_ok(r3d_ctx *ctx, const TmCompact &m, const void *out_nv, const void *out_nt) {
-    if (int rc = tm_sizes_ok(ctx, "trimesh_compact", m.nv, m.nt)) return rc;
+    if (int rc = r3d_mesh_sizes_ok(ctx, "trimesh_compact", m.nv, m.nt)) return rc;
     if (m.flags & ~TM_COMPACT_FLAGS) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_compact: unknown flags %d", m.flags);
-    if (!out_nv || !out_nt || m.cap_v < 0 || m.cap_t < 0 || (m.nv > 0 && !m.pos) || (m.nt > 0 && !m.tri) ||
-        (m.cap_v > 0 && (!m.out_pos || (m.nrm && !m.out_nrm) || (m.col && !m.out_col))) || (m.cap_t > 0 && !m.out_tri))
+    if (!out_nv || !out_nt || m.cap_v < 0 || m.cap_t < 0 || (m.nv > 0 && !m.in.pos) || (m.nt > 0 && !m.in.tri) ||
+        (m.cap_v > 0 && (!m.out.pos || (m.in.nrm && !m.out.nrm) || (m.in.col && !m.out.col))) || (m.cap_t > 0 && !m.out.tri))
         return r3d_fail(ctx, R3D_E_BADARG, "trimesh_compact: a missing array or a negative capacity");
     return R3D_OK;
 }
@@ -537,10 +501,8 @@ int tm_compact(r3d_ctx *ctx, DevArena &ar, const TmCompact &m, int64_t *out_nv, 
     hipStream_t st = ctx->stream;
     *out_nv = *out_nt = 0;
     *wrote = false;
-    if (m.nv == 0) {
-        if (m.nt) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_compact: a triangle index outside [0, 0)");
-        return R3D_OK;
-    }
+    if (int rc = r3d_mesh_empty_ok(ctx, "trimesh_compact", m.nv, m.nt)) return rc;
+    if (m.nv == 0) return R3D_OK;
     const int nv = (int)m.nv;
     const int64_t nt = m.nt;
     int *gone = (int *)ar.get((size_t)nv * 4);
@@ -553,31 +515,26 @@ int tm_compact(r3d_ctx *ctx, DevArena &ar, const TmCompact &m, int64_t *out_nv, 
     R3D_HIP(ctx, hipMemsetAsync(vkeep + nv, 0, 4, st));
     R3D_HIP(ctx, hipMemsetAsync(tkeep + nt, 0, 4, st));
     R3D_HIP(ctx, hipMemsetAsync(hdr, 0, sizeof(TmHdr), st));
-    k_tm_vertex_gone<<<tm_blocks(nv), 256, 0, st>>>(m.pos, m.vkeep, nv, m.flags & R3D_COMPACT_DROP_NON_FINITE, gone);
-    if (nt) k_tm_triangle_keep<<<tm_blocks(nt), 256, 0, st>>>(m.tri, m.tkeep, nt, nv, m.flags & R3D_COMPACT_DROP_DEGENERATE, gone, tkeep, ref, hdr);
-    k_tm_vertex_keep<<<tm_blocks(nv), 256, 0, st>>>(gone, ref, nv, m.flags & R3D_COMPACT_DROP_UNREFERENCED, vkeep);
+    k_tm_vertex_gone<<<r3d_blocks(nv), 256, 0, st>>>(m.in.pos, m.vkeep, nv, m.flags & R3D_COMPACT_DROP_NON_FINITE, gone);
+    if (nt) k_tm_triangle_keep<<<r3d_blocks(nt), 256, 0, st>>>(m.in.tri, m.tkeep, nt, nv, m.flags & R3D_COMPACT_DROP_DEGENERATE, gone, tkeep, ref, hdr);
+    k_tm_vertex_keep<<<r3d_blocks(nv), 256, 0, st>>>(gone, ref, nv, m.flags & R3D_COMPACT_DROP_UNREFERENCED, vkeep);
     R3D_HIP(ctx, hipGetLastError());
     int rc;
     if ((rc = r3d_exclusive_scan_i32(ctx, ar, vkeep, vmap, (int64_t)nv + 1)) || (rc = r3d_exclusive_scan_i32(ctx, ar, tkeep, tmap, nt + 1))) return rc;
     TmHdr h = {};
     int kept_v = 0, kept_t = 0;
-    R3D_HIP(ctx, hipMemcpyAsync(&h, hdr, sizeof(TmHdr), hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(&kept_v, vmap + nv, 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipMemcpyAsync(&kept_t, tmap + nt, 4, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipStreamSynchronize(st));
+    if ((rc = r3d_read_back(ctx, {{&h, hdr, sizeof(TmHdr)}, {&kept_v, vmap + nv, 4}, {&kept_t, tmap + nt, 4}}))) return rc;
     if (h.bad_index) return r3d_fail(ctx, R3D_E_BADARG, "trimesh_compact: a triangle index outside [0, %d)", nv);
     *out_nv = kept_v;
     *out_nt = kept_t;
     if (m.cap_v == 0 && m.cap_t == 0) return R3D_OK;
-    if (m.cap_v < kept_v || m.cap_t < kept_t)
-        return r3d_fail(ctx, R3D_E_BADARG, "trimesh_compact: %d vertices and %d triangles do not fit capacities of %lld and %lld", kept_v, kept_t,
-                        (long long)m.cap_v, (long long)m.cap_t);
+    if ((rc = r3d_fits2(ctx, "trimesh_compact", "vertices", kept_v, "triangles", kept_t, m.cap_v, m.cap_t))) return rc;
     if (kept_v) {
-        k_tm_scatter_rows<<<tm_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.pos, m.out_pos);
-        if (m.nrm) k_tm_scatter_rows<<<tm_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.nrm, m.out_nrm);
-        if (m.col) k_tm_scatter_rows<<<tm_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.col, m.out_col);
+        k_tm_scatter_rows<<<r3d_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.in.pos, m.out.pos);
+        if (m.in.nrm) k_tm_scatter_rows<<<r3d_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.in.nrm, m.out.nrm);
+        if (m.in.col) k_tm_scatter_rows<<<r3d_blocks(nv), 256, 0, st>>>(vkeep, vmap, nv, m.in.col, m.out.col);
     }
-    if (kept_t) k_tm_scatter_triangles<<<tm_blocks(nt), 256, 0, st>>>(tkeep, tmap, vmap, m.tri, nt, m.out_tri);
+    if (kept_t) k_tm_scatter_triangles<<<r3d_blocks(nt), 256, 0, st>>>(tkeep, tmap, vmap, m.in.tri, nt, m.out.tri);
     R3D_HIP(ctx, hipGetLastError());
     *wrote = true;
     return R3D_OK;
@@ -608,20 +565,13 @@ int r3d_trimesh_smooth(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *verti
         return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    const size_t n3 = (size_t)nv * 3;
-    TmSmooth m = {nv, nt, nullptr, nullptr, nullptr, nullptr, kind, iterations, scope, lambda, mu, nullptr, nullptr, nullptr};
+    TmSmooth m = {nv, nt, {}, kind, iterations, scope, lambda, mu, {}};
     int rc;
-    if ((rc = r3d_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = r3d_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = r3d_upload(ctx, ar, colors, n3, &m.col)) ||
-        (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)))
-        return rc;
-    m.out_pos = (double *)ar.get(n3 * 8);
-    m.out_nrm = normals ? (double *)ar.get(n3 * 8) : nullptr;
-    m.out_col = colors ? (double *)ar.get(n3 * 8) : nullptr;
+    if ((rc = r3d_mesh_upload(ctx, ar, {vertices, normals, colors, triangles}, nv, nt, &m.in))) return rc;
+    r3d_mesh_outputs(ar, m.in, nv, nt, false, &m.out);
     if (ar.rc) return ar.rc;
     if ((rc = tm_smooth(ctx, ar, m))) return rc;
-    if ((rc = r3d_download(ctx, out_vertices, m.out_pos, n3)) || (rc = r3d_download(ctx, out_normals, m.out_nrm, normals ? n3 : 0)) ||
-        (rc = r3d_download(ctx, out_colors, m.out_col, colors ? n3 : 0)))
-        return rc;
+    if ((rc = r3d_mesh_download(ctx, {out_vertices, out_normals, out_colors, nullptr}, m.out, nv, 0))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -636,13 +586,14 @@ int r3d_trimesh_smooth_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *d
         return rc;
     {
         const size_t rows = (size_t)nv * 24;
-        const TmSpan out[] = {{d_out_vertices, rows}, {d_out_normals, d_normals ? rows : 0}, {d_out_colors, d_colors ? rows : 0}};
-        const TmSpan in[] = {{d_vertices, rows}, {d_normals, rows}, {d_colors, rows}, {d_triangles, (size_t)nt * 12}};
-        if (int rc = tm_distinct(ctx, "trimesh_smooth_dev", out, 3, in, 4)) return rc;
+        const r3d_span out[] = {{d_out_vertices, rows}, {d_out_normals, d_normals ? rows : 0}, {d_out_colors, d_colors ? rows : 0}};
+        const r3d_span in[] = {{d_vertices, rows}, {d_normals, rows}, {d_colors, rows}, {d_triangles, (size_t)nt * 12}};
+        if (int rc = r3d_distinct(ctx, "trimesh_smooth_dev", out, 3, in, 4)) return rc;
     }
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    const TmSmooth m = {nv, nt, d_vertices, d_normals, d_colors, d_triangles, kind, iterations, scope, lambda, mu, d_out_vertices, d_out_normals, d_out_colors};
+    const TmSmooth m = {nv, nt, {d_vertices, d_normals, d_colors, d_triangles}, kind, iterations, scope, lambda, mu,
+                        {d_out_vertices, d_out_normals, d_out_colors, nullptr}};
     if (int rc = tm_smooth(ctx, ar, m)) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the steps read arena buffers the next call may hand out again
     return R3D_OK;
@@ -655,14 +606,13 @@ int r3d_trimesh_normals(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vert
     if (int rc = tm_normals_args_ok(ctx, nv, nt, vertices, triangles, flags)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    const double *d_pos;
-    const int32_t *d_tri;
+    r3d_mesh_in d;
     int rc;
-    if ((rc = r3d_upload(ctx, ar, vertices, (size_t)nv * 3, &d_pos)) || (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &d_tri))) return rc;
+    if ((rc = r3d_mesh_upload(ctx, ar, {vertices, nullptr, nullptr, triangles}, nv, nt, &d))) return rc;
     double *d_tn = triangle_normals ? (double *)ar.get((size_t)nt * 24) : nullptr;
     double *d_vn = vertex_normals ? (double *)ar.get((size_t)nv * 24) : nullptr;
     if (ar.rc) return ar.rc;
-    if ((rc = tm_normals(ctx, ar, nv, nt, d_pos, d_tri, flags, d_tn, d_vn))) return rc;
+    if ((rc = tm_normals(ctx, ar, nv, nt, d.pos, d.tri, flags, d_tn, d_vn))) return rc;
     if ((rc = r3d_download(ctx, triangle_normals, d_tn, (size_t)nt * 3)) || (rc = r3d_download(ctx, vertex_normals, d_vn, (size_t)nv * 3))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
@@ -674,9 +624,9 @@ int r3d_trimesh_normals_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *
     if (!ctx) return R3D_E_BADARG;
     if (int rc = tm_normals_args_ok(ctx, nv, nt, d_vertices, d_triangles, flags)) return rc;
     {
-        const TmSpan out[] = {{d_triangle_normals, (size_t)nt * 24}, {d_vertex_normals, (size_t)nv * 24}};
-        const TmSpan in[] = {{d_vertices, (size_t)nv * 24}, {d_triangles, (size_t)nt * 12}};
-        if (int rc = tm_distinct(ctx, "trimesh_normals_dev", out, 2, in, 2)) return rc;
+        const r3d_span out[] = {{d_triangle_normals, (size_t)nt * 24}, {d_vertex_normals, (size_t)nv * 24}};
+        const r3d_span in[] = {{d_vertices, (size_t)nv * 24}, {d_triangles, (size_t)nt * 12}};
+        if (int rc = r3d_distinct(ctx, "trimesh_normals_dev", out, 2, in, 2)) return rc;
     }
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
@@ -690,30 +640,22 @@ int r3d_trimesh_compact(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *vert
                         double *out_vertices, double *out_normals, double *out_colors, int32_t *out_triangles, int64_t *out_nv, int64_t *out_nt) {
     R3D_ROCTX_RANGE("r3d_trimesh_compact");
     if (!ctx) return R3D_E_BADARG;
-    TmCompact m = {nv, nt, vertices, normals, colors, triangles, vertex_keep, triangle_keep, flags, cap_vertices, cap_triangles,
-                   out_vertices, out_normals, out_colors, out_triangles};
+    const r3d_mesh_in h_in = {vertices, normals, colors, triangles};
+    const r3d_mesh_out h_out = {out_vertices, out_normals, out_colors, out_triangles};
+    TmCompact m = {nv, nt, h_in, vertex_keep, triangle_keep, flags, cap_vertices, cap_triangles, h_out};
     if (int rc = tm_compact_args_ok(ctx, m, out_nv, out_nt)) return rc;
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);
-    const size_t n3 = (size_t)nv * 3;
     int rc;
-    if ((rc = r3d_upload(ctx, ar, vertices, n3, &m.pos)) || (rc = r3d_upload(ctx, ar, normals, n3, &m.nrm)) || (rc = r3d_upload(ctx, ar, colors, n3, &m.col)) ||
-        (rc = r3d_upload(ctx, ar, triangles, (size_t)nt * 3, &m.tri)) || (rc = r3d_upload(ctx, ar, vertex_keep, (size_t)nv, &m.vkeep)) ||
+    if ((rc = r3d_mesh_upload(ctx, ar, h_in, nv, nt, &m.in)) || (rc = r3d_upload(ctx, ar, vertex_keep, (size_t)nv, &m.vkeep)) ||
         (rc = r3d_upload(ctx, ar, triangle_keep, (size_t)nt, &m.tkeep)))
         return rc;
-    // device outputs as large as the inputs: the counts are not known yet
-    m.out_pos = (double *)ar.get(n3 * 8);
-    m.out_nrm = normals ? (double *)ar.get(n3 * 8) : nullptr;
-    m.out_col = colors ? (double *)ar.get(n3 * 8) : nullptr;
-    m.out_tri = (int32_t *)ar.get((size_t)nt * 12);
+    r3d_mesh_outputs(ar, m.in, nv, nt, true, &m.out);
     if (ar.rc) return ar.rc;
     bool wrote = false;
     if ((rc = tm_compact(ctx, ar, m, out_nv, out_nt, &wrote))) return rc;
     if (!wrote) return R3D_OK;
-    const size_t k3 = (size_t)*out_nv * 3;
-    if ((rc = r3d_download(ctx, out_vertices, m.out_pos, k3)) || (rc = r3d_download(ctx, out_normals, m.out_nrm, normals ? k3 : 0)) ||
-        (rc = r3d_download(ctx, out_colors, m.out_col, colors ? k3 : 0)) || (rc = r3d_download(ctx, out_triangles, m.out_tri, (size_t)*out_nt * 3)))
-        return rc;
+    if ((rc = r3d_mesh_download(ctx, h_out, m.out, *out_nv, *out_nt))) return rc;
     R3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return R3D_OK;
 }
@@ -724,16 +666,16 @@ int r3d_trimesh_compact_dev(r3d_ctx *ctx, int64_t nv, int64_t nt, const double *
                             int64_t *out_nv, int64_t *out_nt) {
     R3D_ROCTX_RANGE("r3d_trimesh_compact_dev");
     if (!ctx) return R3D_E_BADARG;
-    const TmCompact m = {nv, nt, d_vertices, d_normals, d_colors, d_triangles, d_vertex_keep, d_triangle_keep, flags, cap_vertices, cap_triangles,
-                         d_out_vertices, d_out_normals, d_out_colors, d_out_triangles};
+    const TmCompact m = {nv, nt, {d_vertices, d_normals, d_colors, d_triangles}, d_vertex_keep, d_triangle_keep, flags, cap_vertices, cap_triangles,
+                         {d_out_vertices, d_out_normals, d_out_colors, d_out_triangles}};
     if (int rc = tm_compact_args_ok(ctx, m, out_nv, out_nt)) return rc;
     {
         const size_t rows = (size_t)nv * 24, orows = (size_t)cap_vertices * 24;
-        const TmSpan out[] = {{d_out_vertices, orows}, {d_out_normals, d_normals ? orows : 0}, {d_out_colors, d_colors ? orows : 0},
-                              {d_out_triangles, (size_t)cap_triangles * 12}};
-        const TmSpan in[] = {{d_vertices, rows}, {d_normals, rows}, {d_colors, rows}, {d_triangles, (size_t)nt * 12}, {d_vertex_keep, (size_t)nv},
-                             {d_triangle_keep, (size_t)nt}};
-        if (int rc = tm_distinct(ctx, "trimesh_compact_dev", out, 4, in, 6)) return rc;
+        const r3d_span out[] = {{d_out_vertices, orows}, {d_out_normals, d_normals ? orows : 0}, {d_out_colors, d_colors ? orows : 0},
+                                {d_out_triangles, (size_t)cap_triangles * 12}};
+        const r3d_span in[] = {{d_vertices, rows}, {d_normals, rows}, {d_colors, rows}, {d_triangles, (size_t)nt * 12}, {d_vertex_keep, (size_t)nv},
+                               {d_triangle_keep, (size_t)nt}};
+        if (int rc = r3d_distinct(ctx, "trimesh_compact_dev", out, 4, in, 6)) return rc;
     }
     R3D_HIP(ctx, hipSetDevice(ctx->device));
     DevArena ar(ctx);

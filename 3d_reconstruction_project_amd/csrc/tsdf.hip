@@ -841,8 +841,7 @@ int tsdf_extract_count(r3d_tsdf *v, DevArena &ar, TsdfExtractWork &W, int64_t *o
     k_tsdf_extract<false, false><<<(unsigned)n, 256, 0, st>>>(tsdf_view(v), (const int *)v->order.p, (const unsigned long long *)v->unit_keys.p, W.thread_off, W.unit_cnt, nullptr, nullptr, nullptr, nullptr);
     k_tsdf_unit_offsets<<<1, 256, 0, st>>>(W.unit_cnt, n, W.unit_off, d_total);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(&W.total, d_total, 8, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = r3d_read_back(ctx, {{&W.total, d_total, 8}})) return rc;
     *out_n = W.total;
     return R3D_OK;
 }
@@ -889,8 +888,7 @@ int tsdf_mesh_count(r3d_tsdf *v, DevArena &ar, TsdfMeshWork &W, int64_t *out_nv,
     k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt, n, W.unit_off, d_total);
     k_tsdf_unit_offsets<<<1, 256, 0, st>>>(unit_cnt + n, n, W.unit_off + n, d_total + 1);
     R3D_HIP(ctx, hipGetLastError());
-    R3D_HIP(ctx, hipMemcpyAsync(W.total, d_total, 16, hipMemcpyDeviceToHost, st));
-    R3D_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = r3d_read_back(ctx, {{W.total, d_total, 16}})) return rc;
     *out_nv = W.total[0]; *out_nt = W.total[1];
     if (W.total[0] > INT32_MAX || W.total[1] > INT32_MAX)
         return r3d_fail(ctx, R3D_E_UNSUPPORTED, "mesh_from_volume: %lld vertices and %lld triangles do not fit int32 indices", W.total[0], W.total[1]);
@@ -898,9 +896,7 @@ int tsdf_mesh_count(r3d_tsdf *v, DevArena &ar, TsdfMeshWork &W, int64_t *out_nv,
 }
 // the capacity refusal of a non-empty mesh, then the emitting half's scratch: it comes ahead of any arena outputs of the caller
 int tsdf_mesh_fits(r3d_ctx *ctx, DevArena &ar, TsdfMeshWork &W, int64_t cap_v, int64_t cap_t) {
-    if (cap_v < W.total[0] || cap_t < W.total[1])
-        return r3d_fail(ctx, R3D_E_BADARG, "mesh_from_volume: %lld vertices and %lld triangles do not fit capacities of %lld and %lld", W.total[0],
-                        W.total[1], (long long)cap_v, (long long)cap_t);
+    if (int rc = r3d_fits2(ctx, "mesh_from_volume", "vertices", W.total[0], "triangles", W.total[1], cap_v, cap_t)) return rc;
     W.vid = (int32_t *)ar.get((size_t)W.n * TSDF_UNIT * 12);
     return ar.rc;
 }

@@ -42,8 +42,7 @@ _lib.register({
 })
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+_ptr = _lib.ptr
 
 
 def _rows(a, n=None, name="array"):
@@ -69,18 +68,17 @@ def _mask(m, n, name):
     return m
 
 
+def _mesh_rows(kv, kt, nrm, col):
+    """empty output arrays of a clean-up in the entry points' order: vertices, normals and colours (None where the input has none), triangles"""
+    return (np.empty((kv, 3)), np.empty((kv, 3)) if nrm is not None else None, np.empty((kv, 3)) if col is not None else None,
+            np.empty((kt, 3), np.int32))
+
+
 def _lists(entry, n_vertices, triangles, ctx):
     ctx = ctx or _lib.default_context()
     tri = _tri(triangles)
-    nv, nt = int(n_vertices), len(tri)
-    n = ctypes.c_int64()
-    ctx.call(entry, nv, nt, _ptr(tri), 0, None, None, ctypes.byref(n))
-    off, lst = np.zeros(nv + 1, np.int32), np.empty(n.value, np.int32)
-    if n.value:
-        got = ctypes.c_int64()
-        ctx.call(entry, nv, nt, _ptr(tri), n.value, _ptr(off), _ptr(lst), ctypes.byref(got))
-        assert got.value == n.value
-    return off, lst
+    nv = int(n_vertices)
+    return ctx.count_then_fill(entry, (nv, len(tri), _ptr(tri)), 2, lambda n: (np.zeros(nv + 1, np.int32), np.empty(n, np.int32)))[1]
 
 
 def incidence(n_vertices, triangles, ctx=None):
@@ -160,16 +158,8 @@ def compact(vertices, triangles, flags=0, vertex_keep=None, triangle_keep=None, 
     nv, nt = len(vert), len(tri)
     nrm, col = _rows(normals, nv, "normals"), _rows(colors, nv, "colors")
     vk, tk = _mask(vertex_keep, nv, "vertex_keep"), _mask(triangle_keep, nt, "triangle_keep")
-    kv, kt = ctypes.c_int64(), ctypes.c_int64()
     args = (nv, nt, _ptr(vert), _ptr(nrm), _ptr(col), _ptr(tri), _ptr(vk), _ptr(tk), int(flags))
-    ctx.call("r3d_trimesh_compact", *args, 0, 0, None, None, None, None, ctypes.byref(kv), ctypes.byref(kt))
-    ov, ot = np.empty((kv.value, 3)), np.empty((kt.value, 3), np.int32)
-    on = np.empty((kv.value, 3)) if nrm is not None else None
-    oc = np.empty((kv.value, 3)) if col is not None else None
-    if kv.value or kt.value:
-        gv, gt = ctypes.c_int64(), ctypes.c_int64()
-        ctx.call("r3d_trimesh_compact", *args, kv.value, kt.value, _ptr(ov), _ptr(on), _ptr(oc), _ptr(ot), ctypes.byref(gv), ctypes.byref(gt))
-        assert (gv.value, gt.value) == (kv.value, kt.value)
+    _, (ov, on, oc, ot) = ctx.count_then_fill("r3d_trimesh_compact", args, 4, lambda kv, kt: _mesh_rows(kv, kt, nrm, col), n_counts=2)
     return ov, ot, on, oc
 
 
@@ -246,18 +236,12 @@ def dedup(vertices, triangles, flags=DEDUP_VERTICES | DEDUP_TRIANGLES, normals=N
     vert, tri = _rows(vertices), _tri(triangles)
     nv, nt = len(vert), len(tri)
     nrm, col = _rows(normals, nv, "normals"), _rows(colors, nv, "colors")
-    kv, kt = ctypes.c_int64(), ctypes.c_int64()
     args = (nv, nt, _ptr(vert), _ptr(nrm), _ptr(col), _ptr(tri), int(flags))
-    ctx.call("r3d_meshtopo_dedup", *args, 0, 0, None, None, None, None, None, None, ctypes.byref(kv), ctypes.byref(kt))
-    ov, ot = np.empty((kv.value, 3)), np.empty((kt.value, 3), np.int32)
-    on = np.empty((kv.value, 3)) if nrm is not None else None
-    oc = np.empty((kv.value, 3)) if col is not None else None
-    vmap, origin = np.empty(nv, np.int32), np.empty(kt.value, np.int32)
-    if kv.value or kt.value:
-        gv, gt = ctypes.c_int64(), ctypes.c_int64()
-        ctx.call("r3d_meshtopo_dedup", *args, kv.value, kt.value, _ptr(ov), _ptr(on), _ptr(oc), _ptr(ot), _ptr(vmap), _ptr(origin), ctypes.byref(gv),
-                 ctypes.byref(gt))
-        assert (gv.value, gt.value) == (kv.value, kt.value)
+
+    def outputs(kv, kt):
+        return _mesh_rows(kv, kt, nrm, col) + (np.empty(nv, np.int32), np.empty(kt, np.int32))
+
+    _, (ov, on, oc, ot, vmap, origin) = ctx.count_then_fill("r3d_meshtopo_dedup", args, 6, outputs, n_counts=2)
     return ov, ot, on, oc, vmap, origin
 
 

@@ -31,8 +31,7 @@ def poisson_params(depth=8, cycles=10, pre=2, post=2, coarse_sweeps=40, scale=1.
     return PoissonParams(int(depth), int(cycles), int(pre), int(post), int(coarse_sweeps), 0, float(scale), float(alpha), float(omega))
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+_ptr = _lib.ptr
 
 
 def _rows(a, n=None, name="array"):

@@ -64,8 +64,7 @@ def posegraph_params(criteria=None, option=None, trace_capacity=0):
                            int(trace_capacity))
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+_ptr = _lib.ptr
 
 
 def _refuse(msg):

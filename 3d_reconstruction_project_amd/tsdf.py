@@ -56,8 +56,7 @@ def tsdf_params(voxel_length, sdf_trunc, color_type=TSDFVolumeColorType.RGB8, vo
                       int(initial_units))
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+_ptr = _lib.ptr
 
 
 def _extrinsic(extrinsic):
@@ -150,14 +149,11 @@ class ScalableTSDFVolume:
 
     def extract_arrays(self):
         """-> points, normals, colours (None without colour) as float64 [n,3]"""
-        n = self.point_count()
-        xyz, nrm = np.empty((n, 3)), np.empty((n, 3))
-        col = np.empty((n, 3)) if self.has_color else None
-        if n:
-            got = ctypes.c_int64()
-            self.ctx.call("r3d_tsdf_extract_point_cloud", self._h, n, _ptr(xyz), _ptr(nrm), _ptr(col), ctypes.byref(got))
-            assert got.value == n
-        return xyz, nrm, col
+        def outputs(n):
+            return np.empty((n, 3)), np.empty((n, 3)), np.empty((n, 3)) if self.has_color else None
+
+        _, arrays = self.ctx.count_then_fill("r3d_tsdf_extract_point_cloud", (self._h,), 3, outputs)
+        return arrays
 
     def extract_point_cloud(self):
         xyz, nrm, col = self.extract_arrays()
@@ -179,13 +175,10 @@ class ScalableTSDFVolume:
     def extract_triangle_mesh(self):
         """volume.extract_triangle_mesh(): marching cubes on the device -> TriangleMesh (no vertex normals, as in Open3D: call
         compute_vertex_normals()); vertices and triangles in this package's order ("Triangle mesh")"""
-        nv, nt = self.mesh_counts()
-        vert, tri = np.empty((nv, 3)), np.empty((nt, 3), np.int32)
-        col = np.empty((nv, 3)) if self.has_color else None
-        if nv:
-            gv, gt = ctypes.c_int64(), ctypes.c_int64()
-            self.ctx.call("r3d_mesh_from_volume", self._h, nv, nt, _ptr(vert), _ptr(col), _ptr(tri), ctypes.byref(gv), ctypes.byref(gt))
-            assert (gv.value, gt.value) == (nv, nt)
+        def outputs(nv, nt):
+            return np.empty((nv, 3)), np.empty((nv, 3)) if self.has_color else None, np.empty((nt, 3), np.int32)
+
+        _, (vert, col, tri) = self.ctx.count_then_fill("r3d_mesh_from_volume", (self._h,), 3, outputs, n_counts=2)
         return TriangleMesh(vert, tri, col)
 
     def extract_mesh_device(self, d_vertices, d_colors, d_triangles, cap_vertices, cap_triangles):
@@ -213,15 +206,12 @@ class ScalableTSDFVolume:
     def debug_units(self):
         """-> unit indices int32 [n,3] in (X, Y, Z) order, tsdf float32 [n,4096], weight float32 [n,4096], colour float64
         [n,3,4096] (None without colour); voxel (x, y, z) at x*256 + y*16 + z"""
-        n = ctypes.c_int64()
-        self.ctx.call("r3d_debug_tsdf_units", self._h, 0, None, None, None, None, ctypes.byref(n))
-        n = n.value
-        idx, t, w = np.empty((n, 3), np.int32), np.empty((n, UNIT_VOXELS), np.float32), np.empty((n, UNIT_VOXELS), np.float32)
-        c = np.empty((n, 3, UNIT_VOXELS)) if self.has_color else None
-        if n:
-            got = ctypes.c_int64()
-            self.ctx.call("r3d_debug_tsdf_units", self._h, n, _ptr(idx), _ptr(t), _ptr(w), _ptr(c), ctypes.byref(got))
-        return idx, t, w, c
+        def outputs(n):
+            return (np.empty((n, 3), np.int32), np.empty((n, UNIT_VOXELS), np.float32), np.empty((n, UNIT_VOXELS), np.float32),
+                    np.empty((n, 3, UNIT_VOXELS)) if self.has_color else None)
+
+        _, arrays = self.ctx.count_then_fill("r3d_debug_tsdf_units", (self._h,), 4, outputs)
+        return arrays
 
 
 def mc_table():

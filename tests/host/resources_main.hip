@@ -1,5 +1,6 @@
 // Stand-alone host check of csrc/r3d_resources.h on a machine WITHOUT a GPU, where every HIP create call fails cleanly: the
-// failure paths of the owning types, the arena and the staging helpers, which cannot be provoked on a shared card.  Built with the host sanitizers and run by
+// failure paths of the owning types, the arena and the staging helpers, which cannot be provoked on a shared card, and the refusals
+// the mesh entry points share (r3d_internal.h, r3d_mesh.h), which need no device at all.  Built with the host sanitizers and run by
 // tools/cpu_sanitize_resources.sh; not a pytest.  With a GPU present it does nothing.
 #include <stdarg.h>
 #include <stdio.h>
@@ -9,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "../../3d_reconstruction_project_amd/csrc/r3d_internal.h"
+#include "../../3d_reconstruction_project_amd/csrc/r3d_mesh.h"
 
 // what api.hip supplies in the library
 int r3d_fail(r3d_ctx *ctx, int code, const char *fmt, ...) {
@@ -190,6 +191,87 @@ int main() {
         CHECK(counts_zero());
     }
     printf("r3d_upload and r3d_upload_plane return the arena's latched failure and its refusal of a poisoned context\n");
+
+    // the helpers the mesh entry points share (r3d_internal.h, r3d_mesh.h)
+    CHECK(r3d_blocks(0) == 0 && r3d_blocks(1) == 1 && r3d_blocks(256) == 1 && r3d_blocks(257) == 2);
+    CHECK(r3d_blocks(3 * (int64_t)(INT32_MAX / 6)) == 4194304u);   // 3 x 357913941 corners: 1073741823 / 256, rounded up
+    {
+        r3d_ctx ctx;
+        char a[64], b[64];
+        const r3d_span in[] = {{a, 32}, {nullptr, 64}, {b, 0}};
+        const r3d_span same[] = {{a, 32}}, straddle[] = {{a + 24, 16}}, next[] = {{a + 32, 32}, {b, 64}}, two[] = {{b, 32}, {b + 31, 8}};
+        const r3d_span absent[] = {{nullptr, 64}, {a, 0}, {nullptr, 64}}, both[] = {{b, 32}, {b + 16, 8}, {a + 31, 1}};
+        CHECK(r3d_distinct(&ctx, "who", same, 1, in, 3) == R3D_E_BADARG && ctx.err == "who: an output array overlaps an input array");
+        ctx.err.clear();
+        CHECK(r3d_distinct(&ctx, "who", straddle, 1, in, 3) == R3D_E_BADARG && ctx.err == "who: an output array overlaps an input array");
+        CHECK(r3d_distinct(&ctx, "who", two, 2, in, 3) == R3D_E_BADARG && ctx.err == "who: two output arrays overlap");
+        ctx.err.clear();
+        CHECK(r3d_distinct(&ctx, "who", next, 2, in, 3) == R3D_OK && ctx.err.empty());     // adjacent; b as an input has no bytes
+        CHECK(r3d_distinct(&ctx, "who", absent, 3, in, 3) == R3D_OK && ctx.err.empty());   // null twice, and no bytes at a's address
+        CHECK(r3d_distinct(&ctx, "who", both, 3, in, 3) == R3D_E_BADARG && ctx.err == "who: two output arrays overlap");   // in list order
+        const r3d_span first[] = {{a + 31, 1}, {b, 32}, {b + 16, 8}};
+        CHECK(r3d_distinct(&ctx, "who", first, 3, in, 3) == R3D_E_BADARG && ctx.err == "who: an output array overlaps an input array");
+        const r3d_span out_both[] = {{a + 32, 4}, {a + 32, 8}}, in_both[] = {{a + 36, 8}};   // output 1 overlaps output 0 and the input
+        ctx.err.clear();
+        CHECK(r3d_distinct(&ctx, "who", out_both, 2, in_both, 1) == R3D_E_BADARG && ctx.err == "who: an output array overlaps an input array");
+    }
+    printf("r3d_blocks rounds up; r3d_distinct refuses overlaps, inputs first, and lets adjacent, null and empty spans pass\n");
+    {
+        r3d_ctx ctx;
+        CHECK(r3d_fits2(&ctx, "who", "vertices", 5, "triangles", 7, 4, 9) == R3D_E_BADARG);
+        CHECK(ctx.err == "who: 5 vertices and 7 triangles do not fit capacities of 4 and 9");
+        ctx.err.clear();
+        CHECK(r3d_fits2(&ctx, "who", "vertices", 4, "triangles", 9, 4, 9) == R3D_OK && ctx.err.empty());
+        CHECK(r3d_fits2(&ctx, "who", "vertices", 4, "triangles", 10, 4, 9) == R3D_E_BADARG);
+        CHECK(ctx.err == "who: 4 vertices and 10 triangles do not fit capacities of 4 and 9");
+    }
+    {
+        const int64_t max_t = INT32_MAX / 6;
+        r3d_ctx ctx, bad;
+        bad.poisoned = true;
+        CHECK(r3d_mesh_sizes_ok(&ctx, "who", -1, 0) == R3D_E_BADARG && ctx.err == "who: a negative count");
+        CHECK(r3d_mesh_sizes_ok(&ctx, "who", 0, -1) == R3D_E_BADARG && ctx.err == "who: a negative count");
+        CHECK(r3d_mesh_sizes_ok(&ctx, "who", INT32_MAX, max_t + 1) == R3D_E_UNSUPPORTED && ctx.err == "who: 2147483647 vertices do not fit int32 indices");
+        CHECK(r3d_mesh_sizes_ok(&ctx, "who", 4, max_t + 1) == R3D_E_UNSUPPORTED && ctx.err == "who: 6 x 357913942 triangles do not fit int32 offsets");
+        ctx.err.clear();
+        CHECK(r3d_mesh_sizes_ok(&ctx, "who", INT32_MAX - 1, max_t) == R3D_OK && ctx.err.empty());
+        CHECK(r3d_mesh_sizes_ok(&bad, "who", 4, 2) == R3D_E_HIP && bad.err == "who: context poisoned by an earlier timed-out call: destroy it");
+        CHECK(r3d_mesh_sizes_ok(&bad, "who", -1, 2) == R3D_E_BADARG && bad.err == "who: a negative count");
+        CHECK(r3d_mesh_sizes_ok(&bad, "who", 4, max_t + 1) == R3D_E_UNSUPPORTED);   // the limits come before the poison as well
+        CHECK(r3d_mesh_empty_ok(&ctx, "who", 0, 1) == R3D_E_BADARG && ctx.err == "who: a triangle index outside [0, 0)");
+        ctx.err.clear();
+        CHECK(r3d_mesh_empty_ok(&ctx, "who", 0, 0) == R3D_OK && r3d_mesh_empty_ok(&ctx, "who", 1, 1) == R3D_OK && ctx.err.empty());
+    }
+    printf("r3d_fits2, r3d_mesh_sizes_ok and r3d_mesh_empty_ok refuse in order with the shared messages\n");
+    {
+        // without a device the first HIP call of a read-back fails: R3D_E_HIP naming that call, the host side untouched.  The
+        // message tells a copy from the wait, which is how "no copy was issued" shows here.
+        r3d_ctx ctx;
+        int host[2] = {7, 9};
+        CHECK(r3d_read_back(&ctx, {{&host[0], (const void *)0x1000, 4}, {&host[1], (const void *)0x2000, 4}}) == R3D_E_HIP);
+        CHECK(ctx.err.find("hipMemcpyAsync(") == 0 && ctx.err.find(" failed: ") != std::string::npos && host[0] == 7 && host[1] == 9);
+        const int none = r3d_read_back(&ctx, {}), nulls = r3d_read_back(&ctx, {{&host[0], nullptr, 4}, {&host[1], nullptr, 4}});
+        CHECK(none == nulls && (none == R3D_OK || (none == R3D_E_HIP && ctx.err.find("hipStreamSynchronize(") == 0)));
+        ctx.err.clear();
+        CHECK(r3d_read_back(&ctx, {{&host[0], nullptr, 4}}) == none && ctx.err.find("hipMemcpyAsync(") == std::string::npos && host[0] == 7);
+        // the mesh staging over an arena that cannot allocate: the first upload's failure comes back, absent arrays take no slot
+        DevArena ar(&ctx);
+        const double pos[3] = {};
+        r3d_mesh_in d = {pos, pos, pos, (const int32_t *)pos};
+        CHECK(r3d_mesh_upload(&ctx, ar, {nullptr, nullptr, nullptr, nullptr}, 1, 0, &d) == R3D_OK && ar.next == 0);
+        CHECK(d.pos == nullptr && d.nrm == nullptr && d.col == nullptr && d.tri == nullptr);
+        CHECK(r3d_mesh_upload(&ctx, ar, {pos, nullptr, pos, nullptr}, 1, 0, &d) == R3D_E_OOM && ar.next == 1 && d.pos == nullptr);
+        r3d_mesh_out o = {(double *)pos, (double *)pos, (double *)pos, (int32_t *)pos};
+        r3d_mesh_outputs(ar, d, 1, 1, true, &o);   // the arena has latched: nothing more is taken
+        CHECK(ar.rc == R3D_E_OOM && ar.next == 1 && o.pos == nullptr && o.nrm == nullptr && o.col == nullptr && o.tri == nullptr);
+        double out[3] = {1, 2, 3};
+        ctx.err.clear();
+        CHECK(r3d_mesh_download(&ctx, {out, out, out, nullptr}, {(double *)0x1000, nullptr, nullptr, nullptr}, 0, 5) == R3D_OK);   // no rows, absent arrays
+        CHECK(r3d_mesh_download(&ctx, {nullptr, nullptr, nullptr, nullptr}, {(double *)0x1000, (double *)0x1000, nullptr, (int32_t *)0x1000}, 2, 2) == R3D_OK);
+        CHECK(ctx.err.empty() && out[0] == 1 && out[2] == 3);
+        CHECK(counts_zero());
+    }
+    printf("r3d_read_back fails cleanly without a device; the mesh staging skips absent arrays and returns the arena's failure\n");
 
     printf("resources_main: %d checks passed, all five counters zero throughout\n", g_checks);
     return 0;
